@@ -11,6 +11,8 @@ box head -> per-class rotated NMS.  Buildings are independent: rank r processes 
 (weak scaling, no data-path collective); value = buildings of all ranks / max-over-ranks time.
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP events on the launch stream inside
 the timed region) and, at N=1, `cpu_baseline` (the CPU oracle port on a bounded sample).
+`--dump-outputs DIR` saves the detections of rank 0's last timed step; scenes and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -55,7 +57,28 @@ def parse():
                     help="run only the `bf16_bs4` region and print its object (profiling runs of that region alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-points", type=int, default=500_000)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of rank 0's last timed step as DIR/<key>.npy (bbox3d, scores, labels)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(result, out_dir):
+    """The detections dict a caller of the timed path receives, one DIR/<key>.npy per tensor: float32 tensors as float32,
+    every other dtype (the int64 labels) as float64, which holds them exactly."""
+    arrays = {}
+    for k, v in result.items():
+        a = v.detach().cpu().numpy()
+        arrays[k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES, {k: a.shape for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def pmc_traffic(template, section=None, source="conv.hip"):
@@ -284,10 +307,12 @@ def main():
     t0 = time.perf_counter()
     marks = [t0]
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
         marks.append(time.perf_counter())      # (a pass ends with its detections' count on the host: these are pass times)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:       # outside the timed region, before the extra regions run the model again
+        dump_outputs(last, args.dump_outputs)
     per_step = sorted(1e3 * (b - a) for a, b in zip(marks[:-1], marks[1:]))
     SCN.set_profiler(None)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)

@@ -1,7 +1,7 @@
 """Grid chain vs one d3d_conv_prepare per level on the same input: every map the backbone hands on, bit for bit.
   python scripts/chain_probe.py [examples] [points per example]"""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from detection_3d_amd._lib import lib

@@ -2,7 +2,7 @@
 bit, then the time of the sparse convolutions per family with either kernel.
   python scripts/conv_ws_probe.py [points]"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd._lib import lib
 from detection_3d_amd.config import get_cfg

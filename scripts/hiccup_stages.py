@@ -1,7 +1,7 @@
 """Development probe: 300 passes with the timeline marks on; for the passes that take over 1.25 x the median, where the
 time went (host clock and stream time of every stage against the median pass)."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.detector import build_detection_model

@@ -1,7 +1,7 @@
 """Host side of one building's pass: cProfile over 20 passes (sorted by own time) -- which Python / ctypes calls the
 launch thread spends its time in.  python scripts/host_profile.py [points]"""
 import cProfile, os, pstats, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.detector import build_detection_model

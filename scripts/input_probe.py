@@ -1,6 +1,6 @@
 """Development probe: the input layer alone (grid build, point lists, feature pass) at 500 k / 1 M points and a batch of 4."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd import sparseconvnet as scn
 from detection_3d_amd.synthetic import make_scene

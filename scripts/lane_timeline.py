@@ -3,7 +3,7 @@ times -- ms since the caller's stream started the pass -- at which the geometry 
 grid, the plan stream its rulebooks, the caller's stream arrives at the level and goes on, and the host enqueues them.
   python scripts/lane_timeline.py [points]        D3D_PLAN_LANE=0: two streams"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.detector import build_detection_model

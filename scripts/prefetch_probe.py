@@ -1,5 +1,5 @@
 import os, sys, time, tempfile
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.scene_io import ScenePrefetcher, load_scene, scene_targets

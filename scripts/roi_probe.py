@@ -1,6 +1,6 @@
 """Development probe: time of the pooler (d3d_roi_prepare + k_roi_sparse per level) on the bench scene's RoIs."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.detector import build_detection_model

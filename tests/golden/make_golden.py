@@ -1,18 +1,20 @@
 """Generates tests/golden/ref_python.npz by importing the importable pure-torch pieces of the
-reference from /root/reference (run in the build container only; the reference does not travel to
-the GPU box).  Also copies the reference's demo detections (data files) used as realistic box
-distributions:  demo/suncg_test_5_iou_3_augth_2/text_models/room_*.txt  ->  tests/golden/rooms.npz
+reference from a checkout of it (the reference is not needed to run the tests).  Also copies the
+reference's demo detections (data files) used as realistic box distributions:
+demo/suncg_test_5_iou_3_augth_2/text_models/room_*.txt  ->  tests/golden/rooms.npz, and the three
+target configs, verbatim:  configs/{4c,6c,3G6c}/*.yaml  ->  tests/golden/configs/
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference checkout>
 """
 import math
 import os
+import shutil
 import sys
 
 import numpy as np
 import torch
 
-REF = "/root/reference"
+REF = os.path.abspath(sys.argv[1])
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REF)
 
@@ -55,6 +57,10 @@ d = os.path.join(REF, "demo/suncg_test_5_iou_3_augth_2/text_models")
 for i in range(5):
     rooms[f"room_{i}"] = np.loadtxt(os.path.join(d, f"room_{i}.txt")).astype(np.float32)
 np.savez_compressed(os.path.join(HERE, "rooms.npz"), **rooms)
+for cfg_path in ("configs/4c/4c_Fpn432_bs1_lr5_SD.yaml", "configs/6c/6c_Fpn4321_bs1_lr5.yaml",
+                 "configs/3G6c/3G6c_Fpn4321_bs1_lr2.yaml"):     # tests/test_config.py
+    os.makedirs(os.path.dirname(os.path.join(HERE, cfg_path)), exist_ok=True)
+    shutil.copyfile(os.path.join(REF, cfg_path), os.path.join(HERE, cfg_path))
 print({k: v.shape for k, v in out.items()}, {k: v.shape for k, v in rooms.items()})
 
 # ---- round 2: the other reference modules that import cleanly in the build container ------------------------------

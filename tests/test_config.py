@@ -7,6 +7,8 @@ import torch
 
 from detection_3d_amd.config import class_to_label, get_cfg
 
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+
 
 def test_derived_fields_4c():
     c = get_cfg("4c_Fpn432")
@@ -36,12 +38,12 @@ def test_opts_override_and_unknown_key():
         get_cfg("4c_Fpn432", ["MODEL.NOPE", "1"])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/configs"), reason="reference not mounted")
 def test_reference_yaml_files_load_unchanged():
+    # the reference's own yaml files, stored verbatim under tests/golden/configs (tests/golden/make_golden.py)
     pairs = [("configs/4c/4c_Fpn432_bs1_lr5_SD.yaml", "4c_Fpn432"), ("configs/6c/6c_Fpn4321_bs1_lr5.yaml", "6c_Fpn4321"),
              ("configs/3G6c/3G6c_Fpn4321_bs1_lr2.yaml", "3G6c_Fpn4321")]
     for path, name in pairs:
-        a, b = get_cfg(os.path.join("/root/reference", path)), get_cfg(name)
+        a, b = get_cfg(os.path.join(GOLD, path)), get_cfg(name)
         for sec in ("MODEL", "SPARSE3D", "TEST"):
             assert a[sec] == b[sec], (path, sec)
 
