@@ -126,6 +126,10 @@ _SIGS = {
     "d3d_rotate_iou_eval": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "d3d_boxes_iou_3d": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                         ctypes.c_int, ctypes.c_int, vp, vp]),
+    "d3d_match_segments": (ctypes.c_int, [vp, c_int_p, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float),
+                                          ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_float), vp, vp, vp, ctypes.c_size_t, vp]),
+    "d3d_match_segments_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_rotate_nms_3d_batched": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                                  ctypes.c_float, ctypes.c_float, ctypes.c_int, vp, vp, vp,
                                                  ctypes.c_size_t, vp]),

@@ -7,6 +7,7 @@ running entirely on the GPU through libd3d_hip.so (no numpy / numba / spconv rou
     nms_3d_clamped        maskrcnn_benchmark/structures/boxlist_ops_3d.py:14-62 (tensor form)
     box_decode            maskrcnn_benchmark/modeling/box_coder_3d.py:38-65
     limit_period          utils3d/geometric_torch.py:4-10
+    match_segments        rpn/loss_3d.py:178-213 + roi_heads/box_head_3d/loss.py:66-160 per image (Matcher + box_encode)
 """
 import math
 
@@ -68,6 +69,56 @@ def boxes_iou_3d(targets_bbox3d, anchors_bbox3d, aug_thickness=None, criterion=-
 
 
 _NMS_SCRATCH = {}
+_MATCH_MAX_SEGMENTS = 256
+
+
+def match_segments(gt, gt_offsets, pred, pred_seg, aug_thickness=None, criterion=-1, yaw_threshold=4.0, high=0.5,
+                   low=0.5, allow_low_quality=False, encode_weights=(1.0,) * 7, want_reg=True):
+    """d3d_match_segments: label assignment of S segments in one launch set, no [M, N] IoU matrix, no host sync.
+    gt [M, 7] yx_zb with segment s's rows at [gt_offsets[s], gt_offsets[s + 1]) (gt_offsets: host ints, S + 1 of them,
+    starting at 0); pred [N, 7]; pred_seg int32 [N] on the device (segment of each prediction, any order).
+    Per segment this is Matcher(high, low, allow_low_quality)(boxes_iou_3d(gt_s, pred_s, aug, criterion) x yaw mask)
+    followed by box_encode(gt_s[matched.clamp(min=0)], pred_s, encode_weights); yaw_threshold > 1.58: no yaw mask.
+    -> (matched int32 [N]: GLOBAL gt row, -1 below low / no GT in the segment, -2 between; reg [N, 7] or None)."""
+    offs = [int(v) for v in gt_offsets]
+    S = len(offs) - 1
+    if S < 0 or S > _MATCH_MAX_SEGMENTS:
+        raise ValueError(f"match_segments: {S} segments (1..{_MATCH_MAX_SEGMENTS} offsets expected)")
+    if offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"match_segments: GT offsets must start at 0 and not decrease: {offs}")
+    require_gpu(gt, pred, pred_seg)
+    if gt.dim() != 2 or gt.shape[1] != 7 or pred.dim() != 2 or pred.shape[1] != 7:
+        raise ValueError(f"match_segments: boxes must be [*, 7]: gt {tuple(gt.shape)}, pred {tuple(pred.shape)}")
+    if gt.shape[0] != offs[-1]:
+        raise ValueError(f"match_segments: {gt.shape[0]} GT rows, offsets end at {offs[-1]}")
+    if pred_seg.dtype != torch.int32 or pred_seg.shape != (pred.shape[0],):
+        raise ValueError("match_segments: pred_seg must be int32 [N]")
+    if gt.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise ValueError("match_segments: boxes must be fp32")
+    if low > high:
+        raise ValueError("match_segments: low threshold above the high one")
+    M, N = gt.shape[0], pred.shape[0]
+    dev = pred.device
+    matched = torch.empty((N,), dtype=torch.int32, device=dev)
+    reg = torch.empty((N, 7), dtype=torch.float32, device=dev) if want_reg else None
+    if N == 0:
+        return matched, reg
+    if aug_thickness is None:
+        aug_thickness = {'target_Y': 0.0, 'target_Z': 0.0, 'anchor_Y': 0.0, 'anchor_Z': 0.0}
+    aug = floats([aug_thickness['target_Y'], aug_thickness['target_Z'], aug_thickness['anchor_Y'],
+                  aug_thickness['anchor_Z']])
+    nbytes = int(lib().d3d_match_segments_scratch_bytes(M, N))
+    key = ("match",) + _nms_key(dev)
+    buf = _NMS_SCRATCH.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
+        _NMS_SCRATCH[key] = buf
+    check(lib().d3d_match_segments(ptr(gt), _lib.ints(offs), S, ptr(pred), N, ptr(pred_seg), aug, int(criterion),
+                                   float(yaw_threshold) if not yaw_threshold > 1.58 else 4.0, float(high), float(low), int(bool(allow_low_quality)),
+                                   floats([float(w) for w in encode_weights]), ptr(matched), ptr(reg), ptr(buf),
+                                   buf.numel(), stream_of()))
+    return matched, reg
+
 
 
 def _nms_key(dev):      # one scratch per (device, stream): buildings in flight on different streams never share it

@@ -272,6 +272,25 @@ __device__ __forceinline__ void load_box(const IouArgs &a, const float *base, in
   }
 }
 
+// one entry of the matrix: row box rb (target / "boxes"), column box cb (anchor / "query")
+__device__ __forceinline__ float iou_pair(const IouArgs &a, const BoxRec &rb, const BoxRec &cb) {
+  // kernel order (nms_gpu.py:605-611): rbox1 = query (col), rbox2 = box (row).  Most pairs of an anchors x targets
+  // matrix are far apart: their bounding boxes do not touch and the intersection is exactly 0 (NaN corners compare
+  // false and take the full path)
+  const bool apart = cb.hi[0] < rb.lo[0] || rb.hi[0] < cb.lo[0] || cb.hi[1] < rb.lo[1] || rb.hi[1] < cb.lo[1];
+  float v = iou_eval(cb.q, cb.d0, cb.d1, rb.q, rb.d0, rb.d1, a.criterion, PrivatePts(), apart);
+  bool same = true;  // check_same_boxes, nms_gpu.py:653-664
+#pragma unroll
+  for (int d = 0; d < 5; d++) same = same && (fabsf(rb.raw[d] - cb.raw[d]) < (float)1e-6);
+  if (same) v = 1.f;
+  if (a.mode == 1 && !a.only_xy) {
+    const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
+    const float common = fmaxf(cb.z1, rb.z1) - fminf(cb.z0, rb.z0);
+    v = v * (overlap / common);
+  }
+  return v;
+}
+
 __global__ __launch_bounds__(256) void k_iou_matrix(IouArgs a) {
   __shared__ BoxRec srow[64], scol[64];
   const int tid = threadIdx.x;
@@ -289,22 +308,7 @@ __global__ __launch_bounds__(256) void k_iou_matrix(IouArgs a) {
   for (int i = 0; i < 16; i++) {
     const int rr = rg * 16 + i;
     if (r0 + rr >= a.N) break;
-    const BoxRec &rb = srow[rr];
-    // kernel order (nms_gpu.py:605-611): rbox1 = query (col), rbox2 = box (row).  Most pairs of an anchors x targets
-    // matrix are far apart: their bounding boxes do not touch and the intersection is exactly 0 (NaN corners compare
-    // false and take the full path)
-    const bool apart = cb.hi[0] < rb.lo[0] || rb.hi[0] < cb.lo[0] || cb.hi[1] < rb.lo[1] || rb.hi[1] < cb.lo[1];
-    float v = iou_eval(cb.q, cb.d0, cb.d1, rb.q, rb.d0, rb.d1, a.criterion, PrivatePts(), apart);
-    bool same = true;  // check_same_boxes, nms_gpu.py:653-664
-#pragma unroll
-    for (int d = 0; d < 5; d++) same = same && (fabsf(rb.raw[d] - cb.raw[d]) < (float)1e-6);
-    if (same) v = 1.f;
-    if (a.mode == 1 && !a.only_xy) {
-      const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
-      const float common = fmaxf(cb.z1, rb.z1) - fminf(cb.z0, rb.z0);
-      v = v * (overlap / common);
-    }
-    a.out[(size_t)(r0 + rr) * a.K + c0 + c] = v;
+    a.out[(size_t)(r0 + rr) * a.K + c0 + c] = iou_pair(a, srow[rr], cb);
   }
 }
 
@@ -737,6 +741,202 @@ __global__ void k_gather_kept(const float *__restrict__ boxes, const float *__re
   out_scores[i] = scores[j];
 }
 
+// ------------------------------------------------------------------------------------------
+// Label assignment of several segments (examples, or (example, class group) pairs) in one launch set: every prediction
+// (anchor or proposal) is matched against the GT rows of ITS segment only.  IoU = iou_pair with GT as rows (the values
+// of d3d_boxes_iou_3d), the Matcher of matcher.py:13-177 and box_encode (box_coder_3d.py:31-36) fused; no [M, N] matrix.
+//   pass 1: thread = prediction; the GT rows of the block's segments are staged in LDS chunks; best value + argmax per
+//           prediction, per-GT maxima (low-quality rule) as an order-preserving integer max (LDS, then one global
+//           atomic per GT and block: integer max is exact and order-independent, so the result is deterministic)
+//   pass 2 (low-quality rule only): the IoUs are evaluated again where they can decide (q == highest, q > ignore
+//           threshold), cheaper than storing them: most pairs take the bounding-box early-out
+static constexpr int kMatchThreads = 256, kMatchChunk = 256, kMatchMaxSeg = 256;
+struct MatchArgs {
+  IouArgs a;                  // mode 1: rows = GT [M, 7], cols = predictions [N, 7]
+  const int32_t *pred_seg;
+  int S, N, use_yaw, low_quality;
+  float yaw_thr, high, low;
+  float w[7];
+  int32_t *matched;
+  float *reg;
+  float *best;
+  int32_t *arg;
+  unsigned *highest;
+  int off[kMatchMaxSeg + 1];  // GT rows of segment s: [off[s], off[s + 1])
+};
+
+__device__ __forceinline__ unsigned f2ord(float f) {    // order-preserving float -> unsigned (NaN with sign 0 on top)
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// limit_period(v, offset, pi) as the tensor library evaluates it: v / pi is the product with the fp32 reciprocal
+__device__ __forceinline__ float limit_period_pi(float v, float offset) {
+  const float kPi = (float)3.14159265358979323846, kInvPi = 1.f / kPi;
+  return v - floorf(v * kInvPi + offset) * kPi;
+}
+
+// Matcher's quality: IoU x (|limit_period(yaw_gt - yaw_pred)| < YAW_THRESHOLD) (matcher.py:50-55; a masked negative
+// IoU becomes -0.0, as in the tensor form)
+__device__ __forceinline__ float match_quality(const MatchArgs &m, const BoxRec &g, const BoxRec &p) {
+  float v = iou_pair(m.a, g, p);
+  if (m.use_yaw) {
+    const float d = fabsf(limit_period_pi(g.raw[4] - p.raw[4], 0.5f));
+    v = v * (d < m.yaw_thr ? 1.f : 0.f);
+  }
+  return v;
+}
+
+// BoxCoder3D.encode (smooth_dim), operation by operation as the tensor form (training.box_encode) evaluates it
+__device__ __forceinline__ void box_encode_one(const float *g, const float *a, const float *w, float *o) {
+  const float diag = sqrtf(a[4] * a[4] + a[3] * a[3]);
+  float e[7];
+  e[0] = (g[0] - a[0]) / diag;
+  e[1] = (g[1] - a[1]) / diag;
+  e[2] = (g[2] - a[2]) / a[5];
+  e[3] = g[3] / a[3] - 1.f;
+  e[4] = g[4] / a[4] - 1.f;
+  e[5] = g[5] / a[5] - 1.f;
+  e[6] = limit_period_pi(g[6] - a[6], 0.5f);
+#pragma unroll
+  for (int k = 0; k < 7; k++) o[k] = e[k] * w[k];
+}
+
+// matched[p] and the regression target of row gt[max(matched, first row of the segment)] (gt_boxes[matched.clamp(min=0)]);
+// a segment without GT: -1 and zeros (the empty-GT branches of prepare_targets / subsample)
+__device__ __forceinline__ void match_store(const MatchArgs &m, int p, int lo, int hi, int matched) {
+  m.matched[p] = matched;
+  if (!m.reg) return;
+  float *o = m.reg + (size_t)p * 7;
+  if (hi <= lo) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) o[k] = 0.f;
+    return;
+  }
+  box_encode_one(m.a.rows + (size_t)(matched >= 0 ? matched : lo) * 7, m.a.cols + (size_t)p * 7, m.w, o);
+}
+
+// below the low threshold -1, between -2, else the argmax (a NaN maximum is neither, as in the tensor form)
+__device__ __forceinline__ int match_thresholds(const MatchArgs &m, float best, int arg) {
+  if (best < m.low) return -1;
+  if (best < m.high) return -2;
+  return arg;
+}
+
+// the segment of row p (out-of-range ids: no GT) and the union of the GT ranges the block's rows need
+__device__ __forceinline__ void match_rows(const MatchArgs &m, int p, bool want, int &lo, int &hi, int *s_range) {
+  int seg = p < m.N ? m.pred_seg[p] : -1;
+  if (seg < 0 || seg >= m.S) seg = -1;
+  lo = seg >= 0 ? m.off[seg] : 0;
+  hi = seg >= 0 ? m.off[seg + 1] : 0;
+  if (threadIdx.x == 0) {
+    s_range[0] = 0x7fffffff;
+    s_range[1] = 0;
+  }
+  __syncthreads();
+  if (want && hi > lo) {
+    atomicMin(&s_range[0], lo);
+    atomicMax(&s_range[1], hi);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kMatchThreads) void k_match_pass1(MatchArgs m) {
+  __shared__ BoxRec sg[kMatchChunk];
+  __shared__ unsigned shi[kMatchChunk];
+  __shared__ int s_range[2];
+  const int tid = threadIdx.x, p = blockIdx.x * kMatchThreads + tid;
+  int lo, hi;
+  match_rows(m, p, true, lo, hi, s_range);
+  const int blo = s_range[0], bhi = s_range[1];
+  BoxRec pb;
+  if (hi > lo) load_box(m.a, m.a.cols, p, false, pb);
+  float best = 0.f;
+  int arg = -1;
+  for (int c0 = blo; c0 < bhi; c0 += kMatchChunk) {     // block-uniform loop
+    const int cn = min(kMatchChunk, bhi - c0);
+    if (tid < cn) {
+      load_box(m.a, m.a.rows, c0 + tid, true, sg[tid]);
+      shi[tid] = 0u;
+    }
+    __syncthreads();
+    const int r1 = min(hi, c0 + cn);
+    for (int r = max(lo, c0); r < r1; r++) {
+      const float v = match_quality(m, sg[r - c0], pb);
+      // q.max(dim=0): first maximum (lowest GT row); a NaN wins and stays
+      if (arg < 0 || v > best || (v != v && best == best)) {
+        best = v;
+        arg = r;
+      }
+      if (m.low_quality) atomicMax(&shi[r - c0], f2ord(v));
+    }
+    __syncthreads();
+    if (m.low_quality && tid < cn && shi[tid] != 0u) atomicMax(&m.highest[c0 + tid], shi[tid]);
+    __syncthreads();                                     // sg / shi are restaged by the next chunk
+  }
+  if (p >= m.N) return;
+  if (m.low_quality) {
+    m.best[p] = best;
+    m.arg[p] = arg;
+  } else {
+    match_store(m, p, lo, hi, hi > lo ? match_thresholds(m, best, arg) : -1);
+  }
+}
+
+// allow_low_quality_matches (matcher.py:105-177): every GT keeps its best prediction(s) (q == highest, ties included);
+// predictions that would be negatives and have q > max(0.02, highest - 0.05) for some GT are ignored (-2)
+__global__ __launch_bounds__(kMatchThreads) void k_match_pass2(MatchArgs m) {
+  __shared__ BoxRec sg[kMatchChunk];
+  __shared__ float shv[kMatchChunk], sthr[kMatchChunk];
+  __shared__ int s_range[2];
+  const int tid = threadIdx.x, p = blockIdx.x * kMatchThreads + tid;
+  const float best = p < m.N ? m.best[p] : 0.f;
+  const int arg = p < m.N ? m.arg[p] : -1;
+  // best >= high (or NaN): restoring gives the argmax back and the ignore rule needs -1 -> nothing can change
+  const bool need = p < m.N && arg >= 0 && best < m.high;
+  int lo, hi;
+  match_rows(m, p, need, lo, hi, s_range);
+  const int blo = s_range[0], bhi = s_range[1];
+  BoxRec pb;
+  if (need) load_box(m.a, m.a.cols, p, false, pb);
+  bool restore = false, ignore = false;
+  for (int c0 = blo; c0 < bhi; c0 += kMatchChunk) {
+    const int cn = min(kMatchChunk, bhi - c0);
+    if (tid < cn) {
+      load_box(m.a, m.a.rows, c0 + tid, true, sg[tid]);
+      const float h = ord2f(m.highest[c0 + tid]);
+      const float t = h - 0.05f;
+      shv[tid] = h;
+      sthr[tid] = t != t ? t : fmaxf(0.02f, t);          // torch.max(0.02, highest - 0.05): a NaN propagates
+    }
+    __syncthreads();
+    if (need) {
+      const int r1 = min(hi, c0 + cn);
+      for (int r = max(lo, c0); r < r1; r++) {
+        const float h = shv[r - c0], t = sthr[r - c0];
+        // q <= best: below min(highest, threshold) the pair decides nothing (a NaN highest never matches)
+        if (h != h || best < fminf(h, t)) continue;
+        const float q = match_quality(m, sg[r - c0], pb);
+        restore = restore || q == h;
+        ignore = ignore || q > t;
+      }
+    }
+    __syncthreads();
+  }
+  if (p >= m.N) return;
+  if (arg < 0) {          // no GT in the segment
+    match_store(m, p, lo, hi, -1);
+    return;
+  }
+  int mt = match_thresholds(m, best, arg);
+  if (restore) mt = arg;
+  if (ignore && mt == -1) mt = -2;
+  match_store(m, p, lo, hi, mt);
+}
+
 }  // namespace d3d
 
 using namespace d3d;
@@ -769,6 +969,53 @@ int d3d_boxes_iou_3d(const float *targets, int M, const float *anchors, int N, c
   for (int i = 0; i < 4; i++) a.aug[i] = aug_host ? aug_host[i] : 0.f;
   a.out = out;
   hipLaunchKernelGGL(k_iou_matrix, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, a);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+size_t d3d_match_segments_scratch_bytes(int M, int N) {
+  const size_t n = N > 0 ? N : 0, m = M > 0 ? M : 0;
+  return 2 * ((n * 4 + 255) & ~size_t(255)) + ((m * 4 + 255) & ~size_t(255)) + 256;
+}
+
+int d3d_match_segments(const float *gt, const int *gt_off_host, int S, const float *pred, int N, const int32_t *pred_seg,
+                       const float *aug_host, int criterion, float yaw_threshold, float high, float low,
+                       int allow_low_quality, const float *encode_weights_host, int32_t *matched, float *reg_targets,
+                       void *scratch, size_t scratch_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(N >= 0 && S >= 0 && S <= kMatchMaxSeg, "match_segments: N=%d or S=%d out of range (S <= %d)", N, S,
+              kMatchMaxSeg);
+  D3D_REQUIRE(S == 0 || gt_off_host, "match_segments: null GT offsets");
+  D3D_REQUIRE(S == 0 || gt_off_host[0] == 0, "match_segments: GT offsets must start at 0");
+  for (int i = 0; i < S; i++)
+    D3D_REQUIRE(gt_off_host[i + 1] >= gt_off_host[i], "match_segments: GT offsets decrease at segment %d", i);
+  const int M = S ? gt_off_host[S] : 0;
+  D3D_REQUIRE(criterion >= -1 && criterion <= 2, "match_segments: criterion %d", criterion);
+  D3D_REQUIRE(low <= high, "match_segments: low threshold above the high one");
+  if (N == 0) return D3D_OK;
+  D3D_REQUIRE(pred && pred_seg && matched && (M == 0 || gt), "match_segments: null pointer");
+  D3D_REQUIRE(scratch && scratch_bytes >= d3d_match_segments_scratch_bytes(M, N), "match_segments: scratch too small");
+  MatchArgs m;
+  m.a.rows = gt; m.a.cols = pred; m.a.N = M; m.a.K = N; m.a.mode = 1; m.a.criterion = criterion; m.a.only_xy = 0;
+  for (int i = 0; i < 4; i++) m.a.aug[i] = aug_host ? aug_host[i] : 0.f;
+  m.a.out = nullptr;
+  m.pred_seg = pred_seg;
+  m.S = S; m.N = N;
+  m.use_yaw = !(yaw_threshold > 1.58f);
+  m.low_quality = allow_low_quality ? 1 : 0;
+  m.yaw_thr = yaw_threshold; m.high = high; m.low = low;
+  for (int k = 0; k < 7; k++) m.w[k] = encode_weights_host ? encode_weights_host[k] : 1.f;
+  m.matched = matched; m.reg = reg_targets;
+  char *base = (char *)scratch;
+  const size_t nb = ((size_t)N * 4 + 255) & ~size_t(255);
+  m.best = (float *)base;
+  m.arg = (int32_t *)(base + nb);
+  m.highest = (unsigned *)(base + 2 * nb);
+  for (int i = 0; i <= kMatchMaxSeg; i++) m.off[i] = i <= S ? gt_off_host[i] : M;
+  const dim3 grid((N + kMatchThreads - 1) / kMatchThreads);
+  if (m.low_quality && M > 0) D3D_HIP_CHECK(hipMemsetAsync(m.highest, 0, (size_t)M * 4, s));   // below every value
+  hipLaunchKernelGGL(k_match_pass1, grid, dim3(kMatchThreads), 0, s, m);
+  if (m.low_quality) hipLaunchKernelGGL(k_match_pass2, grid, dim3(kMatchThreads), 0, s, m);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

@@ -374,8 +374,8 @@ class RPNModule(nn.Module):
         grouped = self.sep.need_seperate and self.head.seperate_rpn > 1
         if n_examples > 1:
             if self.training:
-                raise NotImplementedError("training with more than one example per batch is not built "
-                                          "(the reference's configs train with IMS_PER_BATCH 1)")
+                return self._forward_train_batch(anchors, objectness, box_regression, features_sparse, targets,
+                                                 n_examples, grouped)
             A = self.anchor_generator.num_anchors_per_location()
             example = torch.cat([f.get_spatial_locations()[:, 3].repeat_interleave(A) for f in features_sparse])
             segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, example,
@@ -398,6 +398,39 @@ class RPNModule(nn.Module):
             scores = torch.cat([scores, torch.ones(gt.shape[0], device=scores.device)], 0)
         loss_obj, loss_reg = self.loss_evaluator(anchors, objectness.reshape(-1), box_regression, gt)
         return proposals, scores, {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg}
+
+    def _forward_train_batch(self, anchors, objectness, box_regression, features_sparse, targets, n_examples, grouped):
+        """Training with several examples (targets: list of B dicts): per-example pre / post top-N selection
+        (inference_3d.py:92-163) as segments of one launch set, GT boxes appended to each example's proposals (:73-78),
+        losses of the whole batch (RPNLoss.batch).  -> (proposals, scores, sep_id or None, example_id, loss dict) with
+        the rows ordered by example, then by class group."""
+        B = int(n_examples)
+        A = self.anchor_generator.num_anchors_per_location()
+        example = torch.cat([f.get_spatial_locations()[:, 3].repeat_interleave(A) for f in features_sparse])
+        segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, example, B, True)
+        G = objectness.shape[1]
+        tg = [self.sep.group_targets(t) if grouped else [t] for t in targets]
+        assert all(len(t) == G for t in tg), (G, [len(t) for t in tg])
+        dev = anchors.device
+        props, scores, sep_id, ex_id = [], [], [], []
+        for s_, (p, sc) in enumerate(segs):
+            gt = tg[s_ // G][s_ % G]["bbox3d"]
+            if self.add_gt_proposals and gt.shape[0]:
+                p = torch.cat([p, gt], 0)
+                sc = torch.cat([sc, torch.ones(gt.shape[0], device=sc.device)], 0)
+            props.append(p)
+            scores.append(sc)
+            sep_id.append(torch.full((p.shape[0],), s_ % G, dtype=torch.int64, device=dev))
+            ex_id.append(torch.full((p.shape[0],), s_ // G, dtype=torch.int64, device=dev))
+        parts = self.loss_evaluator.batch(anchors, objectness, box_regression, example,
+                                          [[t["bbox3d"] for t in tb] for tb in tg])
+        if grouped:
+            losses = {}
+            for gi, (lo, lr) in enumerate(parts):
+                losses[f"loss_objectness_{gi}"], losses[f"loss_rpn_box_reg_{gi}"] = lo, lr
+        else:
+            losses = {"loss_objectness": parts[0][0], "loss_rpn_box_reg": parts[0][1]}
+        return (torch.cat(props), torch.cat(scores), torch.cat(sep_id) if grouped else None, torch.cat(ex_id), losses)
 
     def _forward_grouped(self, anchors, objectness, box_regression, targets):
         """seperate_rpn_selector / seperate_rpn_loss_evaluator (seperate_classifier.py:58-95): one proposal set
@@ -425,15 +458,18 @@ class RPNModule(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------
-def convert_to_roi_format(boxes_yxzb):
+def convert_to_roi_format(boxes_yxzb, batch_ids=None):
     """modeling/poolers_3d.py:107-124 with BoxList3D.convert('standard')
-    (structures/bounding_box_3d.py:221-242, limit_yaw in the constructor :167): batch id 0."""
+    (structures/bounding_box_3d.py:221-242, limit_yaw in the constructor :167): batch id = batch_ids (example index of
+    every box, poolers_3d.py:112-118), 0 when None."""
     b = boxes_yxzb
     std = b[:, [0, 1, 2, 4, 3, 5, 6]].clone()
     std[:, 2] += b[:, 5] * 0.5
     std[:, 6] += math.pi * 0.5
     std[:, 6] = box_ops.limit_period(std[:, 6], 0.0, math.pi)
-    rois = torch.cat([torch.zeros((b.shape[0], 1), dtype=b.dtype, device=b.device), std], 1)
+    ids = (torch.zeros((b.shape[0], 1), dtype=b.dtype, device=b.device) if batch_ids is None
+           else batch_ids.to(b.dtype).view(-1, 1))
+    rois = torch.cat([ids, std], 1)
     rois = rois[:, [0, 2, 1, 3, 5, 4, 6, 7]]
     rois[:, -1] *= 180.0 / math.pi
     return rois
@@ -473,10 +509,11 @@ class Pooler(nn.Module):
                                              roi_levels=levels, level=level, channels_inner=channels_inner)
         return out
 
-    def forward(self, x, boxes_pixels, channels_inner=False):
-        """-> [K, C, ph, pw, pz]; channels_inner (inference only): [K, ph, pw, C, pz]."""
+    def forward(self, x, boxes_pixels, channels_inner=False, batch_ids=None):
+        """-> [K, C, ph, pw, pz]; channels_inner (inference only): [K, ph, pw, C, pz].  batch_ids: example of every box
+        (RoI column 0), None = one example."""
         with torch.no_grad():
-            rois = convert_to_roi_format(boxes_pixels)
+            rois = convert_to_roi_format(boxes_pixels, batch_ids)
         ph, pw, pz = self.output_size
         if not torch.is_grad_enabled():
             # one result tensor filled in place by one launch per level (no nonzero / index_put, no host sync)
@@ -630,11 +667,9 @@ class FPN2MLPFeatureExtractor(nn.Module):
         the example's sites, poolers_3d.py:112-118); None = one example."""
         if self.rows_path_ok() and proposals.shape[0] > 0:
             return self._forward_rows(x0, proposals, batch_ids)                 # metric boxes: pixels on the device
-        if batch_ids is not None:
-            raise NotImplementedError("several examples per batch: only the inference path of the box head is built")
         p = proposals.clone()
         p[:, 0:6] *= self.voxel_scale                                           # convert_metric_to_pixel
-        x1 = self._head_conv(self.pooler(x0, p))
+        x1 = self._head_conv(self.pooler(x0, p, batch_ids=batch_ids))          # BatchNorm3d: all RoIs of the batch
         x2 = x1.reshape(x1.size(0), -1)
         return F.relu(self.fc7(F.relu(self.fc6(x2))))
 
@@ -925,9 +960,39 @@ class ROIBoxHead3D(nn.Module):
         logits, reg = self.predictor(x)
         return self.post_processor(logits, reg, proposals), proposals, scores
 
+    def _forward_train_segments(self, roi_features, proposals, sep_id, example_id, targets, n_examples):
+        """Training with several examples (box_head.py:96-149 + loss.py:66-236 over the images; per class group for
+        3G6c, seperate_classifier.py:111-176): ONE match_segments launch set labels every (example, group) segment, the
+        sampler runs per segment, one box-head pass over all sampled RoIs (pooled with their example index; BatchNorm3d
+        sees the whole batch), losses per group over the batch."""
+        sep = self.sep
+        grouped = sep.need_seperate and sep_id is not None
+        G = sep.group_num if grouped else 1
+        B = int(n_examples)
+        tg = [sep.group_targets(t) if grouped else [t] for t in targets]
+        seg = example_id * G + (sep_id if grouped else 0)
+        proposals, labels, reg_targets, seg_k = self.loss_evaluator.subsample_segments(
+            proposals, seg, [tg[b][g]["bbox3d"] for b in range(B) for g in range(G)],
+            [tg[b][g]["labels"] for b in range(B) for g in range(G)])
+        x = self.feature_extractor(roi_features, proposals, (seg_k // G).to(torch.int32).contiguous())
+        logits, reg = self.predictor(x)
+        if not grouped:
+            cls_loss, box_loss = self.loss_evaluator(logits, reg, proposals, labels, reg_targets)
+            return {"loss_classifier_roi": cls_loss, "loss_box_reg_roi": box_loss}
+        assert logits.shape[1] == sep.total_classes
+        gid = seg_k % G
+        ids_g = [torch.nonzero(gid == gi).view(-1) for gi in range(G)]
+        out = {}
+        for gi, (lg, rg) in enumerate(zip(sep.seperate_pred_logits(logits, ids_g), sep.seperate_pred_box(reg, ids_g))):
+            idx = ids_g[gi]
+            c, b = self.loss_evaluator(lg, rg, proposals[idx], labels[idx], reg_targets[idx])
+            out[f"loss_classifier_roi_{gi}"], out[f"loss_box_reg_roi_{gi}"] = c, b
+        return out
+
     def forward(self, roi_features, proposals, targets=None, sep_id=None, example_id=None, n_examples=1):
         if n_examples > 1:
-            assert not self.training
+            if self.training:
+                return self._forward_train_segments(roi_features, proposals, sep_id, example_id, targets, n_examples)
             return self._forward_eval_segments(roi_features, proposals, sep_id, example_id, n_examples)
         if sep_id is not None:
             return self._forward_grouped(roi_features, proposals, sep_id, targets)
@@ -960,13 +1025,28 @@ class SparseRCNN(nn.Module):
         self.class_to_label = class_to_label(cfg.INPUT.CLASSES)
 
     def forward(self, points, targets=None, return_intermediates=False):
-        """eval: detections dict.  train: dict of the four losses (targets = {"bbox3d" [M,7] yx_zb, "labels" [M]})."""
+        """eval: detections dict.  train: dict of the four losses (targets = {"bbox3d" [M,7] yx_zb, "labels" [M]}; with
+        several examples in `points` a list of B such dicts, as the reference's collate gives them)."""
         if self.training:
             if targets is None:
                 raise ValueError("In training mode, targets should be passed")
-            if self.batch_size_of(points) > 1:
-                raise NotImplementedError("training with more than one example per batch is not built")
+            B = self.batch_size_of(points)
+            if isinstance(targets, (list, tuple)):
+                if len(targets) != B:
+                    raise ValueError(f"{len(targets)} target dicts for a batch of {B} examples")
+                if B == 1:
+                    targets = targets[0]
+            elif B > 1:
+                raise ValueError(f"a batch of {B} examples needs a list of {B} target dicts")
             rpn_features, roi_features = self.backbone(points[:2])
+            if B > 1:
+                proposals, _, sep_id, example_id, rpn_losses = self.rpn(rpn_features, targets, n_examples=B)
+                proposals = proposals.clone()
+                proposals[:, 3:6] = torch.clamp(proposals[:, 3:6], min=0.001)
+                losses = dict(self.roi_heads.box(roi_features, proposals, targets, sep_id=sep_id, example_id=example_id,
+                                                 n_examples=B))
+                losses.update(rpn_losses)
+                return losses
             out = self.rpn(rpn_features, targets)
             proposals, rpn_losses = out[0].clone(), out[-1]
             sep_id = out[2] if len(out) == 4 else None

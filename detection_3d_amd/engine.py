@@ -23,6 +23,35 @@ def _hip_voxelize(pcl, cfg):
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
 
 
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize):
+    """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
+    (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
+    the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets])."""
+    cs, fs, tgs = [], [], []
+    for b, (pcl, tg) in enumerate(scenes):
+        c, f = voxelize_fn(pcl, cfg)
+        cs.append(torch.cat([c, torch.full((c.shape[0], 1), b, dtype=c.dtype, device=c.device)], 1))
+        fs.append(f)
+        tgs.append(tg)
+    if not cs:
+        raise ValueError("collate: no scene")
+    return [torch.cat(cs), torch.cat(fs), len(cs)], tgs
+
+
+def group_batches(items, n):
+    """consecutive items in groups of `n` (the last group may be shorter)"""
+    if n < 1:
+        raise ValueError(f"batch size {n} < 1")
+    group = []
+    for it in items:
+        group.append(it)
+        if len(group) == n:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
 def _rank_world():
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
@@ -73,35 +102,57 @@ def evaluate(cfg, dets, gts):
     return eval_detection_suncg([host(dets[i]) for i in ids], [host(gts[i]) for i in ids], cfg)
 
 
-def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize):
-    """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): one building per rank and step
-    (IMS_PER_BATCH 1 per GPU).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
-    process group with more than one rank exists.  -> dict(buildings_per_s, ms_per_step, last reduced losses)."""
-    rank, world = _rank_world()
-    model.train()
-    opt = T.make_optimizer(cfg, model)
-    ddp = T.wrap_ddp(model, local_rank) if world > 1 else model
-    if world == 1:
-        T.freeze_unused(model)
-    sched = T.make_lr_scheduler(cfg, opt, examples_per_epoch=max(len(files), 1))
-    it, t0, reduced = 0, None, {}
-    while it < steps:
+def _cycled_scenes(files, cfg, device, rank, world, depth):
+    """the rank's buildings, prefetched, cycled epoch after epoch"""
+    while True:
         pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank,
                               world=world, depth=depth)
         if len(pre) == 0:
             raise ValueError(f"rank {rank} of {world} has no building: {len(files)} files")
         for pcl, tg, _path in pre:
-            if it == 1:                      # the first iteration pays allocations and the bucket build
-                if device is not None:
-                    torch.cuda.synchronize(device)
-                t0 = time.perf_counter()
+            yield pcl, tg
+
+
+def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
+          ims_per_gpu=1):
+    """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
+    buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
+    reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
+    process group with more than one rank exists.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced
+    losses)."""
+    rank, world = _rank_world()
+    ims = int(ims_per_gpu)
+    if ims < 1:
+        raise ValueError(f"ims_per_gpu {ims_per_gpu} < 1")
+    model.train()
+    opt = T.make_optimizer(cfg, model)
+    ddp = T.wrap_ddp(model, local_rank) if world > 1 else model
+    if world == 1:
+        T.freeze_unused(model)
+    if ims == 1:
+        sched = T.make_lr_scheduler(cfg, opt, examples_per_epoch=max(len(files), 1))
+    else:                                   # iterations per epoch counted with the global batch (defaults.py:299-301)
+        sched_cfg = cfg.clone()
+        sched_cfg.SOLVER.IMS_PER_BATCH = world * ims
+        sched = T.make_lr_scheduler(sched_cfg, opt, examples_per_epoch=max(len(files), 1))
+    it, t0, reduced = 0, None, {}
+    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth), ims):
+        if it == 1:                          # the first iteration pays allocations and the bucket build
+            if device is not None:
+                torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+        if ims == 1:
+            pcl, tg = batch[0]
             coords, feats = voxelize_fn(pcl, cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
-            it += 1
-            if log_every and rank == 0 and it % log_every == 0:
-                print(f"iter {it}: " + "  ".join(f"{k} {float(v):.4f}" for k, v in sorted(reduced.items())), flush=True)
-            if it >= steps:
-                break
+        else:
+            points, tgs = collate(batch, cfg, voxelize_fn)
+            _, reduced = T.train_step(ddp, opt, sched, points, tgs)
+        it += 1
+        if log_every and rank == 0 and it % log_every == 0:
+            print(f"iter {it}: " + "  ".join(f"{k} {float(v):.4f}" for k, v in sorted(reduced.items())), flush=True)
+        if it >= steps:
+            break
     if device is not None:
         torch.cuda.synchronize(device)
     dt = time.perf_counter() - (t0 if t0 is not None else time.perf_counter())
@@ -110,6 +161,7 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
-    return {"buildings_per_s": (world * timed / dt) if dt > 0 and timed else None,
+    return {"buildings_per_s": (world * ims * timed / dt) if dt > 0 and timed else None,
             "ms_per_step": (1e3 * dt / timed) if timed else None, "steps_timed": timed, "world": world,
+            "ims_per_gpu": ims,
             "losses": {k: float(v.detach()) for k, v in reduced.items()}}

@@ -8,7 +8,10 @@ optimizer / LR schedule surface, and the data-parallel wrapper.
     RPNLoss                            modeling/rpn/loss_3d.py:69-250
     ROILoss                            modeling/roi_heads/box_head_3d/loss.py:20-236
     make_optimizer / WarmupMultiStepLR maskrcnn_benchmark/solver/{build,lr_scheduler}.py
-The IoU matrices come from the HIP kernel (box_ops.boxes_iou_3d); the rest is small tensor algebra.
+The IoU matrices come from the HIP kernel (box_ops.boxes_iou_3d); the rest is small tensor algebra.  Batches of several
+examples (rpn/loss_3d.py:178-250, box_head_3d/loss.py:66-236 over a list of images) match every (example, class group)
+segment in ONE launch set (box_ops.match_segments: IoU + Matcher + box_encode fused, no [M, N] matrix) and sample each
+segment with the same sampler object.
 """
 import math
 from bisect import bisect_right
@@ -96,6 +99,33 @@ def smooth_l1_loss(input, target, anchor_boxes, beta=1. / 9, size_average=True, 
     return loss.mean() if size_average else loss.sum()
 
 
+def segment_offsets(gt_lists):
+    """[GT boxes [m_s, 7] of segment s] -> (concatenated GT [M, 7], host offsets [S + 1] of match_segments)."""
+    offs = [0]
+    for g in gt_lists:
+        offs.append(offs[-1] + int(g.shape[0]))
+    return torch.cat(list(gt_lists), 0) if gt_lists else None, offs
+
+
+def sample_segments(sampler, labels, seg, n_segments):
+    """The per-image sampling of the reference on a batch: `sampler` (one object) is called once per segment on that
+    segment's labels (rows in their order in `labels`).  -> (pos, neg) lists over segments of global row indices."""
+    order = torch.argsort(seg, stable=True)
+    counts = torch.bincount(seg, minlength=n_segments).tolist()                 # one host synchronisation
+    pos, neg, o = [], [], 0
+    for c in counts:
+        rows = order[o:o + c]
+        p, n = sampler(labels[rows])
+        pos.append(rows[p])
+        neg.append(rows[n])
+        o += c
+    return pos, neg
+
+
+def _check_aug(flag, aug):
+    assert box_ops._FLAG_RULES[flag](aug), (flag, aug)
+
+
 class RPNLoss(object):
     def __init__(self, cfg):
         rpn = cfg.MODEL.RPN
@@ -128,6 +158,54 @@ class RPNLoss(object):
         return obj_loss, box_loss
 
 
+    @torch.no_grad()
+    def prepare_targets_segments(self, anchors, pred_seg, gt_lists):
+        """prepare_targets of every segment in one launch set: anchors [n, 7] (a row per prediction), pred_seg int32 [n]
+        = segment of each row, gt_lists[s] = GT boxes of segment s.  -> labels fp32 [n], regression targets [n, 7]."""
+        _check_aug("rpn_label_generation", self.aug)
+        gt, offs = segment_offsets(gt_lists)
+        if gt is None:
+            gt = anchors.new_zeros((0, 7))
+        m = self.matcher
+        matched, reg = box_ops.match_segments(gt.float().contiguous(), offs, anchors.contiguous(), pred_seg, self.aug,
+                                              criterion=2, yaw_threshold=m.yaw_threshold, high=m.high_threshold,
+                                              low=m.low_threshold, allow_low_quality=m.allow_low_quality_matches)
+        labels = (matched >= 0).to(torch.float32)
+        labels[matched == Matcher.BETWEEN_THRESHOLDS] = -1
+        return labels, reg
+
+    def batch(self, anchors, objectness, box_regression, example, gt_groups):
+        """Losses of a batch (loss_3d.py:178-250 over the images): anchors [n, 7] of all examples, objectness [n, G],
+        box_regression [n, 7 G], example int64 [n]; gt_groups[b][g] = GT boxes of example b for class group g (G = 1:
+        no grouping).  ONE match_segments launch set over all (example, group) segments -- the anchors once per group --,
+        the sampler once per segment (BATCH_SIZE_PER_IMAGE each); per group: BCE over the group's sampled anchors of the
+        batch, box loss / their number.  -> list over groups of (objectness loss, box loss)."""
+        n, G = objectness.shape
+        B = len(gt_groups)
+        dev = anchors.device
+        if G == 1:
+            preds, seg = anchors, example
+            obj_flat, reg_flat = objectness.reshape(-1), box_regression
+        else:                                          # row g * n + i = anchor i for group g
+            preds = anchors.repeat(G, 1)
+            seg = (example.view(1, -1) * G + torch.arange(G, device=dev).view(-1, 1)).reshape(-1)
+            obj_flat = objectness.t().reshape(-1)
+            reg_flat = box_regression.view(n, G, 7).transpose(0, 1).reshape(G * n, 7)
+        seg = seg.to(torch.int32).contiguous()
+        labels, reg_targets = self.prepare_targets_segments(preds, seg, [gt_groups[b][g] for b in range(B) for g in range(G)])
+        pos, neg = sample_segments(self.sampler, labels, seg.long(), B * G)
+        out = []
+        for g in range(G):
+            p = torch.cat([pos[b * G + g] for b in range(B)])
+            q = torch.cat([neg[b * G + g] for b in range(B)])
+            sampled = torch.cat([p, q], 0)
+            box_loss = smooth_l1_loss(reg_flat[p], reg_targets[p], preds[p], beta=1.0 / 9, size_average=False,
+                                      yaw_loss_mode=self.yaw_loss_mode) / max(sampled.numel(), 1)
+            obj_loss = F.binary_cross_entropy_with_logits(obj_flat[sampled], labels[sampled])
+            out.append((obj_loss, box_loss))
+        return out
+
+
 class ROILoss(object):
     def __init__(self, cfg):
         rh = cfg.MODEL.ROI_HEADS
@@ -154,6 +232,31 @@ class ROILoss(object):
         pos, neg = self.sampler(labels)
         keep = torch.sort(torch.cat([pos, neg]))[0]             # nonzero(pos | neg) order
         return proposals[keep], labels[keep], reg[keep]
+
+    @torch.no_grad()
+    def subsample_segments(self, proposals, seg, gt_lists, label_lists):
+        """subsample of every segment (loss.py:66-160 per image) with ONE match_segments launch set: proposals [K, 7],
+        seg int64 [K] = segment of each row, gt_lists[s] / label_lists[s] = GT boxes / labels of segment s.
+        -> (sampled proposals, labels int64, regression targets, segment int64) ordered by segment, then by row."""
+        _check_aug("roi_label_generation", self.aug)
+        S = len(gt_lists)
+        gt, offs = segment_offsets(gt_lists)
+        if gt is None:
+            gt = proposals.new_zeros((0, 7))
+        m = self.matcher
+        matched, reg = box_ops.match_segments(gt.float().contiguous(), offs, proposals.contiguous(),
+                                              seg.to(torch.int32).contiguous(), self.aug, criterion=-1, yaw_threshold=4.0,
+                                              high=m.high_threshold, low=m.low_threshold, allow_low_quality=False,
+                                              encode_weights=self.weights)
+        if gt.shape[0]:
+            labels = torch.cat(list(label_lists)).to(torch.int64)[matched.clamp(min=0).long()]
+        else:
+            labels = torch.zeros(proposals.shape[0], dtype=torch.int64, device=proposals.device)
+        labels[matched == Matcher.BELOW_LOW_THRESHOLD] = 0
+        labels[matched == Matcher.BETWEEN_THRESHOLDS] = -1
+        pos, neg = sample_segments(self.sampler, labels, seg, S)
+        keep = torch.cat([torch.sort(torch.cat([p, q]))[0] for p, q in zip(pos, neg)])   # nonzero(pos | neg) per image
+        return proposals[keep], labels[keep], reg[keep], seg[keep]
 
     def __call__(self, class_logits, box_regression, proposals, labels, reg_targets):
         cls_loss = F.cross_entropy(class_logits, labels)

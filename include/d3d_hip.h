@@ -415,6 +415,21 @@ int d3d_rotate_iou_eval(const float *boxes, int N, const float *query, int K, in
  * aug_host = {target_Y, target_Z, anchor_Y, anchor_Z}.                                       */
 int d3d_boxes_iou_3d(const float *targets, int M, const float *anchors, int N,
                      const float *aug_host, int criterion, int only_xy, float *out, void *stream);
+/* Label assignment of several segments in one launch set (rpn/loss_3d.py:178-213 and box_head_3d/loss.py:66-160 per
+ * image, matcher.py:13-177, box_coder_3d.py:31-36): GT [M,7] grouped by segment (rows [gt_off_host[s],
+ * gt_off_host[s+1]) of segment s; gt_off_host[0] = 0, M = gt_off_host[S], S <= 256); predictions pred [N,7] in any order,
+ * pred_seg device int32 [N] = segment of each (out of range: no GT).  Every prediction is matched against its own
+ * segment's GT only: quality = boxes_iou_3d (aug_host, criterion; the values of d3d_boxes_iou_3d) x, unless
+ * yaw_threshold > 1.58, (|limit_period(yaw_gt - yaw_pred, 0.5, pi)| < yaw_threshold); Matcher(high, low,
+ * allow_low_quality).  matched int32 [N] = GLOBAL GT row, -1 below low (and every row of a segment without GT), -2
+ * between; reg_targets [N,7] (may be NULL) = box_encode(gt[max(matched, first row of the segment)], pred) x
+ * encode_weights_host (NULL: ones), zeros for a segment without GT.  No host synchronisation;
+ * scratch >= d3d_match_segments_scratch_bytes(M, N).                                                                  */
+int d3d_match_segments(const float *gt, const int *gt_off_host, int S, const float *pred, int N, const int32_t *pred_seg,
+                       const float *aug_host, int criterion, float yaw_threshold, float high, float low,
+                       int allow_low_quality, const float *encode_weights_host, int32_t *matched, float *reg_targets,
+                       void *scratch, size_t scratch_bytes, void *stream);
+size_t d3d_match_segments_scratch_bytes(int M, int N);
 /* a15/a18. rotate_nms_3d_cc (second/core/non_max_suppression/nms_cpu.py:32-44) + spconv's
  * rotate_non_max_suppression_cpu: boxes [n,7] yx_zb ALREADY sorted by descending score
  * (the callers top-k first, box_torch_ops.py:495-499).  keep int32 [n] receives positions in

@@ -2,7 +2,7 @@
 RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + engine/trainer_sparse3d.py).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000]
+        scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--scenes", type=int, default=0, help="synthetic scenes to write (default: 2 per rank)")
     ap.add_argument("--points", type=int, default=500_000)
     ap.add_argument("--log-every", type=int, default=0)
+    ap.add_argument("--ims-per-gpu", type=int, default=1,
+                    help="buildings per rank and step (IMS_PER_BATCH = ranks x this; the LR schedule counts with it)")
     ap.add_argument("--verify", action="store_true",
                     help="after the steps: compare the weights of all ranks and gather the detections of every scene")
     args = ap.parse_args()
@@ -56,7 +58,7 @@ def main():
     if args.data:
         files = sorted(os.path.join(args.data, f) for f in os.listdir(args.data) if f.endswith((".pth", ".npz")))
     else:
-        n = args.scenes or 2 * WORLD
+        n = args.scenes or 2 * WORLD * max(1, args.ims_per_gpu)
         tmp = os.path.join(tempfile.gettempdir(), f"d3d_train_scenes_{os.environ.get('MASTER_PORT', '0')}")
         files = [os.path.join(tmp, f"scene_{i}.npz") for i in range(n)]
         if rank == 0:
@@ -67,7 +69,8 @@ def main():
         dist.barrier()
     torch.manual_seed(0)                  # same initial weights on every rank (DDP also broadcasts rank 0's)
     model = build_detection_model(cfg).to(dev)
-    out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every)
+    out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
+                       ims_per_gpu=args.ims_per_gpu)
     if args.verify:
         # (1) the averaged-gradient steps leave every rank with the same weights (fingerprint: sum and sum of squares of
         # every parameter in fp64); (2) the sharded inference loop returns every scene's detections on rank 0
