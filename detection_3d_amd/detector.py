@@ -14,6 +14,7 @@ and the RoI losses / post-processing once per class group (SeperateClassifier).
 """
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -285,6 +286,10 @@ class PaddedProposals(object):
 
 _DEFER_PROPOSALS = os.environ.get("D3D_DEFER_PROPOSALS", "1") != "0"
 
+# what RPNModule.forward returns (PaddedProposals aside): proposals [n, 7], scores [n], class group of every row (None:
+# no grouping), example of every row (None: one example), loss dict (None: inference)
+RPNOutput = namedtuple("RPNOutput", "proposals scores sep_id example_id losses", defaults=(None, None, None))
+
 
 class RPNModule(nn.Module):
     """modeling/rpn/rpn_sparse3d.py:137-231 + rpn/inference_3d.py:82-163 (test path)."""
@@ -362,99 +367,65 @@ class RPNModule(nn.Module):
         return out
 
     def forward(self, features_sparse, targets=None, n_examples=1, defer=False):
-        """eval: (proposals, objectness) -- or, with defer, a PaddedProposals when the path allows it.
-        train: (proposals incl. GT boxes, objectness, loss dict)
-        (rpn_sparse3d.py:233-270, rpn/inference_3d.py:53-80,180-199).  n_examples > 1 (inference): returns
-        (proposals, objectness, sep_id or None, example_id) with the rows ordered by example (then class group)."""
+        """-> RPNOutput (rpn_sparse3d.py:233-270, rpn/inference_3d.py:53-80,180-199); plain single-example inference
+        with `defer` -> a PaddedProposals when the path allows it.  Training (targets: list of n_examples dicts), class
+        groups and several examples go through `_forward_segments`."""
         objectness, box_regression = self.head([f.features for f in features_sparse])
         with torch.no_grad():
             anchors = self.anchor_generator.forward_cat(features_sparse)
         mark("rpn head + anchors")
         assert objectness.shape[0] == box_regression.shape[0] == anchors.shape[0]
         grouped = self.sep.need_seperate and self.head.seperate_rpn > 1
-        if n_examples > 1:
-            if self.training:
-                return self._forward_train_batch(anchors, objectness, box_regression, features_sparse, targets,
-                                                 n_examples, grouped)
+        if self.training or grouped or n_examples > 1:
+            return self._forward_segments(anchors, objectness, box_regression, features_sparse, targets, n_examples,
+                                          grouped)
+        out = self.select_proposals(objectness.detach(), box_regression.detach(), anchors, False,
+                                    defer=defer and _DEFER_PROPOSALS)
+        return out if isinstance(out, PaddedProposals) else RPNOutput(*out)
+
+    def _forward_segments(self, anchors, objectness, box_regression, features_sparse, targets, n_examples, grouped):
+        """Pre / post top-N selection per (example, class group) segment (inference_3d.py:92-163; seperate_rpn_selector,
+        seperate_classifier.py:58-95) in one launch set.  Training: GT boxes appended to each segment's proposals
+        (:73-78), losses of the whole batch (RPNLoss), one pair per class group.  -> RPNOutput with the rows ordered by
+        example, then by class group."""
+        B = int(n_examples)
+        G = objectness.shape[1]
+        dev = anchors.device
+        if B > 1:
             A = self.anchor_generator.num_anchors_per_location()
             example = torch.cat([f.get_spatial_locations()[:, 3].repeat_interleave(A) for f in features_sparse])
-            segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, example,
-                                                  n_examples, False)
-            G = objectness.shape[1]
-            dev = anchors.device
-            sep_id = torch.cat([torch.full((p.shape[0],), i % G, dtype=torch.int64, device=dev) for i, (p, _) in enumerate(segs)])
-            ex_id = torch.cat([torch.full((p.shape[0],), i // G, dtype=torch.int64, device=dev) for i, (p, _) in enumerate(segs)])
-            return (torch.cat([p for p, _ in segs]), torch.cat([sc for _, sc in segs]), sep_id if grouped else None, ex_id)
-        if grouped:
-            return self._forward_grouped(anchors, objectness, box_regression, targets)
-        out = self.select_proposals(objectness.detach(), box_regression.detach(), anchors, self.training,
-                                    defer=defer and not self.training and _DEFER_PROPOSALS)
-        if not self.training:
-            return out
-        proposals, scores = out
-        gt = targets["bbox3d"]
-        if self.add_gt_proposals and gt.shape[0]:
-            proposals = torch.cat([proposals, gt], 0)
-            scores = torch.cat([scores, torch.ones(gt.shape[0], device=scores.device)], 0)
-        loss_obj, loss_reg = self.loss_evaluator(anchors, objectness.reshape(-1), box_regression, gt)
-        return proposals, scores, {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg}
-
-    def _forward_train_batch(self, anchors, objectness, box_regression, features_sparse, targets, n_examples, grouped):
-        """Training with several examples (targets: list of B dicts): per-example pre / post top-N selection
-        (inference_3d.py:92-163) as segments of one launch set, GT boxes appended to each example's proposals (:73-78),
-        losses of the whole batch (RPNLoss.batch).  -> (proposals, scores, sep_id or None, example_id, loss dict) with
-        the rows ordered by example, then by class group."""
-        B = int(n_examples)
-        A = self.anchor_generator.num_anchors_per_location()
-        example = torch.cat([f.get_spatial_locations()[:, 3].repeat_interleave(A) for f in features_sparse])
-        segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, example, B, True)
-        G = objectness.shape[1]
-        tg = [self.sep.group_targets(t) if grouped else [t] for t in targets]
-        assert all(len(t) == G for t in tg), (G, [len(t) for t in tg])
-        dev = anchors.device
+        else:
+            example = None
+        segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, example, B,
+                                              self.training)
+        if self.training:
+            tg = [self.sep.group_targets(t) if grouped else [t] for t in targets]
+            assert all(len(t) == G for t in tg), (G, [len(t) for t in tg])
         props, scores, sep_id, ex_id = [], [], [], []
         for s_, (p, sc) in enumerate(segs):
-            gt = tg[s_ // G][s_ % G]["bbox3d"]
-            if self.add_gt_proposals and gt.shape[0]:
-                p = torch.cat([p, gt], 0)
-                sc = torch.cat([sc, torch.ones(gt.shape[0], device=sc.device)], 0)
+            if self.training:
+                gt = tg[s_ // G][s_ % G]["bbox3d"]
+                if self.add_gt_proposals and gt.shape[0]:
+                    p = torch.cat([p, gt], 0)
+                    sc = torch.cat([sc, torch.ones(gt.shape[0], device=sc.device)], 0)
             props.append(p)
             scores.append(sc)
             sep_id.append(torch.full((p.shape[0],), s_ % G, dtype=torch.int64, device=dev))
             ex_id.append(torch.full((p.shape[0],), s_ // G, dtype=torch.int64, device=dev))
-        parts = self.loss_evaluator.batch(anchors, objectness, box_regression, example,
-                                          [[t["bbox3d"] for t in tb] for tb in tg])
-        if grouped:
-            losses = {}
-            for gi, (lo, lr) in enumerate(parts):
-                losses[f"loss_objectness_{gi}"], losses[f"loss_rpn_box_reg_{gi}"] = lo, lr
-        else:
-            losses = {"loss_objectness": parts[0][0], "loss_rpn_box_reg": parts[0][1]}
-        return (torch.cat(props), torch.cat(scores), torch.cat(sep_id) if grouped else None, torch.cat(ex_id), losses)
-
-    def _forward_grouped(self, anchors, objectness, box_regression, targets):
-        """seperate_rpn_selector / seperate_rpn_loss_evaluator (seperate_classifier.py:58-95): one proposal set
-        and one loss pair per class group; proposals carry their group id (`sep_id`)."""
-        props, scores, sep_ids, losses = [], [], [], {}
-        tg = self.sep.group_targets(targets) if self.training else [None] * self.sep.group_num
-        # the groups' top-k / decode / NMS as segments of ONE launch set (seperate_rpn_selector loops the selector)
-        segs = self.select_proposals_segments(objectness.detach(), box_regression.detach(), anchors, None, 1,
-                                              self.training)
-        for gi in range(self.sep.group_num):
-            obj_g, reg_g = objectness[:, gi], box_regression[:, 7 * gi:7 * gi + 7]
-            p, sc = segs[gi]
-            if self.training:
-                gt = tg[gi]["bbox3d"]
-                if self.add_gt_proposals and gt.shape[0]:
-                    p = torch.cat([p, gt], 0)
-                    sc = torch.cat([sc, torch.ones(gt.shape[0], device=sc.device)], 0)
-                lo, lr = self.loss_evaluator(anchors, obj_g, reg_g, gt)
-                losses[f"loss_objectness_{gi}"], losses[f"loss_rpn_box_reg_{gi}"] = lo, lr
-            props.append(p)
-            scores.append(sc)
-            sep_ids.append(torch.full((p.shape[0],), gi, dtype=torch.int64, device=p.device))
-        out = (torch.cat(props), torch.cat(scores), torch.cat(sep_ids))
-        return out + (losses,) if self.training else out
+        losses = None
+        if self.training:
+            if example is None:
+                example = torch.zeros(anchors.shape[0], dtype=torch.int64, device=dev)
+            parts = self.loss_evaluator(anchors, objectness, box_regression, example,
+                                        [[t["bbox3d"] for t in tb] for tb in tg])
+            if grouped:
+                losses = {}
+                for gi, (lo, lr) in enumerate(parts):
+                    losses[f"loss_objectness_{gi}"], losses[f"loss_rpn_box_reg_{gi}"] = lo, lr
+            else:
+                losses = {"loss_objectness": parts[0][0], "loss_rpn_box_reg": parts[0][1]}
+        return RPNOutput(torch.cat(props), torch.cat(scores), torch.cat(sep_id) if grouped else None,
+                         torch.cat(ex_id) if B > 1 else None, losses)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -897,30 +868,6 @@ class ROIBoxHead3D(nn.Module):
         self.loss_evaluator = T.ROILoss(cfg)
         self.sep = SeperateClassifier(cfg.MODEL.SEPARATE_CLASSES_ID, len(cfg.INPUT.CLASSES))
 
-    def _forward_grouped(self, roi_features, proposals, sep_id, targets):
-        """seperate_subsample / roi_cross_entropy_seperated / roi_box_loss_seperated / post_processor
-        (seperate_classifier.py:111-176,299-321)."""
-        sep = self.sep
-        if not self.training:
-            return self._forward_eval_segments(roi_features, proposals, sep_id, None, 1)[0]
-        tg = sep.group_targets(targets)
-        ps, ls, rs, ids = [], [], [], []
-        for gi in range(sep.group_num):
-            p, l, r = self.loss_evaluator.subsample(proposals[sep_id == gi], tg[gi]["bbox3d"], tg[gi]["labels"])
-            ps.append(p); ls.append(l); rs.append(r)
-            ids.append(torch.full((p.shape[0],), gi, dtype=torch.int64, device=p.device))
-        proposals, labels, reg_targets, sep_id = torch.cat(ps), torch.cat(ls), torch.cat(rs), torch.cat(ids)
-        x = self.feature_extractor(roi_features, proposals)
-        logits, reg = self.predictor(x)
-        assert logits.shape[1] == sep.total_classes
-        ids_g = [torch.nonzero(sep_id == gi).view(-1) for gi in range(sep.group_num)]
-        out = {}
-        for gi, (lg, rg) in enumerate(zip(sep.seperate_pred_logits(logits, ids_g), sep.seperate_pred_box(reg, ids_g))):
-            idx = ids_g[gi]
-            c, b = self.loss_evaluator(lg, rg, proposals[idx], labels[idx], reg_targets[idx])
-            out[f"loss_classifier_roi_{gi}"], out[f"loss_box_reg_roi_{gi}"] = c, b
-        return out
-
     def _forward_eval_segments(self, roi_features, proposals, sep_id, example_id, n_examples):
         """Inference for rows ordered by (example, class group): ONE box-head pass over all RoIs (as the reference:
         the head's BatchNorm3d sees every RoI of the batch), one post-processing launch set for all segments.
@@ -961,16 +908,18 @@ class ROIBoxHead3D(nn.Module):
         return self.post_processor(logits, reg, proposals), proposals, scores
 
     def _forward_train_segments(self, roi_features, proposals, sep_id, example_id, targets, n_examples):
-        """Training with several examples (box_head.py:96-149 + loss.py:66-236 over the images; per class group for
-        3G6c, seperate_classifier.py:111-176): ONE match_segments launch set labels every (example, group) segment, the
+        """Training (box_head.py:96-149 + loss.py:66-236 over the images; per class group for 3G6c,
+        seperate_classifier.py:111-176): ONE match_segments launch set labels every (example, group) segment, the
         sampler runs per segment, one box-head pass over all sampled RoIs (pooled with their example index; BatchNorm3d
-        sees the whole batch), losses per group over the batch."""
+        sees the whole batch), losses per group over the batch.  example_id None: one example."""
         sep = self.sep
         grouped = sep.need_seperate and sep_id is not None
         G = sep.group_num if grouped else 1
         B = int(n_examples)
         tg = [sep.group_targets(t) if grouped else [t] for t in targets]
-        seg = example_id * G + (sep_id if grouped else 0)
+        ex = example_id if example_id is not None else torch.zeros(proposals.shape[0], dtype=torch.int64,
+                                                                   device=proposals.device)
+        seg = ex * G + (sep_id if grouped else 0)
         proposals, labels, reg_targets, seg_k = self.loss_evaluator.subsample_segments(
             proposals, seg, [tg[b][g]["bbox3d"] for b in range(B) for g in range(G)],
             [tg[b][g]["labels"] for b in range(B) for g in range(G)])
@@ -990,21 +939,16 @@ class ROIBoxHead3D(nn.Module):
         return out
 
     def forward(self, roi_features, proposals, targets=None, sep_id=None, example_id=None, n_examples=1):
-        if n_examples > 1:
-            if self.training:
-                return self._forward_train_segments(roi_features, proposals, sep_id, example_id, targets, n_examples)
-            return self._forward_eval_segments(roi_features, proposals, sep_id, example_id, n_examples)
-        if sep_id is not None:
-            return self._forward_grouped(roi_features, proposals, sep_id, targets)
-        if self.training:                                                        # box_head.py:96-149
-            proposals, labels, reg_targets = self.loss_evaluator.subsample(proposals, targets["bbox3d"],
-                                                                           targets["labels"])
+        """training (targets: list of n_examples dicts) -> loss dict; inference -> detections dict, a list of them for
+        n_examples > 1"""
+        if self.training:
+            return self._forward_train_segments(roi_features, proposals, sep_id, example_id, targets, n_examples)
+        if n_examples > 1 or sep_id is not None:
+            results = self._forward_eval_segments(roi_features, proposals, sep_id, example_id, n_examples)
+            return results if n_examples > 1 else results[0]
         x = self.feature_extractor(roi_features, proposals)
         logits, reg = self.predictor(x)
-        if not self.training:
-            return self.post_processor(logits, reg, proposals)
-        cls_loss, box_loss = self.loss_evaluator(logits, reg, proposals, labels, reg_targets)
-        return {"loss_classifier_roi": cls_loss, "loss_box_reg_roi": box_loss}
+        return self.post_processor(logits, reg, proposals)
 
 
 class _RoiHeads(nn.Module):
@@ -1031,28 +975,19 @@ class SparseRCNN(nn.Module):
             if targets is None:
                 raise ValueError("In training mode, targets should be passed")
             B = self.batch_size_of(points)
-            if isinstance(targets, (list, tuple)):
-                if len(targets) != B:
-                    raise ValueError(f"{len(targets)} target dicts for a batch of {B} examples")
-                if B == 1:
-                    targets = targets[0]
-            elif B > 1:
-                raise ValueError(f"a batch of {B} examples needs a list of {B} target dicts")
+            if not isinstance(targets, (list, tuple)):
+                if B > 1:
+                    raise ValueError(f"a batch of {B} examples needs a list of {B} target dicts")
+                targets = [targets]
+            if len(targets) != B:
+                raise ValueError(f"{len(targets)} target dicts for a batch of {B} examples")
             rpn_features, roi_features = self.backbone(points[:2])
-            if B > 1:
-                proposals, _, sep_id, example_id, rpn_losses = self.rpn(rpn_features, targets, n_examples=B)
-                proposals = proposals.clone()
-                proposals[:, 3:6] = torch.clamp(proposals[:, 3:6], min=0.001)
-                losses = dict(self.roi_heads.box(roi_features, proposals, targets, sep_id=sep_id, example_id=example_id,
-                                                 n_examples=B))
-                losses.update(rpn_losses)
-                return losses
-            out = self.rpn(rpn_features, targets)
-            proposals, rpn_losses = out[0].clone(), out[-1]
-            sep_id = out[2] if len(out) == 4 else None
+            out = self.rpn(rpn_features, targets, n_examples=B)
+            proposals = out.proposals.clone()
             proposals[:, 3:6] = torch.clamp(proposals[:, 3:6], min=0.001)
-            losses = dict(self.roi_heads.box(roi_features, proposals, targets, sep_id=sep_id))
-            losses.update(rpn_losses)
+            losses = dict(self.roi_heads.box(roi_features, proposals, targets, sep_id=out.sep_id,
+                                             example_id=out.example_id, n_examples=B))
+            losses.update(out.losses)
             return losses
         with torch.no_grad():
             return self._forward_eval(points, return_intermediates)
@@ -1097,12 +1032,7 @@ class SparseRCNN(nn.Module):
                                 "proposals": proposals, "objectness": objectness, "example_id": None,
                                 "sep_id": None}
             return result
-        proposals, objectness = out[0].clone(), out[1]
-        example_id = None
-        if n_examples > 1:
-            sep_id, example_id = out[2], out[3]
-        else:
-            sep_id = out[2] if len(out) == 3 else None
+        proposals, objectness, sep_id, example_id = out.proposals.clone(), out.scores, out.sep_id, out.example_id
         proposals[:, 3:6] = torch.clamp(proposals[:, 3:6], min=0.001)           # BoxList3D.clamp_size
         result = self.roi_heads.box(roi_features, proposals, sep_id=sep_id, example_id=example_id, n_examples=n_examples)
         mark("detections")

@@ -8,10 +8,11 @@ optimizer / LR schedule surface, and the data-parallel wrapper.
     RPNLoss                            modeling/rpn/loss_3d.py:69-250
     ROILoss                            modeling/roi_heads/box_head_3d/loss.py:20-236
     make_optimizer / WarmupMultiStepLR maskrcnn_benchmark/solver/{build,lr_scheduler}.py
-The IoU matrices come from the HIP kernel (box_ops.boxes_iou_3d); the rest is small tensor algebra.  Batches of several
-examples (rpn/loss_3d.py:178-250, box_head_3d/loss.py:66-236 over a list of images) match every (example, class group)
-segment in ONE launch set (box_ops.match_segments: IoU + Matcher + box_encode fused, no [M, N] matrix) and sample each
-segment with the same sampler object.
+Every training batch, one example included, is labelled per (example, class group) segment in ONE launch set
+(box_ops.match_segments: IoU + Matcher + box_encode fused, no [M, N] matrix; rpn/loss_3d.py:178-250,
+box_head_3d/loss.py:66-236 over a list of images), and every segment is sampled with the same sampler object.  Matcher
+and box_encode are the tensor forms of what that kernel computes: Matcher carries the thresholds passed to it, and both
+are the reference the kernel is tested against.
 """
 import math
 from bisect import bisect_right
@@ -136,32 +137,10 @@ class RPNLoss(object):
         self.yaw_loss_mode = cfg.MODEL.LOSS.YAW_MODE
 
     @torch.no_grad()
-    def prepare_targets(self, anchors, gt_boxes):
-        """-> labels fp32 [N] (1 pos, 0 neg, -1 ignored), regression targets [N,7]  (loss_3d.py:178-213)."""
-        if gt_boxes.shape[0] == 0:
-            return torch.zeros(anchors.shape[0], device=anchors.device), torch.zeros_like(anchors)
-        q = box_ops.boxes_iou_3d(gt_boxes, anchors, self.aug, criterion=2, flag='rpn_label_generation')
-        yaw_diff = torch.abs(box_ops.limit_period(gt_boxes[:, -1].view(-1, 1) - anchors[:, -1].view(1, -1), 0.5, math.pi))
-        matched = self.matcher(q, yaw_diff=yaw_diff)
-        labels = (matched >= 0).to(torch.float32)
-        labels[matched == Matcher.BETWEEN_THRESHOLDS] = -1
-        reg = box_encode(gt_boxes[matched.clamp(min=0)], anchors)
-        return labels, reg
-
-    def __call__(self, anchors, objectness, box_regression, gt_boxes):
-        labels, reg_targets = self.prepare_targets(anchors, gt_boxes)
-        pos, neg = self.sampler(labels)
-        sampled = torch.cat([pos, neg], dim=0)
-        box_loss = smooth_l1_loss(box_regression[pos], reg_targets[pos], anchors[pos], beta=1.0 / 9,
-                                  size_average=False, yaw_loss_mode=self.yaw_loss_mode) / max(sampled.numel(), 1)
-        obj_loss = F.binary_cross_entropy_with_logits(objectness[sampled], labels[sampled])
-        return obj_loss, box_loss
-
-
-    @torch.no_grad()
     def prepare_targets_segments(self, anchors, pred_seg, gt_lists):
-        """prepare_targets of every segment in one launch set: anchors [n, 7] (a row per prediction), pred_seg int32 [n]
-        = segment of each row, gt_lists[s] = GT boxes of segment s.  -> labels fp32 [n], regression targets [n, 7]."""
+        """RPNLossComputation.prepare_targets (loss_3d.py:88-109,178-213) of every segment in one launch set: anchors
+        [n, 7] (a row per prediction), pred_seg int32 [n] = segment of each row, gt_lists[s] = GT boxes of segment s.
+        -> labels fp32 [n] (1 pos, 0 neg, -1 ignored), regression targets [n, 7]."""
         _check_aug("rpn_label_generation", self.aug)
         gt, offs = segment_offsets(gt_lists)
         if gt is None:
@@ -174,7 +153,7 @@ class RPNLoss(object):
         labels[matched == Matcher.BETWEEN_THRESHOLDS] = -1
         return labels, reg
 
-    def batch(self, anchors, objectness, box_regression, example, gt_groups):
+    def __call__(self, anchors, objectness, box_regression, example, gt_groups):
         """Losses of a batch (loss_3d.py:178-250 over the images): anchors [n, 7] of all examples, objectness [n, G],
         box_regression [n, 7 G], example int64 [n]; gt_groups[b][g] = GT boxes of example b for class group g (G = 1:
         no grouping).  ONE match_segments launch set over all (example, group) segments -- the anchors once per group --,
@@ -217,26 +196,10 @@ class ROILoss(object):
         self.yaw_loss_mode = cfg.MODEL.LOSS.YAW_MODE
 
     @torch.no_grad()
-    def subsample(self, proposals, gt_boxes, gt_labels):
-        """-> (sampled proposals [S,7], labels int64 [S], regression targets [S,7])  (loss.py:66-160)."""
-        if gt_boxes.shape[0] == 0:
-            labels = torch.zeros(proposals.shape[0], dtype=torch.int64, device=proposals.device)
-            reg = torch.zeros_like(proposals)
-        else:
-            q = box_ops.boxes_iou_3d(gt_boxes, proposals, self.aug, criterion=-1, flag='roi_label_generation')
-            matched = self.matcher(q)
-            labels = gt_labels[matched.clamp(min=0)].to(torch.int64)
-            labels[matched == Matcher.BELOW_LOW_THRESHOLD] = 0
-            labels[matched == Matcher.BETWEEN_THRESHOLDS] = -1
-            reg = box_encode(gt_boxes[matched.clamp(min=0)], proposals, self.weights)
-        pos, neg = self.sampler(labels)
-        keep = torch.sort(torch.cat([pos, neg]))[0]             # nonzero(pos | neg) order
-        return proposals[keep], labels[keep], reg[keep]
-
-    @torch.no_grad()
     def subsample_segments(self, proposals, seg, gt_lists, label_lists):
-        """subsample of every segment (loss.py:66-160 per image) with ONE match_segments launch set: proposals [K, 7],
-        seg int64 [K] = segment of each row, gt_lists[s] / label_lists[s] = GT boxes / labels of segment s.
+        """FastRCNNLossComputation.subsample of every segment (loss.py:66-160 per image) with ONE match_segments launch
+        set: proposals [K, 7], seg int64 [K] = segment of each row, gt_lists[s] / label_lists[s] = GT boxes / labels of
+        segment s.
         -> (sampled proposals, labels int64, regression targets, segment int64) ordered by segment, then by row."""
         _check_aug("roi_label_generation", self.aug)
         S = len(gt_lists)

@@ -7,7 +7,7 @@ Setup (identical in every mode): voxelise + collate both buildings, backbone, RP
 per example, GT boxes added.  Then `reps` times:
     batch: RPNLoss.prepare_targets_segments over all anchors of the batch + the ROI matching of all proposals, each ONE
            d3d_match_segments launch set (k_match_pass1 / k_match_pass2)
-    loop:  the single-example path once per example: boxes_iou_3d (k_iou_matrix) + Matcher + box_encode, RPN and ROI
+    loop:  the same calls once per example (one segment each): one d3d_match_segments launch set per example and stage
     none:  nothing (the setup's kernels, to subtract)
 Prints one JSON line (host wall time per rep of the phase, with a device synchronisation around it)."""
 import argparse
@@ -66,12 +66,15 @@ def main():
                                high=m.high_threshold, low=m.low_threshold, encode_weights=roi_l.weights)
 
     def loop():
+        m = roi_l.matcher
         for b in range(2):
             rows = example == b
-            rpn_l.prepare_targets(anchors[rows], gts[b])
-            q = box_ops.boxes_iou_3d(gts[b], props[b], roi_l.aug, criterion=-1, flag='roi_label_generation')
-            matched = roi_l.matcher(q)
-            T.box_encode(gts[b][matched.clamp(min=0)], props[b], roi_l.weights)
+            a_b = anchors[rows]
+            rpn_l.prepare_targets_segments(a_b, torch.zeros(a_b.shape[0], dtype=torch.int32, device=dev), [gts[b]])
+            box_ops.match_segments(gts[b], [0, gts[b].shape[0]], props[b],
+                                   torch.zeros(props[b].shape[0], dtype=torch.int32, device=dev), roi_l.aug,
+                                   criterion=-1, high=m.high_threshold, low=m.low_threshold,
+                                   encode_weights=roi_l.weights)
 
     fn = {"batch": batch, "loop": loop, "none": lambda: None}[args.mode]
     with torch.no_grad():

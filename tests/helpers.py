@@ -57,3 +57,41 @@ def label_differences_sit_on_thresholds(lab_a, lab_b, q_a, q_b, low, high, eps=1
         if not ok:
             bad.append(int(j))
     return len(diff), bad
+
+
+def rpn_targets_reference(lossf, anchors, gt_boxes):
+    """What d3d_match_segments fuses, in tensor ops, for one RPN segment (rpn/loss_3d.py:88-109,178-213):
+    boxes_iou_3d + Matcher (yaw mask, low-quality rule) + box_encode.  lossf: training.RPNLoss.
+    -> labels fp32 [N] (1 pos, 0 neg, -1 ignored), regression targets [N, 7]."""
+    import math
+    import torch
+    from detection_3d_amd import box_ops, training as T
+    if gt_boxes.shape[0] == 0:
+        return torch.zeros(anchors.shape[0], device=anchors.device), torch.zeros_like(anchors)
+    q = box_ops.boxes_iou_3d(gt_boxes, anchors, lossf.aug, criterion=2, flag='rpn_label_generation')
+    yaw_diff = torch.abs(box_ops.limit_period(gt_boxes[:, -1].view(-1, 1) - anchors[:, -1].view(1, -1), 0.5, math.pi))
+    matched = lossf.matcher(q, yaw_diff=yaw_diff)
+    labels = (matched >= 0).to(torch.float32)
+    labels[matched == T.Matcher.BETWEEN_THRESHOLDS] = -1
+    return labels, T.box_encode(gt_boxes[matched.clamp(min=0)], anchors)
+
+
+def roi_subsample_reference(lossf, proposals, gt_boxes, gt_labels):
+    """The same for one RoI segment plus its sampling (box_head_3d/loss.py:66-160): boxes_iou_3d + Matcher + box_encode,
+    then lossf.sampler.  lossf: training.ROILoss.  -> (sampled proposals, labels int64, regression targets), in row
+    order."""
+    import torch
+    from detection_3d_amd import box_ops, training as T
+    if gt_boxes.shape[0] == 0:
+        labels = torch.zeros(proposals.shape[0], dtype=torch.int64, device=proposals.device)
+        reg = torch.zeros_like(proposals)
+    else:
+        q = box_ops.boxes_iou_3d(gt_boxes, proposals, lossf.aug, criterion=-1, flag='roi_label_generation')
+        matched = lossf.matcher(q)
+        labels = gt_labels[matched.clamp(min=0)].to(torch.int64)
+        labels[matched == T.Matcher.BELOW_LOW_THRESHOLD] = 0
+        labels[matched == T.Matcher.BETWEEN_THRESHOLDS] = -1
+        reg = T.box_encode(gt_boxes[matched.clamp(min=0)], proposals, lossf.weights)
+    pos, neg = lossf.sampler(labels)
+    keep = torch.sort(torch.cat([pos, neg]))[0]
+    return proposals[keep], labels[keep], reg[keep]

@@ -4,9 +4,10 @@ through the detector tail as SEGMENTS of one launch set.
 The reference loops: examples in rpn/inference_3d.py:92-163 and box_head_3d/inference.py:66-99, class groups in
 modeling/seperate_classifier.py:58-95,299-321.  Here every (example, group) is a segment of one top-k / decode / batched NMS /
 post-processing launch set.  Checked: (1) against the batch-aware CPU oracle port stage by stage on the GPU's own input to
-each stage, (2) against this package's single-example / single-group path called once per segment -- to the bit (the
-backbone's BatchNorm and the box head's BatchNorm3d see the whole batch in both the reference and here, so a batch is NOT
-the concatenation of single-example passes before those stages; after them it is)."""
+each stage, (2) against this package's plain single-example inference functions (select_proposals,
+PostProcessor.forward) called once per segment -- to the bit (the backbone's BatchNorm and the box head's BatchNorm3d
+see the whole batch in both the reference and here, so a batch is NOT the concatenation of single-example passes before
+those stages; after them it is)."""
 import numpy as np
 import pytest
 import torch
@@ -114,7 +115,8 @@ def test_batch_backbone_and_tail_vs_oracle(batch3, dev):
 
 
 def test_batch_segments_equal_the_single_example_calls(batch3, dev):
-    """RPN selection and post-processing of the batch == the single-example functions called on each example's rows."""
+    """RPN selection and post-processing of the batch == the plain single-example inference functions called on each
+    example's rows."""
     cfg, model, results, mid, _, _ = batch3
     rpn, box = model.rpn, model.roi_heads.box
     feats = mid["rpn_features"]

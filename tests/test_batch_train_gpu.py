@@ -2,7 +2,7 @@
 images; data3d/data.py:15,23-35 collation).
 
 (1)-(2) d3d_match_segments -- IoU + Matcher + box_encode of every (example, class group) segment in one launch set --
-against this package's single-example path (boxes_iou_3d + Matcher + box_encode) called once per segment;
+against the same steps in tensor ops (boxes_iou_3d + Matcher + box_encode, tests/helpers.py) once per segment;
 (3) the sparse RoI backward with example ids against the dense backward of the B-example map;
 (4) a duplicated batch [A, A] against the single example A; (5) heterogeneous batches train; (6) the driver."""
 import math
@@ -98,8 +98,9 @@ def _check_segment(q, m_ref, m_got, ctx):
 
 
 def _rpn_segments(dev, cfg, anchors, seg, gt_lists):
-    """RPN mode over arbitrary segments, checked per segment against prepare_targets' own pieces"""
+    """RPN mode over arbitrary segments, checked per segment against the tensor-op reference and its own pieces"""
     from detection_3d_amd import box_ops, training as T
+    from tests.helpers import rpn_targets_reference
     lossf = T.RPNLoss(cfg)
     labels, reg = lossf.prepare_targets_segments(anchors, seg.to(torch.int32).contiguous(), gt_lists)
     gt, offs = T.segment_offsets(gt_lists)
@@ -111,7 +112,7 @@ def _rpn_segments(dev, cfg, anchors, seg, gt_lists):
     for s, g in enumerate(gt_lists):
         rows = torch.nonzero(seg == s).view(-1)
         a_s = anchors[rows]
-        lab_ref, reg_ref = lossf.prepare_targets(a_s, g)
+        lab_ref, reg_ref = rpn_targets_reference(lossf, a_s, g)
         assert torch.equal(labels[rows], lab_ref), s
         if g.shape[0] == 0:
             assert (matched[rows] == -1).all() and torch.equal(reg[rows], torch.zeros_like(reg_ref))
@@ -131,7 +132,7 @@ def _rpn_segments(dev, cfg, anchors, seg, gt_lists):
     return labels, n_ties
 
 
-def test_match_segments_rpn_vs_single_example_path(dev):
+def test_match_segments_rpn_vs_tensor_reference(dev):
     from oracle import detector_port as P
     from tests.helpers import label_differences_sit_on_thresholds
     from detection_3d_amd import box_ops
@@ -167,8 +168,9 @@ def model_aug(cfg):
     return {'target_Y': ay[0], 'anchor_Y': ay[1], 'target_Z': az[0], 'anchor_Z': az[1]}
 
 
-def test_match_segments_roi_vs_single_example_path(dev):
+def test_match_segments_roi_vs_tensor_reference(dev):
     from detection_3d_amd import box_ops, training as T
+    from tests.helpers import roi_subsample_reference
     cfg = _cfg()
     _, _, gts, labs = _examples(dev, cfg)
     rng = np.random.RandomState(4)
@@ -218,7 +220,7 @@ def test_match_segments_roi_vs_single_example_path(dev):
     assert (torch.diff(s_k) >= 0).all()
     for s, g in enumerate(gts):
         rows = torch.nonzero(seg == s).view(-1)
-        p1, l1, r1 = lossf.subsample(props[rows], g, labs[s])
+        p1, l1, r1 = roi_subsample_reference(lossf, props[rows], g, labs[s])
         assert torch.equal(p_k[s_k == s], p1) and torch.equal(l_k[s_k == s], l1) and torch.equal(r_k[s_k == s], r1)
 
 

@@ -407,16 +407,19 @@ def test_3g6c_training_step_and_group_labels_at_full_size(full3g, dev):
         assert np.array_equal(tg[g]["bbox3d"].cpu().numpy(), want_tg[g][0])
         assert np.array_equal(tg[g]["labels"].cpu().numpy(), want_tg[g][1])
         gt = tg[g]["bbox3d"]
-        labels, _ = lossf.prepare_targets(anchors, gt)
+        seg = torch.zeros(anchors.shape[0], dtype=torch.int32, device=anchors.device)
+        labels, reg = lossf.prepare_targets_segments(anchors, seg, [gt])
         labels = labels.cpu().numpy()
         want, (q_o, yaw_o, _) = P.rpn_labels(cfg, a_np, want_tg[g][0], return_iou=True)
-        # (a) the device's Matcher on the device's own IoU = the port's Matcher on the same matrix, exactly
+        # (a) the device's Matcher on the device's own IoU = the port's Matcher on the same matrix, exactly; both take the
+        # lowest GT row on a tie, so the regression targets are box_encode of the port's matches to the bit
         q_g = box_ops.boxes_iou_3d(gt, anchors, lossf.aug, criterion=2, flag='rpn_label_generation')
         yaw_g = torch.abs(box_ops.limit_period(gt[:, -1].view(-1, 1) - anchors[:, -1].view(1, -1), 0.5, np.pi))
         m = P.matcher(q_g.cpu().numpy(), rpn.FG_IOU_THRESHOLD, rpn.BG_IOU_THRESHOLD, True, yaw_g.cpu().numpy(), rpn.YAW_THRESHOLD)
         same = (m >= 0).astype(np.float32)
         same[m == -2] = -1
         assert np.array_equal(labels, same), g
+        assert torch.equal(reg, T.box_encode(gt[torch.from_numpy(m).to(gt.device).clamp(min=0)], anchors)), g
         # (b) against the oracle IoU: the matrices agree to 1e-4, and a label differs only where an IoU sits on a threshold
         assert np.array_equal(yaw_g.cpu().numpy(), yaw_o)
         assert np.abs(q_g.cpu().numpy() - q_o).max() <= 1e-4

@@ -30,7 +30,8 @@ def test_label_generation_against_oracle_iou(dev):
         rpn_feats, _ = model.backbone([coords, feats])
         anchors = torch.cat(model.rpn.anchor_generator(rpn_feats), 0)
     lossf = model.rpn.loss_evaluator
-    labels, reg = lossf.prepare_targets(anchors, targets["bbox3d"])
+    seg = torch.zeros(anchors.shape[0], dtype=torch.int32, device=dev)
+    labels, reg = lossf.prepare_targets_segments(anchors, seg, [targets["bbox3d"]])
     q = oracle.boxes_iou_3d(targets["bbox3d"].cpu().numpy(), anchors.cpu().numpy(), lossf.aug, criterion=2)
     yaw = torch.abs(T.box_ops.limit_period(targets["bbox3d"][:, -1].view(-1, 1) - anchors[:, -1].view(1, -1), 0.5, np.pi))
     want = lossf.matcher(torch.from_numpy(q).to(dev), yaw_diff=yaw)
