@@ -39,6 +39,8 @@ _SIGS = {
     "d3d_conv_ws_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_late_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_dw_deterministic": (ctypes.c_int, [ctypes.c_int]),
+    "d3d_conv_dw_thread_mode": (ctypes.c_int, [ctypes.c_int, vp, ctypes.c_size_t]),
+    "d3d_conv_dw_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "d3d_grid_chain_head": (ctypes.c_int, [ctypes.c_int]),
     "d3d_sort_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_sort_pairs": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
@@ -104,6 +106,12 @@ _SIGS = {
                                                                 ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                                 vp, vp]),
+    "d3d_roi_align_rotated_3d_sparse_backward_deterministic": (
+        ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, c_int_p, vp, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                       ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_size_t, vp]),
+    "d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes": (
+        ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                          ctypes.c_int]),
     "d3d_bn_forward": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, vp,
                                       ctypes.c_size_t, vp]),
@@ -252,6 +260,30 @@ def raw_stream(device=None):
 
 def stream_of(device=None):
     return ctypes.c_void_p(raw_stream(device))
+
+
+def deterministic():
+    """torch.use_deterministic_algorithms(True) is in force: the library's ops take their fixed-order forms.  Read at
+    call time, so switching the flag takes effect on the next call."""
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def fills_uninitialized():
+    """torch fills every new tensor (torch.empty, resize_) with NaN / the largest integer on the current stream: in
+    deterministic mode with torch.utils.deterministic.fill_uninitialized_memory (its default)."""
+    return torch.are_deterministic_algorithms_enabled() and torch.utils.deterministic.fill_uninitialized_memory
+
+
+def alert_not_deterministic(op):
+    """What torch's own ops do in deterministic mode when they have no deterministic form: raise (or, with
+    warn_only=True, warn and go on with the nondeterministic form)."""
+    msg = (f"{op} does not have a deterministic implementation, but you set "
+           "'torch.use_deterministic_algorithms(True)'.")
+    if torch.is_deterministic_algorithms_warn_only_enabled():
+        import warnings
+        warnings.warn(msg)
+        return
+    raise RuntimeError(msg)
 
 
 def require_gpu(*tensors):

@@ -232,31 +232,61 @@ static bool g_dw_deterministic = [] {
   const char *e = getenv("D3D_DW_DETERMINISTIC");
   return e && e[0] != '0';
 }();
-static constexpr int kDwDetPartials = 32;   // workgroups (and partial sums) per offset and tile group in deterministic mode
+// d3d_conv_dw_thread_mode: the fixed order for the calling thread only, partials in the caller's buffer
+struct DwThreadMode {
+  bool on = false;
+  void *scratch = nullptr;
+  size_t bytes = 0;
+};
+static thread_local DwThreadMode t_dw;
+static constexpr int kDwDetPartials = 32;   // at most this many workgroups (and partial sums) per offset and tile group
+static constexpr size_t kDwDetBudget = 64u << 20;   // bytes of partials: fewer partials where G x [K, cin, COUT] exceeds it
+// partial sums of the fixed-order dW: a function of the plan's run count and the layer's size only
+static inline int dw_det_partials(int n_runs, size_t n) {
+  const size_t by_budget = std::max<size_t>(1, kDwDetBudget / (n * sizeof(float)));
+  return (int)std::min<size_t>((size_t)std::min(n_runs, kDwDetPartials), by_budget);
+}
 
 template <int CP, int COUT>
 static int launch_dw_t(d3d_meta *m, const Plan &p, const float *in, int cin, const float *d_out, float *dW, hipStream_t s) {
   constexpr int T = (CP / 32) * (COUT / 32);
   constexpr int TPG = T < 16 ? T : 16;
   const int nz = (T + TPG - 1) / TPG;
-  if (g_dw_deterministic) {
+  if (g_dw_deterministic || t_dw.on) {
     // fixed summation order: run r belongs to workgroup r % G, which adds its runs' blocks in order; the G partial
-    // sums are added in order by k_dw_reduce.  Scratch: G x (K, cin, COUT) floats of the feature lane.
-    D3D_REQUIRE(m, "deterministic conv backward needs the metadata (its scratch lane)");
+    // sums are added in order by k_dw_reduce.  Scratch: G x (K, cin, COUT) floats, G <= kDwDetPartials and within
+    // kDwDetBudget bytes (one partial at least) -- the caller's buffer (d3d_conv_dw_thread_mode), else the feature
+    // lane, else a stream-ordered allocation when the lane is too small.
     const int run = kDwBlocksPerWg;
     const int n_runs = (p.n_blk + run - 1) / run;
-    const int G = std::min(n_runs, kDwDetPartials);
     const size_t n = (size_t)p.K * cin * COUT;
-    const size_t mark = m->feat_arena.used;
-    float *part = m->feat_arena.get<float>((size_t)G * n);
-    if (!part) {
-      set_error("deterministic conv backward: %zu bytes of scratch do not fit the feature lane", (size_t)G * n * 4);
-      return D3D_ERR_NOMEM;
+    const int G = dw_det_partials(n_runs, n);
+    const size_t bytes = (size_t)G * n * sizeof(float);
+    auto launch = [&](float *part) {
+      hipLaunchKernelGGL((k_conv_dw<CP, COUT, true>), dim3(G, p.K, nz), dim3(256), 0, s, in, cin, d_out, p.nbrT,
+                         p.n_blk * 32, p.rows, p.blkmask, p.n_blk, run, run, nz, part);
+      hipLaunchKernelGGL(k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, G, n, dW);
+    };
+    if (t_dw.on && t_dw.scratch) {
+      D3D_REQUIRE(t_dw.bytes >= bytes, "deterministic conv backward: scratch %zu < %zu bytes (d3d_conv_dw_scratch_bytes)",
+                  t_dw.bytes, bytes);
+      launch((float *)t_dw.scratch);
+    } else {
+      D3D_REQUIRE(m, "deterministic conv backward needs the metadata (its scratch lane)");
+      D3D_LOCK(m);   // the mark / reset of the feature lane must not interleave with another thread's allocations
+      const size_t mark = m->feat_arena.used;
+      float *part = m->feat_arena.get<float>((size_t)G * n);
+      if (part) {
+        launch(part);
+        m->feat_arena.used = mark;   // stream-ordered scratch
+      } else {                       // the lane is too small: a stream-ordered buffer of its own, the same partials
+        m->feat_arena.used = mark;
+        void *buf = nullptr;
+        D3D_HIP_CHECK(hipMallocAsync(&buf, bytes, s));
+        launch((float *)buf);
+        D3D_HIP_CHECK(hipFreeAsync(buf, s));
+      }
     }
-    hipLaunchKernelGGL((k_conv_dw<CP, COUT, true>), dim3(G, p.K, nz), dim3(256), 0, s, in, cin, d_out, p.nbrT, p.n_blk * 32,
-                       p.rows, p.blkmask, p.n_blk, run, run, nz, part);
-    hipLaunchKernelGGL(k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, G, n, dW);
-    m->feat_arena.used = mark;   // stream-ordered scratch
     D3D_LAUNCH_CHECK();
     return D3D_OK;
   }
@@ -606,6 +636,22 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, co
 int d3d_conv_dw_deterministic(int on) {
   const int was = g_dw_deterministic ? 1 : 0;
   if (on >= 0) g_dw_deterministic = on != 0;
+  return was;
+}
+
+size_t d3d_conv_dw_scratch_bytes(int filter_volume, int cin, int cout) {
+  if (filter_volume <= 0 || cin <= 0 || cout <= 0) return 0;
+  const size_t n = (size_t)filter_volume * cin * cout;
+  return (size_t)dw_det_partials(kDwDetPartials, n) * n * sizeof(float);
+}
+
+int d3d_conv_dw_thread_mode(int on, void *scratch, size_t scratch_bytes) {
+  const int was = t_dw.on ? 1 : 0;
+  if (on < 0) return was;
+  D3D_REQUIRE(on == 0 || (scratch && scratch_bytes > 0), "conv_dw_thread_mode: fixed order needs a scratch buffer");
+  t_dw.on = on != 0;
+  t_dw.scratch = t_dw.on ? scratch : nullptr;
+  t_dw.bytes = t_dw.on ? scratch_bytes : 0;
   return was;
 }
 

@@ -215,6 +215,7 @@ int scan_exclusive_i32(const int32_t *in, int32_t *out, int n, int32_t *total_de
 int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *vals_in,
                    int32_t *vals_out, int n, int bits, Arena &scratch, hipStream_t s, bool descending,
                    const int32_t *n_dev = nullptr);
+size_t sort_scratch_bytes(int n, int bits);   // what sort_pairs_u32 takes from its arena at most
 int finalize_plan(d3d_meta *m, const int32_t *nbr, int n_rows, int K, Plan &plan, hipStream_t s,
                   uint32_t *mask_in);
 int plan_rules(d3d_meta *m, Plan &p, hipStream_t s, long *out);

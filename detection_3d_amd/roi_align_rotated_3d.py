@@ -3,12 +3,16 @@
 SparseConvNetTensor through its hash grid (no dense [1,128,256,256,32] = 1.07 GB map)."""
 import torch
 
-from ._lib import check, floats, ints, lib, ptr, require_gpu, stream_of
+from ._lib import alert_not_deterministic, check, deterministic, floats, ints, lib, ptr, require_gpu, stream_of
 
 
 def roi_align_rotated_3d_backward(grad, rois, spatial_scale, pooled_height, pooled_width, pooled_zsize,
                                   batch_size, channels, height, width, zsize, sampling_ratio):
-    """_C.roi_align_rotated_3d_backward (csrc/ROIAlignRotated3D.h:28-47) -> dense gradient [B,C,H,W,Z]."""
+    """_C.roi_align_rotated_3d_backward (csrc/ROIAlignRotated3D.h:28-47) -> dense gradient [B,C,H,W,Z].
+    fp32 atomics: under torch.use_deterministic_algorithms(True) it raises, as torch's ops without a deterministic form
+    do (the training path pools sparse maps, whose backward has a fixed-order form)."""
+    if deterministic():
+        alert_not_deterministic("roi_align_rotated_3d_backward (dense input)")
     g = grad.detach().to(torch.float32).contiguous()
     r = rois.detach().to(torch.float32).contiguous()
     require_gpu(g, r)
@@ -52,7 +56,8 @@ def roi_align_rotated_3d_forward(input, rois, spatial_scale, pooled_height, pool
 
 class _RoiSparseFn(torch.autograd.Function):
     """forward: d3d_roi_align_rotated_3d_sparse_forward; backward: the dense backward of
-    layers/roi_align_rotated_3d.py:29-51 restricted to the active sites (scatter-add into feature rows)."""
+    layers/roi_align_rotated_3d.py:29-51 restricted to the active sites (scatter-add into feature rows) -- under
+    torch.use_deterministic_algorithms(True) its fixed-order form, which gives the same bits in every run."""
 
     @staticmethod
     def forward(ctx, feats, rois, metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio):
@@ -72,10 +77,29 @@ class _RoiSparseFn(torch.autograd.Function):
         metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio, shape = ctx.args
         g = grad.contiguous()
         d_feats = torch.zeros(shape, dtype=torch.float32, device=g.device)
+        if deterministic():
+            if sampling_ratio > 0:
+                _sparse_backward_deterministic(g, rois, metadata, spatial_size, crop, spatial_scale, ph, pw, pz,
+                                               sampling_ratio, d_feats)
+                return d_feats, None, None, None, None, None, None, None, None, None
+            alert_not_deterministic("roi_align_rotated_3d_sparse backward with adaptive sampling (sampling_ratio <= 0)")
         check(lib().d3d_roi_align_rotated_3d_sparse_backward(
             metadata._h, ints(spatial_size), ptr(g), shape[1], ints(crop), ptr(rois), rois.shape[0],
             float(spatial_scale), ph, pw, pz, int(sampling_ratio), ptr(d_feats), stream_of()))
         return d_feats, None, None, None, None, None, None, None, None, None
+
+
+def _sparse_backward_deterministic(grad, rois, metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio,
+                                   d_feats):
+    """d3d_roi_align_rotated_3d_sparse_backward_deterministic: d_feats [n_active, C] += the gradient, in a fixed order;
+    its scratch comes from torch's allocator (stream-ordered, released when the call returns)."""
+    K, C, n_rows = rois.shape[0], d_feats.shape[1], d_feats.shape[0]
+    nbytes = lib().d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(K, C, ph, pw, pz,
+                                                                                       int(sampling_ratio), n_rows)
+    scratch = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=d_feats.device)
+    check(lib().d3d_roi_align_rotated_3d_sparse_backward_deterministic(
+        metadata._h, ints(spatial_size), ptr(grad), C, ints(crop), ptr(rois), K, float(spatial_scale), ph, pw, pz,
+        int(sampling_ratio), ptr(d_feats), n_rows, ptr(scratch), int(nbytes), stream_of()))
 
 
 def roi_align_rotated_3d_sparse(feat_s3d, rois, spatial_scale, pooled_height, pooled_width, pooled_zsize,

@@ -657,6 +657,30 @@ def _dinput_supported(cin):
     return cin in (32, 64, 128, 256)
 
 
+class _dw_fixed_order:
+    """Context of one conv backward call: under torch.use_deterministic_algorithms(True) the library sums dWeight in a
+    fixed order for this thread (d3d_conv_dw_thread_mode), its partial sums in a buffer from torch's allocator; with
+    the flag off nothing changes."""
+
+    def __init__(self, d_weight, fv, cin, cout):
+        self.on = d_weight is not None and _lib.deterministic()
+        if self.on:
+            nbytes = lib().d3d_conv_dw_scratch_bytes(fv, cin, cout)
+            self.scratch = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=d_weight.device)
+            self.nbytes = int(nbytes)
+
+    def __enter__(self):
+        if self.on:
+            rc = lib().d3d_conv_dw_thread_mode(1, ptr(self.scratch), self.nbytes)
+            if rc < 0:
+                check(rc)
+
+    def __exit__(self, *exc):
+        if self.on:
+            lib().d3d_conv_dw_thread_mode(0, None, 0)
+        return False
+
+
 def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features, d_input_features,
                                     d_output_features, weight, d_weight, d_bias, want_d_input=True):
     """sparseconvnet.h:106-111.  d_input_features is resized and overwritten, d_weight (pre-zeroed by the
@@ -673,8 +697,9 @@ def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
         packed_t = pack_weight_transposed(weight, flip=True)
-    check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t), cout,
-                                       ptr(do), ptr(din), ptr(d_weight), stream_of()))
+    with _dw_fixed_order(d_weight, fv, cin, cout):
+        check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t), cout,
+                                           ptr(do), ptr(din), ptr(d_weight), stream_of()))
 
 
 def Convolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
@@ -689,8 +714,9 @@ def Convolution_backward(input_size, output_size, filter_size, filter_stride, m,
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
         packed_t = pack_weight_transposed(weight, flip=False)
-    check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                  ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+    with _dw_fixed_order(d_weight, fv, cin, cout):
+        check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
+                                      ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
 
 
 def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
@@ -705,8 +731,9 @@ def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, 
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
         packed_t = pack_weight_transposed(weight, flip=False)
-    check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                    ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+    with _dw_fixed_order(d_weight, fv, cin, cout):
+        check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
+                                        ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
 
 
 def BatchNormalization_backward(input_features, d_input_features, output_features, d_output_features,

@@ -15,6 +15,7 @@ import os
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from . import modules as scn
 from ..timeline import mark as _tmark
 
@@ -144,7 +145,10 @@ class FPN_Net(torch.nn.Module):
 
     def forward(self, net0):
         if TWO_LANE and _is_gpu_input(net0):
-            if ASYNC_GEOMETRY and not PLAN_LANE:
+            # (not while torch fills new tensors -- deterministic mode: the pass's side streams do not wait for the
+            # fill kernels that the caller's stream holds for the tensors it allocates, and a fill can land after the
+            # side stream's write; the two-lane pass gives the same bits)
+            if ASYNC_GEOMETRY and not PLAN_LANE and not _lib.fills_uninitialized():
                 return self._forward_async_geometry(net0)
             return self._forward_two_lane(net0)
         net1 = self.layers_in[1](self._to_compute(self.layers_in[0](net0)))

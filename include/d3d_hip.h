@@ -305,9 +305,19 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size_host, const int *out_siz
 /* Process-wide switch of the dWeight accumulation of the three backward entry points above: 0 (default) = fp32 atomics
  * like the reference (SCN/CUDA/Convolution.cu:249-442 accumulates with atomicAdd: the last bits differ from run to run),
  * 1 = a fixed summation order (every workgroup sums its row blocks in order into a partial dWeight held in the
- * metadata's feature lane -- at most 32 x [fv, Cin, Cout] floats --, the partials are added in order): the same bits in
+ * metadata's feature lane, taken under its lock, or in a stream-ordered allocation when the lane is too small -- at
+ * most 32 x [fv, Cin, Cout] floats and at most 64 MB unless one partial is larger --, the partials are added in order): the same bits in
  * every run; the backward pass of a 6c training step at 500 k points takes 15.7 instead of 10.1 ms.  on < 0: query.  -> previous setting.  Environment: D3D_DW_DETERMINISTIC=1.       */
 int d3d_conv_dw_deterministic(int on);
+/* The same fixed-order dWeight for the calling thread only (what torch.use_deterministic_algorithms(True) selects in the
+ * Python wrappers), whatever the process-wide switch says.  on = 1: the three backward entry points above, called from
+ * this thread, sum dWeight in a fixed order with their partial sums in `scratch` (device memory of at least
+ * d3d_conv_dw_scratch_bytes(fv, Cin, Cout) bytes for every layer called; it must stay valid until the launches have
+ * run).  on = 0: back to the process-wide setting.  on < 0: query.  -> previous thread setting, or an error (< 0).
+ * The number of partials is min(32, row-block runs, 64 MB / (4 fv Cin Cout)), at least one: a function of the rulebook
+ * and the layer's size, so the bits are the same in every run.                                                      */
+int d3d_conv_dw_thread_mode(int on, void *scratch, size_t scratch_bytes);
+size_t d3d_conv_dw_scratch_bytes(int filter_volume, int cin, int cout);
 /* BatchNormalization_backward (SCN/sparseconvnet.h:27-32; SCN/CPU/BatchNormalization.cpp:62-107). */
 int d3d_bn_backward(const float *in, const float *out, const float *d_out, float *d_in, int rows,
                     int planes, const float *save_mean, const float *save_invstd, const float *weight,
@@ -332,6 +342,23 @@ int d3d_roi_align_rotated_3d_sparse_backward(d3d_meta *m, const int *spatial_siz
                                              const float *rois, int K, float spatial_scale, int ph,
                                              int pw, int pz, int sampling_ratio, float *d_feats,
                                              void *stream);
+/* The same gradient in a fixed summation order, with no float atomics: the same bits in every run
+ * (torch.use_deterministic_algorithms(True)).  Taps are merged per (RoI, bin, step of 8 sub-samples, cell) into
+ * records, the records are sorted stably by destination row, and every row adds its records in list order
+ * (lists longer than 64 records in chunks of 64 whose partial sums are added in chunk order).  d_feats [n_rows, C]
+ * (n_rows = the grid's active sites) is accumulated into.  sampling_ratio must be > 0.  `scratch`: device memory of
+ * d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(K, C, ph, pw, pz, sampling_ratio, n_rows)
+ * bytes (0: arguments out of range).  It is sized for one record per tap (K x NB x sampling_ratio^3 x 8 records:
+ * records, sort buffers and chunk partials all scale with that bound) -- about 310 MB for the box head's K = 512,
+ * [7,7,3] bins, C = 128 at sampling ratio 2, twice that at two examples per batch.                                  */
+int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const int *spatial_size_host,
+                                                           const float *top_diff, int C, const int *crop_host,
+                                                           const float *rois, int K, float spatial_scale, int ph,
+                                                           int pw, int pz, int sampling_ratio, float *d_feats,
+                                                           int n_rows, void *scratch, size_t scratch_bytes,
+                                                           void *stream);
+size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(int K, int C, int ph, int pw, int pz,
+                                                                           int sampling_ratio, int n_rows);
 
 /* a8. BatchNormalization_updateOutput (SCN/sparseconvnet.h:21-26; SCN/CPU/BatchNormalization.cpp:12-60).
  * train!=0: batch statistics, running update r = m*r + (1-m)*batch.  train==0: uses

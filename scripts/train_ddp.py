@@ -3,6 +3,7 @@ RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + 
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
+        [--deterministic [--seed S]]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="3G6c_Fpn4321")
     ap.add_argument("--steps", type=int, default=20)
@@ -37,7 +38,23 @@ def main():
                     help="buildings per rank and step (IMS_PER_BATCH = ranks x this; the LR schedule counts with it)")
     ap.add_argument("--verify", action="store_true",
                     help="after the steps: compare the weights of all ranks and gather the detections of every scene")
-    args = ap.parse_args()
+    ap.add_argument("--deterministic", action="store_true",
+                    help="torch.use_deterministic_algorithms(True): the same losses and weights in every run of the "
+                         "same world size (the library's backward ops take their fixed-order forms)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the weights and of the samplers")
+    return ap.parse_args(argv)
+
+
+def seed_everything(args):
+    """Before the model is built: the torch flag (with --deterministic) and the seeds of the initial weights and of
+    the samplers (torch.randperm on the device draws from torch's generator)."""
+    if args.deterministic:
+        torch.use_deterministic_algorithms(True)
+    torch.manual_seed(args.seed)          # same initial weights on every rank (DDP also broadcasts rank 0's)
+
+
+def main():
+    args = parse_args()
     rank, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29533")
@@ -67,7 +84,7 @@ def main():
                 if not os.path.exists(f):
                     write_scene_file(f, i, args.points, cfg.INPUT.CLASSES)
         dist.barrier()
-    torch.manual_seed(0)                  # same initial weights on every rank (DDP also broadcasts rank 0's)
+    seed_everything(args)
     model = build_detection_model(cfg).to(dev)
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
                        ims_per_gpu=args.ims_per_gpu)
@@ -89,7 +106,8 @@ def main():
             out["detections_per_scene"] = [int(dets[k]["bbox3d"].shape[0]) for k in sorted(dets)]
             out["gt_per_scene"] = [int(gts[k]["bbox3d"].shape[0]) for k in sorted(gts)]
     if rank == 0:
-        out.update(config=args.config, n_gpus=WORLD, points_per_building=args.points if not args.data else None,
+        out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic,
+                   points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
     dist.barrier()
