@@ -186,6 +186,19 @@ _SIGS = {
     "d3d_rows_to_bf16": (ctypes.c_int, [vp, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp]),
     "d3d_bn_apply_dt": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_float,
                                        ctypes.c_int, vp]),
+    "d3d_pack_conv_weight_transposed_dt": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          vp, ctypes.c_int, vp]),
+    "d3d_subm_conv_backward_dt": (ctypes.c_int, [vp, c_int_p, c_int_p, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int,
+                                                 vp, vp, vp, ctypes.c_int, vp]),
+    "d3d_conv_backward_dt": (ctypes.c_int, [vp, c_int_p, c_int_p, c_int_p, c_int_p, vp, ctypes.c_int, ctypes.c_int, vp,
+                                            ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]),
+    "d3d_deconv_backward_dt": (ctypes.c_int, [vp, c_int_p, c_int_p, c_int_p, c_int_p, vp, ctypes.c_int, ctypes.c_int, vp,
+                                              ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]),
+    "d3d_bn_forward_dt": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_float,
+                                         ctypes.c_float, ctypes.c_int, ctypes.c_float, vp, ctypes.c_size_t, ctypes.c_int,
+                                         vp]),
+    "d3d_bn_backward_dt": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
+                                          ctypes.c_float, vp, ctypes.c_size_t, ctypes.c_int, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -228,6 +228,197 @@ __global__ __launch_bounds__(256) void k_dw_reduce(const float *__restrict__ par
   dW[e] += v;
 }
 
+// ---- bf16 storage: dW[k] += in[rows_k]^T . dOut[rows_k] on v_mfma_f32_32x32x16_bf16 (fp32 accumulators, fp32 dW) ----
+// The decomposition of k_conv_dw (offset per blockIdx.y, ballot-found runs of 32-row blocks, chunks of dense offsets,
+// the DET form's partials), with half the bytes per row and K = 16 rows per MFMA instead of 2.  Both operands sum over
+// the row index, so both tiles are staged row-major in LDS as gathered (16-byte pieces) and read column-wise with
+// ds_read_b64_tr_b16.
+typedef unsigned short bf16_t;   // bf16 storage at the ABI (raw bits)
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// LDS row stride (elements) of a staged [32][w] tile: >= w and = 32 (mod 64), so that the 32 lanes of a half-wave's
+// transposed read (4 rows x 32 columns, 8 bytes a lane) fall on 64 different banks
+constexpr int dw_lds_ld(int w) { return w + (32 - w % 64 + 64) % 64; }
+
+// The 32x32x16 operand fragment of columns col0 .. col0+31 over rows row0 .. row0+15 of a row-major LDS tile: lane l
+// gets column col0 + (l & 31), rows row0 + 8 (l >> 5) + j in element j -- A[i][k] (or B[k][j]) with the row as k.
+// Two ds_read_b64_tr_b16 (rows +0..3, +4..7): lane 4q + p of a 16-lane group gives the address of row q, columns
+// 4p .. 4p+3 of the group's 4 x 16 block, and lane i receives column i with row q in element q.  The instruction
+// gathers across lanes: EXEC must be full (callers branch on wave-uniform conditions only).
+__device__ __forceinline__ bf16x8 dw_frag(const bf16_t *tile, int ld, int row0, int col0, int lane) {
+  const int i = lane & 15;
+  const bf16_t *a = tile + (row0 + 8 * (lane >> 5) + (i >> 2)) * ld + col0 + 16 * ((lane >> 4) & 1) + 4 * (i & 3);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)a);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(a + 4 * ld));
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// CS = stored Cin (16 .. 256), `cin` = Cin of dW (<= CS: the first layer stores 9 channels as 16); dW rows ci >= cin are
+// not written.  DET as k_conv_dw.
+template <int CS, int COUT, bool DET>
+__global__ __launch_bounds__(256) void k_conv_dw_bf16(const bf16_t *__restrict__ in, int cin,
+                                                      const bf16_t *__restrict__ d_out,
+                                                      const int32_t *__restrict__ nbrT, int npos,
+                                                      const int32_t *__restrict__ rows,
+                                                      const uint32_t *__restrict__ blkmask, int n_blk, int run,
+                                                      int chunk, int nz_tiles, float *__restrict__ dW) {
+  constexpr int CP = CS < 32 ? 32 : CS;            // Cin covered by output tiles
+  constexpr int NTI = CP / 32, NTJ = COUT / 32, T = NTI * NTJ;
+  constexpr int TPG = T < 16 ? T : 16;             // tiles per group (grid.z)
+  constexpr int TPW = (TPG + 3) / 4;               // tiles per wave
+  constexpr int A8 = CS / 8, B8 = COUT / 8;        // 16-byte pieces per row
+  constexpr int NA = (32 * A8 + 255) / 256, NB = (32 * B8 + 255) / 256;  // pieces per thread and block
+  constexpr int LDA = dw_lds_ld(CP), LDB = dw_lds_ld(COUT);
+  static_assert(kDwBlocksPerWg == 64, "one ballot covers the longest run");
+  __shared__ __attribute__((aligned(16))) bf16_t As[32 * LDA];
+  __shared__ __attribute__((aligned(16))) bf16_t Bs[32 * LDB];
+  const int k = blockIdx.y;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = lane & 31, kk = lane >> 5;
+  int b0 = blockIdx.x * run;
+  const int n_runs = (n_blk + run - 1) / run;
+  int rx = blockIdx.x;
+  auto run_mask = [&](int first) -> unsigned long long {
+    const uint32_t mm = (lane < run && first + lane < n_blk) ? blkmask[first + lane] : 0u;
+    return __ballot((mm >> k) & 1u);
+  };
+  unsigned long long active = run_mask(b0);
+  if constexpr (!DET) {
+    const int c = blockIdx.z / nz_tiles;
+    for (int d = 0; d < c * chunk && active; d++) active &= active - 1;
+    unsigned long long keep = 0, rest = active;
+    for (int d = 0; d < chunk && rest; d++) {
+      keep |= rest & (~rest + 1);
+      rest &= rest - 1;
+    }
+    active = keep;
+    if (!active) return;
+  }
+  const int zt = blockIdx.z % nz_tiles;
+  f32x16 acc[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; t++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+  if constexpr (CS < CP) {   // channels CS .. CP-1 of the A tile are never staged: zeros
+    for (int e = threadIdx.x; e < 32 * (CP - CS); e += 256) As[(e / (CP - CS)) * LDA + CS + e % (CP - CS)] = 0;
+  }
+
+  int ia[NA], ib[NB];
+  u32x4 sa[NA], sb[NB];
+  uint32_t real_a = 0, real_b = 0;
+  auto load_idx = [&](int b) {
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+      const int e = threadIdx.x + j * 256;
+      ia[j] = nbrT[(size_t)k * npos + b * 32 + (e < 32 * A8 ? e / A8 : 0)];
+    }
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const int e = threadIdx.x + j * 256;
+      ib[j] = rows[b * 32 + (e < 32 * B8 ? e / B8 : 0)];
+    }
+  };
+  auto issue_data = [&]() {   // branch-free: an absent row reads row 0 and is zeroed in commit()
+    real_a = real_b = 0;
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+      const int e = threadIdx.x + j * 256;
+      const int sidx = e < 32 * A8 ? ia[j] : -1;
+      if (sidx >= 0) real_a |= 1u << j;
+      sa[j] = *(const u32x4 *)(in + (size_t)(sidx < 0 ? 0 : sidx) * CS + (e % A8) * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const int e = threadIdx.x + j * 256;
+      const int o = e < 32 * B8 ? ib[j] : -1;
+      if (o >= 0) real_b |= 1u << j;
+      sb[j] = *(const u32x4 *)(d_out + (size_t)(o < 0 ? 0 : o) * COUT + (e % B8) * 8);
+    }
+  };
+  auto commit = [&]() {
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+      const int e = threadIdx.x + j * 256;
+      if (e < 32 * A8) *(u32x4 *)(As + (e / A8) * LDA + (e % A8) * 8) = ((real_a >> j) & 1u) ? sa[j] : zero;
+    }
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const int e = threadIdx.x + j * 256;
+      if (e < 32 * B8) *(u32x4 *)(Bs + (e / B8) * LDB + (e % B8) * 8) = ((real_b >> j) & 1u) ? sb[j] : zero;
+    }
+  };
+  auto pop = [&]() -> int {
+    if constexpr (DET) {
+      while (!active) {
+        rx += gridDim.x;
+        if (rx >= n_runs) return -1;
+        b0 = rx * run;
+        active = run_mask(b0);
+      }
+    } else {
+      if (!active) return -1;
+    }
+    const int j = __builtin_ctzll(active);
+    active &= active - 1;
+    return b0 + j;
+  };
+
+  int bc = pop();
+  if (bc >= 0) {
+    load_idx(bc);
+    issue_data();
+  }
+  int bn = pop();
+  if (bn >= 0) load_idx(bn);
+  while (bc >= 0) {
+    commit();
+    __syncthreads();
+    const int bnn = bn >= 0 ? pop() : -1;
+    if (bn >= 0) {
+      issue_data();
+      if (bnn >= 0) load_idx(bnn);
+    }
+#pragma unroll
+    for (int t = 0; t < TPW; t++) {
+      const int tile = zt * TPG + wave * TPW + t;
+      if (wave * TPW + t >= TPG || tile >= T) continue;   // wave-uniform: EXEC stays full for the transposed reads
+      const int ti = tile / NTJ, tj = tile % NTJ;
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const bf16x8 a = dw_frag(As, LDA, 16 * s, ti * 32, lane);
+        const bf16x8 b = dw_frag(Bs, LDB, 16 * s, tj * 32, lane);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[t], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    bc = bn;
+    bn = bnn;
+  }
+#pragma unroll
+  for (int t = 0; t < TPW; t++) {
+    const int tile = zt * TPG + wave * TPW + t;
+    if (wave * TPW + t >= TPG || tile >= T) continue;
+    const int ti = tile / NTJ, tj = tile % NTJ;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+      const int ci = ti * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
+      const int co = tj * 32 + i;
+      if constexpr (DET) {
+        if (ci < cin) dW[(((size_t)blockIdx.x * gridDim.y + k) * cin + ci) * COUT + co] = acc[t][reg];
+      } else {
+        if (ci < cin) atomicAdd(dW + ((size_t)k * cin + ci) * COUT + co, acc[t][reg]);
+      }
+    }
+  }
+}
+
 static bool g_dw_deterministic = [] {
   const char *e = getenv("D3D_DW_DETERMINISTIC");
   return e && e[0] != '0';
@@ -247,23 +438,29 @@ static inline int dw_det_partials(int n_runs, size_t n) {
   return (int)std::min<size_t>((size_t)std::min(n_runs, kDwDetPartials), by_budget);
 }
 
-template <int CP, int COUT>
-static int launch_dw_t(d3d_meta *m, const Plan &p, const float *in, int cin, const float *d_out, float *dW, hipStream_t s) {
-  constexpr int T = (CP / 32) * (COUT / 32);
-  constexpr int TPG = T < 16 ? T : 16;
+// the dW kernels of both storage types (S = float: k_conv_dw, bf16: k_conv_dw_bf16), atomic and fixed-order form
+template <typename S>
+using DwKernel = void (*)(const S *, int, const S *, const int32_t *, int, const int32_t *, const uint32_t *, int, int, int,
+                          int, float *);
+
+// grid, run length and scratch of one dW launch; T = output tiles (32 x 32) of the layer, `cin` = Cin of dW
+template <typename S>
+static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomic, DwKernel<S> k_det, const S *in, int cin,
+                          const S *d_out, int cout, float *dW, hipStream_t s) {
+  const int TPG = T < 16 ? T : 16;
   const int nz = (T + TPG - 1) / TPG;
   if (g_dw_deterministic || t_dw.on) {
     // fixed summation order: run r belongs to workgroup r % G, which adds its runs' blocks in order; the G partial
-    // sums are added in order by k_dw_reduce.  Scratch: G x (K, cin, COUT) floats, G <= kDwDetPartials and within
+    // sums are added in order by k_dw_reduce.  Scratch: G x (K, cin, cout) floats, G <= kDwDetPartials and within
     // kDwDetBudget bytes (one partial at least) -- the caller's buffer (d3d_conv_dw_thread_mode), else the feature
     // lane, else a stream-ordered allocation when the lane is too small.
     const int run = kDwBlocksPerWg;
     const int n_runs = (p.n_blk + run - 1) / run;
-    const size_t n = (size_t)p.K * cin * COUT;
+    const size_t n = (size_t)p.K * cin * cout;
     const int G = dw_det_partials(n_runs, n);
     const size_t bytes = (size_t)G * n * sizeof(float);
     auto launch = [&](float *part) {
-      hipLaunchKernelGGL((k_conv_dw<CP, COUT, true>), dim3(G, p.K, nz), dim3(256), 0, s, in, cin, d_out, p.nbrT,
+      hipLaunchKernelGGL(k_det, dim3(G, p.K, nz), dim3(256), 0, s, in, cin, d_out, p.nbrT,
                          p.n_blk * 32, p.rows, p.blkmask, p.n_blk, run, run, nz, part);
       hipLaunchKernelGGL(k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, G, n, dW);
     };
@@ -306,10 +503,15 @@ static int launch_dw_t(d3d_meta *m, const Plan &p, const float *in, int cin, con
   }
   const int n_chunks = (int)((run + chunk - 1) / chunk);
   dim3 grid((unsigned)((p.n_blk + run - 1) / run), p.K, nz * n_chunks);
-  hipLaunchKernelGGL((k_conv_dw<CP, COUT, false>), grid, dim3(256), 0, s, in, cin, d_out, p.nbrT, p.n_blk * 32, p.rows,
+  hipLaunchKernelGGL(k_atomic, grid, dim3(256), 0, s, in, cin, d_out, p.nbrT, p.n_blk * 32, p.rows,
                      p.blkmask, p.n_blk, (int)run, (int)chunk, nz, dW);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
+}
+template <int CP, int COUT>
+static int launch_dw_t(d3d_meta *m, const Plan &p, const float *in, int cin, const float *d_out, float *dW, hipStream_t s) {
+  return launch_dw_with<float>(m, p, (CP / 32) * (COUT / 32), k_conv_dw<CP, COUT, false>, k_conv_dw<CP, COUT, true>, in,
+                               cin, d_out, COUT, dW, s);
 }
 template <int CP>
 static int launch_dw_c(d3d_meta *m, const Plan &p, const float *in, int cin, const float *d_out, int cout, float *dW,
@@ -336,12 +538,61 @@ static int launch_dw(d3d_meta *m, const Plan &p, const float *in, int cin, const
   return D3D_ERR_UNSUPPORTED;
 }
 
+template <int CS>
+static int launch_dw_bf16_c(d3d_meta *m, const Plan &p, const bf16_t *in, int cin, const bf16_t *d_out, int cout,
+                            float *dW, hipStream_t s) {
+  constexpr int NTI = CS < 32 ? 1 : CS / 32;
+  switch (cout) {
+    case 32: return launch_dw_with<bf16_t>(m, p, NTI, k_conv_dw_bf16<CS, 32, false>, k_conv_dw_bf16<CS, 32, true>, in, cin, d_out, 32, dW, s);
+    case 64: return launch_dw_with<bf16_t>(m, p, NTI * 2, k_conv_dw_bf16<CS, 64, false>, k_conv_dw_bf16<CS, 64, true>, in, cin, d_out, 64, dW, s);
+    case 128: return launch_dw_with<bf16_t>(m, p, NTI * 4, k_conv_dw_bf16<CS, 128, false>, k_conv_dw_bf16<CS, 128, true>, in, cin, d_out, 128, dW, s);
+    case 256: return launch_dw_with<bf16_t>(m, p, NTI * 8, k_conv_dw_bf16<CS, 256, false>, k_conv_dw_bf16<CS, 256, true>, in, cin, d_out, 256, dW, s);
+  }
+  set_error("bf16 conv backward: Cout=%d not supported", cout);
+  return D3D_ERR_UNSUPPORTED;
+}
+// dW[K, cin, cout] += ... from bf16 rows stored `cs` channels wide
+static int launch_dw_bf16(d3d_meta *m, const Plan &p, const void *in_, int cs, int cin, const void *d_out_, int cout,
+                          float *dW, hipStream_t s) {
+  if (p.n_rows == 0) return D3D_OK;
+  const bf16_t *in = (const bf16_t *)in_, *d_out = (const bf16_t *)d_out_;
+  D3D_REQUIRE(in && d_out && dW, "bf16 conv backward: null pointer");
+  D3D_REQUIRE((((uintptr_t)in | (uintptr_t)d_out) & 15) == 0, "bf16 conv backward: rows must be 16-byte aligned");
+  switch (cs) {
+    case 16: return launch_dw_bf16_c<16>(m, p, in, cin, d_out, cout, dW, s);
+    case 32: return launch_dw_bf16_c<32>(m, p, in, cin, d_out, cout, dW, s);
+    case 64: return launch_dw_bf16_c<64>(m, p, in, cin, d_out, cout, dW, s);
+    case 128: return launch_dw_bf16_c<128>(m, p, in, cin, d_out, cout, dW, s);
+    case 256: return launch_dw_bf16_c<256>(m, p, in, cin, d_out, cout, dW, s);
+  }
+  set_error("bf16 conv backward: stored Cin=%d not supported", cs);
+  return D3D_ERR_UNSUPPORTED;
+}
+
+// Shapes of a bf16 backward call, checked before anything is launched: rows stored `cs` = 16 .. 256 channels wide for a
+// weight of Cin = cin (cs = the padded width of cin), Cout 32 .. 256; dInput is the bf16 convolution with Cin' = cout and
+// Cout' = cin, so it needs cin = cs in 32 .. 256.
+static int check_bwd_bf16(int cs, int cin, int cout, bool want_d_in) {
+  const bool cs_ok = cs == 16 || cs == 32 || cs == 64 || cs == 128 || cs == 256;
+  const bool cout_ok = cout == 32 || cout == 64 || cout == 128 || cout == 256;
+  if (!cs_ok || !cout_ok || cin < 1 || cin > cs || (cs > 16 && 2 * cin <= cs)) {
+    set_error("bf16 conv backward: Cin=%d stored as %d, Cout=%d not supported", cin, cs, cout);
+    return D3D_ERR_UNSUPPORTED;
+  }
+  if (want_d_in && (cin != cs || cs < 32)) {
+    set_error("bf16 conv backward: dInput for Cin=%d (stored %d) is not built", cin, cs);
+    return D3D_ERR_UNSUPPORTED;
+  }
+  return D3D_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // BatchNorm backward (CPU/BatchNormalization.cpp:62-107): partial sums of d' = dOut * relu' and
 // (x - mean) d', fixed-order reduction, then the elementwise pass.
 static constexpr int kBnBwdBlocks = 128;
-__global__ __launch_bounds__(256) void k_bn_bwd_partial(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ dy, int rows, int C,
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_partial(const T *__restrict__ x, const T *__restrict__ y,
+                                                        const T *__restrict__ dy, int rows, int C,
                                                         const float *__restrict__ mean, float leak,
                                                         double *__restrict__ partial) {
   extern __shared__ double red[];
@@ -355,9 +606,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float *__restrict_
     const float mu = mean[c];
     for (int r = r0 + rl; r < r1; r += row_lanes) {
       const size_t i = (size_t)r * C + c;
-      const float d = dy[i] * ((y[i] > 0) ? 1.f : leak);
+      const float d = ld1(dy + i) * ((ld1(y + i) > 0) ? 1.f : leak);
       s += (double)d;
-      dp += (double)((x[i] - mu) * d);
+      dp += (double)((ld1(x + i) - mu) * d);
     }
     red[tid * 2] = s;
     red[tid * 2 + 1] = dp;
@@ -375,8 +626,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float *__restrict_
 }
 // Same sums with 16-byte loads: threads = float4 channel groups x concurrent rows (1024 per workgroup), butterfly
 // inside the wave, one LDS entry per wave -- the layout of k_bn_stats (bn.hip).  planes % 4 == 0, planes/4 | 1024.
-__global__ __launch_bounds__(1024) void k_bn_bwd_partial4(const float *__restrict__ x, const float *__restrict__ y,
-                                                          const float *__restrict__ dy, int rows, int C,
+template <typename T>
+__global__ __launch_bounds__(1024) void k_bn_bwd_partial4(const T *__restrict__ x, const T *__restrict__ y,
+                                                          const T *__restrict__ dy, int rows, int C,
                                                           const float *__restrict__ mean, float leak,
                                                           double *__restrict__ partial) {
   __shared__ double red[4][1024];
@@ -392,7 +644,7 @@ __global__ __launch_bounds__(1024) void k_bn_bwd_partial4(const float *__restric
     double s[4] = {0, 0, 0, 0}, dp[4] = {0, 0, 0, 0};
     for (int r = r0 + rl; r < r1; r += RL) {
       const size_t i = (size_t)r * C + g4 * 4;
-      const f32x4 vx = *(const f32x4 *)(x + i), vy = *(const f32x4 *)(y + i), vd = *(const f32x4 *)(dy + i);
+      const f32x4 vx = load4<T>(x + i), vy = load4<T>(y + i), vd = load4<T>(dy + i);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const float d = vd[j] * ((vy[j] > 0) ? 1.f : leak);
@@ -434,8 +686,9 @@ __global__ __launch_bounds__(1024) void k_bn_bwd_partial4(const float *__restric
   }
 }
 // dx for 4 channels per thread
-__global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float *__restrict__ x, const float *__restrict__ y,
-                                                       const float *__restrict__ dy, float *__restrict__ dx,
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply4(const T *__restrict__ x, const T *__restrict__ y,
+                                                       const T *__restrict__ dy, T *__restrict__ dx,
                                                        size_t total4, int C, const float *__restrict__ mean,
                                                        const float *__restrict__ invstd,
                                                        const float *__restrict__ weight,
@@ -445,19 +698,20 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float *__restrict__
   if (t >= total4) return;
   const size_t i = t * 4;
   const int c = (int)(i % C);
-  const f32x4 vx = *(const f32x4 *)(x + i), vy = *(const f32x4 *)(y + i), vd = *(const f32x4 *)(dy + i);
+  const f32x4 vx = load4<T>(x + i), vy = load4<T>(y + i), vd = load4<T>(dy + i);
   f32x4 o;
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const float d = vd[j] * ((vy[j] > 0) ? 1.f : leak);
     o[j] = (d - grad_mean[c + j] - (vx[j] - mean[c + j]) * kcoef[c + j]) * invstd[c + j] * (weight ? weight[c + j] : 1.f);
   }
-  *(f32x4 *)(dx + i) = o;
+  store4(dx + i, o);
 }
 // the same arithmetic with one 4-channel group per thread walking rows (parameters read once per thread, see
 // k_bn_apply_rows in bn.hip); C4 = C / 4 divides 256
-__global__ __launch_bounds__(256) void k_bn_bwd_apply_rows(const float *__restrict__ x, const float *__restrict__ y,
-                                                           const float *__restrict__ dy, float *__restrict__ dx,
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply_rows(const T *__restrict__ x, const T *__restrict__ y,
+                                                           const T *__restrict__ dy, T *__restrict__ dx,
                                                            int rows, int C, const float *__restrict__ mean,
                                                            const float *__restrict__ invstd,
                                                            const float *__restrict__ weight,
@@ -488,14 +742,14 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_rows(const float *__restri
   size_t r = (size_t)blockIdx.x * RPI + rl;
   for (; r + step < (size_t)rows; r += 2 * step) {   // 2 rows = 6 loads in flight
     const size_t i0 = r * C + c, i1 = (r + step) * C + c;
-    const f32x4 x0 = *(const f32x4 *)(x + i0), y0 = *(const f32x4 *)(y + i0), d0 = *(const f32x4 *)(dy + i0);
-    const f32x4 x1 = *(const f32x4 *)(x + i1), y1 = *(const f32x4 *)(y + i1), d1 = *(const f32x4 *)(dy + i1);
-    *(f32x4 *)(dx + i0) = one(x0, y0, d0);
-    *(f32x4 *)(dx + i1) = one(x1, y1, d1);
+    const f32x4 x0 = load4<T>(x + i0), y0 = load4<T>(y + i0), d0 = load4<T>(dy + i0);
+    const f32x4 x1 = load4<T>(x + i1), y1 = load4<T>(y + i1), d1 = load4<T>(dy + i1);
+    store4(dx + i0, one(x0, y0, d0));
+    store4(dx + i1, one(x1, y1, d1));
   }
   for (; r < (size_t)rows; r += step) {
     const size_t i0 = r * C + c;
-    *(f32x4 *)(dx + i0) = one(*(const f32x4 *)(x + i0), *(const f32x4 *)(y + i0), *(const f32x4 *)(dy + i0));
+    store4(dx + i0, one(load4<T>(x + i0), load4<T>(y + i0), load4<T>(dy + i0)));
   }
 }
 __global__ __launch_bounds__(256) void k_bn_bwd_finish(const double *__restrict__ partial, int nblk, int rows,
@@ -525,8 +779,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_finish(const double *__restrict_
   grad_mean[c] = (float)(s / rows);
   kcoef[c] = (float)dp * is * is / rows;
 }
-__global__ __launch_bounds__(256) void k_bn_bwd_apply(const float *__restrict__ x, const float *__restrict__ y,
-                                                      const float *__restrict__ dy, float *__restrict__ dx,
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, const T *__restrict__ y,
+                                                      const T *__restrict__ dy, T *__restrict__ dx,
                                                       size_t total, int C, const float *__restrict__ mean,
                                                       const float *__restrict__ invstd,
                                                       const float *__restrict__ weight,
@@ -535,8 +790,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float *__restrict__ 
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int c = (int)(i % C);
-  const float d = dy[i] * ((y[i] > 0) ? 1.f : leak);
-  dx[i] = (d - grad_mean[c] - (x[i] - mean[c]) * kcoef[c]) * invstd[c] * (weight ? weight[c] : 1.f);
+  const float d = ld1(dy + i) * ((ld1(y + i) > 0) ? 1.f : leak);
+  st1(dx + i, (d - grad_mean[c] - (ld1(x + i) - mean[c]) * kcoef[c]) * invstd[c] * (weight ? weight[c] : 1.f));
 }
 
 // Input layer backward (CPU/IOLayers.cpp:30-47): every point receives multiplier * d_out[site].
@@ -550,6 +805,50 @@ __global__ void k_input_backward(const float *__restrict__ d_out, int planes, co
   const float mult = (average && e > b) ? (float)1 / (e - b) : (float)1;
   const float g = mult * d_out[t];
   for (int j = b; j < e; j++) d_in[(size_t)idx[j] * planes + c] = g;
+}
+
+// d3d_bn_backward / _dt for storage type T (float, or bf16 as raw 16-bit words): fp32 arithmetic, fp64 partial sums
+template <typename T>
+static int bn_backward_t(const T *in, const T *out, const T *d_out, T *d_in, int rows, int planes, const float *save_mean,
+                         const float *save_invstd, const float *weight, float *d_weight, float *d_bias, float leakiness,
+                         void *scratch, size_t scratch_bytes, hipStream_t s) {
+  D3D_REQUIRE(planes > 0 && rows >= 0 && save_mean && save_invstd, "bn_backward: bad arguments");
+  if (rows == 0) return D3D_OK;
+  D3D_REQUIRE(in && out && d_out && d_in, "bn_backward: null features");
+  D3D_REQUIRE(planes >= 256 ? (planes % 256 == 0) : (256 % planes == 0), "bn_backward: planes=%d unsupported", planes);
+  D3D_REQUIRE(scratch && scratch_bytes >= d3d_bn_backward_scratch_bytes(planes), "bn_backward: scratch too small");
+  int nblk = kBnBwdBlocks;
+  if (rows < nblk * 64) nblk = std::max(1, (rows + 63) / 64);
+  double *partial = (double *)scratch;
+  float *grad_mean = (float *)((char *)scratch + (size_t)kBnBwdBlocks * 2 * planes * sizeof(double));
+  float *kcoef = grad_mean + planes;
+  const bool vec4 = planes % 4 == 0 && 1024 % (planes / 4) == 0 && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)d_out | (uintptr_t)d_in) & 15) == 0;
+  if (vec4) {
+    const int RL = 1024 / (planes / 4);
+    nblk = std::max(1, std::min(kBnBwdBlocks, (rows + 8 * RL - 1) / (8 * RL)));
+    hipLaunchKernelGGL(k_bn_bwd_partial4<T>, dim3(nblk), dim3(1024), 0, s, in, out, d_out, rows, planes, save_mean, leakiness,
+                       partial);
+  } else {
+    hipLaunchKernelGGL(k_bn_bwd_partial<T>, dim3(nblk), dim3(256), 256 * 2 * sizeof(double), s, in, out, d_out, rows, planes,
+                       save_mean, leakiness, partial);
+  }
+  hipLaunchKernelGGL(k_bn_bwd_finish, dim3((planes + 31) / 32), dim3(256), 0, s, partial, nblk, rows, planes,
+                     save_invstd, grad_mean, kcoef, d_weight, d_bias);
+  size_t total = (size_t)rows * planes;
+  if (vec4 && planes / 4 <= 256 && 256 % (planes / 4) == 0) {
+    const int rpi = 256 / (planes / 4);
+    const long need = ((long)rows + rpi - 1) / rpi;
+    const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
+    hipLaunchKernelGGL(k_bn_bwd_apply_rows<T>, dim3(blocks), dim3(256), 0, s, in, out, d_out, d_in, rows, planes, save_mean,
+                       save_invstd, weight, grad_mean, kcoef, leakiness);
+  } else if (vec4)
+    hipLaunchKernelGGL(k_bn_bwd_apply4<T>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in,
+                       total / 4, planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
+  else
+    hipLaunchKernelGGL(k_bn_bwd_apply<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in, total,
+                       planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
 }
 
 }  // namespace d3d
@@ -633,6 +932,89 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, co
   return D3D_OK;
 }
 
+// bf16 storage: `cs` = stored width of `in` (and of d_in), `cin` = Cin of the weight / d_weight
+int d3d_subm_conv_backward_dt(d3d_meta *m, const int *size, const int *filt, const void *in, int cs, int cin,
+                              const void *packed_wt_flipped, int cout, const void *d_out, void *d_in, float *d_weight,
+                              int dtype, void *stream) {
+  if (dtype == D3D_F32) {
+    D3D_REQUIRE(cs == cin, "subm_conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
+    return d3d_subm_conv_backward(m, size, filt, (const float *)in, cin, (const float *)packed_wt_flipped, cout,
+                                  (const float *)d_out, (float *)d_in, d_weight, stream);
+  }
+  D3D_REQUIRE(dtype == D3D_BF16, "subm_conv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && size && filt, "null argument");
+  for (int d = 0; d < 3; d++) D3D_REQUIRE(filt[d] % 2 == 1, "submanifold backward needs odd filter sizes");
+  int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
+  if (rc) return rc;
+  const Plan *p = find_plan(m, 0, size, filt, nullptr);
+  if (d_in) {
+    rc = launch_conv_bf16(m, *p, d_out, cout, packed_wt_flipped, cs, nullptr, d_in, s, nullptr);
+    if (rc) return rc;
+  }
+  if (d_weight) return launch_dw_bf16(m, *p, in, cs, cin, d_out, cout, d_weight, s);
+  return D3D_OK;
+}
+
+int d3d_conv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
+                         const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out, void *d_in,
+                         float *d_weight, int dtype, void *stream) {
+  if (dtype == D3D_F32) {
+    D3D_REQUIRE(cs == cin, "conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
+    return d3d_conv_backward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_wt, cout,
+                             (const float *)d_out, (float *)d_in, d_weight, stream);
+  }
+  D3D_REQUIRE(dtype == D3D_BF16, "conv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
+  const Plan *fwd = find_plan(m, 1, in_size, filt, stride);
+  if (!fwd) {
+    set_error("conv backward: forward rulebook not built");
+    return D3D_ERR_STATE;
+  }
+  if (d_in) {
+    const Plan *dec = nullptr;
+    int rc = get_deconv_plan(m, in_size, filt, stride, s, &dec);
+    if (rc) return rc;
+    rc = launch_conv_bf16(m, *dec, d_out, cout, packed_wt, cs, nullptr, d_in, s, nullptr);
+    if (rc) return rc;
+  }
+  if (d_weight) return launch_dw_bf16(m, *fwd, in, cs, cin, d_out, cout, d_weight, s);
+  return D3D_OK;
+}
+
+int d3d_deconv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
+                           const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out,
+                           void *d_in, float *d_weight, int dtype, void *stream) {
+  if (dtype == D3D_F32) {
+    D3D_REQUIRE(cs == cin, "deconv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
+    return d3d_deconv_backward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_wt,
+                               cout, (const float *)d_out, (float *)d_in, d_weight, stream);
+  }
+  D3D_REQUIRE(dtype == D3D_BF16, "deconv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
+  const Plan *conv = find_plan(m, 1, out_size, filt, stride);  // fine -> coarse rulebook
+  if (!conv) {
+    set_error("deconv backward: strided rulebook not built");
+    return D3D_ERR_STATE;
+  }
+  if (d_in) {
+    int rc = launch_conv_bf16(m, *conv, d_out, cout, packed_wt, cs, nullptr, d_in, s, nullptr);
+    if (rc) return rc;
+  }
+  if (d_weight) {
+    const Plan *dec = nullptr;
+    int rc = get_deconv_plan(m, out_size, filt, stride, s, &dec);
+    if (rc) return rc;
+    return launch_dw_bf16(m, *dec, in, cs, cin, d_out, cout, d_weight, s);
+  }
+  return D3D_OK;
+}
+
 int d3d_conv_dw_deterministic(int on) {
   const int was = g_dw_deterministic ? 1 : 0;
   if (on >= 0) g_dw_deterministic = on != 0;
@@ -662,44 +1044,21 @@ size_t d3d_bn_backward_scratch_bytes(int planes) {
 int d3d_bn_backward(const float *in, const float *out, const float *d_out, float *d_in, int rows, int planes,
                     const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
                     float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(planes > 0 && rows >= 0 && save_mean && save_invstd, "bn_backward: bad arguments");
-  if (rows == 0) return D3D_OK;
-  D3D_REQUIRE(in && out && d_out && d_in, "bn_backward: null features");
-  D3D_REQUIRE(planes >= 256 ? (planes % 256 == 0) : (256 % planes == 0), "bn_backward: planes=%d unsupported", planes);
-  D3D_REQUIRE(scratch && scratch_bytes >= d3d_bn_backward_scratch_bytes(planes), "bn_backward: scratch too small");
-  int nblk = kBnBwdBlocks;
-  if (rows < nblk * 64) nblk = std::max(1, (rows + 63) / 64);
-  double *partial = (double *)scratch;
-  float *grad_mean = (float *)((char *)scratch + (size_t)kBnBwdBlocks * 2 * planes * sizeof(double));
-  float *kcoef = grad_mean + planes;
-  const bool vec4 = planes % 4 == 0 && 1024 % (planes / 4) == 0 && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)d_out | (uintptr_t)d_in) & 15) == 0;
-  if (vec4) {
-    const int RL = 1024 / (planes / 4);
-    nblk = std::max(1, std::min(kBnBwdBlocks, (rows + 8 * RL - 1) / (8 * RL)));
-    hipLaunchKernelGGL(k_bn_bwd_partial4, dim3(nblk), dim3(1024), 0, s, in, out, d_out, rows, planes, save_mean, leakiness,
-                       partial);
-  } else {
-    hipLaunchKernelGGL(k_bn_bwd_partial, dim3(nblk), dim3(256), 256 * 2 * sizeof(double), s, in, out, d_out, rows, planes,
-                       save_mean, leakiness, partial);
-  }
-  hipLaunchKernelGGL(k_bn_bwd_finish, dim3((planes + 31) / 32), dim3(256), 0, s, partial, nblk, rows, planes,
-                     save_invstd, grad_mean, kcoef, d_weight, d_bias);
-  size_t total = (size_t)rows * planes;
-  if (vec4 && planes / 4 <= 256 && 256 % (planes / 4) == 0) {
-    const int rpi = 256 / (planes / 4);
-    const long need = ((long)rows + rpi - 1) / rpi;
-    const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
-    hipLaunchKernelGGL(k_bn_bwd_apply_rows, dim3(blocks), dim3(256), 0, s, in, out, d_out, d_in, rows, planes, save_mean,
-                       save_invstd, weight, grad_mean, kcoef, leakiness);
-  } else if (vec4)
-    hipLaunchKernelGGL(k_bn_bwd_apply4, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in,
-                       total / 4, planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in, total,
-                       planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
+  return bn_backward_t(in, out, d_out, d_in, rows, planes, save_mean, save_invstd, weight, d_weight, d_bias, leakiness,
+                       scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int d3d_bn_backward_dt(const void *in, const void *out, const void *d_out, void *d_in, int rows, int planes,
+                       const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
+                       float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, int dtype, void *stream) {
+  if (dtype == D3D_F32)
+    return d3d_bn_backward((const float *)in, (const float *)out, (const float *)d_out, (float *)d_in, rows, planes,
+                           save_mean, save_invstd, weight, d_weight, d_bias, leakiness, scratch, scratch_bytes, stream);
+  D3D_REQUIRE(dtype == D3D_BF16, "bn_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  typedef unsigned short bf16_t;
+  return bn_backward_t((const bf16_t *)in, (const bf16_t *)out, (const bf16_t *)d_out, (bf16_t *)d_in, rows, planes,
+                       save_mean, save_invstd, weight, d_weight, d_bias, leakiness, scratch, scratch_bytes,
+                       (hipStream_t)stream);
 }
 
 int d3d_input_layer_backward(d3d_meta *m, const float *d_out, int planes, float *d_in, void *stream) {

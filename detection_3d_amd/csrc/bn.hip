@@ -45,29 +45,6 @@ __device__ __forceinline__ void stat_reduce_rows(const double *__restrict__ src,
   }
 }
 
-// 4 consecutive channels of a row as fp32: fp32 storage (16-byte load) or bf16 storage (8-byte load)
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <typename T>
-__device__ __forceinline__ f32x4_t load4(const T *p);
-template <>
-__device__ __forceinline__ f32x4_t load4<float>(const float *p) {
-  return *(const f32x4_t *)p;
-}
-template <>
-__device__ __forceinline__ f32x4_t load4<unsigned short>(const unsigned short *p) {
-  const uint2 v = *(const uint2 *)p;
-  return f32x4_t{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
-                 __uint_as_float(v.y & 0xffff0000u)};
-}
-__device__ __forceinline__ void store4(float *p, f32x4_t v) { *(f32x4_t *)p = v; }
-__device__ __forceinline__ void store4(unsigned short *p, f32x4_t v) {
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  bf16x4 b;
-#pragma unroll
-  for (int j = 0; j < 4; j++) b[j] = (__bf16)v[j];   // round to nearest even
-  *(uint2 *)p = __builtin_bit_cast(uint2, b);
-}
-
 // Column statistics in ONE launch.  Workgroup b sums slice b of the rows in fp64 (threads = float4 channel
 // groups x concurrent rows, 4 rows in flight per thread) and parks sum / sum-of-squares in partial[b]; the
 // last workgroup of each group of kStatGroup slices to arrive (ticket counter) adds that group's partials,
@@ -469,6 +446,29 @@ int d3d_bn_apply_dt(const void *in, void *out, int rows, int planes, const float
                      (unsigned short *)out, rows, planes, mean, invstd, weight, bias, leakiness);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
+}
+
+int d3d_bn_forward_dt(const void *in, void *out, int rows, int planes, float *save_mean, float *save_invstd,
+                      float *running_mean, float *running_var, const float *weight, const float *bias, float eps,
+                      float momentum, int train, float leakiness, void *scratch, size_t scratch_bytes, int dtype,
+                      void *stream) {
+  if (dtype == D3D_F32)
+    return d3d_bn_forward((const float *)in, (float *)out, rows, planes, save_mean, save_invstd, running_mean, running_var,
+                          weight, bias, eps, momentum, train, leakiness, scratch, scratch_bytes, stream);
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(dtype == D3D_BF16, "bn_forward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  D3D_REQUIRE(save_mean && save_invstd && running_mean && running_var && planes > 0 && rows >= 0, "bn_forward_dt: bad arguments");
+  if (rows == 0) return D3D_OK;
+  const int C4 = planes >> 2;
+  D3D_REQUIRE(in && out && (planes & 3) == 0 && C4 <= 256 && 256 % C4 == 0, "bn_forward_dt: bad arguments (planes=%d)", planes);
+  if (train) {
+    int rc = run_stats((const unsigned short *)in, rows, planes, scratch, scratch_bytes, s, 1, save_mean, save_invstd,
+                       running_mean, running_var, eps, momentum);
+    if (rc) return rc;
+  } else {
+    hipLaunchKernelGGL(k_bn_eval_stats, dim3((planes + 63) / 64), dim3(64), 0, s, running_mean, running_var, planes, eps, save_mean, save_invstd);
+  }
+  return d3d_bn_apply_dt(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, dtype, stream);
 }
 
 int d3d_rows_to_bf16(const float *in, long rows, int cin, int width, void *out, void *stream) {

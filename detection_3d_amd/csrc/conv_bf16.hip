@@ -52,6 +52,24 @@ __global__ void k_pack_weight_bf16(const float *__restrict__ w, int fv, int cin,
   packed[t] = (__bf16)(ci < cin ? w[((size_t)k * cin + ci) * cout + co] : 0.f);
 }
 
+// W^T of offset k = flip ? K-1-k' : k' in k_pack_weight_bf16's layout -- a weight with Cin' = cout (stored cp wide) and
+// Cout' = cin: packed_t[k'][g][ci][j] = bf16(w[k][ci][8g+j])  (zero for 8g+j >= cout)
+__global__ void k_pack_weight_t_bf16(const float *__restrict__ w, int fv, int cin, int cout, int cp, int flip,
+                                     __bf16 *__restrict__ packed) {
+  long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long total = (long)fv * cp * cin;
+  if (t >= total) return;
+  int j = (int)(t & 7);
+  long u = t >> 3;
+  int ci = (int)(u % cin);
+  u /= cin;
+  int g = (int)(u % (cp / 8));
+  int kp = (int)(u / (cp / 8));
+  int k = flip ? fv - 1 - kp : kp;
+  int co = 8 * g + j;
+  packed[t] = (__bf16)(co < cout ? w[((size_t)k * cin + ci) * cout + co] : 0.f);
+}
+
 // 8 bf16 (one 16-byte piece of a row) <-> 8 floats
 __device__ __forceinline__ void unpack8(u32x4 v, float *f) {
 #pragma unroll
@@ -452,6 +470,23 @@ int d3d_pack_conv_weight_dt(const float *w, int fv, int cin, int cout, void *pac
   const long total = (long)fv * cp * cout;
   hipLaunchKernelGGL(k_pack_weight_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout, cp,
                      (__bf16 *)packed);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+int d3d_pack_conv_weight_transposed_dt(const float *w, int fv, int cin, int cout, int flip, void *packed, int dtype,
+                                       void *stream) {
+  if (dtype == D3D_F32) return d3d_pack_conv_weight_transposed(w, fv, cin, cout, flip, (float *)packed, stream);
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(dtype == D3D_BF16 && w && packed && fv > 0, "pack_conv_weight_transposed_dt: bad arguments");
+  const int cp = padded_cin_bf16(cout);
+  if (cp < 0 || !(cin == 32 || cin == 64 || cin == 128 || cin == 256)) {   // Cout' = cin: a width launch_cb dispatches
+    set_error("pack_conv_weight_transposed_dt: bf16 W^T for Cin=%d Cout=%d is not built", cin, cout);
+    return D3D_ERR_UNSUPPORTED;
+  }
+  const long total = (long)fv * cp * cin;
+  hipLaunchKernelGGL(k_pack_weight_t_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout, cp,
+                     flip, (__bf16 *)packed);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

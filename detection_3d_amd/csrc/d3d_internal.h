@@ -102,6 +102,33 @@ __device__ __forceinline__ d3d_f32x4 bn_act(d3d_f32x4 x, d3d_f32x4 w, d3d_f32x4 
   return t;
 }
 
+// 4 consecutive channels of a row as fp32: fp32 storage (16-byte load) or bf16 storage (8-byte load, raw 16-bit
+// words); store4 rounds bf16 to nearest even.  ld1 / st1: one channel.
+template <typename T>
+__device__ __forceinline__ d3d_f32x4 load4(const T *p);
+template <>
+__device__ __forceinline__ d3d_f32x4 load4<float>(const float *p) {
+  return *(const d3d_f32x4 *)p;
+}
+template <>
+__device__ __forceinline__ d3d_f32x4 load4<unsigned short>(const unsigned short *p) {
+  const uint2 v = *(const uint2 *)p;
+  return d3d_f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
+                   __uint_as_float(v.y & 0xffff0000u)};
+}
+__device__ __forceinline__ void store4(float *p, d3d_f32x4 v) { *(d3d_f32x4 *)p = v; }
+__device__ __forceinline__ void store4(unsigned short *p, d3d_f32x4 v) {
+  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+  bf16x4 b;
+#pragma unroll
+  for (int j = 0; j < 4; j++) b[j] = (__bf16)v[j];   // round to nearest even
+  *(uint2 *)p = __builtin_bit_cast(uint2, b);
+}
+__device__ __forceinline__ float ld1(const float *p) { return *p; }
+__device__ __forceinline__ float ld1(const unsigned short *p) { return __uint_as_float((unsigned)*p << 16); }
+__device__ __forceinline__ void st1(float *p, float v) { *p = v; }
+__device__ __forceinline__ void st1(unsigned short *p, float v) { *p = __builtin_bit_cast(unsigned short, (__bf16)v); }
+
 // Output-stationary rulebook ("plan") of one convolution:
 //   rows   [n_blk*32]      output row of every position, sorted by neighbour mask, -1 padded
 //   nbrT   [K][n_blk*32]   input row feeding position p through filter offset k, or -1

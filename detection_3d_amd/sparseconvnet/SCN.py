@@ -611,10 +611,18 @@ def BatchNormalization_updateOutput(input_features, output_features, saveMean, s
     b = bias if (bias is not None and bias.numel()) else None
     nbytes = _bn_scratch_bytes(planes)
     scratch = _bn_scratch(input_features.device, nbytes)
-    check(lib().d3d_bn_forward(ptr(input_features), ptr(output_features), rows, planes, ptr(saveMean),
-                               ptr(saveInvStd), ptr(runningMean), ptr(runningVar), ptr(w), ptr(b),
-                               float(eps), float(momentum), int(bool(train)), float(leakiness),
-                               ptr(scratch), scratch.numel(), stream_of()))
+    if input_features.dtype == torch.float32:
+        check(lib().d3d_bn_forward(ptr(input_features), ptr(output_features), rows, planes, ptr(saveMean),
+                                   ptr(saveInvStd), ptr(runningMean), ptr(runningVar), ptr(w), ptr(b),
+                                   float(eps), float(momentum), int(bool(train)), float(leakiness),
+                                   ptr(scratch), scratch.numel(), stream_of()))
+        return
+    dt = dtype_code(input_features)      # bf16 rows; statistics, parameters and running stats fp32
+    _require_f32(saveMean, saveInvStd, runningMean, runningVar)
+    check(lib().d3d_bn_forward_dt(ptr(input_features), ptr(output_features), rows, planes, ptr(saveMean),
+                                  ptr(saveInvStd), ptr(runningMean), ptr(runningVar), ptr(w), ptr(b),
+                                  float(eps), float(momentum), int(bool(train)), float(leakiness),
+                                  ptr(scratch), scratch.numel(), dt, stream_of()))
 
 
 def batch_stats(features):
@@ -639,11 +647,19 @@ def SparseToDense_updateOutput(spatial_size, m, input_features, output, nPlanes,
                                             int(batch_size), ptr(output), stream_of()))
 
 
-def pack_weight_transposed(weight, flip):
+def pack_weight_transposed(weight, flip, dtype=torch.float32):
     """Packing of W^T ([fv, 1, Cin, Cout] -> a conv weight with Cin'=Cout, Cout'=Cin; `flip` reverses the
-    offset order, needed for the submanifold dInput)."""
+    offset order, needed for the submanifold dInput) in the layout of the features' storage type."""
     require_gpu(weight)
     fv, groups, cin, cout = weight.shape
+    if dtype == torch.bfloat16:
+        nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, BF16)
+        if nbytes == 0:
+            raise _lib.D3DError(f"unsupported bf16 conv shape for backward fv={fv} Cin={cin} Cout={cout}")
+        packed = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+        check(lib().d3d_pack_conv_weight_transposed_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout,
+                                                       int(bool(flip)), ptr(packed), BF16, stream_of()))
+        return packed
     n = lib().d3d_packed_weight_floats(fv, cout, cin)
     if n == 0:
         raise _lib.D3DError(f"unsupported conv shape for backward fv={fv} Cin={cin} Cout={cout}")
@@ -651,6 +667,24 @@ def pack_weight_transposed(weight, flip):
     check(lib().d3d_pack_conv_weight_transposed(ptr(weight.detach()), fv, cin, cout, int(bool(flip)), ptr(packed),
                                                 stream_of()))
     return packed
+
+
+def _require_f32(*tensors):
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.D3DError(f"expected a float32 tensor, got {t.dtype}")
+
+
+def _backward_dtype(feats, d_out, d_weight, cin):
+    """d3d_dtype of a conv backward call, checked before anything is launched: fp32 or bf16 features, the upstream
+    gradient of the same type, rows stored as the weight's Cin expects, an fp32 dWeight."""
+    dt = dtype_code(feats)
+    if d_out.dtype != feats.dtype:
+        raise _lib.D3DError(f"conv backward: features are {feats.dtype} but the output gradient is {d_out.dtype}")
+    if feats.nelement() and feats.shape[1] != stored_planes(cin, feats.dtype):
+        raise _lib.D3DError(f"conv backward: features have {feats.shape[1]} channels, weight expects {cin}")
+    _require_f32(d_weight)
+    return dt
 
 
 def _dinput_supported(cin):
@@ -687,6 +721,7 @@ def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features
     caller, submanifoldConvolution.py backward) is accumulated into."""
     require_gpu(input_features, d_output_features, weight, d_weight)
     fv, _, cin, cout = weight.shape
+    dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
     size, filt = _size3(spatial_size), _size3(filter_size)
     do = d_output_features.contiguous()
     din = None
@@ -696,10 +731,15 @@ def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features
             raise _lib.D3DError(f"dInput for Cin={cin} is not built (only the first layer has such a Cin)")
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=True)
+        packed_t = pack_weight_transposed(weight, flip=True, dtype=input_features.dtype)
     with _dw_fixed_order(d_weight, fv, cin, cout):
-        check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t), cout,
-                                           ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        if dt == F32:
+            check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t),
+                                               cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        else:
+            check(lib().d3d_subm_conv_backward_dt(m._h, ints(size), ints(filt), ptr(input_features),
+                                                  input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
+                                                  ptr(d_weight), dt, stream_of()))
 
 
 def Convolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
@@ -707,16 +747,22 @@ def Convolution_backward(input_size, output_size, filter_size, filter_stride, m,
     """sparseconvnet.h:92-98."""
     require_gpu(input_features, d_output_features, weight, d_weight)
     fv, _, cin, cout = weight.shape
+    dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
     isz, osz, filt, st = _size3(input_size), _size3(output_size), _size3(filter_size), _size3(filter_stride)
     do = d_output_features.contiguous()
     din = packed_t = None
     if want_d_input:
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False)
+        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype)
     with _dw_fixed_order(d_weight, fv, cin, cout):
-        check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                      ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        if dt == F32:
+            check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
+                                          ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        else:
+            check(lib().d3d_conv_backward_dt(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features),
+                                             input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
+                                             ptr(d_weight), dt, stream_of()))
 
 
 def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
@@ -724,16 +770,22 @@ def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, 
     """sparseconvnet.h:153-158."""
     require_gpu(input_features, d_output_features, weight, d_weight)
     fv, _, cin, cout = weight.shape
+    dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
     isz, osz, filt, st = _size3(input_size), _size3(output_size), _size3(filter_size), _size3(filter_stride)
     do = d_output_features.contiguous()
     din = packed_t = None
     if want_d_input:
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False)
+        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype)
     with _dw_fixed_order(d_weight, fv, cin, cout):
-        check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                        ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        if dt == F32:
+            check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
+                                            ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
+        else:
+            check(lib().d3d_deconv_backward_dt(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features),
+                                               input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
+                                               ptr(d_weight), dt, stream_of()))
 
 
 def BatchNormalization_backward(input_features, d_input_features, output_features, d_output_features,
@@ -741,15 +793,25 @@ def BatchNormalization_backward(input_features, d_input_features, output_feature
                                 leakiness):
     """sparseconvnet.h:27-32 (d_output_features is NOT modified in place, unlike the reference)."""
     require_gpu(input_features, output_features, d_output_features, saveMean, saveInvStd)
+    dtype_code(input_features)
+    if not (output_features.dtype == d_output_features.dtype == d_input_features.dtype == input_features.dtype):
+        raise _lib.D3DError("BatchNorm backward: features, output, output gradient and input gradient must share a dtype")
+    _require_f32(saveMean, saveInvStd, weight, d_weight, d_bias)
     rows, planes = input_features.shape
     d_input_features.resize_(rows, planes)
     w = weight if (weight is not None and weight.numel()) else None
     nbytes = lib().d3d_bn_backward_scratch_bytes(planes)
     scratch = _scratch(input_features.device, nbytes)
-    check(lib().d3d_bn_backward(ptr(input_features), ptr(output_features), ptr(d_output_features.contiguous()),
-                                ptr(d_input_features), rows, planes, ptr(saveMean), ptr(saveInvStd), ptr(w),
-                                ptr(d_weight), ptr(d_bias), float(leakiness), ptr(scratch), scratch.numel(),
-                                stream_of()))
+    if input_features.dtype == torch.float32 and d_output_features.dtype == torch.float32:
+        check(lib().d3d_bn_backward(ptr(input_features), ptr(output_features), ptr(d_output_features.contiguous()),
+                                    ptr(d_input_features), rows, planes, ptr(saveMean), ptr(saveInvStd), ptr(w),
+                                    ptr(d_weight), ptr(d_bias), float(leakiness), ptr(scratch), scratch.numel(),
+                                    stream_of()))
+        return
+    check(lib().d3d_bn_backward_dt(ptr(input_features), ptr(output_features), ptr(d_output_features.contiguous()),
+                                   ptr(d_input_features), rows, planes, ptr(saveMean), ptr(saveInvStd), ptr(w),
+                                   ptr(d_weight), ptr(d_bias), float(leakiness), ptr(scratch), scratch.numel(),
+                                   dtype_code(input_features), stream_of()))
 
 
 def InputLayer_updateGradInput(m, d_input_features, d_output_features):

@@ -66,8 +66,9 @@ class FPN_Net(torch.nn.Module):
         self.residual_blocks = residual_blocks
         self.reps = reps
         self.fuse_adds, self.skip_unused = fuse_adds, skip_unused
-        # storage type of the feature maps between the input layer and the maps handed to RPN / pooler (inference):
-        # torch.bfloat16 = BASELINE.json configs[4] (bf16 rows and weights, fp32 accumulation, fp32 statistics)
+        # storage type of the feature maps between the input layer and the maps handed to RPN / pooler:
+        # torch.bfloat16 = BASELINE.json configs[4] (bf16 rows and weights, fp32 accumulation, fp32 statistics); in
+        # training the rows' gradients are bf16 too, parameters, their gradients and the BatchNorm statistics fp32
         self.compute_dtype = torch.float32
         n_scales = len(nPlanesF)
         assert len(self.down_kernels) == n_scales - 1 == len(self.down_strides)
@@ -129,7 +130,8 @@ class FPN_Net(torch.nn.Module):
         """input-layer output (fp32 [n, 9]) -> storage type of the backbone: bf16 rows are padded to 16 channels"""
         if self.compute_dtype == torch.float32 or net.features.dtype == self.compute_dtype:
             return net
-        assert not torch.is_grad_enabled() or not net.features.requires_grad, "bf16 storage is an inference path"
+        assert not torch.is_grad_enabled() or not net.features.requires_grad, \
+            "bf16 storage: no gradient for the input features"
         f = net.features
         width = scn.SCN.stored_planes(f.shape[1], self.compute_dtype)
         if f.is_cuda and f.dtype == torch.float32 and self.compute_dtype == torch.bfloat16:

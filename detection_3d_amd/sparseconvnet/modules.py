@@ -191,8 +191,8 @@ class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, bias, running_mean, running_var, eps, momentum, train, leakiness):
         out = feats.new_empty(0)
-        save_mean = feats.new_empty(running_mean.shape[0])
-        save_invstd = feats.new_empty(running_mean.shape[0])
+        save_mean = running_mean.new_empty(running_mean.shape[0])     # fp32 statistics, also for bf16 rows
+        save_invstd = running_mean.new_empty(running_mean.shape[0])
         SCN.BatchNormalization_updateOutput(feats, out, save_mean, save_invstd, running_mean, running_var, weight, bias,
                                             eps, momentum, train, leakiness)
         ctx.save_for_backward(feats, out, weight, save_mean, save_invstd)
@@ -390,7 +390,9 @@ class BatchNormalization(Module):
             return _PendingBN(f, (mean, invstd, self.weight if self.affine else None,
                                   self.bias if self.affine else None, self.leakiness), input.metadata,
                               input.spatial_size)
-        if f.dtype != torch.float32:    # bf16 storage: inference with batch statistics only (the deferred form below)
+        wants_grad = torch.is_grad_enabled() and (f.requires_grad or (self.affine and self.weight.requires_grad))
+        if f.dtype != torch.float32 and not wants_grad:
+            # bf16 storage without a gradient: batch statistics, normalised rows (the deferred form above)
             mean, invstd = SCN.batch_mean_invstd(f, self.eps)
             return _like(input, SCN.bn_apply(f, mean, invstd, self.weight if self.affine else None,
                                              self.bias if self.affine else None, self.leakiness))
@@ -400,8 +402,10 @@ class BatchNormalization(Module):
             cp = _col_partials(input, f) if not torch.is_grad_enabled() else None
             if cp is not None:
                 mean, var = SCN.stats_from_partials(cp[0], cp[1], f.shape[0], self.eps, want_invstd=False)
-            else:
+            elif f.dtype == torch.float32:
                 mean, var = SCN.batch_stats(f.detach())
+            else:   # bf16 rows with a gradient outside training mode: the statistics of the exact fp32 values
+                mean, var = SCN.batch_stats(f.detach().float())
         y = _apply(_BatchNormFn, f, self.weight if self.affine else None, self.bias if self.affine else None,
                                mean, var, self.eps, self.momentum, self.training, self.leakiness)
         return _like(input, y)

@@ -302,6 +302,24 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size_host, const int *out_siz
                         const int *filter_host, const int *stride_host, const float *in, int cin,
                         const float *packed_wt, int cout, const float *d_out, float *d_in,
                         float *d_weight, void *stream);
+/* bf16 storage (d3d_dtype; D3D_F32 forwards to the functions above).  `in`, `d_out` and `d_in` are bf16 rows; `cs` is
+ * the STORED width of `in` and `d_in` (16, 32, 64, 128 or 256, as for the forward _dt functions) and `cin` the Cin of
+ * the weight and of d_weight [fv, cin, cout], which stays fp32 (cs is cin padded to the next stored width: the first
+ * layer stores 9 channels as 16 and its d_weight keeps 9).  dWeight is fp32-accumulated on v_mfma_f32_32x32x16_bf16
+ * (atomic or fixed-order form as above); dInput is the bf16 forward convolution with the W^T packing of
+ * d3d_pack_conv_weight_transposed_dt(..., D3D_BF16) and needs cin = cs >= 32.  Other shapes: D3D_ERR_UNSUPPORTED before
+ * any launch.                                                                                                     */
+int d3d_pack_conv_weight_transposed_dt(const float *w, int filter_volume, int cin, int cout, int flip, void *packed,
+                                       int dtype, void *stream);   /* size d3d_packed_weight_bytes(fv, cout, cin, dtype) */
+int d3d_subm_conv_backward_dt(d3d_meta *m, const int *spatial_size_host, const int *filter_host, const void *in,
+                              int cs, int cin, const void *packed_wt_flipped, int cout, const void *d_out, void *d_in,
+                              float *d_weight, int dtype, void *stream);
+int d3d_conv_backward_dt(d3d_meta *m, const int *in_size_host, const int *out_size_host, const int *filter_host,
+                         const int *stride_host, const void *in, int cs, int cin, const void *packed_wt, int cout,
+                         const void *d_out, void *d_in, float *d_weight, int dtype, void *stream);
+int d3d_deconv_backward_dt(d3d_meta *m, const int *in_size_host, const int *out_size_host, const int *filter_host,
+                           const int *stride_host, const void *in, int cs, int cin, const void *packed_wt, int cout,
+                           const void *d_out, void *d_in, float *d_weight, int dtype, void *stream);
 /* Process-wide switch of the dWeight accumulation of the three backward entry points above: 0 (default) = fp32 atomics
  * like the reference (SCN/CUDA/Convolution.cu:249-442 accumulates with atomicAdd: the last bits differ from run to run),
  * 1 = a fixed summation order (every workgroup sums its row blocks in order into a partial dWeight held in the
@@ -324,6 +342,11 @@ int d3d_bn_backward(const float *in, const float *out, const float *d_out, float
                     float *d_weight, float *d_bias, float leakiness, void *scratch,
                     size_t scratch_bytes, void *stream);
 size_t d3d_bn_backward_scratch_bytes(int planes);
+/* the same for bf16 rows `in`, `out` (the forward's output, for the activation's mask), `d_out` and `d_in`: fp32 arithmetic,
+ * the same fp64 partial sums; save_mean / save_invstd / weight and d_weight / d_bias stay fp32. */
+int d3d_bn_backward_dt(const void *in, const void *out, const void *d_out, void *d_in, int rows, int planes,
+                       const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
+                       float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, int dtype, void *stream);
 /* InputLayer_updateGradInput (SCN/sparseconvnet.h:164-167; SCN/CPU/IOLayers.cpp:30-47). */
 int d3d_input_layer_backward(d3d_meta *m, const float *d_out, int planes, float *d_in, void *stream);
 /* SparseToDense_updateGradInput (SCN/sparseconvnet.h:218-222): d_in [n_active, planes] gathered from the
@@ -368,6 +391,12 @@ int d3d_bn_forward(const float *in, float *out, int rows, int planes, float *sav
                    float *save_invstd, float *running_mean, float *running_var,
                    const float *weight, const float *bias, float eps, float momentum, int train,
                    float leakiness, void *scratch, size_t scratch_bytes, void *stream);
+/* d3d_bn_forward on rows of the given storage type (bf16: statistics in fp64 / fp32 as for fp32 rows, y rounded once;
+ * save_mean, save_invstd and the running statistics fp32, same semantics). */
+int d3d_bn_forward_dt(const void *in, void *out, int rows, int planes, float *save_mean, float *save_invstd,
+                      float *running_mean, float *running_var, const float *weight, const float *bias, float eps,
+                      float momentum, int train, float leakiness, void *scratch, size_t scratch_bytes, int dtype,
+                      void *stream);
 int d3d_bn_batch_stats(const float *in, int rows, int planes, float *mean, float *var_unbiased,
                        void *scratch, size_t scratch_bytes, void *stream);
 /* mean(0) and invstd = powf(var_unbiased(0) + eps, -0.5): what the eval path with track_running_stats=False
