@@ -870,10 +870,10 @@ int d3d_pack_conv_weight_transposed(const float *w, int fv, int cin, int cout, i
   return D3D_OK;
 }
 
-// d_in [rows_in, cin] (overwritten), d_weight [fv, cin, cout] (accumulated into; pre-zero it)
-int d3d_subm_conv_backward(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
-                           const float *packed_wt_flipped, int cout, const float *d_out, float *d_in,
-                           float *d_weight, void *stream) {
+// fp32 rows (D3D_F32, or D3D_F32_X3: dInput through launch_conv_dt, dWeight exact either way)
+static int subm_backward_f32(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
+                             const void *packed_wt_flipped, int cout, const float *d_out, float *d_in, float *d_weight,
+                             int dtype, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && size && filt, "null argument");
   for (int d = 0; d < 3; d++) D3D_REQUIRE(filt[d] % 2 == 1, "submanifold backward needs odd filter sizes");
@@ -881,16 +881,16 @@ int d3d_subm_conv_backward(d3d_meta *m, const int *size, const int *filt, const 
   if (rc) return rc;
   const Plan *p = find_plan(m, 0, size, filt, nullptr);
   if (d_in) {
-    rc = launch_conv(m, *p, d_out, cout, packed_wt_flipped, cin, nullptr, d_in, s);
+    rc = launch_conv_dt(m, *p, d_out, cout, packed_wt_flipped, cin, nullptr, d_in, s, nullptr, dtype);
     if (rc) return rc;
   }
   if (d_weight) return launch_dw(m, *p, in, cin, d_out, cout, d_weight, s);
   return D3D_OK;
 }
 
-int d3d_conv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                      const int *stride, const float *in, int cin, const float *packed_wt, int cout,
-                      const float *d_out, float *d_in, float *d_weight, void *stream) {
+static int conv_backward_f32(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
+                             const float *in, int cin, const void *packed_wt, int cout, const float *d_out, float *d_in,
+                             float *d_weight, int dtype, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
   const Plan *fwd = find_plan(m, 1, in_size, filt, stride);
@@ -902,16 +902,16 @@ int d3d_conv_backward(d3d_meta *m, const int *in_size, const int *out_size, cons
     const Plan *dec = nullptr;
     int rc = get_deconv_plan(m, in_size, filt, stride, s, &dec);
     if (rc) return rc;
-    rc = launch_conv(m, *dec, d_out, cout, packed_wt, cin, nullptr, d_in, s);
+    rc = launch_conv_dt(m, *dec, d_out, cout, packed_wt, cin, nullptr, d_in, s, nullptr, dtype);
     if (rc) return rc;
   }
   if (d_weight) return launch_dw(m, *fwd, in, cin, d_out, cout, d_weight, s);
   return D3D_OK;
 }
 
-int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                        const int *stride, const float *in, int cin, const float *packed_wt, int cout,
-                        const float *d_out, float *d_in, float *d_weight, void *stream) {
+static int deconv_backward_f32(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
+                               const float *in, int cin, const void *packed_wt, int cout, const float *d_out, float *d_in,
+                               float *d_weight, int dtype, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
   const Plan *conv = find_plan(m, 1, out_size, filt, stride);  // fine -> coarse rulebook
@@ -920,7 +920,7 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, co
     return D3D_ERR_STATE;
   }
   if (d_in) {
-    int rc = launch_conv(m, *conv, d_out, cout, packed_wt, cin, nullptr, d_in, s);
+    int rc = launch_conv_dt(m, *conv, d_out, cout, packed_wt, cin, nullptr, d_in, s, nullptr, dtype);
     if (rc) return rc;
   }
   if (d_weight) {
@@ -932,16 +932,37 @@ int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, co
   return D3D_OK;
 }
 
+// d_in [rows_in, cin] (overwritten), d_weight [fv, cin, cout] (accumulated into; pre-zero it)
+int d3d_subm_conv_backward(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
+                           const float *packed_wt_flipped, int cout, const float *d_out, float *d_in,
+                           float *d_weight, void *stream) {
+  return subm_backward_f32(m, size, filt, in, cin, packed_wt_flipped, cout, d_out, d_in, d_weight, D3D_F32, stream);
+}
+
+int d3d_conv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
+                      const int *stride, const float *in, int cin, const float *packed_wt, int cout,
+                      const float *d_out, float *d_in, float *d_weight, void *stream) {
+  return conv_backward_f32(m, in_size, out_size, filt, stride, in, cin, packed_wt, cout, d_out, d_in, d_weight, D3D_F32,
+                           stream);
+}
+
+int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
+                        const int *stride, const float *in, int cin, const float *packed_wt, int cout,
+                        const float *d_out, float *d_in, float *d_weight, void *stream) {
+  return deconv_backward_f32(m, in_size, out_size, filt, stride, in, cin, packed_wt, cout, d_out, d_in, d_weight, D3D_F32,
+                             stream);
+}
+
 // bf16 storage: `cs` = stored width of `in` (and of d_in), `cin` = Cin of the weight / d_weight
 int d3d_subm_conv_backward_dt(d3d_meta *m, const int *size, const int *filt, const void *in, int cs, int cin,
                               const void *packed_wt_flipped, int cout, const void *d_out, void *d_in, float *d_weight,
                               int dtype, void *stream) {
-  if (dtype == D3D_F32) {
+  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
     D3D_REQUIRE(cs == cin, "subm_conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return d3d_subm_conv_backward(m, size, filt, (const float *)in, cin, (const float *)packed_wt_flipped, cout,
-                                  (const float *)d_out, (float *)d_in, d_weight, stream);
+    return subm_backward_f32(m, size, filt, (const float *)in, cin, packed_wt_flipped, cout,
+                             (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
   }
-  D3D_REQUIRE(dtype == D3D_BF16, "subm_conv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  D3D_REQUIRE(dtype == D3D_BF16, "subm_conv_backward_dt: dtype %d is not a d3d_dtype", dtype);
   if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && size && filt, "null argument");
@@ -960,12 +981,12 @@ int d3d_subm_conv_backward_dt(d3d_meta *m, const int *size, const int *filt, con
 int d3d_conv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                          const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out, void *d_in,
                          float *d_weight, int dtype, void *stream) {
-  if (dtype == D3D_F32) {
+  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
     D3D_REQUIRE(cs == cin, "conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return d3d_conv_backward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_wt, cout,
-                             (const float *)d_out, (float *)d_in, d_weight, stream);
+    return conv_backward_f32(m, in_size, out_size, filt, stride, (const float *)in, cin, packed_wt, cout,
+                             (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
   }
-  D3D_REQUIRE(dtype == D3D_BF16, "conv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  D3D_REQUIRE(dtype == D3D_BF16, "conv_backward_dt: dtype %d is not a d3d_dtype", dtype);
   if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
@@ -988,12 +1009,12 @@ int d3d_conv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, c
 int d3d_deconv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                            const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out,
                            void *d_in, float *d_weight, int dtype, void *stream) {
-  if (dtype == D3D_F32) {
+  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
     D3D_REQUIRE(cs == cin, "deconv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return d3d_deconv_backward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_wt,
-                               cout, (const float *)d_out, (float *)d_in, d_weight, stream);
+    return deconv_backward_f32(m, in_size, out_size, filt, stride, (const float *)in, cin, packed_wt, cout,
+                               (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
   }
-  D3D_REQUIRE(dtype == D3D_BF16, "deconv_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  D3D_REQUIRE(dtype == D3D_BF16, "deconv_backward_dt: dtype %d is not a d3d_dtype", dtype);
   if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");

@@ -549,6 +549,21 @@ int launch_conv(d3d_meta *m, const Plan &p, const float *in, int cin, const floa
   return D3D_ERR_UNSUPPORTED;
 }
 
+void launch_conv_reduce(const float *partial, int n_split, int npos, int cout, const int32_t *rows, const float *residual,
+                        float *out, hipStream_t s) {
+  const long total = (long)npos * (cout / 4);
+  hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, partial, n_split, npos,
+                     cout / 4, rows, residual, out, nullptr);
+}
+
+int launch_conv_dt(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,
+                   const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype) {
+  if (dtype == D3D_BF16 || (dtype == D3D_F32_X3 && conv_x3_serves(p.K, cin, cout)))
+    return launch_conv_bf16(m, p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
+  return launch_conv(m, p, (const float *)in, cin, (const float *)packed_w, cout, (const float *)residual, (float *)out,
+                     s, bn);
+}
+
 }  // namespace d3d
 
 using namespace d3d;
@@ -637,7 +652,8 @@ int d3d_deconv_forward(d3d_meta *m, const int *in_size, const int *out_size, con
   return launch_conv(m, *p, in, cin, packed_w, cout, residual, out, s, bn);
 }
 
-// ---- storage-type aware forms (d3d_dtype): D3D_F32 forwards to the functions above, D3D_BF16 runs conv_bf16.hip.
+// ---- storage-type aware forms (d3d_dtype): D3D_F32 forwards to the functions above, D3D_BF16 runs conv_bf16.hip,
+// D3D_F32_X3 runs conv_bf16.hip's bf16x3 form where conv_x3_serves(K, cin, cout) and k_conv elsewhere (launch_conv_dt).
 // For bf16, `cin` is the stored row width (16, 32, 64, 128 or 256 channels; narrower inputs are zero padded).
 int d3d_subm_conv_forward_dt(d3d_meta *m, const int *size, const int *filt, const void *in, int cin,
                              const void *packed_w, int cout, const void *residual, void *out, int dtype, void *stream,
@@ -646,7 +662,7 @@ int d3d_subm_conv_forward_dt(d3d_meta *m, const int *size, const int *filt, cons
     return d3d_subm_conv_forward(m, size, filt, (const float *)in, cin, (const float *)packed_w, cout,
                                  (const float *)residual, (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(dtype == D3D_BF16 && m && size && filt, "subm_conv_forward_dt: bad arguments");
+  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && size && filt, "subm_conv_forward_dt: bad arguments");
   int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
   if (rc) return rc;
   Plan *p = const_cast<Plan *>(find_plan(m, 0, size, filt, nullptr));
@@ -656,7 +672,7 @@ int d3d_subm_conv_forward_dt(d3d_meta *m, const int *size, const int *filt, cons
     if (rc) return rc;
     *macs_host = (double)nr * cin * cout;
   }
-  return launch_conv_bf16(m, *p, in, cin, packed_w, cout, residual, out, s, bn);
+  return launch_conv_dt(m, *p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
 }
 
 int d3d_conv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
@@ -666,7 +682,8 @@ int d3d_conv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, co
     return d3d_conv_forward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_w, cout,
                             (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(dtype == D3D_BF16 && m && in_size && out_size && filt && stride, "conv_forward_dt: bad arguments");
+  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && in_size && out_size && filt && stride,
+              "conv_forward_dt: bad arguments");
   int rc = d3d_conv_prepare(m, in_size, out_size, filt, stride, stream, nullptr, nullptr);
   if (rc) return rc;
   Plan *p = const_cast<Plan *>(find_plan(m, 1, in_size, filt, stride));
@@ -676,7 +693,7 @@ int d3d_conv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, co
     if (rc) return rc;
     *macs_host = (double)nr * cin * cout;
   }
-  return launch_conv_bf16(m, *p, in, cin, packed_w, cout, nullptr, out, s, bn);
+  return launch_conv_dt(m, *p, in, cin, packed_w, cout, nullptr, out, s, bn, dtype);
 }
 
 int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
@@ -686,7 +703,8 @@ int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, 
     return d3d_deconv_forward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_w, cout,
                               (const float *)residual, (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(dtype == D3D_BF16 && m && in_size && out_size && filt && stride, "deconv_forward_dt: bad arguments");
+  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && in_size && out_size && filt && stride,
+              "deconv_forward_dt: bad arguments");
   const Plan *p = nullptr;
   int rc = get_deconv_plan(m, out_size, filt, stride, s, &p);
   if (rc) return rc;
@@ -696,7 +714,7 @@ int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, 
     if (rc) return rc;
     *macs_host = (double)nr * cin * cout;
   }
-  return launch_conv_bf16(m, *p, in, cin, packed_w, cout, residual, out, s, bn);
+  return launch_conv_dt(m, *p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
 }
 
 }  // extern "C"

@@ -262,8 +262,16 @@ struct BnPre {  // fused BatchNorm(+leaky ReLU) prologue of a convolution; mean 
 };
 void conv_timing_take(hipEvent_t *start, hipEvent_t *stop);   // events armed by d3d_conv_time_next (or nullptr), disarms
 // conv_bf16.hip
+// dtype D3D_BF16, or D3D_F32_X3 (fp32 rows, bf16x3 products) for the shapes conv_x3_serves admits
 int launch_conv_bf16(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,
-                     const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn);
+                     const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype = D3D_BF16);
+bool conv_x3_serves(int fv, int cin, int cout);   // filter volume (Plan::K), Cin, Cout
+// conv.hip: k_conv_reduce of fp32 partials [n_split][npos][cout] (no column statistics)
+void launch_conv_reduce(const float *partial, int n_split, int npos, int cout, const int32_t *rows, const float *residual,
+                        float *out, hipStream_t s);
+// a launch of any d3d_dtype: D3D_F32 and the D3D_F32_X3 shapes conv_x3_serves declines run launch_conv
+int launch_conv_dt(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,
+                   const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype);
 int launch_conv(d3d_meta *m, const Plan &p, const float *in, int cin, const float *packed_w, int cout,
                 const float *residual, float *out, hipStream_t s, const d3d_bn_prologue *bn = nullptr);
 // conv_ws.hip: the weight-sharing kernel for the large launches of the wide layers; false = not taken

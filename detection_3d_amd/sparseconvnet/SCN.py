@@ -294,7 +294,7 @@ class Metadata_3(object):
         return trip[:n.value]
 
 
-F32, BF16 = 0, 1        # d3d_dtype
+F32, BF16, F32_X3 = 0, 1, 2        # d3d_dtype
 
 
 def dtype_code(t):
@@ -304,6 +304,33 @@ def dtype_code(t):
     if t.dtype == torch.bfloat16:
         return BF16
     raise _lib.D3DError(f"unsupported feature dtype {t.dtype} (float32 or bfloat16)")
+
+
+def matmul_allows_tf32():
+    """torch's opt-in to reduced-precision fp32 matrix products, read at call time:
+    torch.backends.cuda.matmul.fp32_precision, or torch.backends.fp32_precision when that is 'none'.  Both
+    set_float32_matmul_precision('high' / 'medium') and the newer fp32_precision = 'tf32' set it.  (Not
+    torch.get_float32_matmul_precision(), which raises once the two APIs have been mixed; not the cuDNN conv flag,
+    which is 'tf32' by default.)"""
+    p = torch.backends.cuda.matmul.fp32_precision
+    if p == "none":
+        p = torch.backends.fp32_precision
+    return p == "tf32"
+
+
+def conv_dtype_code(dtype):
+    """d3d_dtype of the sparse convolutions of features of `dtype`: bf16 -> BF16; fp32 -> F32_X3 (bf16x3 products,
+    include/d3d_hip.h) when torch allows TF32 matmuls, else F32."""
+    if dtype == torch.float32:
+        return F32_X3 if matmul_allows_tf32() else F32
+    if dtype == torch.bfloat16:
+        return BF16
+    raise _lib.D3DError(f"unsupported feature dtype {dtype} (float32 or bfloat16)")
+
+
+def _packed_code(packed):
+    """d3d_dtype a packed weight was made for (pack_weight: F32 float32, BF16 bfloat16, F32_X3 raw int16 words)"""
+    return {torch.float32: F32, torch.bfloat16: BF16, torch.int16: F32_X3}.get(packed.dtype)
 
 
 def stored_planes(planes, dtype):
@@ -327,13 +354,24 @@ def n_rulebook_bits():
     return 32
 
 
-def pack_weight(weight, dtype=torch.float32):
+def pack_weight(weight, dtype=torch.float32, code=None):
     """[fv, 1, Cin, Cout] reference layout (fp32 parameter) -> MFMA k-interleaved layout of the compute type
-    (device tensor; bf16: Cin zero padded to the stored row width)."""
+    (device tensor; bf16: Cin zero padded to the stored row width).  `code`: the d3d_dtype to pack for
+    (default conv_dtype_code(dtype)); F32_X3 packings are int16 tensors of 4 bytes per weight."""
     require_gpu(weight)
     fv, groups, cin, cout = weight.shape
     if groups != 1:
         raise _lib.D3DError("groups != 1 is not supported")
+    if code is None:
+        code = conv_dtype_code(dtype)
+    if code == F32_X3:
+        nbytes = lib().d3d_packed_weight_bytes(fv, cin, cout, F32_X3)
+        if nbytes == 0:
+            raise _lib.D3DError(f"unsupported conv shape fv={fv} Cin={cin} Cout={cout}")
+        packed = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+        check(lib().d3d_pack_conv_weight_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout, ptr(packed),
+                                            F32_X3, stream_of()))
+        return packed
     if dtype == torch.bfloat16:
         nbytes = lib().d3d_packed_weight_bytes(fv, cin, cout, BF16)
         if nbytes == 0:
@@ -497,13 +535,14 @@ def bn_apply(features, mean, invstd, weight, bias, leakiness):
 
 
 def _conv_common(weight, packed, feats):
-    """-> (filter volume, stored Cin of `feats`, Cout, packed weights of feats' dtype, d3d_dtype)"""
+    """-> (filter volume, stored Cin of `feats`, Cout, packed weights for the d3d_dtype, d3d_dtype)"""
     fv, groups, cin, cout = weight.shape
-    if packed is None or packed.dtype != feats.dtype:
-        packed = pack_weight(weight, feats.dtype)
+    code = conv_dtype_code(feats.dtype)
+    if packed is None or _packed_code(packed) != code:
+        packed = pack_weight(weight, feats.dtype, code)
     if feats.shape[1] != stored_planes(cin, feats.dtype):
         raise _lib.D3DError(f"convolution: features have {feats.shape[1]} channels, weight expects {cin}")
-    return fv, feats.shape[1], cout, packed, dtype_code(feats)
+    return fv, feats.shape[1], cout, packed, code
 
 
 def SubmanifoldConvolution_updateOutput(spatial_size, filter_size, m, input_features,
@@ -647,11 +686,22 @@ def SparseToDense_updateOutput(spatial_size, m, input_features, output, nPlanes,
                                             int(batch_size), ptr(output), stream_of()))
 
 
-def pack_weight_transposed(weight, flip, dtype=torch.float32):
+def pack_weight_transposed(weight, flip, dtype=torch.float32, code=None):
     """Packing of W^T ([fv, 1, Cin, Cout] -> a conv weight with Cin'=Cout, Cout'=Cin; `flip` reverses the
-    offset order, needed for the submanifold dInput) in the layout of the features' storage type."""
+    offset order, needed for the submanifold dInput) in the layout of the d3d_dtype `code` (default
+    conv_dtype_code(dtype))."""
     require_gpu(weight)
     fv, groups, cin, cout = weight.shape
+    if code is None:
+        code = conv_dtype_code(dtype)
+    if code == F32_X3:
+        nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, F32_X3)
+        if nbytes == 0:
+            raise _lib.D3DError(f"unsupported conv shape for backward fv={fv} Cin={cin} Cout={cout}")
+        packed = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+        check(lib().d3d_pack_conv_weight_transposed_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout,
+                                                       int(bool(flip)), ptr(packed), F32_X3, stream_of()))
+        return packed
     if dtype == torch.bfloat16:
         nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, BF16)
         if nbytes == 0:
@@ -678,7 +728,7 @@ def _require_f32(*tensors):
 def _backward_dtype(feats, d_out, d_weight, cin):
     """d3d_dtype of a conv backward call, checked before anything is launched: fp32 or bf16 features, the upstream
     gradient of the same type, rows stored as the weight's Cin expects, an fp32 dWeight."""
-    dt = dtype_code(feats)
+    dt = conv_dtype_code(feats.dtype)
     if d_out.dtype != feats.dtype:
         raise _lib.D3DError(f"conv backward: features are {feats.dtype} but the output gradient is {d_out.dtype}")
     if feats.nelement() and feats.shape[1] != stored_planes(cin, feats.dtype):
@@ -731,7 +781,7 @@ def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features
             raise _lib.D3DError(f"dInput for Cin={cin} is not built (only the first layer has such a Cin)")
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=True, dtype=input_features.dtype)
+        packed_t = pack_weight_transposed(weight, flip=True, dtype=input_features.dtype, code=dt)
     with _dw_fixed_order(d_weight, fv, cin, cout):
         if dt == F32:
             check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t),
@@ -754,7 +804,7 @@ def Convolution_backward(input_size, output_size, filter_size, filter_stride, m,
     if want_d_input:
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype)
+        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype, code=dt)
     with _dw_fixed_order(d_weight, fv, cin, cout):
         if dt == F32:
             check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
@@ -777,7 +827,7 @@ def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, 
     if want_d_input:
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype)
+        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype, code=dt)
     with _dw_fixed_order(d_weight, fv, cin, cout):
         if dt == F32:
             check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,

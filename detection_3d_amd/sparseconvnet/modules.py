@@ -233,15 +233,17 @@ class _PackedWeightMixin(object):
     """Caches the MFMA-layout copy of `weight` until the parameter changes."""
 
     def _packed(self, dtype=torch.float32):
-        """packed copy of the (fp32) parameter in the layout / storage type of the features it will meet"""
+        """packed copy of the (fp32) parameter in the layout of the d3d_dtype the features it will meet run as --
+        keyed by that code, not the dtype: fp32 features pack differently under torch's TF32 opt-in (SCN.conv_dtype_code)"""
         w = self.weight
         tag = (w._version, w.data_ptr(), w.device)
         if getattr(self, "_packed_tag", None) != tag:
             self._packed_w = {}
             self._packed_tag = tag
-        p = self._packed_w.get(dtype)
+        code = SCN.conv_dtype_code(dtype)
+        p = self._packed_w.get(code)
         if p is None:
-            p = self._packed_w[dtype] = SCN.pack_weight(w, dtype)
+            p = self._packed_w[code] = SCN.pack_weight(w, dtype, code)
         return p
 
 

@@ -248,7 +248,21 @@ int d3d_deconv_forward(d3d_meta *m, const int *in_size_host, const int *out_size
  * (raw 16-bit words), accumulation is fp32 on v_mfma_f32_32x32x16_bf16, BatchNorm statistics stay fp64/fp32.
  * For D3D_BF16 `cin` is the STORED row width: 16, 32, 64, 128 or 256 channels (narrower inputs are zero padded by
  * the caller; d3d_pack_conv_weight_dt pads the weights to match).  D3D_F32 forwards to the fp32 entry points.      */
-typedef enum { D3D_F32 = 0, D3D_BF16 = 1 } d3d_dtype;
+typedef enum { D3D_F32 = 0, D3D_BF16 = 1, D3D_F32_X3 = 2 } d3d_dtype;
+/* D3D_F32_X3: fp32 rows, residual and outputs, as D3D_F32, with bf16x3 products -- what torch's
+ * set_float32_matmul_precision('high') / matmul.fp32_precision = 'tf32' permits (gfx950 has no xf32 MFMA).  Each fp32
+ * value x (row after the fused BatchNorm prologue, or weight) is split into hi = x truncated to bf16 and
+ * lo = bf16(x - hi), and a 16-wide K step sums lo*Whi, hi*Wlo, hi*Whi (in that order) on v_mfma_f32_32x32x16_bf16 into
+ * one fp32 accumulator.  Error of a product <= 2^-13 |x||w| (lo*Wlo dropped: < 2^-14; rounding of the two lo: 2^-16
+ * each); of an output, with the fp32 accumulation, <= 2.5e-4 * sum_k |x_k||w_k|.  A non-finite x splits as (x, 0):
+ * Inf and NaN reach the outputs as in D3D_F32 (a weight that bf16 holds exactly gets lo = hi * 2^-24, so that Inf * w
+ * keeps its sign).  Bit-stable from run to run.  The library picks the launches by (filter volume, Cin, Cout), where
+ * bf16x3 measured faster: Cin in {32, 64, 128, 256}, Cout in {32, 64, 128}, except 2x2x2 filters with Cin >= 128; every
+ * other shape (the 9-channel input layer among them) runs the exact fp32 kernel, and d3d_pack_conv_weight_dt /
+ * _transposed_dt pack each shape for the kernel that will read it (4 bytes per weight either way,
+ * d3d_packed_weight_bytes).  Rows are stored exactly `cin` wide as for D3D_F32.  The consumer's column statistics
+ * (d3d_bn_prologue.out_stats) come only from exact launches (*out_stats_rows = 0 otherwise).  In the backward
+ * functions dInput runs the same way on W^T; dWeight is the exact fp32 accumulation of D3D_F32 (atomic or fixed order). */
 size_t d3d_packed_weight_bytes(int filter_volume, int cin, int cout, int dtype);
 int d3d_pack_conv_weight_dt(const float *w, int filter_volume, int cin, int cout, void *packed, int dtype,
                             void *stream);

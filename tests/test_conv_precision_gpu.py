@@ -1,0 +1,391 @@
+"""fp32 sparse convolutions as bf16x3 (D3D_F32_X3) when torch allows TF32 matmuls.
+
+Oracle: fp64 numpy on the rulebooks of the CPU oracle.  Per output element the bf16x3 error is bounded by
+2.5e-4 * sum_k |x_k||w_k| (2^-13 per product from the split, plus fp32 accumulation: DESIGN.md 4d); against the
+product-norm ||x o w||_2 it stays below 1e-3, which plain bf16 products of the same data exceed.  Every test that
+changes the precision setting restores it.
+
+The modes are set with torch.set_float32_matmul_precision('high' / 'highest'), which sets the legacy and the new API
+alike: on torch 2.10 assigning torch.backends.cuda.matmul.fp32_precision = 'tf32' alone leaves the two disagreeing, and
+torch's own matmuls (the detector's heads) then raise.  The library reads either (test_conv_precision_cpu.py)."""
+import contextlib
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from tests.helpers import nbr_to_rules, small_scene
+
+pytestmark = pytest.mark.gpu
+HARD = 2.5e-4
+STAT = 1e-3
+
+
+def _saved():
+    """both APIs' state (the legacy level read while the two agree, as they do between tests)"""
+    return (torch.get_float32_matmul_precision(), torch.backends.cuda.matmul.fp32_precision,
+            torch.backends.fp32_precision)
+
+
+def _restore(saved):
+    legacy, matmul, generic = saved
+    torch.set_float32_matmul_precision(legacy)
+    torch.backends.fp32_precision = generic
+    torch.backends.cuda.matmul.fp32_precision = matmul
+
+
+@contextlib.contextmanager
+def _precision(value):
+    """'tf32' -> set_float32_matmul_precision('high'), 'ieee' -> 'highest' for the block, restored afterwards"""
+    saved = _saved()
+    torch.set_float32_matmul_precision("high" if value == "tf32" else "highest")
+    try:
+        yield
+    finally:
+        _restore(saved)
+
+
+@pytest.fixture(autouse=True)
+def _restore_precision():
+    saved = _saved()
+    yield
+    _restore(saved)
+
+
+@pytest.fixture(params=[1, 2])
+def row_blocks(request):
+    """1 or 2 row blocks per weight fetch (the widths the bf16x3 form has), forced on for every launch size"""
+    from detection_3d_amd._lib import check, lib
+    check(lib().d3d_conv_bf16_tuning(request.param, 0))
+    yield request.param
+    check(lib().d3d_conv_bf16_tuning(2, -1))
+
+
+def served(fv, cin, cout):
+    """the launch classes the library runs as bf16x3 (conv_x3_serves); the others stay exact"""
+    return cin in (32, 64, 128, 256) and cout in (32, 64, 128) and not (fv == 8 and cin >= 128)
+
+
+def _check_mode(got, exact, fv, cin, cout):
+    """bf16x3 launches differ from the exact ones; the classes kept exact give the exact bits"""
+    if served(fv, cin, cout):
+        assert not torch.equal(got, exact)
+    else:
+        assert torch.equal(got, exact)
+
+
+def _rules_conv64(x, w, rules, n_out):
+    """fp64: y, sum_k |x||w|, ||x o w||_2 and the products of bf16-rounded operands, per output element (an output
+    meets an offset at most once in these rulebooks, so a fancy-indexed add per offset is exact)"""
+    K, cin, cout = w.shape
+    x64, w64 = x.astype(np.float64), w.astype(np.float64)
+    xb = torch.from_numpy(x).to(torch.bfloat16).double().numpy()
+    wb = torch.from_numpy(w).to(torch.bfloat16).double().numpy()
+    y, a, s2, yb = (np.zeros((n_out, cout)) for _ in range(4))
+    for k in range(K):
+        sel = rules[:, 2] == k
+        i, o = rules[sel, 0], rules[sel, 1]
+        assert np.unique(o).size == o.size
+        y[o] += x64[i] @ w64[k]
+        a[o] += np.abs(x64[i]) @ np.abs(w64[k])
+        s2[o] += (x64[i] ** 2) @ (w64[k] ** 2)
+        yb[o] += xb[i] @ wb[k]
+    return y, a, np.sqrt(s2), yb
+
+
+def _check_bounds(got, y, a, norm, yb=None):
+    got = got.double().cpu().numpy()
+    err = np.abs(got - y)
+    assert np.isfinite(got).all()
+    assert (err <= HARD * a + 1e-30).all(), float((err / np.maximum(a, 1e-30)).max())
+    live = norm > 0
+    stat = float((err[live] / norm[live]).max())
+    assert stat <= STAT, stat
+    if yb is not None:     # the test tells bf16x3 from plain bf16 products
+        ctrl = float((np.abs(yb - y)[live] / norm[live]).max())
+        assert ctrl > STAT, ctrl
+    return stat
+
+
+def _scene(dev, cin, n_points, size, seed=4):
+    from detection_3d_amd import sparseconvnet as scn
+    rng = np.random.RandomState(seed * 1000 + cin)
+    _, coords, _ = small_scene(seed, n_points, tuple(s / 50.0 * 0.9 for s in size), size)
+    feats = rng.randn(coords.shape[0], cin).astype(np.float32)
+    t = scn.InputLayer(3, size, mode=4)([torch.from_numpy(coords), torch.from_numpy(feats).to(dev)])
+    _, loc = oracle.input_sites(coords)
+    return t, t.features.detach().cpu().numpy(), loc
+
+
+def _both(fn):
+    """fn() under the default setting and under 'tf32'"""
+    with _precision("ieee"):
+        exact = fn()
+    with _precision("tf32"):
+        x3 = fn()
+    return exact, x3
+
+
+@pytest.mark.parametrize("cin,cout,n_points", [(32, 32, 6000), (64, 64, 6000), (128, 128, 6000), (256, 256, 3000),
+                                               (64, 128, 6000), (256, 128, 3000), (128, 64, 6000), (64, 64, 120000),
+                                               (128, 128, 60000), (32, 64, 120000)])
+def test_layers_against_fp64(dev, cin, cout, n_points, row_blocks):
+    """submanifold 3x3x3, strided 2x2x2 and its deconvolution: within the bounds against fp64, and bf16x3 exactly where
+    the library runs it (the classes it keeps exact give the exact path's bits)"""
+    from detection_3d_amd import sparseconvnet as scn
+    size = (128, 128, 32) if n_points > 10000 else (64, 64, 16)
+    t, x, loc = _scene(dev, cin, n_points, size)
+    torch.manual_seed(cin + cout)
+    sub = scn.SubmanifoldConvolution(3, cin, cout, 3, False).to(dev)
+    down = scn.Convolution(3, cin, cout, [2, 2, 2], [2, 2, 2], False).to(dev)
+    up = scn.Deconvolution(3, cout, cin, [2, 2, 2], [2, 2, 2], False).to(dev)
+    with torch.no_grad():
+        exact, got = _both(lambda: sub(t).features.clone())
+        nbr, _ = oracle.subm_nbr(loc, [3, 3, 3])
+        w = sub.weight.detach().cpu().numpy().reshape(27, cin, cout)
+        _check_bounds(got, *_rules_conv64(x, w, nbr_to_rules(nbr), x.shape[0]))
+        _check_mode(got, exact, 27, cin, cout)
+        # strided 2/2 (8 offsets) and its deconvolution, on the coarse rows the exact path made
+        d_exact, d_got = _both(lambda: down(t))
+        lo, ru = oracle.conv_rules(loc, [2, 2, 2], [2, 2, 2], [s // 2 for s in size])
+        wd = down.weight.detach().cpu().numpy().reshape(8, cin, cout)
+        _check_bounds(d_got.features, *_rules_conv64(x, wd, ru, lo.shape[0]))
+        _check_mode(d_got.features, d_exact.features, 8, cin, cout)
+        u_exact, u_got = _both(lambda: up(d_exact).features.clone())
+        xd = d_exact.features.cpu().numpy()
+        wu = up.weight.detach().cpu().numpy().reshape(8, cout, cin)
+        _check_bounds(u_got, *_rules_conv64(xd, wu, ru[:, [1, 0, 2]], loc.shape[0]))
+        _check_mode(u_got, u_exact, 8, cout, cin)
+
+
+@pytest.mark.parametrize("c", [32, 128, 256])
+def test_fused_bn_and_residual_equal_separate_pass(dev, c, row_blocks):
+    """BatchNorm + leaky ReLU deferred into the bf16x3 gather: the same bits as the materialised fp32 tensor through
+    the same convolution, with a residual added in the epilogue"""
+    from detection_3d_amd import sparseconvnet as scn
+    from detection_3d_amd.sparseconvnet import modules
+    t, x, loc = _scene(dev, c, 6000, (64, 64, 16), seed=5)
+    t.features = t.features * 2 + 0.5
+    torch.manual_seed(1)
+    bn = scn.BatchNormLeakyReLU(c, momentum=0.95, leakiness=0.333, track_running_stats=False).to(dev).eval()
+    conv = scn.SubmanifoldConvolution(3, c, 64, 3, False).to(dev)
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+        res = scn.SparseConvNetTensor(torch.randn(loc.shape[0], 64, device=dev), t.metadata, t.spatial_size)
+        outs = []
+        with _precision("tf32"):
+            for fused in (True, False):
+                modules.FUSE_BN_INTO_CONV = fused
+                try:
+                    outs.append(conv(bn(t), residual=res).features.clone())
+                finally:
+                    modules.FUSE_BN_INTO_CONV = True
+        with _precision("ieee"):
+            exact = conv(bn(t), residual=res).features
+    assert torch.equal(outs[0], outs[1])
+    assert not torch.equal(outs[0], exact)
+    assert float((outs[0] - exact).abs().max()) <= 1e-3 * float(exact.abs().max())
+
+
+def test_bit_stable_and_switching(dev):
+    """the same call twice: the same bits; tf32 -> ieee -> tf32 in one process: each mode its own bits again (the
+    packed-weight cache is keyed by the mode)"""
+    from detection_3d_amd import sparseconvnet as scn
+    t, _, _ = _scene(dev, 128, 20000, (128, 128, 32))
+    torch.manual_seed(2)
+    conv = scn.SubmanifoldConvolution(3, 128, 128, 3, False).to(dev)
+    with torch.no_grad():
+        with _precision("tf32"):
+            a1, a2 = conv(t).features.clone(), conv(t).features.clone()
+        with _precision("ieee"):
+            b1 = conv(t).features.clone()
+        torch.backends.cuda.matmul.fp32_precision = "tf32"        # the new API selects the same (no torch GEMM here)
+        a3 = conv(t).features.clone()
+        torch.backends.cuda.matmul.fp32_precision = "ieee"
+        b2 = conv(t).features.clone()
+    assert torch.equal(a1, a2) and torch.equal(a1, a3)
+    assert torch.equal(b1, b2)
+    assert not torch.equal(a1, b1)
+
+
+@pytest.mark.parametrize("cin,cout", [(64, 64), (256, 128)])
+def test_non_finite_rows_propagate_as_in_fp32(dev, cin, cout):
+    from detection_3d_amd import sparseconvnet as scn
+    t, _, _ = _scene(dev, cin, 6000, (64, 64, 16), seed=6)
+    f = t.features.clone()
+    f[3, 5] = float("inf")
+    f[40, :] = float("-inf")
+    f[100, 7] = float("nan")
+    f[200, 0] = float("inf")
+    f[200, 1] = float("nan")
+    t2 = scn.SparseConvNetTensor(f, t.metadata, t.spatial_size)
+    torch.manual_seed(3)
+    sub = scn.SubmanifoldConvolution(3, cin, cout, 3, False).to(dev)
+    down = scn.Convolution(3, cin, cout, [2, 2, 2], [2, 2, 2], False).to(dev)
+    with torch.no_grad():
+        for layer, fv in ((sub, 27), (down, 8)):
+            exact, got = _both(lambda: layer(t2).features.clone())
+            assert not torch.isfinite(exact).all()
+            for cls in (torch.isnan, torch.isposinf, torch.isneginf):
+                assert torch.equal(cls(got), cls(exact)), cls.__name__
+            fin = torch.isfinite(exact)
+            _check_mode(got[fin], exact[fin], fv, cin, cout)
+
+
+@pytest.mark.parametrize("cin,cout,n_points", [(32, 64, 6000), (128, 128, 6000), (64, 64, 60000), (128, 256, 6000)])
+def test_backward_dinput_bounds_and_dweight_exact(dev, cin, cout, n_points):
+    """dInput runs bf16x3 on W^T within the forward bounds against fp64; dWeight is the exact kernel's: the same bits as
+    the default mode in the fixed-order form, and within the run-to-run spread of fp32 atomics in the atomic form"""
+    from detection_3d_amd import sparseconvnet as scn
+    size = (128, 128, 32) if n_points > 10000 else (64, 64, 16)
+    t, x, loc = _scene(dev, cin, n_points, size, seed=7)
+    torch.manual_seed(4)
+    sub = scn.SubmanifoldConvolution(3, cin, cout, 3, False).to(dev)
+    down = scn.Convolution(3, cin, cout, [2, 2, 2], [2, 2, 2], False).to(dev)
+    g = torch.from_numpy(np.random.RandomState(9).randn(loc.shape[0], cout).astype(np.float32)).to(dev)
+
+    def run(layer, deterministic):
+        layer.weight.grad = None
+        inp = t.features.detach().clone().requires_grad_(True)
+        was = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(deterministic)
+        try:
+            y = layer(scn.SparseConvNetTensor(inp, t.metadata, t.spatial_size)).features
+            y.backward(g[: y.shape[0]])
+        finally:
+            torch.use_deterministic_algorithms(was)
+        return inp.grad.clone(), layer.weight.grad.clone()
+
+    nbr, _ = oracle.subm_nbr(loc, [3, 3, 3])
+    _, ru = oracle.conv_rules(loc, [2, 2, 2], [2, 2, 2], [s // 2 for s in size])
+    for layer, rules, K in ((sub, nbr_to_rules(nbr), 27), (down, ru, 8)):
+        w = layer.weight.detach().cpu().numpy().reshape(K, cin, cout)
+        for deterministic in (True, False):
+            (dx0, dw0), (dx3, dw3) = _both(lambda: run(layer, deterministic))
+            if deterministic:
+                assert torch.equal(dw3, dw0)
+            else:
+                assert float((dw3 - dw0).abs().max()) <= 1e-5 * float(dw0.abs().max())
+            _check_mode(dx3, dx0, K, cout, cin)                 # dInput: W^T, Cin' = Cout
+            # dX[in] = sum over rules g[out] @ W[k]^T: the forward with the rules' roles swapped and W^T
+            gn = g[: int(rules[:, 1].max()) + 1].cpu().numpy()
+            _check_bounds(dx3, *_rules_conv64(gn, np.ascontiguousarray(w.transpose(0, 2, 1)), rules[:, [1, 0, 2]],
+                                              x.shape[0])[:3])
+
+
+def _flatten(maps):
+    out = []
+    for m in maps:
+        if isinstance(m, (list, tuple)):
+            out += _flatten(m)
+        elif hasattr(m, "features"):
+            out.append(m)
+    return out
+
+
+def test_detector_4c_backbone_and_detections(dev):
+    """4c at 200 k points in eval mode: the backbone maps under 'tf32' agree with the default within MAP_TOL (measured
+    5.8e-5 of a map's largest magnitude at the worst map; 2x margin), and the detections are reported"""
+    from detection_3d_amd.config import get_cfg
+    from detection_3d_amd.detector import build_detection_model
+    from detection_3d_amd.synthetic import make_scene
+    from detection_3d_amd.voxelize import voxelize
+    MAP_TOL = 1.2e-4
+    cfg = get_cfg("4c_Fpn432")
+    torch.manual_seed(1)
+    model = build_detection_model(cfg).to(dev).eval()
+    pcl = make_scene(11, 200000)
+    coords, feats = voxelize(torch.from_numpy(pcl).to(dev), 50, cfg.SPARSE3D.VOXEL_FULL_SCALE)
+    with torch.no_grad():
+        (m0, r0), (m3, r3) = _both(lambda: (_flatten(model.backbone([coords, feats])), model([coords, feats])))
+    assert len(m0) == len(m3) >= 3
+    worst = 0.0
+    for a, b in zip(m3, m0):
+        assert torch.equal(a.get_spatial_locations(), b.get_spatial_locations())
+        rel = float((a.features - b.features).abs().max()) / max(float(b.features.abs().max()), 1e-30)
+        worst = max(worst, rel)
+        assert rel > 0
+    print(f"backbone maps: max relative difference {worst:.3g}")
+    assert worst <= MAP_TOL, worst
+    n0, n3, ious = detection_agreement(r0, r3)
+    print(f"{len(m0)} maps; detections: {n0} default, {n3} tf32; IoU of same-label matches: "
+          f"min {min(ious, default=float('nan')):.4f} median {float(np.median(ious)) if ious else float('nan'):.4f}")
+    assert abs(n0 - n3) <= max(2, n0 // 10)
+
+
+def detection_agreement(r0, r3):
+    """-> (count, count, best 3-D IoU against the other run's boxes of the same label for every default detection)"""
+    def parts(r):
+        d = r[0] if isinstance(r, (list, tuple)) else r
+        return d["bbox3d"].detach().cpu().numpy(), d["labels"].detach().cpu().numpy()
+    (b0, l0), (b3, l3) = parts(r0), parts(r3)
+    ious = []
+    for lab in np.unique(l0):
+        p, q = b0[l0 == lab], b3[l3 == lab]
+        if len(p) and len(q):
+            ious += list(np.asarray(oracle.boxes_iou_3d(q, p)).reshape(len(q), len(p)).max(0))
+    return len(b0), len(b3), ious
+
+
+def test_training_step_6c_deterministic_bits(dev):
+    """a 6c training step under 'tf32' and torch.use_deterministic_algorithms(True): finite losses, and the same bits
+    (losses and every gradient) in two runs"""
+    from detection_3d_amd import engine, training as T
+    from detection_3d_amd.config import get_cfg
+    from detection_3d_amd.detector import build_detection_model
+    from detection_3d_amd.synthetic import make_scene, make_targets
+    cfg = get_cfg("6c_Fpn4321")
+    torch.manual_seed(0)
+    model = build_detection_model(cfg).to(dev).train()
+    T.freeze_unused(model)
+    pcl = torch.from_numpy(make_scene(7, 60000, (25.0, 19.0, 2.7))).to(dev)
+    b, l = make_targets(7, (25.0, 19.0, 2.7))
+    points, tgs = engine.collate([(pcl, {"bbox3d": torch.from_numpy(b).to(dev), "labels": torch.from_numpy(l).to(dev)})],
+                                 cfg)
+    points, tgs = [points[0][:, :3].contiguous(), points[1]], tgs[0]
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+
+    def step():
+        model.load_state_dict(state)
+        model.zero_grad(set_to_none=True)
+        torch.manual_seed(1234)
+        losses = model(points, tgs)
+        sum(losses.values()).backward()
+        return ({k: v.detach().clone() for k, v in losses.items()},
+                {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None})
+
+    was = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        with _precision("tf32"):
+            l1, g1 = step()
+            l2, g2 = step()
+    finally:
+        torch.use_deterministic_algorithms(was)
+    assert len(l1) >= 4 and all(bool(torch.isfinite(v).all()) for v in l1.values())
+    for k in l1:
+        assert torch.equal(l1[k], l2[k]), k
+    assert set(g1) == set(g2) and len(g1) > 50
+    assert not [k for k in g1 if not torch.equal(g1[k], g2[k])]
+
+
+def test_bf16_storage_ignores_the_setting(dev):
+    """compute_dtype = bfloat16: the same bits under 'tf32' as under the default"""
+    from detection_3d_amd import sparseconvnet as scn
+    size = (256, 256, 32)
+    _, coords, feats = small_scene(7, 60000, (5.0, 4.0, 0.6), size)
+    torch.manual_seed(0)
+    net = scn.FPN_Net([256, 256, 32], 3, ['xyz', 'color', 'normal'], 1, [32, 64, 64, 128, 128], nPlaneM=128,
+                      residual_blocks=True, fpn_scales_from_top=[2, 1], roi_scales_from_top=(2, 1),
+                      downsample=[[[2, 2, 2]] * 4] * 2, rpn_map_sizes=[[64, 64, 8], [32, 32, 4]],
+                      voxel_scale=50, rpn_3d_2d_selector=[1, 2, 3], bn_momentum=0.95,
+                      track_running_stats=False).to(dev).eval()
+    net.compute_dtype = torch.bfloat16
+    inp = [torch.from_numpy(coords), torch.from_numpy(feats).to(dev)]
+    with torch.no_grad():
+        a, b = _both(lambda: _flatten(net(inp)))
+    assert len(a) == len(b) > 0
+    for x, y in zip(a, b):
+        assert torch.equal(x.features, y.features)
