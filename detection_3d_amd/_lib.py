@@ -38,6 +38,8 @@ _SIGS = {
     "d3d_grid_chain_enable": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_ws_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_late_mode": (ctypes.c_int, [ctypes.c_int]),
+    "d3d_conv_split_mode": (ctypes.c_int, [ctypes.c_int]),
+    "d3d_conv_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
     "d3d_conv_dw_deterministic": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_dw_thread_mode": (ctypes.c_int, [ctypes.c_int, vp, ctypes.c_size_t]),
     "d3d_conv_dw_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

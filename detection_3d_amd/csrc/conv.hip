@@ -432,6 +432,23 @@ static bool g_conv_late = [] {            // D3D_CONV_LATE=0: gathers issued ahe
   const char *e = getenv("D3D_CONV_LATE");
   return !(e && e[0] == '0');
 }();
+static int g_conv_split = 0;   // d3d_conv_split_mode: 0 automatic, 1 never split, 2 split wherever the form allows it
+
+int conv_n_split(bool allowed, int K, long waves, long target) {
+  if (!allowed || K <= 1 || g_conv_split == 1) return 1;
+  const int n = (int)std::min<long>(K, (target + waves - 1) / waves);
+  if (g_conv_split == 2) return std::max(n, 2);
+  return waves < target ? n : 1;
+}
+
+// d3d_conv_last_form: family, CT, NCT, COUT, BPW, RB, VEC, LATE, n_split, stats, n_blk, K
+static constexpr int kFormFields = 12;
+static thread_local int t_last_form[kFormFields] = {};
+void conv_record_form(int family, int ct, int nct, int cout, int bpw, int rb, bool vec, bool late, int n_split,
+                      bool stats, int n_blk, int K) {
+  const int f[kFormFields] = {family, ct, nct, cout, bpw, rb, vec ? 1 : 0, late ? 1 : 0, n_split, stats ? 1 : 0, n_blk, K};
+  std::copy(f, f + kFormFields, t_last_form);
+}
 
 // d3d_conv_time_next: HIP events the next k_conv launch of this thread is bracketed with (measurement only)
 static thread_local hipEvent_t t_time_start = nullptr, t_time_stop = nullptr;
@@ -454,10 +471,7 @@ static int launch_t(d3d_meta *m, const Plan &p, const float *in, int cin, const 
   constexpr int threads = BPW * WPBLK * 64;
   const int npos = p.n_blk * 32;
   const long waves = (long)p.n_blk * WPBLK;
-  int n_split = 1;
-  if (BPW == 1 && p.K > 1 && m) {
-    if (waves < kSplitTargetWaves) n_split = (int)std::min<long>(p.K, (kSplitTargetWaves + waves - 1) / waves);
-  }
+  int n_split = conv_n_split(BPW == 1 && m, p.K, waves, kSplitTargetWaves);
   float *partial = nullptr;
   size_t mark = 0;
   if (n_split > 1) {
@@ -476,20 +490,24 @@ static int launch_t(d3d_meta *m, const Plan &p, const float *in, int cin, const 
   const hipEvent_t ev_start = t_time_start, ev_stop = t_time_stop;
   t_time_start = t_time_stop = nullptr;
   if (ev_start) (void)hipEventRecord(ev_start, s);
-  if (cin == CT * NCT && n_split == 1 && launch_conv_ws(p, in, cin, wp, COUT, residual, out, s, pre, stat, in_bytes)) {
-    // (taken by the weight-sharing kernel: same products in the same order)
-  } else if (cin == CT * NCT && g_conv_late && CT >= 32)
-    hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, true, true>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT, npos,
-                       p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
-                       n_split > 1 ? nullptr : stat);
-  else if (cin == CT * NCT)
-    hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, true>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT, npos,
-                       p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
-                       n_split > 1 ? nullptr : stat);
-  else
-    hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, false>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT, npos,
-                       p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
-                       n_split > 1 ? nullptr : stat);
+  const bool vec = cin == CT * NCT, late = vec && g_conv_late && CT >= 32;
+  if (vec && n_split == 1 && launch_conv_ws(p, in, cin, wp, COUT, residual, out, s, pre, stat, in_bytes)) {
+    // (taken by the weight-sharing kernel: same products in the same order; it records its form)
+  } else {
+    conv_record_form(kFormConv, CT, NCT, COUT, BPW, 1, vec, late, n_split, stat != nullptr, p.n_blk, p.K);
+    if (late)
+      hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, true, true>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT,
+                         npos, p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
+                         n_split > 1 ? nullptr : stat);
+    else if (vec)
+      hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, true>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT, npos,
+                         p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
+                         n_split > 1 ? nullptr : stat);
+    else
+      hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, false>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT, npos,
+                         p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
+                         n_split > 1 ? nullptr : stat);
+  }
   if (ev_stop) (void)hipEventRecord(ev_stop, s);   // k_conv alone: the reduction of an offset-split launch follows
   if (n_split > 1) {
     const long total = (long)npos * (COUT / 4);
@@ -574,6 +592,18 @@ int d3d_conv_late_mode(int on) {
   const int was = g_conv_late ? 1 : 0;
   if (on >= 0) g_conv_late = on != 0;
   return was;
+}
+
+int d3d_conv_split_mode(int mode) {
+  const int was = g_conv_split;
+  if (mode >= 0 && mode <= 2) g_conv_split = mode;
+  return was;
+}
+
+int d3d_conv_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kFormFields; i++) out[i] = t_last_form[i];
+  std::fill(t_last_form, t_last_form + kFormFields, 0);
+  return kFormFields;
 }
 
 int d3d_conv_time_next(void *start_event, void *stop_event) {

@@ -461,9 +461,7 @@ static int launch_tb(d3d_meta *m, const Plan &p, const T *in, const bf16_t *wp, 
   constexpr int threads = BPW * WPBLK * 64;
   const int npos = p.n_blk * 32;
   const long waves = (long)((p.n_blk + RB - 1) / RB) * WPBLK;
-  int n_split = 1;
-  if (BPW == 1 && p.K > 1 && m && waves < kSplitTargetWavesB)
-    n_split = (int)std::min<long>(p.K, (kSplitTargetWavesB + waves - 1) / waves);
+  int n_split = conv_n_split(BPW == 1 && m, p.K, waves, kSplitTargetWavesB);
   float *partial = nullptr;
   size_t mark = 0;
   if (n_split > 1) {
@@ -475,6 +473,7 @@ static int launch_tb(d3d_meta *m, const Plan &p, const T *in, const bf16_t *wp, 
   hipEvent_t ev_start, ev_stop;
   conv_timing_take(&ev_start, &ev_stop);
   if (ev_start) (void)hipEventRecord(ev_start, s);
+  conv_record_form(sizeof(T) == 4 ? kFormX3 : kFormBf16, CT, NCT, COUT, BPW, RB, true, false, n_split, false, p.n_blk, p.K);
   hipLaunchKernelGGL((k_conv_bf16<CT, NCT, COUT, BPW, RB, T>), grid, dim3(threads), 0, s, in, wp, p.nbrT, npos, p.rows,
                      p.blkmask, p.n_blk, residual, out, n_split, partial, pre);
   if (ev_stop) (void)hipEventRecord(ev_stop, s);

@@ -248,12 +248,14 @@ bool launch_conv_ws(const Plan &p, const float *in, int cin, const float *wp, in
   const int npos = p.n_blk * 32;
   if (cin == 64 && cout == 64) {
     constexpr int RBW = 4;
+    conv_record_form(kFormWs, 64, 1, 64, RBW, 1, true, false, 1, stat != nullptr, p.n_blk, p.K);
     hipLaunchKernelGGL((k_conv_ws<64, 64, 64, RBW>), dim3((p.n_blk + RBW - 1) / RBW), dim3(RBW * 64), 0, s, in, wp, p.nbrT,
                        npos, p.rows, p.blkmask, p.n_blk, residual, out, pre, in_bytes, stat);
     return true;
   }
   if (cin == 128 && cout == 128) {
     constexpr int RBW = 4;
+    conv_record_form(kFormWs, 32, 4, 128, RBW, 1, true, false, 1, stat != nullptr, p.n_blk, p.K);
     hipLaunchKernelGGL((k_conv_ws<128, 128, 32, RBW>), dim3((p.n_blk + RBW - 1) / RBW), dim3(RBW * 64), 0, s, in, wp, p.nbrT,
                        npos, p.rows, p.blkmask, p.n_blk, residual, out, pre, in_bytes, stat);
     return true;

@@ -261,6 +261,13 @@ struct BnPre {  // fused BatchNorm(+leaky ReLU) prologue of a convolution; mean 
   float leak;
 };
 void conv_timing_take(hipEvent_t *start, hipEvent_t *stop);   // events armed by d3d_conv_time_next (or nullptr), disarms
+// offset-split count of a launch of `waves` waves against `target` under d3d_conv_split_mode; 1 where the form cannot
+// split (allowed == false: several row blocks per workgroup, or no scratch arena)
+int conv_n_split(bool allowed, int K, long waves, long target);
+// d3d_conv_last_form: what the calling thread's most recent convolution launch ran (host side only)
+enum ConvFamily { kFormNone = 0, kFormConv = 1, kFormWs = 2, kFormBf16 = 3, kFormX3 = 4 };
+void conv_record_form(int family, int ct, int nct, int cout, int bpw, int rb, bool vec, bool late, int n_split,
+                      bool stats, int n_blk, int K);
 // conv_bf16.hip
 // dtype D3D_BF16, or D3D_F32_X3 (fp32 rows, bf16x3 products) for the shapes conv_x3_serves admits
 int launch_conv_bf16(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,

@@ -66,6 +66,16 @@ int d3d_conv_ws_mode(int mode);
 /* ... and whether k_conv requests the next step's gathered rows behind the step's first MFMAs (1, default) or ahead of its
  * matrix work (0).  Same results.  on < 0: query only.  -> previous setting.  Environment: D3D_CONV_LATE.              */
 int d3d_conv_late_mode(int on);
+/* Test hook of every sparse convolution launch (k_conv and the bf16 / bf16x3 kernel, process-wide): 0 (default) =
+ * offset-split below the launch's wave target, 1 = never split, 2 = split every launch whose form allows it (one row
+ * block per workgroup, filter volume > 1).  Same products, other summation grouping.  mode < 0: query only.
+ * -> the previous setting.                                                                                          */
+int d3d_conv_split_mode(int mode);
+/* The form of the calling thread's most recent sparse convolution launch, recorded on the host: up to n of the ints
+ * family (0 none, 1 k_conv, 2 k_conv_ws, 3 bf16, 4 bf16x3), CT, NCT, COUT, BPW, RB, VEC, LATE, n_split, statistics
+ * epilogue written (0 / 1), row blocks, filter volume.  The record is cleared by the call (out may be null).
+ * -> the number of fields the record has.                                                                            */
+int d3d_conv_last_form(int *out, int n);
 /* ... and how many of the leading levels form a chain (and read-back) of their own before the chain over the rest (default
  * 1: the first strided grid is wanted long before a chain over all levels ends; 0: one chain).  -> previous setting.   */
 int d3d_grid_chain_head(int levels);

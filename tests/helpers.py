@@ -1,5 +1,7 @@
 """Shared test helpers: small synthetic scenes and a numpy composition of the FPN backbone out of
 oracle ops (the checker for the HIP backbone)."""
+import contextlib
+
 import numpy as np
 
 import oracle
@@ -95,3 +97,52 @@ def roi_subsample_reference(lossf, proposals, gt_boxes, gt_labels):
     pos, neg = lossf.sampler(labels)
     keep = torch.sort(torch.cat([pos, neg]))[0]
     return proposals[keep], labels[keep], reg[keep]
+
+
+def rules_conv64(x, w, rules, n_out):
+    """fp64: y, sum_k |x||w|, ||x o w||_2 and the products of bf16-rounded operands, per output element (an output
+    meets an offset at most once in these rulebooks, so a fancy-indexed add per offset is exact)"""
+    import torch
+    K, cin, cout = w.shape
+    x64, w64 = x.astype(np.float64), w.astype(np.float64)
+    xb = torch.from_numpy(x).to(torch.bfloat16).double().numpy()
+    wb = torch.from_numpy(w).to(torch.bfloat16).double().numpy()
+    y, a, s2, yb = (np.zeros((n_out, cout)) for _ in range(4))
+    for k in range(K):
+        sel = rules[:, 2] == k
+        i, o = rules[sel, 0], rules[sel, 1]
+        assert np.unique(o).size == o.size
+        y[o] += x64[i] @ w64[k]
+        a[o] += np.abs(x64[i]) @ np.abs(w64[k])
+        s2[o] += (x64[i] ** 2) @ (w64[k] ** 2)
+        yb[o] += xb[i] @ wb[k]
+    return y, a, np.sqrt(s2), yb
+
+
+def saved_precision():
+    """torch's fp32 matmul precision, both APIs' state (the legacy level read while the two agree, as they do between
+    tests)"""
+    import torch
+    return (torch.get_float32_matmul_precision(), torch.backends.cuda.matmul.fp32_precision,
+            torch.backends.fp32_precision)
+
+
+def restore_precision(saved):
+    import torch
+    legacy, matmul, generic = saved
+    torch.set_float32_matmul_precision(legacy)
+    torch.backends.fp32_precision = generic
+    torch.backends.cuda.matmul.fp32_precision = matmul
+
+
+@contextlib.contextmanager
+def precision(value):
+    """'tf32' -> set_float32_matmul_precision('high'), 'ieee' -> 'highest' for the block, restored afterwards (fp32
+    sparse convolutions run as bf16x3 under 'tf32')"""
+    import torch
+    saved = saved_precision()
+    torch.set_float32_matmul_precision("high" if value == "tf32" else "highest")
+    try:
+        yield
+    finally:
+        restore_precision(saved)

@@ -8,42 +8,18 @@ changes the precision setting restores it.
 The modes are set with torch.set_float32_matmul_precision('high' / 'highest'), which sets the legacy and the new API
 alike: on torch 2.10 assigning torch.backends.cuda.matmul.fp32_precision = 'tf32' alone leaves the two disagreeing, and
 torch's own matmuls (the detector's heads) then raise.  The library reads either (test_conv_precision_cpu.py)."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from tests.helpers import nbr_to_rules, small_scene
+from tests.helpers import precision as _precision, restore_precision as _restore, rules_conv64 as _rules_conv64
+from tests.helpers import saved_precision as _saved
 
 pytestmark = pytest.mark.gpu
 HARD = 2.5e-4
 STAT = 1e-3
-
-
-def _saved():
-    """both APIs' state (the legacy level read while the two agree, as they do between tests)"""
-    return (torch.get_float32_matmul_precision(), torch.backends.cuda.matmul.fp32_precision,
-            torch.backends.fp32_precision)
-
-
-def _restore(saved):
-    legacy, matmul, generic = saved
-    torch.set_float32_matmul_precision(legacy)
-    torch.backends.fp32_precision = generic
-    torch.backends.cuda.matmul.fp32_precision = matmul
-
-
-@contextlib.contextmanager
-def _precision(value):
-    """'tf32' -> set_float32_matmul_precision('high'), 'ieee' -> 'highest' for the block, restored afterwards"""
-    saved = _saved()
-    torch.set_float32_matmul_precision("high" if value == "tf32" else "highest")
-    try:
-        yield
-    finally:
-        _restore(saved)
 
 
 @pytest.fixture(autouse=True)
@@ -73,25 +49,6 @@ def _check_mode(got, exact, fv, cin, cout):
         assert not torch.equal(got, exact)
     else:
         assert torch.equal(got, exact)
-
-
-def _rules_conv64(x, w, rules, n_out):
-    """fp64: y, sum_k |x||w|, ||x o w||_2 and the products of bf16-rounded operands, per output element (an output
-    meets an offset at most once in these rulebooks, so a fancy-indexed add per offset is exact)"""
-    K, cin, cout = w.shape
-    x64, w64 = x.astype(np.float64), w.astype(np.float64)
-    xb = torch.from_numpy(x).to(torch.bfloat16).double().numpy()
-    wb = torch.from_numpy(w).to(torch.bfloat16).double().numpy()
-    y, a, s2, yb = (np.zeros((n_out, cout)) for _ in range(4))
-    for k in range(K):
-        sel = rules[:, 2] == k
-        i, o = rules[sel, 0], rules[sel, 1]
-        assert np.unique(o).size == o.size
-        y[o] += x64[i] @ w64[k]
-        a[o] += np.abs(x64[i]) @ np.abs(w64[k])
-        s2[o] += (x64[i] ** 2) @ (w64[k] ** 2)
-        yb[o] += xb[i] @ wb[k]
-    return y, a, np.sqrt(s2), yb
 
 
 def _check_bounds(got, y, a, norm, yb=None):
