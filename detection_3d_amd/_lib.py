@@ -35,7 +35,6 @@ _SIGS = {
     "d3d_geometry_async_start": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "d3d_geometry_async_wait": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), vp]),
     "d3d_geometry_async_finish": (ctypes.c_int, [vp]),
-    "d3d_grid_chain_enable": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_ws_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_late_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_split_mode": (ctypes.c_int, [ctypes.c_int]),
@@ -43,7 +42,6 @@ _SIGS = {
     "d3d_conv_dw_deterministic": (ctypes.c_int, [ctypes.c_int]),
     "d3d_conv_dw_thread_mode": (ctypes.c_int, [ctypes.c_int, vp, ctypes.c_size_t]),
     "d3d_conv_dw_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "d3d_grid_chain_head": (ctypes.c_int, [ctypes.c_int]),
     "d3d_sort_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_sort_pairs": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
     "d3d_conv_time_next": (ctypes.c_int, [vp, vp]),

@@ -1378,17 +1378,11 @@ namespace d3d {
 // while it waits.  The thread builds the listed rulebooks in order on the geometry stream and publishes, per entry,
 // the output site count and an event; the caller picks an entry up when it needs it (d3d_geometry_async_wait).
 // A new strided grid is complete (hash table, coordinates, site count) as soon as its count has been read back, before
-// the strided rulebook that d3d_conv_prepare builds with it: it is entered into the metadata then, and a geometry thread
-// may mark the moment on its stream (t_on_grid) so that the grid's views do not wait for the rulebook.
-static thread_local void (*t_on_grid)(void *, hipStream_t) = nullptr;
-static thread_local void *t_on_grid_arg = nullptr;
-static void publish_grid(d3d_meta *m, Grid &go, int n_out, const int *out_size, hipStream_t s) {
+// the strided rulebook that d3d_conv_prepare builds with it: it is entered into the metadata then.
+static void publish_grid(d3d_meta *m, Grid &go, int n_out, const int *out_size) {
   go.n = n_out;
-  {
-    D3D_LOCK(m);
-    m->grids[Size3{out_size[0], out_size[1], out_size[2]}] = go;
-  }
-  if (t_on_grid) t_on_grid(t_on_grid_arg, s);
+  D3D_LOCK(m);
+  m->grids[Size3{out_size[0], out_size[1], out_size[2]}] = go;
 }
 
 struct GeoAsync {
@@ -2149,7 +2143,7 @@ int d3d_conv_prepare(d3d_meta *m, const int *in_size, const int *out_size, const
       D3D_HIP_CHECK(hipStreamSynchronize(s));
       n_out = (int)*(int32_t *)&m->host_words[1];
       A.used = mark;
-      publish_grid(m, go, n_out, out_size, s);
+      publish_grid(m, go, n_out, out_size);
       int rc = finalize_plan(m, nbr_fwd, n_out, K, p, s, nullptr);
       if (rc) return rc;
     } else if (n_entries > 0) {
@@ -2176,7 +2170,7 @@ int d3d_conv_prepare(d3d_meta *m, const int *in_size, const int *out_size, const
       D3D_HIP_CHECK(hipMemcpyAsync(&m->host_words[1], total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
       D3D_HIP_CHECK(hipStreamSynchronize(s));
       n_out = (int)*(int32_t *)&m->host_words[1];
-      publish_grid(m, go, n_out, out_size, s);
+      publish_grid(m, go, n_out, out_size);
       D3D_HIP_CHECK(fill_ones(nbr_fwd, sizeof(int32_t) * ((size_t)n_out * K + 1), s));
       hipLaunchKernelGGL(k_conv_fill, grid1d(n_entries), dim3(256), 0, s, gi->loc, n_entries, geo, K, eslot, tab, nbr_fwd, nbr_dec,
                          (const int32_t *)nullptr);
@@ -2185,7 +2179,7 @@ int d3d_conv_prepare(d3d_meta *m, const int *in_size, const int *out_size, const
       rc = finalize_plan(m, nbr_fwd, n_out, K, p, s, nullptr);
       if (rc) return rc;
     } else {
-      publish_grid(m, go, 0, out_size, s);
+      publish_grid(m, go, 0, out_size);
       int rc = finalize_plan(m, nullptr, 0, K, p, s, nullptr);
       if (rc) return rc;
     }
@@ -2451,16 +2445,9 @@ static int run_grid_chain(d3d_meta *m, const std::vector<ChainSpec> &specs, hipS
   return D3D_OK;
 }
 
-// D3D_GRID_CHAIN=0 (or d3d_grid_chain_enable(0)): one d3d_conv_prepare (and read-back) per level, for A/B runs
-static bool g_chain_enabled = [] {
-  const char *e = getenv("D3D_GRID_CHAIN");
-  return !(e && e[0] == '0');
-}();
-
-static int g_chain_head = [] {
-  const char *e = getenv("D3D_GRID_CHAIN_HEAD");
-  return e ? atoi(e) : 1;
-}();
+// levels of the first chain: the feature pass wants the first strided grid (and its rulebooks) a few hundred microseconds
+// after the input grid, before a chain over all levels has finished -- so it gets a read-back of its own
+constexpr size_t kChainHead = 1;
 
 static void geo_run_grids(d3d_meta *m, GeoAsync *g) {      // the grids of the pyramid: two chains, two read-backs
   int rc = geo_begin(g);
@@ -2475,73 +2462,45 @@ static void geo_run_grids(d3d_meta *m, GeoAsync *g) {      // the grids of the p
     bool failed;
     int first;                              // row of `rows` the running chain's level 0 is
   } hk = {g, &rows, false, 0};
-  if (g_chain_enabled && rc == D3D_OK) {
-    std::vector<ChainSpec> specs(rows.size());
-    for (size_t j = 0; j < rows.size(); j++) {
-      const int *sp = g->specs[rows[j]].data() + 1;
-      for (int d = 0; d < 3; d++) {
-        specs[j].in_size[d] = sp[d];
-        specs[j].out_size[d] = sp[3 + d];
-        specs[j].filt[d] = sp[6 + d];
-        specs[j].stride[d] = sp[9 + d];
-      }
-      specs[j].need_dec = g->specs[rows[j]][0] == 1;      // kind 3: a strided grid whose decoded table nobody will ask for
+  std::vector<ChainSpec> specs(rows.size());
+  for (size_t j = 0; j < rows.size(); j++) {
+    const int *sp = g->specs[rows[j]].data() + 1;
+    for (int d = 0; d < 3; d++) {
+      specs[j].in_size[d] = sp[d];
+      specs[j].out_size[d] = sp[3 + d];
+      specs[j].filt[d] = sp[6 + d];
+      specs[j].stride[d] = sp[9 + d];
     }
-    // Two chains: the first level alone -- the feature pass wants it (and its rulebooks) a few hundred microseconds after
-    // the input grid, before a chain over all levels has finished -- then every other level in one go.
-    const ChainHook on_grid = [](void *a, int level, int, hipStream_t on) {       // the grid exists: its views may start
-      Hook *h = (Hook *)a;
-      const int i = (*h->rows)[h->first + level];
-      if (hipEventRecord(h->g->gev[i], on) != hipSuccess) return;
-      std::lock_guard<std::mutex> lk(h->g->mu);
-      h->g->grid_ready[i] = 1;
-      h->g->cv.notify_all();
-    };
-    const ChainHook on_done = [](void *a, int level, int n_sites, hipStream_t on) {   // its strided rulebook is enqueued
-      Hook *h = (Hook *)a;
-      const int i = (*h->rows)[h->first + level];
-      int rc2 = D3D_OK;
-      if (hipEventRecord(h->g->ev[i], on) != hipSuccess) {
-        set_error("geometry thread: hipEventRecord failed");
-        rc2 = D3D_ERR_HIP;
-      }
-      if (!geo_publish(h->g, i, rc2, n_sites)) h->failed = true;
-    };
-    const size_t cut = std::min<size_t>(g_chain_head, specs.size());
-    for (int part = 0; part < 2 && rc == D3D_OK && !hk.failed; part++) {
-      const size_t lo = part == 0 ? 0 : cut, hi = part == 0 ? cut : specs.size();
-      if (lo >= hi) continue;
-      std::vector<ChainSpec> seg(specs.begin() + lo, specs.begin() + hi);
-      std::vector<int> n_out;
-      hk.first = (int)lo;
-      rc = run_grid_chain(m, seg, g->stream, n_out, on_grid, on_done, &hk);
-    }
-    if (rc != D3D_OK) geo_publish(g, rows[0], rc, 0);
-    return;
+    specs[j].need_dec = g->specs[rows[j]][0] == 1;      // kind 3: a strided grid whose decoded table nobody will ask for
   }
-  for (int i : rows) {
-    const int *sp = g->specs[i].data() + 1;
-    int n_out = 0;
-    struct Mark {
-      GeoAsync *g;
-      int i;
-    } mk = {g, i};
-    t_on_grid_arg = &mk;
-    t_on_grid = [](void *a, hipStream_t on) {       // the grid exists: its submanifold views may start
-      Mark *k = (Mark *)a;
-      if (hipEventRecord(k->g->gev[k->i], on) != hipSuccess) return;   // (then the views wait for the whole entry)
-      std::lock_guard<std::mutex> lk(k->g->mu);
-      k->g->grid_ready[k->i] = 1;
-      k->g->cv.notify_all();
-    };
-    if (rc == D3D_OK) rc = d3d_conv_prepare(m, sp, sp + 3, sp + 6, sp + 9, g->stream, &n_out, nullptr);
-    t_on_grid = nullptr;
-    if (rc == D3D_OK && hipEventRecord(g->ev[i], g->stream) != hipSuccess) {
+  const ChainHook on_grid = [](void *a, int level, int, hipStream_t on) {       // the grid exists: its views may start
+    Hook *h = (Hook *)a;
+    const int i = (*h->rows)[h->first + level];
+    if (hipEventRecord(h->g->gev[i], on) != hipSuccess) return;
+    std::lock_guard<std::mutex> lk(h->g->mu);
+    h->g->grid_ready[i] = 1;
+    h->g->cv.notify_all();
+  };
+  const ChainHook on_done = [](void *a, int level, int n_sites, hipStream_t on) {   // its strided rulebook is enqueued
+    Hook *h = (Hook *)a;
+    const int i = (*h->rows)[h->first + level];
+    int rc2 = D3D_OK;
+    if (hipEventRecord(h->g->ev[i], on) != hipSuccess) {
       set_error("geometry thread: hipEventRecord failed");
-      rc = D3D_ERR_HIP;
+      rc2 = D3D_ERR_HIP;
     }
-    if (!geo_publish(g, i, rc, n_out)) return;
+    if (!geo_publish(h->g, i, rc2, n_sites)) h->failed = true;
+  };
+  const size_t cut = std::min(kChainHead, specs.size());
+  for (int part = 0; part < 2 && rc == D3D_OK && !hk.failed; part++) {
+    const size_t lo = part == 0 ? 0 : cut, hi = part == 0 ? cut : specs.size();
+    if (lo >= hi) continue;
+    std::vector<ChainSpec> seg(specs.begin() + lo, specs.begin() + hi);
+    std::vector<int> n_out;
+    hk.first = (int)lo;
+    rc = run_grid_chain(m, seg, g->stream, n_out, on_grid, on_done, &hk);
   }
+  if (rc != D3D_OK) geo_publish(g, rows[0], rc, 0);
 }
 static void geo_run_views(d3d_meta *m, GeoAsync *g) {      // the views: each behind the newest grid listed before it
   int rc = geo_begin(g);
@@ -2580,18 +2539,6 @@ static void geo_run_views(d3d_meta *m, GeoAsync *g) {      // the views: each be
 }  // namespace d3d
 
 extern "C" {
-
-// (levels of the first chain: 1 = the first strided grid gets a read-back of its own, 0 = one chain for all levels)
-int d3d_grid_chain_head(int levels) {
-  const int was = g_chain_head;
-  g_chain_head = levels < 0 ? 0 : levels;
-  return was;
-}
-int d3d_grid_chain_enable(int on) {
-  const int was = g_chain_enabled ? 1 : 0;
-  g_chain_enabled = on != 0;
-  return was;
-}
 
 int d3d_geometry_async_start(d3d_meta *m, const int *specs, int n, void *stream, void *view_stream) {
   D3D_REQUIRE(m && (n == 0 || specs) && n >= 0 && n <= 128, "geometry_async_start: bad arguments");

@@ -397,10 +397,10 @@ _TLS = threading.local()
 
 
 def set_after_input_build(hook, prefetch_filter=None):
-    """hook(metadata, spatial_size[, run_forward]) is called by this thread's next InputLayer_updateOutput calls between
+    """hook(metadata, spatial_size, run_forward) is called by this thread's next InputLayer_updateOutput calls between
     the grid build (whose site count has just been read back) and the feature pass of the input layer -- where a caller
-    can start the level-0 rulebook on another stream (FPN_Net._forward_two_lane) and, through run_forward(stream), place
-    the feature pass itself.  None removes it.
+    can start the geometry of the pyramid on side streams (FPN_Net._forward_async_geometry) and, through
+    run_forward(stream), place the feature pass itself.  None removes it.
     prefetch_filter: the filter of the submanifold rulebook the caller will prepare first on the same stream; its
     neighbour table is then probed while the host waits for the site count (d3d_input_layer_build_prefetch)."""
     _TLS.after_input_build = hook
@@ -414,8 +414,10 @@ def InputLayer_prepare(m):
 
 def InputLayer_updateOutput(m, spatial_size, input_coords, input_features, output_features,
                             batch_size, mode):
-    """sparseconvnet.h:159-163.  input_coords int64 [N,3|4] on CPU or GPU."""
-    require_gpu(input_features)
+    """sparseconvnet.h:159-163.  input_coords int64 [N,3|4] on CPU or GPU; input_features [N,C] on the GPU, strided
+    ones (a column slice of a point cloud) are copied."""
+    if not input_features.is_cuda:
+        require_gpu(input_features)
     dev = input_features.device
     coords = _coords_to_device(input_coords, dev)
     n, ncols = coords.shape
@@ -428,28 +430,31 @@ def InputLayer_updateOutput(m, spatial_size, input_coords, input_features, outpu
     planes = input_features.shape[1]
     output_features.resize_(na.value, planes)       # (allocated on the caller's stream, whichever stream fills it)
     feats = input_features.contiguous()
+    # work the caller's stream holds on the pass's operands behind the count read-back (everything before it is complete
+    # once the host has the count): the copy of strided features, the NaN fill of resize_ in deterministic mode
+    caller = torch.cuda.current_stream(dev) if feats is not input_features or _lib.fills_uninitialized() else None
     done = []
 
     def run_forward(on=None):
         """the input layer's feature pass (d3d_input_layer_forward), on stream `on` (a torch stream) or the current one;
-        the hook may call it where it suits its streams -- e.g. right behind the point lists on a side stream.
-        -> the tensor being filled (None when the pass was already enqueued)"""
+        the hook may call it where it suits its streams -- e.g. right behind the point lists on a side stream.  `on`
+        waits for the caller's stream only when that holds work on the operands (else the level-0 neighbour probes
+        enqueued there would be put in front of the pass).  -> the tensor being filled (None when already enqueued)"""
         if done:
             return None
         done.append(True)
         if on is None:
             check(lib().d3d_input_layer_forward(m._h, ptr(feats), planes, ptr(output_features), stream_of()))
         else:
+            if caller is not None:
+                on.wait_stream(caller)
             with torch.cuda.stream(on):
                 check(lib().d3d_input_layer_forward(m._h, ptr(feats), planes, ptr(output_features), stream_of()))
         return output_features
 
     hook = getattr(_TLS, "after_input_build", None)
     if hook is not None:
-        if hook.__code__.co_argcount >= 3:
-            hook(m, spatial_size, run_forward)
-        else:
-            hook(m, spatial_size)
+        hook(m, spatial_size, run_forward)
     run_forward()
 
 

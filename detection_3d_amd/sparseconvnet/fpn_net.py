@@ -2,7 +2,7 @@
 SparseConvNet/sparseconvnet/fpn_net.py:12-137 (so `backbone.*` checkpoint keys load unchanged),
 same outputs as its forward_fpn (:168-265), executed by the HIP ops of libd3d_hip.so.
 
-Execution switches that do not change any returned tensor (TWO_LANE below is a third):
+Execution switches that do not change any returned tensor (SIDE_STREAMS below is a third):
   * fuse_adds     -- residual / lateral additions run in the epilogue of the producing
                      convolution instead of a separate AddTable / add_feature_planes pass;
   * skip_unused   -- the top-down levels whose outputs nothing consumes for the configured
@@ -15,18 +15,11 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib
 from . import modules as scn
 from ..timeline import mark as _tmark
 
-TWO_LANE = True     # grid chain of the coarser levels on a side stream while the finer ones convolve
-PLAN_LANE = os.environ.get("D3D_PLAN_LANE", "0") != "0"   # ... and each level's submanifold / deconvolution rulebooks on a third
-                    # (measured: 6.2-6.6 ms per building against 6.1-6.4 without -- the kernels it overlaps slow each other down)
-ASYNC_GEOMETRY = os.environ.get("D3D_ASYNC_GEOMETRY", "1") != "0"   # the grid chain is run by a thread of the library
-                    # (d3d_geometry_async_*): its count read-backs no longer stop this thread from enqueueing
-ASYNC_VIEWS = os.environ.get("D3D_ASYNC_VIEWS", "1") != "0"         # ... and that thread also enqueues the views (third stream)
-SIDE_START = os.environ.get("D3D_SIDE_START", "scene")              # "main": side streams wait for the caller's stream at the
-                    # input grid (and the point lists go to the geometry stream), as before the grid chain -- A/B runs
+SIDE_STREAMS = True     # GPU inputs: the geometry of the pyramid on side streams (_forward_async_geometry); False: the
+                        # one-stream pass (tests)
 _GEO_STREAMS = {}   # (device, caller's stream) -> side streams
 # priority of the side streams: 0 = normal (default), -1 = high (geometry ahead of the convolutions).  Measured in pairs on
 # two boxes: 4.80 (high) against 4.82 ms (normal) per building on one, 5.28-5.37 against 4.86-4.95 on the other -- high
@@ -40,14 +33,13 @@ def _is_gpu_input(net0):
 
 
 def _geometry_stream(main):
-    """-> (geometry stream, its reusable per-level events, plan stream, its events) of the caller's stream"""
+    """-> (geometry stream, its reusable events, plan stream) of the caller's stream"""
     key = (main.device.index, main.cuda_stream)
     st = _GEO_STREAMS.get(key)
     if st is None:
         st = _GEO_STREAMS[key] = (torch.cuda.Stream(device=main.device, priority=_SIDE_PRIORITY),
-                                  [torch.cuda.Event() for _ in range(16)],
-                                  torch.cuda.Stream(device=main.device, priority=_SIDE_PRIORITY),
-                                  [torch.cuda.Event() for _ in range(16)])
+                                  [torch.cuda.Event() for _ in range(2)],
+                                  torch.cuda.Stream(device=main.device, priority=_SIDE_PRIORITY))
     return st
 
 
@@ -146,24 +138,19 @@ class FPN_Net(torch.nn.Module):
         return [None if t is None else scn.SparseConvNetTensor(t.features.float(), t.metadata, t.spatial_size) for t in maps]
 
     def forward(self, net0):
-        if TWO_LANE and _is_gpu_input(net0):
-            # (not while torch fills new tensors -- deterministic mode: the pass's side streams do not wait for the
-            # fill kernels that the caller's stream holds for the tensors it allocates, and a fill can land after the
-            # side stream's write; the two-lane pass gives the same bits)
-            if ASYNC_GEOMETRY and not PLAN_LANE and not _lib.fills_uninitialized():
-                return self._forward_async_geometry(net0)
-            return self._forward_two_lane(net0)
+        if SIDE_STREAMS and _is_gpu_input(net0):
+            return self._forward_async_geometry(net0)
         net1 = self.layers_in[1](self._to_compute(self.layers_in[0](net0)))
         return self.forward_fpn(net1)
 
-    def _geometry_specs(self, size0, views=False):
-        """The d3d_conv_prepare calls of the pyramid in the order _geometry_steps makes them, as rows of 13 ints
-        (kind 1, in_size, out_size, filter, stride), and for every level the rows it needs before its convolutions may be
-        enqueued: (its last grid row, its 3x3x3 view row), -1 = none.  With `views` the rulebooks that are views of a grid are listed too
-        (what _geometry_steps builds with full=True): the 3x3x3 submanifold rulebook (kind 0) of every level but the
-        first right behind its grid -- the row a level then waits for -- and, after all grids, the lateral 1x1x1
-        rulebooks and the deconvolution views (kind 2) of the top-down path.
-        -> (rows, last row per level, last row of all)"""
+    def _geometry_specs(self, size0):
+        """The calls the library's geometry thread makes for the pyramid (d3d_geometry_async_start), as rows of 13 ints
+        (kind, in_size, out_size, filter, stride): the d3d_conv_prepare calls in the order _geometry_steps makes them
+        (kind 1 or 3, see below), the 3x3x3 submanifold rulebook (kind 0) of every level but the first right behind its
+        grids and, after all grids, the lateral 1x1x1 rulebooks and the deconvolution views (kind 2) of the top-down
+        path -- the views _geometry_steps builds with full=True.  For every level the rows it needs before its
+        convolutions may be enqueued: (its last grid row, its 3x3x3 view row), -1 = none.
+        -> (rows, rows per level, last row of all)"""
         n_scales = len(self.m_downs)
         n3d = len(self.fpn_scales_from_top)
         sel2d = sorted({i - n3d for i in self.rpn_3d_2d_selector if i >= n3d}) if self.skip_unused else range(n3d)
@@ -172,7 +159,7 @@ class FPN_Net(torch.nn.Module):
         lowest_up = n_scales - 1 - min(n_scales - 1, needed)
         size = scn.toLongTensor(self.dimension, size0)
         three, one = [3] * self.dimension, [1] * self.dimension
-        specs, last, later, sizes = [], [], [], []
+        specs, last, later = [], [], []
         for k in range(n_scales):
             if k > 0:
                 filt = scn.toLongTensor(self.dimension, self.down_kernels[k - 1])
@@ -180,12 +167,11 @@ class FPN_Net(torch.nn.Module):
                 out = (size - filt) // stride + 1
                 # kind 3: no deconvolution / backward view of this rulebook will be asked for (inference, below the
                 # finest level the top-down path reaches): its decoded table is not built
-                need_dec = self.training or torch.is_grad_enabled() or k > lowest_up or not views
+                need_dec = self.training or torch.is_grad_enabled() or k > lowest_up
                 specs.append([1 if need_dec else 3] + size.tolist() + out.tolist() + filt.tolist() + stride.tolist())
-                if views and k > lowest_up:
+                if k > lowest_up:
                     later.append([2] + out.tolist() + size.tolist() + filt.tolist() + stride.tolist())
                 size = out
-            sizes.append(size)
             if k in pro2d:
                 conv = pro2d[k]
                 out = (size - conv.filter_size) // conv.filter_stride + 1
@@ -194,79 +180,78 @@ class FPN_Net(torch.nn.Module):
                              + conv.filter_stride.tolist())
             grid_row = len(specs) - 1 if (k > 0 or k in pro2d) else -1     # the level's last grid / strided rulebook
             view_row = -1
-            if views:
-                if k > 0:           # (level 0's is built by the caller while the point lists are sorted)
-                    specs.append([0] + size.tolist() + size.tolist() + three + one)
-                    view_row = len(specs) - 1
-                if k >= lowest_up:
-                    later.append([0] + size.tolist() + size.tolist() + one + one)
+            if k > 0:               # (level 0's is built by the caller while the point lists are sorted)
+                specs.append([0] + size.tolist() + size.tolist() + three + one)
+                view_row = len(specs) - 1
+            if k >= lowest_up:
+                later.append([0] + size.tolist() + size.tolist() + one + one)
             # a level waits for both: its 3x3x3 view starts as soon as the GRID exists, before the strided rulebook
             last.append((grid_row, view_row))
         specs += later
         return specs, last, len(specs) - 1
 
     def _forward_async_geometry(self, net0):
-        """The pass with the grid chain run by a thread of the library (d3d_geometry_async_start): every new grid costs
-        a blocking read-back of its site count, and while this thread waited for one it could not enqueue the feature
-        kernels of the level before -- by the end of the bottom-up path the caller's stream had caught up with its own
-        launch thread.  Here the chain of all levels starts right after the input grid exists and runs at its own pace
-        on the geometry stream; this thread picks a level up (count + stream dependency) when it is about to enqueue
-        it.  With ASYNC_VIEWS the same thread also enqueues, on a third stream, the rulebooks that are views of a
-        finished grid (3x3x3 right behind each grid; lateral and deconvolution views at the end).  Same kernels on the
-        same data (bit-identical)."""
+        """The pass of every GPU input, with the grid chain run by a thread of the library (d3d_geometry_async_start):
+        every new grid costs a blocking read-back of its site count, and while this thread waited for one it could not
+        enqueue the feature kernels of the level before -- by the end of the bottom-up path the caller's stream had
+        caught up with its own launch thread.  Here the chain of all levels starts right after the input grid exists and
+        runs at its own pace on the geometry stream; this thread picks a level up (count + stream dependency) when it is
+        about to enqueue it.  A second thread of the library enqueues, on the plan stream, the rulebooks that are views
+        of a finished grid (3x3x3 right behind each grid; lateral and deconvolution views at the end).  Same kernels on
+        the same data as the one-stream pass (bit-identical).
+
+        Both side streams start at `scene_start`, behind what the caller's stream held when the pass began, not behind
+        what the pass enqueues there itself.  What the host enqueued on the caller's stream before the input grid's count
+        read-back (the coordinates' copy, the grid) is complete when the hook below runs.  The torch tensors written on a
+        side stream, and why each write follows the tensor's allocation and any fill (in deterministic mode torch fills
+        every new tensor with NaN on the allocating stream):
+          * the input layer's output features: allocated by resize_ on the caller's stream after the read-back, written
+            on the plan stream by run_forward -- which makes the plan stream wait for the caller's stream first whenever
+            that holds a fill of them or a copy of strided input features (SCN.InputLayer_updateOutput).  The only
+            tensor allocated on the caller's stream and written on a side stream.
+          * their bf16 rows (rows_to_bf16): allocated, filled and written on the plan stream, in that order.
+        Everything else the side streams write -- grids, rulebooks, point lists, views -- lives in the metadata's arena,
+        whose reuse from scene to scene is ordered by scene_start.  The caller's stream waits for the plan stream's input
+        work (plan0) before it enqueues anything of the pass, so no block the allocator hands out again is still in use
+        on a side stream; and for both side streams at the end."""
         main = torch.cuda.current_stream(net0[1].device)
-        geo, pool, plan = _geometry_stream(main)[:3]
-        if not ASYNC_VIEWS:
-            plan = None
-        plan0 = pool[-1]
+        geo, pool, plan = _geometry_stream(main)
+        scene_start, plan0 = pool
+        scene_start.record(main)
         state = {}
 
-        # both side streams start behind what the caller's stream held when the pass began (arena reuse from scene to scene
-        # is ordered by that stream); they do NOT wait for what the pass itself enqueues there, see below
-        scene_start = pool[-2]
-        scene_start.record(main)
-
-        def after_input_build(md, size, run_forward=None):
+        def after_input_build(md, size, run_forward):
             # The host has just seen the input grid's site count, i.e. the grid is complete: the side streams need not
             # wait for the caller's stream, which already holds the hash probes of level 0's rulebook (~0.1 ms).
-            if SIDE_START == "main":
-                geo.wait_stream(main)
-            else:
-                geo.wait_event(scene_start)
+            geo.wait_event(scene_start)
             md.set_geometry_stream(geo.cuda_stream)
-            if plan is not None and SIDE_START != "main":
-                plan.wait_event(scene_start)
-                with torch.cuda.stream(plan):
-                    scn.SCN.InputLayer_prepare(md)          # point lists: own scratch (no lane of the arena), ~0.1 ms
-                    if run_forward is not None:             # ... and the per-voxel means right behind them, beside the
-                        means = run_forward(plan)           # sort of level 0's rulebook on the caller's stream
-                        if means is not None and self.compute_dtype == torch.bfloat16 and means.dtype == torch.float32:
-                            # ... and their bf16 rows (one launch; a pad and a cast on the caller's stream were three
-                            # and sat in front of the first convolution)
-                            width = scn.SCN.stored_planes(means.shape[1], self.compute_dtype)
-                            state["stored"] = (means, scn.SCN.rows_to_bf16(means, width))
-                    plan0.record(plan)
-            else:
-                with torch.cuda.stream(geo):
-                    scn.SCN.InputLayer_prepare(md)
-                    plan0.record(geo)
+            plan.wait_event(scene_start)
+            with torch.cuda.stream(plan):
+                scn.SCN.InputLayer_prepare(md)          # point lists: own scratch (no lane of the arena), ~0.1 ms
+                means = run_forward(plan)               # ... and the per-voxel means right behind them, beside the
+                                                        # sort of level 0's rulebook on the caller's stream
+                if means is not None and self.compute_dtype == torch.bfloat16 and means.dtype == torch.float32:
+                    # ... and their bf16 rows (one launch; a pad and a cast on the caller's stream were three and sat
+                    # in front of the first convolution)
+                    width = scn.SCN.stored_planes(means.shape[1], self.compute_dtype)
+                    state["stored"] = (means, scn.SCN.rows_to_bf16(means, width))
+                plan0.record(plan)
             # level 0's 3x3x3 rulebook on this stream (sort + transpose of the probed table, ~0.15 ms); the plan lane is
             # carved out of the feature lane only afterwards, and its stream continues behind this build (whose scratch
             # may reach into what becomes the plan lane)
             _tmark("input grid known (host)", -1, host=True)
             scn.SCN.SubmanifoldConvolution_prepare(size, (3,) * self.dimension, md)
             _tmark("level-0 rulebook", -1, main)
-            if plan is not None:
-                _tmark("point lists + input means", -1, plan)
-                plan.wait_stream(main)
-                md.set_plan_stream(plan.cuda_stream)
+            _tmark("point lists + input means", -1, plan)
+            plan.wait_stream(main)
+            md.set_plan_stream(plan.cuda_stream)
             cache = getattr(self, "_spec_cache", None)
-            key = tuple(scn.SCN._size3(size)) + (plan is not None, bool(self.training), torch.is_grad_enabled())
+            key = tuple(scn.SCN._size3(size)) + (bool(self.training), torch.is_grad_enabled())
             if cache is None or cache[0] != key:
-                cache = self._spec_cache = (key,) + self._geometry_specs(size, views=plan is not None)
+                cache = self._spec_cache = (key,) + self._geometry_specs(size)
             state["last"], state["all"] = cache[2], cache[3]
             # the chain of strided grids starts at once on the geometry stream (one read-back for all of its levels)
-            md.geometry_async_start(cache[1], geo.cuda_stream, plan.cuda_stream if plan is not None else None)
+            md.geometry_async_start(cache[1], geo.cuda_stream, plan.cuda_stream)
             state["md"] = md
             main.wait_event(plan0)
 
@@ -279,15 +264,11 @@ class FPN_Net(torch.nn.Module):
         md = net.metadata
         n_scales = len(self.m_downs)
         try:
-            if "md" not in state:                           # (an input layer that did not go through the hook)
-                after_input_build(md, net.spatial_size)
-
             def lane(k):
                 _tmark("host enters", k, host=True)
                 _tmark("main arrives", k, main)
-                rows = (state["all"],) if k >= n_scales else state["last"][k]
-                for idx in rows:
-                    if idx >= 0 and (k < n_scales or plan is not None):
+                for idx in (state["all"],) if k >= n_scales else state["last"][k]:
+                    if idx >= 0:
                         md.geometry_async_wait(idx, main.cuda_stream)
                 _tmark("main continues", k, main)
                 _tmark("host leaves", k, host=True)
@@ -303,108 +284,9 @@ class FPN_Net(torch.nn.Module):
                 md.geometry_async_finish()
             finally:
                 main.wait_stream(geo)
-                if plan is not None:
-                    main.wait_stream(plan)
-                    md.set_plan_stream(None)
-                md.set_geometry_stream(None)
-        return out
-
-    def _forward_two_lane(self, net0):
-        """Forward pass on three HIP streams: the chain of strided grids (small dependent kernels and one count
-        read-back per grid) is built on a high-priority side stream, level k+1 while the convolutions of level k run on
-        the caller's stream; the rulebooks that are views of a finished grid (3x3x3 / 1x1x1 submanifold, deconvolution)
-        are built on a third stream as soon as their grid exists, instead of by the first convolution that needs them,
-        so neither the grid chain nor the convolutions wait behind their hash probes and sorts.  Same kernels on the
-        same data as the one-stream pass (bit-identical).  Meanwhile the metadata accepts new grids on the geometry
-        stream only and gives each stream its own part of the arena (d3d_meta_set_geometry_stream / _plan_stream).
-        PLAN_LANE False: two streams, the views built on the caller's stream on first use (round 1)."""
-        main = torch.cuda.current_stream(net0[1].device)
-        geo, pool, plan, ppool = _geometry_stream(main)
-        if not PLAN_LANE:
-            plan = None
-        plan0 = pool[-1]
-        three = (3,) * self.dimension
-
-        started = []
-
-        def after_input_build(md, size):
-            # the level-0 grid exists: its 3x3x3 rulebook (hash probes + sort, ~0.4 ms) starts at once while the
-            # geometry stream sorts the input layer's point lists, which the feature pass then only has to wait for
-            started.append(md)
-            geo.wait_stream(main)
-            md.set_geometry_stream(geo.cuda_stream)
-            if plan is not None:
-                plan.wait_stream(main)
-                md.set_plan_stream(plan.cuda_stream)
-                with torch.cuda.stream(plan):
-                    scn.SCN.SubmanifoldConvolution_prepare(size, three, md)
-            else:
-                scn.SCN.SubmanifoldConvolution_prepare(size, three, md)
-            with torch.cuda.stream(geo):
-                scn.SCN.InputLayer_prepare(md)
-                plan0.record(geo)
-            main.wait_event(plan0)
-
-        scn.SCN.set_after_input_build(after_input_build)
-        try:
-            net = self.layers_in[0](net0)                   # input layer: grid of level 0
-        finally:
-            scn.SCN.set_after_input_build(None)
-        md = net.metadata
-        if not started:                                     # (an input layer that did not go through the hook)
-            geo.wait_stream(main)
-            md.set_geometry_stream(geo.cuda_stream)
-            if plan is not None:
-                plan.wait_stream(main)
-                md.set_plan_stream(plan.cuda_stream)
-        steps, events, pevents = self._geometry_steps(net, False, views=plan is not None), [], []
-        n_scales = len(self.m_downs)
-
-        def lane(k):        # level k is about to be enqueued: build its grid now (level k-1 is already in the queue)
-            if k >= n_scales:                               # the top-down path follows: every view has to be there
-                if plan is not None:
-                    main.wait_stream(plan)
-                return
-            _tmark("host enters", k, host=True)
-            _tmark("main arrives", k, main)
-            while len(events) <= k:
-                i = len(events)
-                ev = pool[i] if i < len(pool) - 1 else torch.cuda.Event()
-                with torch.cuda.stream(geo):
-                    _tmark("geo starts", i, geo)
-                    views = next(steps)
-                    ev.record(geo)
-                    _tmark("geo done", i, geo)
-                events.append(ev)
-                _tmark("host has count", i, host=True)
-                if plan is not None:
-                    pev = ppool[i] if i < len(ppool) else torch.cuda.Event()
-                    with torch.cuda.stream(plan):
-                        plan.wait_event(ev)
-                        _tmark("plan starts", i, plan)
-                        views[0]()                          # the 3x3x3 rulebook the level's blocks need
-                        pev.record(plan)
-                        _tmark("plan 3x3x3 done", i, plan)
-                        for v in views[1:]:                 # lateral and deconvolution views: needed on the way up
-                            v()
-                        _tmark("plan views done", i, plan)
-                    pevents.append(pev)
-            main.wait_event(events[k])
-            if plan is not None:
-                main.wait_event(pevents[k])
-            _tmark("main continues", k, main)
-            _tmark("host leaves", k, host=True)
-
-        try:
-            lane(0)
-            net = self.layers_in[1](self._to_compute(net))
-            out = self.forward_fpn(net, prepared=True, lane=lane)
-        finally:
-            main.wait_stream(geo)
-            if plan is not None:
                 main.wait_stream(plan)
                 md.set_plan_stream(None)
-            md.set_geometry_stream(None)
+                md.set_geometry_stream(None)
         return out
 
     def unused_modules(self):
@@ -446,13 +328,11 @@ class FPN_Net(torch.nn.Module):
                 i += 1
         return net
 
-    def _geometry_steps(self, net, full, views=False):
+    def _geometry_steps(self, net, full):
         """Generator over the pyramid levels k = 0 .. n_scales-1: enqueues (on the current stream) everything level k
         needs -- the strided grid + rulebook k-1 -> k (one host read-back of the site count), the z-collapsing RPN
         projection grid of that level and, with `full`, the submanifold 3x3x3 / 1x1x1 rulebooks and the deconvolution
-        view k -> k-1 (otherwise built by the first convolution that needs them) -- then yields k.  With `views` it
-        yields instead the list of calls that build those rulebooks (3x3x3 first), for the caller to run on a stream of
-        its choice."""
+        view k -> k-1 (otherwise built by the first convolution that needs them) -- then yields k."""
         md, n_scales = net.metadata, len(self.m_downs)
         needed = max(self.fpn_scales_from_top + self.roi_scales_from_top) if self.skip_unused else n_scales - 1
         lowest_up = n_scales - 1 - min(n_scales - 1, needed)          # finest level the top-down path reaches
@@ -472,16 +352,14 @@ class FPN_Net(torch.nn.Module):
                 conv = pro2d[k]
                 scn.SCN.Convolution_prepare(size, (size - conv.filter_size) // conv.filter_stride + 1,
                                             conv.filter_size, conv.filter_stride, md)
-            todo = [lambda size=size: scn.SCN.SubmanifoldConvolution_prepare(size, (3,) * self.dimension, md)]
-            if k >= lowest_up:                                                                 # lateral 1x1x1
-                todo.append(lambda size=size: scn.SCN.SubmanifoldConvolution_prepare(size, (1,) * self.dimension, md))
-            if k > lowest_up:
-                todo.append(lambda size=size, k=k: scn.SCN.Deconvolution_prepare(
-                    size, sizes[k - 1], self.down_kernels[k - 1], self.down_strides[k - 1], md))
             if full:
-                for f in todo:
-                    f()
-            yield todo if views else k
+                scn.SCN.SubmanifoldConvolution_prepare(size, (3,) * self.dimension, md)
+                if k >= lowest_up:                                                             # lateral 1x1x1
+                    scn.SCN.SubmanifoldConvolution_prepare(size, (1,) * self.dimension, md)
+                if k > lowest_up:
+                    scn.SCN.Deconvolution_prepare(size, sizes[k - 1], self.down_kernels[k - 1], self.down_strides[k - 1],
+                                                  md)
+            yield k
 
     def prepare_geometry(self, net, full=False):
         """All strided grids / rulebooks of the pyramid, built before the first feature kernel: each new grid costs

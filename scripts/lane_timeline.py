@@ -1,13 +1,13 @@
-"""Where the streams of one building's pass are, level by level (FPN_Net.TIMELINE marks): for every pyramid level the
-times -- ms since the caller's stream started the pass -- at which the geometry stream starts / finishes the level's
-grid, the plan stream its rulebooks, the caller's stream arrives at the level and goes on, and the host enqueues them.
-  python scripts/lane_timeline.py [points]        D3D_PLAN_LANE=0: two streams"""
+"""Where the streams of one building's pass are, level by level (timeline marks of FPN_Net._forward_async_geometry): for
+every pyramid level the times -- ms since the caller's stream started the pass -- at which the host enters and leaves
+the level and the caller's stream arrives at it and goes on; then the pass's other marks (input grid, level-0 rulebook,
+point lists and input means, the ends of the down and the top-down path).
+  python scripts/lane_timeline.py [points]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from detection_3d_amd.config import get_cfg
 from detection_3d_amd.detector import build_detection_model
-from detection_3d_amd.sparseconvnet import fpn_net
 from detection_3d_amd import timeline
 from detection_3d_amd.synthetic import make_scene
 from detection_3d_amd.voxelize import voxelize
@@ -41,9 +41,8 @@ with torch.no_grad():
             if ev is not None and k < 0:
                 rows.setdefault((k, label + " [host enqueued]"), []).append((host - h0) * 1e3)
         rows.setdefault((-1, "pass done"), []).append(start.elapsed_time(end))
-labels = ["host enters", "geo starts", "geo done", "host has count", "plan starts", "plan 3x3x3 done", "plan views done",
-          "main arrives", "main continues", "host leaves"]
-print(f"plan lane {'on' if fpn_net.PLAN_LANE else 'off'}; median of 6 passes, ms since the pass started")
+labels = ["host enters", "main arrives", "main continues", "host leaves"]
+print("median of 6 passes, ms since the pass started")
 print("level " + " ".join(f"{l[:15]:>15}" for l in labels))
 for k in sorted({k for k, _ in rows if k >= 0}):
     cells = []

@@ -138,9 +138,10 @@ def test_buildings_in_flight_match_the_serial_loop_to_the_bit(setup, dev):
         assert pipe.map([]) == []
 
 
-def test_two_lane_pass_matches_the_one_stream_pass_to_the_bit(setup, dev):
-    """FPN_Net._forward_two_lane (grid chain on a side stream, per-stream arena lanes) vs the one-stream pass: every
-    backbone map and the detections are identical to the bit; a grid requested on the wrong stream is refused."""
+def test_side_stream_pass_matches_the_one_stream_pass_to_the_bit(setup, dev):
+    """FPN_Net._forward_async_geometry (grid chain and views on side streams, per-stream arena lanes) vs the one-stream
+    pass: every backbone map and the detections are identical to the bit; a grid requested on the wrong stream is
+    refused."""
     from detection_3d_amd import _lib
     from detection_3d_amd.sparseconvnet import SCN, fpn_net
     from detection_3d_amd.synthetic import make_scene
@@ -149,18 +150,18 @@ def test_two_lane_pass_matches_the_one_stream_pass_to_the_bit(setup, dev):
     pcl = torch.from_numpy(make_scene(21, 50000)).to(dev)
     outs = {}
     try:
-        for two in (False, True, True):
-            fpn_net.TWO_LANE = two
+        for side in (False, True, True):
+            fpn_net.SIDE_STREAMS = side
             c, f = voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
             res, mid = model([c, f], return_intermediates=True)
             torch.cuda.synchronize()
             got = [m.features.clone() for m in mid["rpn_features"] + mid["roi_features"]] + \
                   [res["bbox3d"], res["scores"], res["labels"], mid["proposals"]]
-            if two in outs:
-                assert all(torch.equal(a, b) for a, b in zip(outs[two], got))
-            outs[two] = got
+            if side in outs:
+                assert all(torch.equal(a, b) for a, b in zip(outs[side], got))
+            outs[side] = got
     finally:
-        fpn_net.TWO_LANE = True
+        fpn_net.SIDE_STREAMS = True
     assert len(outs[False]) == len(outs[True])
     for a, b in zip(outs[False], outs[True]):
         assert a.shape == b.shape and torch.equal(a, b)
@@ -178,10 +179,41 @@ def test_two_lane_pass_matches_the_one_stream_pass_to_the_bit(setup, dev):
     torch.cuda.synchronize()
 
 
+def test_column_slice_features_give_the_same_bits_on_both_passes(setup, dev):
+    """Features handed over as a column slice of a wider tensor (not contiguous, as `pcl[:, 3:12]`): the input layer
+    copies them on the caller's stream after the side streams of the pass have started, and the plan stream that
+    computes the voxel means from the copy waits for it.  Maps, proposals and detections equal those of the one-stream
+    pass and of the contiguous features to the bit.  (A race need not show in any one run: this guards the ordering,
+    SCN.InputLayer_updateOutput holds it.)"""
+    from detection_3d_amd.sparseconvnet import fpn_net
+    from detection_3d_amd.synthetic import make_scene
+    from detection_3d_amd.voxelize import voxelize
+    cfg, model = setup[0], setup[1]
+    pcl = torch.from_numpy(make_scene(23, 60000)).to(dev)
+    c, f = voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
+    sliced = torch.cat([torch.zeros_like(f[:, :3]), f], 1)[:, 3:]
+    assert not sliced.is_contiguous() and torch.equal(sliced, f)
+    outs = {}
+    try:
+        for name, side, feats in (("sliced", True, sliced), ("one-stream", False, sliced), ("contiguous", True, f)):
+            fpn_net.SIDE_STREAMS = side
+            res, mid = model([c, feats], return_intermediates=True)
+            torch.cuda.synchronize()
+            outs[name] = [m.features.clone() for m in mid["rpn_features"] + mid["roi_features"]] + \
+                         [mid["proposals"], res["bbox3d"], res["scores"], res["labels"]]
+    finally:
+        fpn_net.SIDE_STREAMS = True
+    assert outs["sliced"][-3].shape[0] > 0
+    for other in ("one-stream", "contiguous"):
+        assert len(outs[other]) == len(outs["sliced"])
+        for a, b in zip(outs["sliced"], outs[other]):
+            assert a.shape == b.shape and torch.equal(a, b), other
+
+
 @pytest.mark.parametrize("n_points", [60, 700, 5000])
 def test_tiny_buildings_run_through_every_path(setup, dev, n_points):
     """Few points (coarse levels of one or two sites, far fewer anchors than the pre-NMS top-k, possibly no detection):
-    the two-lane pass, the one-stream pass and the staged pipeline all run and agree to the bit."""
+    the side-stream pass, the one-stream pass and the staged pipeline all run and agree to the bit."""
     from detection_3d_amd.serving import BuildingPipeline
     from detection_3d_amd.sparseconvnet import fpn_net
     from detection_3d_amd.synthetic import make_scene
@@ -190,13 +222,13 @@ def test_tiny_buildings_run_through_every_path(setup, dev, n_points):
     pcl = torch.from_numpy(make_scene(31, 40000)[:n_points].copy()).to(dev)
     res = {}
     try:
-        for two in (True, False):
-            fpn_net.TWO_LANE = two
+        for side in (True, False):
+            fpn_net.SIDE_STREAMS = side
             c, f = voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
-            res[two] = model([c, f])
+            res[side] = model([c, f])
             torch.cuda.synchronize()
     finally:
-        fpn_net.TWO_LANE = True
+        fpn_net.SIDE_STREAMS = True
     piped = BuildingPipeline(model, cfg, in_flight=2, device=dev).map([pcl, pcl, pcl])
     torch.cuda.synchronize()
     for other in [res[False]] + piped:

@@ -256,6 +256,37 @@ def test_conv_dw_deterministic_small_arena(dev, monkeypatch):
         assert torch.equal(x, y) and torch.equal(x, z) and torch.equal(x, w)
 
 
+def test_backbone_takes_the_side_stream_pass_in_deterministic_mode(dev, monkeypatch):
+    """Under the flag, with torch's NaN fill of new tensors on, a GPU input goes through the side-stream pass
+    (FPN_Net._forward_async_geometry), whose input layer orders its side-stream write behind the fill: every map is
+    finite and equal to the bit to the one-stream pass's under the same flag."""
+    from detection_3d_amd.config import get_cfg
+    from detection_3d_amd.detector import build_detection_model
+    from detection_3d_amd.sparseconvnet import fpn_net
+    from detection_3d_amd.synthetic import make_scene
+    from detection_3d_amd.voxelize import voxelize
+    assert torch.utils.deterministic.fill_uninitialized_memory
+    cfg = get_cfg("4c_Fpn432")
+    torch.manual_seed(0)
+    model = build_detection_model(cfg).to(dev).eval()
+    calls = []
+    real = fpn_net.FPN_Net._forward_async_geometry
+    monkeypatch.setattr(fpn_net.FPN_Net, "_forward_async_geometry", lambda self, net0: calls.append(1) or real(self, net0))
+    c, f = voxelize(torch.from_numpy(make_scene(8, 60000)).to(dev), cfg.SPARSE3D.VOXEL_SCALE,
+                    cfg.SPARSE3D.VOXEL_FULL_SCALE)
+    maps = {}
+    with torch.no_grad(), _flag(True):
+        for side in (True, False):
+            monkeypatch.setattr(fpn_net, "SIDE_STREAMS", side)
+            rpn, roi = model.backbone([c, f])
+            torch.cuda.synchronize()
+            maps[side] = [m.features.clone() for m in rpn + roi]
+    assert len(calls) == 1
+    assert len(maps[True]) == len(maps[False]) > 0
+    for a, b in zip(maps[True], maps[False]):
+        assert a.shape == b.shape and a.shape[0] > 0 and torch.isfinite(a).all() and torch.equal(a, b)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def _scene(dev, seed, n_points, extent):
     from detection_3d_amd.synthetic import make_scene, make_targets

@@ -84,10 +84,11 @@ def test_geometry_schedule_of_the_4c_backbone(monkeypatch):
 
 
 @pytest.mark.parametrize("name", ["4c_Fpn432", "3G6c_Fpn4321"])
-def test_async_geometry_specs_are_the_grid_calls_of_the_schedule(monkeypatch, name):
+def test_geometry_specs_list_the_grids_and_views_of_the_schedule(monkeypatch, name):
     """FPN_Net._geometry_specs -- the list the library's geometry thread works through (d3d_geometry_async_start) -- holds
-    exactly the d3d_conv_prepare calls _geometry_steps makes, in the same order, and `last[k]` points at the last one a
-    level needs before its convolutions may be enqueued."""
+    exactly the d3d_conv_prepare calls _geometry_steps makes, in the same order, `last[k]` points at the last one a
+    level needs before its convolutions may be enqueued, every level waits for its 3x3x3 rulebook (listed right behind
+    its grids), and the rulebooks of the top-down path -- the `full` ones of _geometry_steps -- come last."""
     cfg = get_cfg(name)
     net = build_backbone(cfg)
     calls = []
@@ -101,16 +102,14 @@ def test_async_geometry_specs_are_the_grid_calls_of_the_schedule(monkeypatch, na
     per_level = []
     for k in net._geometry_steps(Net0(), False):
         per_level.append(len(calls))
-    specs, last, last_all = net._geometry_specs(Net0.spatial_size)
-    assert all(s[0] == 1 for s in specs) and [tuple(s[1:]) for s in specs] == calls
-    assert len(last) == len(net.m_downs) and last_all == len(specs) - 1
+    v, vlast, vall = net._geometry_specs(Net0.spatial_size)
+    grid_rows = [i for i, s in enumerate(v) if s[0] in (1, 3)]
+    assert all(v[i][0] == 1 for i in grid_rows)                         # (gradients on: every decoded table is built)
+    assert [tuple(v[i][1:]) for i in grid_rows] == calls and vall == len(v) - 1
+    assert len(vlast) == len(net.m_downs)
     for k, n_after in enumerate(per_level):
         before = per_level[k - 1] if k else 0
-        assert last[k] == ((n_after - 1 if n_after > before else -1), -1)
-    # with the views: the same grids in the same order, every level waits for its 3x3x3 rulebook (listed right behind
-    # its grids), and the rulebooks of the top-down path -- the `full` ones of _geometry_steps -- come last
-    v, vlast, vall = net._geometry_specs(Net0.spatial_size, views=True)
-    assert [tuple(s[1:]) for s in v if s[0] == 1] == calls and vall == len(v) - 1
+        assert vlast[k][0] == (grid_rows[n_after - 1] if n_after > before else -1)
     full = []
     monkeypatch.setattr(SCN, "SubmanifoldConvolution_prepare", lambda sz, f, m: full.append((0, SCN._size3(sz), SCN._size3(f))))
     monkeypatch.setattr(SCN, "Deconvolution_prepare", lambda i, o, f, s, m: full.append((2, SCN._size3(i), SCN._size3(o))))
