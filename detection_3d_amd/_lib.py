@@ -112,6 +112,16 @@ _SIGS = {
     "d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes": (
         ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                           ctypes.c_int]),
+    "d3d_roi_align_rotated_3d_sparse_backward_bf16": (
+        ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, c_int_p, vp, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                       ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_size_t, vp]),
+    "d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16": (
+        ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, c_int_p, vp, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                       ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_size_t, vp]),
+    "d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes": (
+        ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                          ctypes.c_int]),
     "d3d_bn_forward": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, vp,
                                       ctypes.c_size_t, vp]),
@@ -131,6 +141,14 @@ _SIGS = {
                                                                       ctypes.c_int, c_float_p, vp, ctypes.c_int,
                                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                                       ctypes.c_int, vp, ctypes.c_int, vp, vp]),
+    "d3d_roi_align_rotated_3d_sparse_forward_bf16": (ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, c_int_p, vp,
+                                                                    ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                    vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "d3d_roi_align_rotated_3d_sparse_forward_levels_bf16": (ctypes.c_int, [vp, ctypes.c_int, c_int_p, ctypes.POINTER(vp),
+                                                                           ctypes.c_int, c_float_p, vp, ctypes.c_int,
+                                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                           ctypes.c_int, vp, ctypes.c_int, vp, vp]),
     "d3d_rotate_iou_eval": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "d3d_boxes_iou_3d": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                         ctypes.c_int, ctypes.c_int, vp, vp]),
@@ -156,6 +174,8 @@ _SIGS = {
                                         ctypes.POINTER(ctypes.c_float), ctypes.c_float, vp, vp]),
     "d3d_rpn_head": (ctypes.c_int, [ctypes.POINTER(vp), c_int_p, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp,
                                     ctypes.c_int, vp, vp, vp]),
+    "d3d_rpn_head_bf16": (ctypes.c_int, [ctypes.POINTER(vp), c_int_p, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp,
+                                         ctypes.c_int, vp, vp, vp]),
     "d3d_mlp_heads": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp]),
     "d3d_rotate_nms_3d_sorted": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, vp, vp, vp,
                                                 ctypes.c_size_t, vp]),

@@ -127,7 +127,7 @@ static constexpr int kRoiWaves = 4;  // waves per RoI (8 measured the same; what
 // the workgroups of the other levels' RoIs to exit at once -- with two levels each launch fills half the wave slots).
 struct RoiLevel {
   const HashEntry *tab;   // null: this level is not pooled by the launch
-  const float *feats;
+  const void *feats;      // rows of the launch's storage type T
   const int32_t *extent;  // occupied extent of the grid on the device, or null: H, W, Z below
   const int32_t *dense;   // null, or the dense index of the grid's bounding box [b][e0][e1][e2] (1 + site id, 0 = empty)
   int cap, H, W, Z;
@@ -138,9 +138,13 @@ static constexpr int kRoiMaxLevels = 4;
 struct RoiLevels {
   RoiLevel v[kRoiMaxLevels];
 };
+// T = storage type of the feature rows and of the output: float, or unsigned short (bf16 bits: the rows are widened as
+// they are read, the taps are summed in fp32 in the same order, and the bin's mean is rounded once at the store, so the
+// result is the fp32 kernel's on the widened map, rounded to bf16).
+template <typename T>
 __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_roi_sparse(
     RoiLevels lv, int C, const float *__restrict__ rois, const int32_t *__restrict__ roi_levels,
-    int PH, int PW, int PZ, int sampling_ratio, int layout, float *__restrict__ out) {
+    int PH, int PW, int PZ, int sampling_ratio, int layout, T *__restrict__ out) {
   const int n = blockIdx.x, cc = blockIdx.y;
   const int l = roi_levels ? __builtin_amdgcn_readfirstlane(roi_levels[n]) : 0;
   if (l < 0 || l >= kRoiMaxLevels) return;   // -1: a padding row (d3d_roi_prepare_counted)
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
   if (!L.tab) return;                         // pooled from another pyramid level (by another launch)
   const HashEntry *__restrict__ tab = L.tab;
   const int32_t *__restrict__ dense = L.dense;
-  const float *__restrict__ feats = L.feats;
+  const T *__restrict__ feats = (const T *)L.feats;
   const int cap = L.cap;
   const float spatial_scale = L.scale;
   int H = L.H, W = L.W, Z = L.Z;
@@ -172,13 +176,19 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
   const bool pair = ok1 && (C % 2 == 0);  // 8-byte aligned pair load
   const size_t n_out = (size_t)n;
   auto load2 = [&](int row) -> f32x2 {
-    const float *p = feats + (size_t)row * C + c0;
+    const T *p = feats + (size_t)row * C + c0;
     f32x2 v = {0.f, 0.f};
-    if (pair)
-      v = *(const f32x2 *)p;
-    else {
-      if (ok0) v[0] = p[0];
-      if (ok1) v[1] = p[1];
+    if (pair) {
+      if constexpr (sizeof(T) == 4) {
+        v = *(const f32x2 *)p;
+      } else {
+        const unsigned u = *(const unsigned *)p;   // two bf16 channels: 4-byte aligned (C even)
+        v[0] = __uint_as_float(u << 16);
+        v[1] = __uint_as_float(u & 0xffff0000u);
+      }
+    } else {
+      if (ok0) v[0] = ld1(p);
+      if (ok1) v[1] = ld1(p + 1);
     }
     return v;
   };
@@ -308,14 +318,14 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
       if (bin >= NB) break;
       const f32x2 r = acc[gi] / count;
       if (layout == 0) {
-        float *o = out + (n_out * C + c0) * NB + bin;
-        if (ok0) o[0] = r[0];
-        if (ok1) o[NB] = r[1];
+        T *o = out + (n_out * C + c0) * NB + bin;
+        if (ok0) st1(o, r[0]);
+        if (ok1) st1(o + NB, r[1]);
       } else {
         const int pz = bin % PZ, cell = bin / PZ;
-        float *o = out + ((n_out * (size_t)(PH * PW) + cell) * C + c0) * PZ + pz;
-        if (ok0) o[0] = r[0];
-        if (ok1) o[PZ] = r[1];
+        T *o = out + ((n_out * (size_t)(PH * PW) + cell) * C + c0) * PZ + pz;
+        if (ok0) st1(o, r[0]);
+        if (ok1) st1(o + PZ, r[1]);
       }
     }
   }
@@ -357,19 +367,21 @@ __global__ __launch_bounds__(256) void k_roi_dense_bwd(const float *__restrict__
 
 // Backward of the sparse variant: the dense gradient of RoIAlignRotated3DBackwardFeature (:238-354)
 // restricted to the active sites (what SparseToDense_updateGradInput would gather back).  Keeps the
-// backward's own bound test `z > zsize` (:190).  fp32 atomics, like the reference.
+// backward's own bound test `z > zsize` (:190).  fp32 atomics, like the reference.  TT = storage type of top_diff
+// (float, or bf16 bits widened as they are read); d_feats is fp32 either way.
 static constexpr int kRoiBwdCch = 64;
+template <typename TT>
 __global__ __launch_bounds__(256) void k_roi_sparse_bwd(
     const HashEntry *__restrict__ tab, int cap, int C, int H, int W, int Z, const float *__restrict__ rois,
-    float spatial_scale, int PH, int PW, int PZ, int sampling_ratio, const float *__restrict__ top_diff,
+    float spatial_scale, int PH, int PW, int PZ, int sampling_ratio, const TT *__restrict__ top_diff,
     float *__restrict__ d_feats) {
   extern __shared__ float tile[];  // [kRoiBwdCch][NB + 1]
   const int n = blockIdx.x, cc = blockIdx.y;
   const int NB = PH * PW * PZ, LD = NB + 1;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int nch = min(kRoiBwdCch, C - cc * kRoiBwdCch);
-  const float *g0 = top_diff + ((size_t)n * C + (size_t)cc * kRoiBwdCch) * NB;
-  for (int idx = threadIdx.x; idx < nch * NB; idx += 256) tile[(idx / NB) * LD + idx % NB] = g0[idx];
+  const TT *g0 = top_diff + ((size_t)n * C + (size_t)cc * kRoiBwdCch) * NB;
+  for (int idx = threadIdx.x; idx < nch * NB; idx += 256) tile[(idx / NB) * LD + idx % NB] = ld1(g0 + idx);
   __syncthreads();
   const RoiGeom g = roi_geom(rois + (size_t)n * 8, spatial_scale, PH, PW, PZ, sampling_ratio);
   const int NS = g.gh * g.gw * g.gz;
@@ -426,16 +438,17 @@ __global__ __launch_bounds__(256) void k_roi_sparse_bwd(
 static constexpr int kRoiDetChunk = 64;   // records per chunk = lanes of a wave (one cooperative load of the chunk)
 static constexpr int kRoiDetCpl = 4;      // channels per lane in one pass over a chunk (256 channels)
 
-// [K][C][NB] -> [K][NB][C] through a 32 x 33 tile
-__global__ __launch_bounds__(256) void k_roi_det_transpose(const float *__restrict__ in, int C, int NB,
+// [K][C][NB] -> [K][NB][C] through a 32 x 33 tile (TT: float, or bf16 bits widened to fp32)
+template <typename TT>
+__global__ __launch_bounds__(256) void k_roi_det_transpose(const TT *__restrict__ in, int C, int NB,
                                                            float *__restrict__ out) {
   __shared__ float t[32][33];
   const int n = blockIdx.x, b0 = blockIdx.y * 32, c0 = blockIdx.z * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const float *src = in + (size_t)n * C * NB;
+  const TT *src = in + (size_t)n * C * NB;
   for (int j = ty; j < 32; j += 8) {
     const int c = c0 + j, b = b0 + tx;
-    t[j][tx] = (c < C && b < NB) ? src[(size_t)c * NB + b] : 0.f;
+    t[j][tx] = (c < C && b < NB) ? ld1(src + (size_t)c * NB + b) : 0.f;
   }
   __syncthreads();
   float *dst = out + (size_t)n * NB * C;
@@ -517,13 +530,15 @@ __global__ __launch_bounds__(256) void k_roi_det_bounds(const uint32_t *__restri
 // one wave per chunk [a, a + kRoiDetChunk) of the sorted records: lane j loads record a + j, then the wave walks the
 // chunk in order, all channels at once (lane = channels lane, lane + 64, ...).  A run of one row that is the whole of
 // the row's list goes to d_feats; otherwise it is the chunk's first run (slot 0) or last run (slot 1) and goes to
-// part[chunk][slot].
+// part[chunk][slot].  TO = float: d_feats is added to; TO = bf16 bits: the row's sum is rounded and written (the row was
+// zeroed: 0 + sum is the sum itself, as a sum that starts from +0 is never -0).
+template <typename TO>
 __global__ __launch_bounds__(256) void k_roi_det_sum(const uint32_t *__restrict__ skey, const int32_t *__restrict__ sval,
                                                      const int32_t *__restrict__ rec_src, const float *__restrict__ rec_w,
                                                      int n_max, const int32_t *__restrict__ total,
                                                      const int32_t *__restrict__ rbeg, const int32_t *__restrict__ rend,
                                                      const float *__restrict__ topT, int C, float *__restrict__ part,
-                                                     float *__restrict__ d_feats) {
+                                                     TO *__restrict__ d_feats) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int chunk = blockIdx.x * 4 + wave;
   const int a = chunk * kRoiDetChunk;
@@ -545,12 +560,25 @@ __global__ __launch_bounds__(256) void k_roi_det_sum(const uint32_t *__restrict_
     int cur = __shfl(my_key, 0, 64), seg = 0;
     auto flush = [&](int row, int sa, int sb) {
       const bool whole = rbeg[row] == a + sa && rend[row] == a + sb;
-      float *dst = whole ? d_feats + (size_t)row * C : part + ((size_t)chunk * 2 + (sa == 0 ? 0 : 1)) * C;
+      if (whole) {
+        TO *dst = d_feats + (size_t)row * C;
 #pragma unroll
-      for (int j = 0; j < kRoiDetCpl; j++) {
-        const int c = cb + lane + 64 * j;
-        if (c < C) dst[c] = whole ? dst[c] + acc[j] : acc[j];
-        acc[j] = 0.f;
+        for (int j = 0; j < kRoiDetCpl; j++) {
+          const int c = cb + lane + 64 * j;
+          if (c < C) {
+            if constexpr (sizeof(TO) == 4) dst[c] = dst[c] + acc[j];
+            else st1(dst + c, acc[j]);
+          }
+          acc[j] = 0.f;
+        }
+      } else {
+        float *dst = part + ((size_t)chunk * 2 + (sa == 0 ? 0 : 1)) * C;
+#pragma unroll
+        for (int j = 0; j < kRoiDetCpl; j++) {
+          const int c = cb + lane + 64 * j;
+          if (c < C) dst[c] = acc[j];
+          acc[j] = 0.f;
+        }
       }
     };
     for (int p0 = 0; p0 < len; p0 += 4) {
@@ -585,10 +613,12 @@ __global__ __launch_bounds__(256) void k_roi_det_sum(const uint32_t *__restrict_
   }
 }
 
-// one wave per row whose list spans several chunks: d_feats[row] += its chunk partials, in chunk order
+// one wave per row whose list spans several chunks: d_feats[row] += its chunk partials, in chunk order (TO as in
+// k_roi_det_sum)
+template <typename TO>
 __global__ __launch_bounds__(256) void k_roi_det_join(const int32_t *__restrict__ rbeg, const int32_t *__restrict__ rend,
                                                       int n_rows, const float *__restrict__ part, int C,
-                                                      float *__restrict__ d_feats) {
+                                                      TO *__restrict__ d_feats) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n_rows) return;
   const int rb = rbeg[row], re = rend[row];
@@ -601,8 +631,19 @@ __global__ __launch_bounds__(256) void k_roi_det_join(const int32_t *__restrict_
       const int slot = (k == c0 && rb != k * kRoiDetChunk) ? 1 : 0;
       acc += part[((size_t)k * 2 + slot) * C + c];
     }
-    d_feats[(size_t)row * C + c] += acc;
+    if constexpr (sizeof(TO) == 4) d_feats[(size_t)row * C + c] += acc;
+    else st1(d_feats + (size_t)row * C + c, acc);
   }
+}
+
+// fp32 -> bf16 (round to nearest even), n elements; in 16-byte and out 8-byte aligned (checked by the caller)
+__global__ __launch_bounds__(256) void k_roi_f32_to_bf16(const float *__restrict__ in, long n,
+                                                         unsigned short *__restrict__ out) {
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i + 4 <= n)
+    store4(out + i, load4<float>(in + i));
+  else
+    for (long j = i; j < n; j++) st1(out + j, in[j]);
 }
 
 // scratch layout of the fixed-order backward (offsets from a 256-aligned base)
@@ -744,7 +785,7 @@ int d3d_roi_align_rotated_3d_forward(const float *input, int B, int C, int H, in
 }
 
 // fills lv (one pyramid level of a pooling launch) from the grid of spatial size `size`
-static int roi_level_of(d3d_meta *m, const int *size, const float *feats, const int *crop, float spatial_scale,
+static int roi_level_of(d3d_meta *m, const int *size, const void *feats, const int *crop, float spatial_scale,
                         hipStream_t s, RoiLevel *lv) {
   std::map<Size3, Grid>::iterator it;
   bool have_grid;
@@ -769,29 +810,31 @@ static int roi_level_of(d3d_meta *m, const int *size, const float *feats, const 
   return D3D_OK;
 }
 
-int d3d_roi_align_rotated_3d_sparse_forward(d3d_meta *m, const int *size, const float *feats, int C,
-                                            const int *crop, const float *rois, int K,
-                                            float spatial_scale, int ph, int pw, int pz,
-                                            int sampling_ratio, const int *roi_levels, int level, int layout,
-                                            float *out, void *stream) {
+}  // extern "C"
+
+template <typename T>
+static int roi_sparse_forward(d3d_meta *m, const int *size, const T *feats, int C, const int *crop, const float *rois, int K,
+                              float spatial_scale, int ph, int pw, int pz, int sampling_ratio, const int *roi_levels,
+                              int level, int layout, T *out, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && size && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0, "roi_align_sparse: bad arguments");
   D3D_REQUIRE(!roi_levels || (level >= 0 && level < kRoiMaxLevels), "roi_align_sparse: level %d (< %d)", level, kRoiMaxLevels);
+  D3D_REQUIRE(sizeof(T) == 4 || ((uintptr_t)feats & 3) == 0, "roi_align_sparse: bf16 rows not 4-byte aligned");
   RoiLevels lv = {};
   if (int rc = roi_level_of(m, size, feats, crop, spatial_scale, s, &lv.v[roi_levels ? level : 0])) return rc;
   if (K == 0) return D3D_OK;
   D3D_REQUIRE(feats && rois && out, "roi_align_sparse: null pointer");
   D3D_REQUIRE(layout == 0 || layout == 1, "roi_align_sparse: layout must be 0 ([K,C,ph,pw,pz]) or 1 ([K,ph,pw,C,pz])");
-  hipLaunchKernelGGL(k_roi_sparse, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
+  hipLaunchKernelGGL(k_roi_sparse<T>, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
                      roi_levels, ph, pw, pz, sampling_ratio, layout, out);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
 
-int d3d_roi_align_rotated_3d_sparse_forward_levels(d3d_meta *m, int n_levels, const int *sizes_host,
-                                                   const float *const *feats_host, int C, const float *scales_host,
-                                                   const float *rois, int K, int ph, int pw, int pz, int sampling_ratio,
-                                                   const int *roi_levels, int layout, float *out, void *stream) {
+template <typename T>
+static int roi_sparse_forward_levels(d3d_meta *m, int n_levels, const int *sizes_host, const T *const *feats_host, int C,
+                                     const float *scales_host, const float *rois, int K, int ph, int pw, int pz,
+                                     int sampling_ratio, const int *roi_levels, int layout, T *out, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && sizes_host && feats_host && scales_host && n_levels >= 1 && n_levels <= kRoiMaxLevels,
               "roi_align_sparse_levels: 1..%d levels", kRoiMaxLevels);
@@ -801,14 +844,53 @@ int d3d_roi_align_rotated_3d_sparse_forward_levels(d3d_meta *m, int n_levels, co
   RoiLevels lv = {};
   for (int l = 0; l < n_levels; l++) {
     D3D_REQUIRE(feats_host[l], "roi_align_sparse_levels: null feature pointer of level %d", l);
+    D3D_REQUIRE(sizeof(T) == 4 || ((uintptr_t)feats_host[l] & 3) == 0, "roi_align_sparse_levels: bf16 rows not 4-byte aligned");
     if (int rc = roi_level_of(m, sizes_host + 3 * l, feats_host[l], nullptr, scales_host[l], s, &lv.v[l])) return rc;
   }
   if (K == 0) return D3D_OK;
   D3D_REQUIRE(rois && out, "roi_align_sparse_levels: null pointer");
-  hipLaunchKernelGGL(k_roi_sparse, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
+  hipLaunchKernelGGL(k_roi_sparse<T>, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
                      roi_levels, ph, pw, pz, sampling_ratio, layout, out);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
+}
+
+extern "C" {
+
+int d3d_roi_align_rotated_3d_sparse_forward(d3d_meta *m, const int *size, const float *feats, int C,
+                                            const int *crop, const float *rois, int K,
+                                            float spatial_scale, int ph, int pw, int pz,
+                                            int sampling_ratio, const int *roi_levels, int level, int layout,
+                                            float *out, void *stream) {
+  return roi_sparse_forward<float>(m, size, feats, C, crop, rois, K, spatial_scale, ph, pw, pz, sampling_ratio, roi_levels,
+                                   level, layout, out, stream);
+}
+
+int d3d_roi_align_rotated_3d_sparse_forward_bf16(d3d_meta *m, const int *size, const void *feats, int C, const int *crop,
+                                                 const float *rois, int K, float spatial_scale, int ph, int pw, int pz,
+                                                 int sampling_ratio, const int *roi_levels, int level, int layout,
+                                                 void *out, void *stream) {
+  return roi_sparse_forward<unsigned short>(m, size, (const unsigned short *)feats, C, crop, rois, K, spatial_scale, ph,
+                                            pw, pz, sampling_ratio, roi_levels, level, layout, (unsigned short *)out,
+                                            stream);
+}
+
+int d3d_roi_align_rotated_3d_sparse_forward_levels(d3d_meta *m, int n_levels, const int *sizes_host,
+                                                   const float *const *feats_host, int C, const float *scales_host,
+                                                   const float *rois, int K, int ph, int pw, int pz, int sampling_ratio,
+                                                   const int *roi_levels, int layout, float *out, void *stream) {
+  return roi_sparse_forward_levels<float>(m, n_levels, sizes_host, feats_host, C, scales_host, rois, K, ph, pw, pz,
+                                          sampling_ratio, roi_levels, layout, out, stream);
+}
+
+int d3d_roi_align_rotated_3d_sparse_forward_levels_bf16(d3d_meta *m, int n_levels, const int *sizes_host,
+                                                        const void *const *feats_host, int C, const float *scales_host,
+                                                        const float *rois, int K, int ph, int pw, int pz,
+                                                        int sampling_ratio, const int *roi_levels, int layout, void *out,
+                                                        void *stream) {
+  return roi_sparse_forward_levels<unsigned short>(m, n_levels, sizes_host, (const unsigned short *const *)feats_host, C,
+                                                   scales_host, rois, K, ph, pw, pz, sampling_ratio, roi_levels, layout,
+                                                   (unsigned short *)out, stream);
 }
 
 int d3d_roi_align_rotated_3d_backward(const float *top_diff, int B, int C, int H, int W, int Z,
@@ -827,13 +909,8 @@ int d3d_roi_align_rotated_3d_backward(const float *top_diff, int B, int C, int H
   return D3D_OK;
 }
 
-// d_feats [n_active, C] is accumulated into (zero it first)
-int d3d_roi_align_rotated_3d_sparse_backward(d3d_meta *m, const int *size, const float *top_diff, int C,
-                                             const int *crop, const float *rois, int K, float spatial_scale,
-                                             int ph, int pw, int pz, int sampling_ratio, float *d_feats,
-                                             void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0, "roi_align_sparse_backward: bad arguments");
+// the grid of spatial size `size`, or D3D_ERR_STATE
+static int roi_grid_of(d3d_meta *m, const int *size, const char *what, const Grid **out) {
   std::map<Size3, Grid>::iterator it;
   bool have_grid;
   {
@@ -842,17 +919,68 @@ int d3d_roi_align_rotated_3d_sparse_backward(d3d_meta *m, const int *size, const
     have_grid = it != m->grids.end();
   }
   if (!have_grid) {
-    set_error("roi_align_sparse_backward: no grid of spatial size [%d,%d,%d]", size[0], size[1], size[2]);
+    set_error("%s: no grid of spatial size [%d,%d,%d]", what, size[0], size[1], size[2]);
     return D3D_ERR_STATE;
   }
+  *out = &it->second;
+  return D3D_OK;
+}
+
+// d_feats [n_active, C] is accumulated into (zero it first)
+int d3d_roi_align_rotated_3d_sparse_backward(d3d_meta *m, const int *size, const float *top_diff, int C,
+                                             const int *crop, const float *rois, int K, float spatial_scale,
+                                             int ph, int pw, int pz, int sampling_ratio, float *d_feats,
+                                             void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0, "roi_align_sparse_backward: bad arguments");
+  const Grid *gp;
+  if (int rc = roi_grid_of(m, size, "roi_align_sparse_backward", &gp)) return rc;
   if (K == 0) return D3D_OK;
   D3D_REQUIRE(top_diff && rois && d_feats, "roi_align_sparse_backward: null pointer");
-  const Grid &g = it->second;
+  const Grid &g = *gp;
   const int NB = ph * pw * pz;
   size_t lds = (size_t)kRoiBwdCch * (NB + 1) * sizeof(float);
   D3D_REQUIRE(lds <= 64 * 1024, "roi_align_sparse_backward: pooled volume %d too large", NB);
-  hipLaunchKernelGGL(k_roi_sparse_bwd, dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch), dim3(256), lds, s, g.tab, g.cap, C,
-                     crop[0], crop[1], crop[2], rois, spatial_scale, ph, pw, pz, sampling_ratio, top_diff, d_feats);
+  hipLaunchKernelGGL(k_roi_sparse_bwd<float>, dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch), dim3(256), lds, s, g.tab, g.cap,
+                     C, crop[0], crop[1], crop[2], rois, spatial_scale, ph, pw, pz, sampling_ratio, top_diff, d_feats);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+size_t d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes(int C, int n_rows) {
+  if (C <= 0 || n_rows < 0) return 0;
+  return (size_t)n_rows * C * sizeof(float) + 256;   // + alignment of the caller's base
+}
+
+int d3d_roi_align_rotated_3d_sparse_backward_bf16(d3d_meta *m, const int *size, const void *top_diff, int C,
+                                                  const int *crop, const float *rois, int K, float spatial_scale, int ph,
+                                                  int pw, int pz, int sampling_ratio, void *d_feats, int n_rows,
+                                                  void *scratch, size_t scratch_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0 && n_rows >= 0,
+              "roi_align_sparse_backward_bf16: bad arguments");
+  const int NB = ph * pw * pz;
+  const size_t lds = (size_t)kRoiBwdCch * (NB + 1) * sizeof(float);
+  D3D_REQUIRE(lds <= 64 * 1024, "roi_align_sparse_backward_bf16: pooled volume %d too large", NB);
+  const size_t need = d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes(C, n_rows);
+  D3D_REQUIRE(scratch_bytes >= need, "roi_align_sparse_backward_bf16: scratch %zu < %zu bytes", scratch_bytes, need);
+  const Grid *gp;
+  if (int rc = roi_grid_of(m, size, "roi_align_sparse_backward_bf16", &gp)) return rc;
+  D3D_REQUIRE(n_rows == gp->n, "roi_align_sparse_backward_bf16: n_rows %d != %d active sites", n_rows, gp->n);
+  if (n_rows == 0) return D3D_OK;
+  D3D_REQUIRE(d_feats && scratch && (K == 0 || (top_diff && rois)), "roi_align_sparse_backward_bf16: null pointer");
+  D3D_REQUIRE(((uintptr_t)d_feats & 7) == 0, "roi_align_sparse_backward_bf16: d_feats not 8-byte aligned");
+  float *acc = (float *)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+  const long total = (long)n_rows * C;
+  D3D_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(float) * (size_t)total, s));
+  if (K > 0) {
+    const Grid &g = *gp;
+    hipLaunchKernelGGL(k_roi_sparse_bwd<unsigned short>, dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch), dim3(256), lds, s,
+                       g.tab, g.cap, C, crop[0], crop[1], crop[2], rois, spatial_scale, ph, pw, pz, sampling_ratio,
+                       (const unsigned short *)top_diff, acc);
+  }
+  hipLaunchKernelGGL(k_roi_f32_to_bf16, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, s, acc, total,
+                     (unsigned short *)d_feats);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
@@ -863,37 +991,18 @@ size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(int 
   return roi_det_layout(K, C, ph, pw, pz, sampling_ratio, n_rows, L) ? L.bytes : 0;
 }
 
-int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const int *size, const float *top_diff, int C,
-                                                           const int *crop, const float *rois, int K,
-                                                           float spatial_scale, int ph, int pw, int pz,
-                                                           int sampling_ratio, float *d_feats, int n_rows,
-                                                           void *scratch, size_t scratch_bytes, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0 && n_rows >= 0,
-              "roi_align_sparse_backward_deterministic: bad arguments");
-  D3D_REQUIRE(sampling_ratio > 0,
-              "roi_align_sparse_backward_deterministic: sampling_ratio %d (adaptive sampling has no record bound before "
-              "the launch)", sampling_ratio);
-  std::map<Size3, Grid>::iterator it;
-  bool have_grid;
-  {
-    D3D_LOCK(m);
-    it = m->grids.find(Size3{size[0], size[1], size[2]});
-    have_grid = it != m->grids.end();
-  }
-  if (!have_grid) {
-    set_error("roi_align_sparse_backward_deterministic: no grid of spatial size [%d,%d,%d]", size[0], size[1], size[2]);
-    return D3D_ERR_STATE;
-  }
-  if (K == 0 || n_rows == 0) return D3D_OK;
-  D3D_REQUIRE(top_diff && rois && d_feats && scratch, "roi_align_sparse_backward_deterministic: null pointer");
-  const Grid &g = it->second;
-  RoiDetLayout L;
-  D3D_REQUIRE(roi_det_layout(K, C, ph, pw, pz, sampling_ratio, n_rows, L),
-              "roi_align_sparse_backward_deterministic: %d RoIs x %d bins x %d samples is too many records", K,
-              ph * pw * pz, sampling_ratio * sampling_ratio * sampling_ratio);
-  D3D_REQUIRE(scratch_bytes >= L.bytes, "roi_align_sparse_backward_deterministic: scratch %zu < %zu bytes", scratch_bytes,
-              L.bytes);
+size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes(int K, int C, int ph, int pw, int pz,
+                                                                                int sampling_ratio, int n_rows) {
+  return d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(K, C, ph, pw, pz, sampling_ratio, n_rows);
+}
+
+}  // extern "C"
+
+// the launches of the fixed-order backward (arguments checked by the caller): TT = storage type of top_diff, TO of d_feats
+template <typename TT, typename TO>
+static int roi_det_run(const Grid &g, const int *crop, const TT *top_diff, int C, const float *rois, int K,
+                       float spatial_scale, int ph, int pw, int pz, int sampling_ratio, TO *d_feats, int n_rows,
+                       const RoiDetLayout &L, void *scratch, hipStream_t s) {
   char *base = (char *)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
   int32_t *cnt = (int32_t *)(base + L.cnt), *offs = (int32_t *)(base + L.offs), *total = (int32_t *)(base + L.total);
   uint32_t *rkey = (uint32_t *)(base + L.rkey), *skey = (uint32_t *)(base + L.skey);
@@ -901,7 +1010,8 @@ int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const in
   float *rw = (float *)(base + L.rw), *topT = (float *)(base + L.topT), *part = (float *)(base + L.part);
   int32_t *rbeg = (int32_t *)(base + L.rbeg), *rend = (int32_t *)(base + L.rend);
   const int NB = ph * pw * pz;
-  hipLaunchKernelGGL(k_roi_det_transpose, dim3(K, (NB + 31) / 32, (C + 31) / 32), dim3(256), 0, s, top_diff, C, NB, topT);
+  hipLaunchKernelGGL(k_roi_det_transpose<TT>, dim3(K, (NB + 31) / 32, (C + 31) / 32), dim3(256), 0, s, top_diff, C, NB,
+                     topT);
   hipLaunchKernelGGL((k_roi_det_taps<false>), dim3(K), dim3(256), 0, s, g.tab, g.cap, crop[0], crop[1], crop[2], rois,
                      spatial_scale, ph, pw, pz, sampling_ratio, n_rows, cnt, nullptr, nullptr, nullptr, nullptr, nullptr);
   D3D_LAUNCH_CHECK();
@@ -920,12 +1030,70 @@ int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const in
   D3D_HIP_CHECK(hipMemsetAsync(rend, 0, 4 * (size_t)n_rows, s));
   hipLaunchKernelGGL(k_roi_det_bounds, dim3((unsigned)((L.n_max + 255) / 256)), dim3(256), 0, s, skey, (int)L.n_max,
                      total, rbeg, rend);
-  hipLaunchKernelGGL(k_roi_det_sum, dim3((unsigned)((L.n_chunks + 3) / 4)), dim3(256), 0, s, skey, sval, rsrc, rw,
+  hipLaunchKernelGGL(k_roi_det_sum<TO>, dim3((unsigned)((L.n_chunks + 3) / 4)), dim3(256), 0, s, skey, sval, rsrc, rw,
                      (int)L.n_max, total, rbeg, rend, topT, C, part, d_feats);
-  hipLaunchKernelGGL(k_roi_det_join, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, rbeg, rend, n_rows, part, C,
+  hipLaunchKernelGGL(k_roi_det_join<TO>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, rbeg, rend, n_rows, part, C,
                      d_feats);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
+}
+
+extern "C" {
+
+int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const int *size, const float *top_diff, int C,
+                                                           const int *crop, const float *rois, int K,
+                                                           float spatial_scale, int ph, int pw, int pz,
+                                                           int sampling_ratio, float *d_feats, int n_rows,
+                                                           void *scratch, size_t scratch_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0 && n_rows >= 0,
+              "roi_align_sparse_backward_deterministic: bad arguments");
+  D3D_REQUIRE(sampling_ratio > 0,
+              "roi_align_sparse_backward_deterministic: sampling_ratio %d (adaptive sampling has no record bound before "
+              "the launch)", sampling_ratio);
+  const Grid *gp;
+  if (int rc = roi_grid_of(m, size, "roi_align_sparse_backward_deterministic", &gp)) return rc;
+  if (K == 0 || n_rows == 0) return D3D_OK;
+  D3D_REQUIRE(top_diff && rois && d_feats && scratch, "roi_align_sparse_backward_deterministic: null pointer");
+  RoiDetLayout L;
+  D3D_REQUIRE(roi_det_layout(K, C, ph, pw, pz, sampling_ratio, n_rows, L),
+              "roi_align_sparse_backward_deterministic: %d RoIs x %d bins x %d samples is too many records", K,
+              ph * pw * pz, sampling_ratio * sampling_ratio * sampling_ratio);
+  D3D_REQUIRE(scratch_bytes >= L.bytes, "roi_align_sparse_backward_deterministic: scratch %zu < %zu bytes", scratch_bytes,
+              L.bytes);
+  return roi_det_run<float, float>(*gp, crop, top_diff, C, rois, K, spatial_scale, ph, pw, pz, sampling_ratio, d_feats,
+                                   n_rows, L, scratch, s);
+}
+
+int d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16(d3d_meta *m, const int *size, const void *top_diff, int C,
+                                                                const int *crop, const float *rois, int K,
+                                                                float spatial_scale, int ph, int pw, int pz,
+                                                                int sampling_ratio, void *d_feats, int n_rows,
+                                                                void *scratch, size_t scratch_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && size && crop && C > 0 && K >= 0 && ph > 0 && pw > 0 && pz > 0 && n_rows >= 0,
+              "roi_align_sparse_backward_deterministic_bf16: bad arguments");
+  D3D_REQUIRE(sampling_ratio > 0,
+              "roi_align_sparse_backward_deterministic_bf16: sampling_ratio %d (adaptive sampling has no record bound "
+              "before the launch)", sampling_ratio);
+  RoiDetLayout L;
+  D3D_REQUIRE(roi_det_layout(K, C, ph, pw, pz, sampling_ratio, n_rows, L),
+              "roi_align_sparse_backward_deterministic_bf16: %d RoIs x %d bins x %d samples is too many records", K,
+              ph * pw * pz, sampling_ratio * sampling_ratio * sampling_ratio);
+  D3D_REQUIRE(K == 0 || scratch_bytes >= L.bytes, "roi_align_sparse_backward_deterministic_bf16: scratch %zu < %zu bytes",
+              scratch_bytes, L.bytes);
+  const Grid *gp;
+  if (int rc = roi_grid_of(m, size, "roi_align_sparse_backward_deterministic_bf16", &gp)) return rc;
+  D3D_REQUIRE(n_rows == gp->n, "roi_align_sparse_backward_deterministic_bf16: n_rows %d != %d active sites", n_rows,
+              gp->n);
+  if (n_rows == 0) return D3D_OK;
+  D3D_REQUIRE(d_feats && (K == 0 || (top_diff && rois && scratch)),
+              "roi_align_sparse_backward_deterministic_bf16: null pointer");
+  D3D_HIP_CHECK(hipMemsetAsync(d_feats, 0, sizeof(unsigned short) * (size_t)n_rows * C, s));   // rows with no record
+  if (K == 0) return D3D_OK;
+  return roi_det_run<unsigned short, unsigned short>(*gp, crop, (const unsigned short *)top_diff, C, rois, K, spatial_scale,
+                                                     ph, pw, pz, sampling_ratio, (unsigned short *)d_feats, n_rows, L,
+                                                     scratch, s);
 }
 
 }  // extern "C"

@@ -136,6 +136,110 @@ __global__ __launch_bounds__(C / 32 * 64) void k_rpn_head(RpnMaps maps, const fl
   }
 }
 
+// bf16 form (d3d_rpn_head_bf16): rows and weights in bf16, v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  The weights
+// are packed [C/8][cout][8] (packed[g][co][j] = W[co][8g + j]): lane (r, h) of k-step q reads the 16 bytes of group
+// 2q + h of column r -- B[k = 16q + 8h + j][col r], the operand's lane map -- and a half-wave's reads are one 512-byte
+// run.  The rows are staged in LDS as bf16; stage 1 rounds t = relu(x W1^T + b1) to bf16 in place of the rows (what a
+// bf16 F.linear hands to the next layer), stage 2 is the fp32 kernel's, partial tiles in fp32 added in slice order.
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+struct RpnMapsBf16 {
+  const unsigned short *p[D3D_RPN_MAX_MAPS];
+  int start[D3D_RPN_MAX_MAPS + 1];
+  int n_maps;
+};
+
+template <int QB>
+__device__ __forceinline__ f32x16 tile_product_bf16(const unsigned short *__restrict__ As, int lda,
+                                                    const unsigned short *__restrict__ wp, int cout, int colbase, int r,
+                                                    int h, int q0, int q1) {
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc[i] = 0.f;
+  const unsigned short *wl = wp + ((size_t)h * cout + colbase + r) * 8;
+  for (int qb = q0; qb < q1; qb += QB) {
+    bf16x8_t b[QB];
+#pragma unroll
+    for (int j = 0; j < QB; j++) {
+      const int q = qb + j < q1 ? qb + j : q1 - 1;      // (a short last batch repeats its last fragment, unused)
+      b[j] = *(const bf16x8_t *)(wl + (size_t)(2 * q) * cout * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < QB; j++) {
+      if (qb + j < q1) {
+        const bf16x8_t a = *(const bf16x8_t *)(As + r * lda + (qb + j) * 16 + h * 8);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[j], acc, 0, 0, 0);
+      }
+    }
+  }
+  return acc;
+}
+
+template <int C>
+__global__ __launch_bounds__(C / 32 * 64) void k_rpn_head_bf16(RpnMapsBf16 maps, const unsigned short *__restrict__ w1p,
+                                                               const float *__restrict__ b1,
+                                                               const unsigned short *__restrict__ w2p,
+                                                               const float *__restrict__ b2, int a, int out_tiles,
+                                                               float *__restrict__ obj, float *__restrict__ reg) {
+  constexpr int W = C / 32, LDA = C + 8, LPR = C / 8;   // LDA: +16 B per row keeps the 16-byte pieces aligned
+  __shared__ __attribute__((aligned(16))) unsigned short As[32 * LDA];
+  __shared__ float Ps[(W < kRpnMaxSlices * 2 ? W : kRpnMaxSlices * 2) * 1024];
+  const int n = maps.start[maps.n_maps];
+  const int row0 = blockIdx.x * 32;
+  const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6, r = lane & 31, h = lane >> 5;
+
+  for (int i = tid; i < 32 * LPR; i += W * 64) {
+    const int row = i / LPR, c8 = i % LPR, g = row0 + row;
+    uint4 v = {0u, 0u, 0u, 0u};
+    if (g < n) {
+      int m = 0;
+      while (m + 1 < maps.n_maps && g >= maps.start[m + 1]) m++;
+      v = *(const uint4 *)(maps.p[m] + (size_t)(g - maps.start[m]) * C + c8 * 8);
+    }
+    *(uint4 *)(As + row * LDA + c8 * 8) = v;
+  }
+  __syncthreads();
+  {
+    const f32x16 acc = tile_product_bf16<8>(As, LDA, w1p, C, wib * 32, r, h, 0, C / 16);
+    const int col = wib * 32 + r;
+    const float bias = b1[col];
+    __syncthreads();  // every wave has read the rows
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+      float v = acc[i] + bias;
+      v = v < 0.f ? 0.f : v;   // relu; a NaN stays a NaN
+      st1(As + row * LDA + col, v);
+    }
+    __syncthreads();
+  }
+  const int nout = out_tiles * 32;
+  int S = 1;
+  while (2 * S * out_tiles <= W && 2 * S <= kRpnMaxSlices) S *= 2;
+  const int nq = (C / 16) / S;
+  for (int item = wib; item < out_tiles * S; item += W) {
+    const int t = item / S, sl = item - t * S;
+    const f32x16 acc = tile_product_bf16<4>(As, LDA, w2p, nout, t * 32, r, h, sl * nq, (sl + 1) * nq);
+    float *pt = Ps + (size_t)item * 1024;
+#pragma unroll
+    for (int i = 0; i < 16; i++) pt[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = acc[i];
+  }
+  __syncthreads();
+  for (int e = tid; e < out_tiles * 1024; e += W * 64) {
+    const int t = e >> 10, row = (e >> 5) & 31, c = e & 31;
+    const int col = t * 32 + c;
+    const size_t g = (size_t)row0 + row;
+    if (col >= 8 * a || g >= (size_t)n) continue;
+    float v = 0.f;
+    for (int sl = 0; sl < S; sl++) v += Ps[(size_t)(t * S + sl) * 1024 + row * 32 + c];
+    v += b2[col];
+    if (col < a)
+      obj[g * a + col] = v;
+    else
+      reg[g * (7 * a) + (col - a)] = v;
+  }
+}
+
 }  // namespace d3d
 
 using namespace d3d;
@@ -175,6 +279,48 @@ int d3d_rpn_head(const float *const *maps_host, const int *rows_host, int n_maps
   else
     hipLaunchKernelGGL((k_rpn_head<256, false>), grid, dim3(512), 0, s, maps, w1_packed, b1, w2_packed, b2, a, out_tiles,
                        objectness, regression, 3, (float *)nullptr);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+int d3d_rpn_head_bf16(const void *const *maps_host, const int *rows_host, int n_maps, int channels, const void *w1_packed,
+                      const float *b1, const void *w2_packed, const float *b2, int a, float *objectness,
+                      float *regression, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(maps_host && rows_host && n_maps >= 1 && n_maps <= D3D_RPN_MAX_MAPS, "rpn_head_bf16: 1..%d maps",
+              D3D_RPN_MAX_MAPS);
+  D3D_REQUIRE(channels == 128 || channels == 256, "rpn_head_bf16: %d channels (built for 128 and 256)", channels);
+  D3D_REQUIRE(a >= 1 && w1_packed && b1 && w2_packed && b2, "rpn_head_bf16: bad arguments");
+  D3D_REQUIRE(8 * a <= channels, "rpn_head_bf16: %d output columns for %d channels (at most one 32-column tile per wave)",
+              8 * a, channels);
+  D3D_REQUIRE((((uintptr_t)w1_packed | (uintptr_t)w2_packed) & 15) == 0, "rpn_head_bf16: weights not 16-byte aligned");
+  RpnMapsBf16 maps;
+  long n = 0;
+  for (int m = 0; m < D3D_RPN_MAX_MAPS; m++) {
+    maps.p[m] = nullptr;
+    maps.start[m] = (int)n;
+    if (m < n_maps) {
+      D3D_REQUIRE(rows_host[m] >= 0 && (rows_host[m] == 0 || maps_host[m]), "rpn_head_bf16: map %d", m);
+      D3D_REQUIRE(((uintptr_t)maps_host[m] & 15) == 0, "rpn_head_bf16: map %d not 16-byte aligned", m);
+      maps.p[m] = (const unsigned short *)maps_host[m];
+      n += rows_host[m];
+    }
+  }
+  D3D_REQUIRE(n * 7L * a < (1L << 31), "rpn_head_bf16: %ld rows", n);
+  maps.start[D3D_RPN_MAX_MAPS] = (int)n;
+  for (int m = n_maps; m <= D3D_RPN_MAX_MAPS; m++) maps.start[m] = (int)n;
+  maps.n_maps = n_maps;
+  if (n == 0) return D3D_OK;
+  D3D_REQUIRE(objectness && regression, "rpn_head_bf16: null output");
+  const int out_tiles = (8 * a + 31) / 32;
+  const dim3 grid((unsigned)((n + 31) / 32));
+  const unsigned short *w1 = (const unsigned short *)w1_packed, *w2 = (const unsigned short *)w2_packed;
+  if (channels == 128)
+    hipLaunchKernelGGL(k_rpn_head_bf16<128>, grid, dim3(256), 0, s, maps, w1, b1, w2, b2, a, out_tiles, objectness,
+                       regression);
+  else
+    hipLaunchKernelGGL(k_rpn_head_bf16<256>, grid, dim3(512), 0, s, maps, w1, b1, w2, b2, a, out_tiles, objectness,
+                       regression);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

@@ -109,6 +109,29 @@ _FUSED_RPN_HEAD = os.environ.get("D3D_RPN_HEAD", "fused") != "gemm"     # "gemm"
 _FUSED_BOX_MLP = os.environ.get("D3D_BOX_MLP", "gemm") == "fused"
 
 
+HEAD_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _as(t, dtype):
+    """a parameter (or a tensor derived from one) as an operand of type `dtype`: itself when it has that type; under
+    autograd a differentiable cast (the fp32 master receives the gradient); at inference a copy cached per version"""
+    if t is None or t.dtype == dtype:
+        return t
+    if torch.is_grad_enabled():
+        return t.to(dtype)
+    key = (t.data_ptr(), t._version, dtype)
+    c = getattr(t, "_d3d_cast", None)
+    if c is None or c[0] != key:
+        c = (key, t.detach().to(dtype))
+        t._d3d_cast = c
+    return c[1]
+
+
+def _linear_as(layer, x):
+    """nn.Linear on operands of x's type (bf16 heads: bf16 weight and bias, fp32 accumulation in the library GEMM)"""
+    return F.linear(x, _as(layer.weight, x.dtype), _as(layer.bias, x.dtype))
+
+
 # ----------------------------------------------------------------------------------------------
 class AnchorGenerator(nn.Module):
     """modeling/rpn/anchor_generator_sparse3d.py:44-120,207-241: one anchor size per selected map,
@@ -202,66 +225,80 @@ class RPNHead(nn.Module):
 
     @staticmethod
     def _lin(layer, x):
-        return F.linear(x, layer.weight.view(layer.weight.shape[0], -1), layer.bias)
+        w, b = layer.weight, layer.bias
+        if x.dtype != w.dtype:          # bf16 heads: bf16 operands (autograd casts the fp32 masters)
+            w, b = _as(w, x.dtype), _as(b, x.dtype)
+        return F.linear(x, w.view(w.shape[0], -1), b)
 
     def _fused_ok(self, features):
+        """d3d_rpn_head (fp32) / d3d_rpn_head_bf16 serve the maps: 128 or 256 channels, 1..6 maps of one type, and at most
+        one 32-column output tile per wave (8a <= C; a wider head takes the library GEMMs)"""
         c = self.conv.weight.shape[0]
-        return (_FUSED_RPN_HEAD and c in (128, 256) and 1 <= len(features) <= 6 and
-                all(f.is_cuda and f.dtype == torch.float32 and f.is_contiguous() and f.dim() == 2 and f.shape[1] == c
+        a = self.num_anchors_per_location * self.seperate_rpn
+        dt = features[0].dtype if features else None
+        return (_FUSED_RPN_HEAD and c in (128, 256) and 8 * a <= c and 1 <= len(features) <= 6 and
+                dt in HEAD_DTYPES and
+                all(f.is_cuda and f.dtype == dt and f.is_contiguous() and f.dim() == 2 and f.shape[1] == c
                     for f in features))
 
-    def _packed(self):
+    def _packed(self, dtype=torch.float32):
         """The operands of d3d_rpn_head: W[co][4g+j] -> [g][co][j]; objectness and regression weights stacked into one
-        [8a, C] operand padded to whole 32-column tiles.  Re-made when a parameter changes (in-place updates bump
-        `_version`, loads and `.to()` replace the storage)."""
+        [8a, C] operand padded to whole 32-column tiles.  bf16 (d3d_rpn_head_bf16): W[co][8g+j] -> [g][co][j] in bf16,
+        biases fp32.  Re-made when a parameter changes (in-place updates bump `_version`, loads and `.to()` replace the
+        storage)."""
         ps = (self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias,
               self.bbox_pred.weight, self.bbox_pred.bias)
         key = tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_pack", (None,))[0] != key:
+        cache = "_pack" if dtype == torch.float32 else "_pack_bf16"
+        if getattr(self, cache, (None,))[0] != key:
             c = self.conv.weight.shape[0]
+            g = 4 if dtype == torch.float32 else 8
 
-            def pack(w):                                    # [cout, c] -> [c/4, cout, 4]
-                return w.view(w.shape[0], c // 4, 4).permute(1, 0, 2).contiguous()
+            def pack(w):                                    # [cout, c] -> [c/g, cout, g]
+                return w.view(w.shape[0], c // g, g).permute(1, 0, 2).contiguous().to(dtype)
 
             w2 = torch.cat([self.cls_logits.weight.detach().view(-1, c), self.bbox_pred.weight.detach().view(-1, c)], 0)
             pad = (-w2.shape[0]) % 32
             if pad:
                 w2 = torch.cat([w2, w2.new_zeros(pad, c)], 0)
-            self._pack = (key, pack(self.conv.weight.detach().view(c, c)), self.conv.bias.detach().contiguous(),
-                          pack(w2), torch.cat([self.cls_logits.bias.detach(), self.bbox_pred.bias.detach()]).contiguous())
-        return self._pack[1:]
+            setattr(self, cache, (key, pack(self.conv.weight.detach().view(c, c)), self.conv.bias.detach().contiguous(),
+                                  pack(w2),
+                                  torch.cat([self.cls_logits.bias.detach(), self.bbox_pred.bias.detach()]).contiguous()))
+        return getattr(self, cache)[1:]
 
     def _forward_fused(self, features):
-        """One d3d_rpn_head launch over the maps' rows where they lie (no concatenation, no library GEMMs)."""
+        """One d3d_rpn_head (_bf16) launch over the maps' rows where they lie (no concatenation, no library GEMMs)."""
         import ctypes
-        w1, b1, w2, b2 = self._packed()
+        bf16 = features[0].dtype == torch.bfloat16
+        w1, b1, w2, b2 = self._packed(features[0].dtype)
         a = self.num_anchors_per_location * self.seperate_rpn
         n = sum(f.shape[0] for f in features)
         dev = features[0].device
         obj = torch.empty((n, a), dtype=torch.float32, device=dev)
         reg = torch.empty((n, 7 * a), dtype=torch.float32, device=dev)
         maps = (ctypes.c_void_p * len(features))(*[f.data_ptr() for f in features])
-        check(lib().d3d_rpn_head(maps, _ints(tuple(int(f.shape[0]) for f in features)), len(features),
-                                 int(features[0].shape[1]), ptr(w1), ptr(b1), ptr(w2), ptr(b2), a, ptr(obj), ptr(reg),
-                                 stream_of()))
+        fn = lib().d3d_rpn_head_bf16 if bf16 else lib().d3d_rpn_head
+        check(fn(maps, _ints(tuple(int(f.shape[0]) for f in features)), len(features), int(features[0].shape[1]), ptr(w1),
+                 ptr(b1), ptr(w2), ptr(b2), a, ptr(obj), ptr(reg), stream_of()))
         return obj.view(-1, self.seperate_rpn), reg.view(-1, 7 * self.seperate_rpn)
 
     def forward(self, features):
         """features: list of [n_s, C]  ->  objectness [sum n_s*A], regression [sum n_s*A, 7] in the
-        flattening order of cat_scales_obj_reg (:19-77): scale, site, anchor."""
+        flattening order of cat_scales_obj_reg (:19-77): scale, site, anchor.  bf16 features (bf16 heads): bf16
+        operands, fp32 outputs."""
         if not torch.is_grad_enabled() and self._fused_ok(features):
             return self._forward_fused(features)
         if not torch.is_grad_enabled() and len(features) > 1:
             # the head is shared by the scales and acts per site: one GEMM over the concatenated sites
             t = F.relu(self._lin(self.conv, torch.cat(features, 0)))
-            return (self._lin(self.cls_logits, t).reshape(-1, self.seperate_rpn),
-                    self._lin(self.bbox_pred, t).reshape(-1, 7 * self.seperate_rpn))
+            return (self._lin(self.cls_logits, t).reshape(-1, self.seperate_rpn).float(),
+                    self._lin(self.bbox_pred, t).reshape(-1, 7 * self.seperate_rpn).float())
         obj, reg = [], []
         for f in features:
             t = F.relu(self._lin(self.conv, f))
             obj.append(self._lin(self.cls_logits, t).reshape(-1, self.seperate_rpn))
             reg.append(self._lin(self.bbox_pred, t).reshape(-1, 7 * self.seperate_rpn))
-        return torch.cat(obj, 0), torch.cat(reg, 0)
+        return torch.cat(obj, 0).float(), torch.cat(reg, 0).float()
 
 
 class PaddedProposals(object):
@@ -470,7 +507,7 @@ class Pooler(nn.Module):
         ph, pw, pz = self.output_size
         rois, levels = roi_prepare(boxes_metric, voxel_scale, self.scales, self.canonical_size, batch_ids, count)
         K, C = rois.shape[0], x[0].features.shape[1]
-        out = torch.empty((K, ph, pw, C, pz) if channels_inner else (K, C, ph, pw, pz), dtype=torch.float32,
+        out = torch.empty((K, ph, pw, C, pz) if channels_inner else (K, C, ph, pw, pz), dtype=x[0].features.dtype,
                           device=rois.device)
         if _ROI_ONE_LAUNCH and len(x) <= 4 and all(f.metadata is x[0].metadata for f in x):
             return roi_align_rotated_3d_sparse_levels_into(out, x, rois, self.scales, self.sampling_ratio, levels,
@@ -489,7 +526,7 @@ class Pooler(nn.Module):
         if not torch.is_grad_enabled():
             # one result tensor filled in place by one launch per level (no nonzero / index_put, no host sync)
             K, C = rois.shape[0], x[0].features.shape[1]
-            out = torch.empty((K, ph, pw, C, pz) if channels_inner else (K, C, ph, pw, pz), dtype=torch.float32,
+            out = torch.empty((K, ph, pw, C, pz) if channels_inner else (K, C, ph, pw, pz), dtype=x[0].features.dtype,
                               device=rois.device)
             levels = self.map_levels(boxes_pixels).to(torch.int32) if len(self.scales) > 1 else None
             for level, (fmap, scale) in enumerate(zip(x, self.scales)):   # crop = occupied extent, found on the device
@@ -500,7 +537,7 @@ class Pooler(nn.Module):
         if len(self.scales) == 1:
             return roi_align_rotated_3d_sparse(x[0], rois, self.scales[0], ph, pw, pz, self.sampling_ratio)
         levels = self.map_levels(boxes_pixels)
-        result = torch.zeros((rois.shape[0], x[0].features.shape[1], ph, pw, pz), dtype=torch.float32,
+        result = torch.zeros((rois.shape[0], x[0].features.shape[1], ph, pw, pz), dtype=x[0].features.dtype,
                              device=rois.device)
         for level, (fmap, scale) in enumerate(zip(x, self.scales)):
             idx = torch.nonzero(levels == level).squeeze(1)
@@ -545,15 +582,16 @@ class FPN2MLPFeatureExtractor(nn.Module):
 
     def _head_conv(self, pooled):
         """conv3d (kernel [1,1,pz] over a z extent of exactly pz) + BatchNorm3d + ReLU.  The convolution
-        is one [K*ph*pw, C*pz] x [C*pz, rep] GEMM (rocBLAS) instead of a MIOpen conv3d search."""
+        is one [K*ph*pw, C*pz] x [C*pz, rep] GEMM (rocBLAS) instead of a MIOpen conv3d search.  bf16 pooled rows (bf16
+        heads): the GEMM on bf16 operands, its result widened to fp32 for BatchNorm3d (fp32 statistics and output)."""
         conv, bn, relu = self.conv3d[0], self.conv3d[1], self.conv3d[2]
         K, C, ph, pw, pz = pooled.shape
         if tuple(conv.kernel_size) == (1, 1, pz) and tuple(conv.stride) == (1, 1, 1):
             a = pooled.permute(0, 2, 3, 1, 4).reshape(K * ph * pw, C * pz)
-            y = torch.addmm(conv.bias, a, conv.weight.view(conv.out_channels, C * pz).t())
+            y = torch.addmm(_as(conv.bias, a.dtype), a, _as(conv.weight, a.dtype).view(conv.out_channels, C * pz).t())
             y = y.view(K, ph, pw, conv.out_channels, 1).permute(0, 3, 1, 2, 4)
-            return relu(bn(y.contiguous()))
-        return self.conv3d(pooled)
+            return relu(bn(y.contiguous().float()))
+        return self.conv3d(pooled.float())
 
     def _fc6_rows_weight(self, cells):
         """fc6.weight with its input index reordered from (channel, cell) to (cell, channel): the operand for the
@@ -593,14 +631,17 @@ class FPN2MLPFeatureExtractor(nn.Module):
             pooled = self.pooler.pool_metric(x0, p, self.voxel_scale, channels_inner=True, batch_ids=batch_ids)
         mark("rois pooled")
         K, ph, pw, C, pz = pooled.shape
-        y = torch.addmm(conv.bias, pooled.view(K * ph * pw, C * pz), conv.weight.view(conv.out_channels, C * pz).t())
+        dt = pooled.dtype       # bf16 heads: bf16 GEMM operands, BatchNorm on the widened rows (fp32 statistics)
+        y = torch.addmm(_as(conv.bias, dt), pooled.view(K * ph * pw, C * pz),
+                        _as(conv.weight, dt).view(conv.out_channels, C * pz).t()).float()
         rep = y.shape[1]
         out, sm, si = y.new_empty(0), y.new_empty(rep), y.new_empty(rep)
         run = getattr(self, "_bn_running", None)      # throw-away running statistics (momentum 0: overwritten per call)
         if run is None or run[0].device != y.device or run[0].shape[0] != rep:
             run = self._bn_running = (y.new_zeros(rep), y.new_ones(rep))
         SCN.BatchNormalization_updateOutput(y, out, sm, si, run[0], run[1], bn.weight, bn.bias, bn.eps, 0.0, True, 0.0)
-        h = torch.addmm(self.fc6.bias, out.view(K, ph * pw * rep), self._fc6_rows_weight(ph * pw).t())
+        h = torch.addmm(_as(self.fc6.bias, dt), out.view(K, ph * pw * rep).to(dt),
+                        _as(self._fc6_rows_weight(ph * pw), dt).t())
         h = self._fc7_and_heads(h)
         mark("box features")
         return h
@@ -616,6 +657,8 @@ class FPN2MLPFeatureExtractor(nn.Module):
         """relu(fc7(relu(h6))) -- and, when the box head has handed its predictor over (`_heads`), cls_score and bbox_pred
         of the result in the same launch (d3d_mlp_heads; they ride on the returned tensor for FPNPredictor.forward, which
         produces the same bits when it is called on its own)."""
+        if h6.dtype != torch.float32:                 # bf16 heads: library GEMM on bf16 operands
+            return F.relu(_linear_as(self.fc7, F.relu(h6)))
         if not (_mlp_rows_ok(h6) and self.fc7.in_features == self.fc7.out_features == h6.shape[1]):
             return F.relu(self.fc7(F.relu(h6)))
         w1, b1 = self._fc7_packed()
@@ -642,6 +685,9 @@ class FPN2MLPFeatureExtractor(nn.Module):
         p[:, 0:6] *= self.voxel_scale                                           # convert_metric_to_pixel
         x1 = self._head_conv(self.pooler(x0, p, batch_ids=batch_ids))          # BatchNorm3d: all RoIs of the batch
         x2 = x1.reshape(x1.size(0), -1)
+        dt = x0[0].features.dtype
+        if dt != torch.float32:                 # bf16 heads: fc6 and fc7 on bf16 operands, bf16 box features
+            return F.relu(_linear_as(self.fc7, F.relu(_linear_as(self.fc6, x2.to(dt)))))
         return F.relu(self.fc7(F.relu(self.fc6(x2))))
 
 
@@ -673,6 +719,9 @@ class FPNPredictor(nn.Module):
                 and self.bbox_pred.out_features == 7 * self.cls_score.out_features)
 
     def forward(self, x):
+        """-> class logits [K, nc], box regression [K, 7 nc], fp32 (bf16 features: bf16 operands, widened results)"""
+        if x.dtype != torch.float32:
+            return _linear_as(self.cls_score, x).float(), _linear_as(self.bbox_pred, x).float()
         if self.fusable(x):
             w2, b2, a, key = self.packed()
             done = getattr(x, "_d3d_heads", None)        # computed with fc7 in one launch (FPN2MLPFeatureExtractor)
@@ -967,10 +1016,22 @@ class SparseRCNN(nn.Module):
         self.rpn = RPNModule(cfg)
         self.roi_heads = _RoiHeads(cfg)
         self.class_to_label = class_to_label(cfg.INPUT.CLASSES)
+        # operand type of the heads (RPN head, RoI pooling, box head): torch.float32, or torch.bfloat16 (bf16 maps, pooled
+        # rows and GEMM operands; parameters, their gradients, BatchNorm statistics, the heads' outputs, proposal
+        # selection, post-processing and losses stay fp32).  Independent of backbone.compute_dtype.
+        self.head_dtype = torch.float32
+
+    def _pass_head_dtype(self):
+        """validates head_dtype and hands it to the backbone, whose maps the heads then receive in that type (the
+        heads follow the type of what they are given)"""
+        if not any(self.head_dtype == d for d in HEAD_DTYPES):
+            raise ValueError(f"head_dtype {self.head_dtype!r}: torch.float32 or torch.bfloat16")
+        self.backbone.head_dtype = self.head_dtype
 
     def forward(self, points, targets=None, return_intermediates=False):
         """eval: detections dict.  train: dict of the four losses (targets = {"bbox3d" [M,7] yx_zb, "labels" [M]}; with
         several examples in `points` a list of B such dicts, as the reference's collate gives them)."""
+        self._pass_head_dtype()
         if self.training:
             if targets is None:
                 raise ValueError("In training mode, targets should be passed")
@@ -1013,6 +1074,7 @@ class SparseRCNN(nn.Module):
         return self.backbone.stage_geometry(points)
 
     def stage_features(self, net):
+        self._pass_head_dtype()
         return self.backbone.stage_features(net)
 
     def stage_tail(self, features, return_intermediates=False, n_examples=1):

@@ -54,19 +54,30 @@ def roi_align_rotated_3d_forward(input, rois, spatial_scale, pooled_height, pool
     return _RoiDenseFn.apply(inp, r, spatial_scale, pooled_height, pooled_width, pooled_zsize, sampling_ratio)
 
 
+def _forward_fn(feats):
+    """the sparse forward entry point for the map's storage type (fp32 or bf16: pooled rows of the same type)"""
+    if feats.dtype == torch.bfloat16:
+        return lib().d3d_roi_align_rotated_3d_sparse_forward_bf16
+    if feats.dtype != torch.float32:
+        raise TypeError(f"roi_align_rotated_3d_sparse: {feats.dtype} maps (float32 or bfloat16)")
+    return lib().d3d_roi_align_rotated_3d_sparse_forward
+
+
 class _RoiSparseFn(torch.autograd.Function):
     """forward: d3d_roi_align_rotated_3d_sparse_forward; backward: the dense backward of
     layers/roi_align_rotated_3d.py:29-51 restricted to the active sites (scatter-add into feature rows) -- under
-    torch.use_deterministic_algorithms(True) its fixed-order form, which gives the same bits in every run."""
+    torch.use_deterministic_algorithms(True) its fixed-order form, which gives the same bits in every run.
+    bf16 maps: pooled bf16 rows (the fp32 op on the widened map, rounded), bf16 gradients of the map (fp32 sums,
+    rounded once per row: the `_bf16` entry points)."""
 
     @staticmethod
     def forward(ctx, feats, rois, metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio):
         f = feats.contiguous()
         K, C = rois.shape[0], f.shape[1]
-        out = torch.empty((K, C, ph, pw, pz), dtype=torch.float32, device=f.device)
-        check(lib().d3d_roi_align_rotated_3d_sparse_forward(
-            metadata._h, ints(spatial_size), ptr(f), C, ints(crop), ptr(rois), K, float(spatial_scale), ph, pw, pz,
-            int(sampling_ratio), None, 0, 0, ptr(out), stream_of()))
+        fn = _forward_fn(f)
+        out = torch.empty((K, C, ph, pw, pz), dtype=f.dtype, device=f.device)
+        check(fn(metadata._h, ints(spatial_size), ptr(f), C, ints(crop), ptr(rois), K, float(spatial_scale), ph, pw, pz,
+                 int(sampling_ratio), None, 0, 0, ptr(out), stream_of()))
         ctx.save_for_backward(rois)
         ctx.args = (metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio, f.shape)
         return out
@@ -75,6 +86,10 @@ class _RoiSparseFn(torch.autograd.Function):
     def backward(ctx, grad):
         (rois,) = ctx.saved_tensors
         metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio, shape = ctx.args
+        if grad.dtype == torch.bfloat16:        # the gradient of bf16 pooled rows (a bf16 map)
+            return (_sparse_backward_bf16(grad.contiguous(), rois, metadata, spatial_size, crop,
+                                          spatial_scale, ph, pw, pz, sampling_ratio, shape),
+                    None, None, None, None, None, None, None, None, None)
         g = grad.contiguous()
         d_feats = torch.zeros(shape, dtype=torch.float32, device=g.device)
         if deterministic():
@@ -102,6 +117,31 @@ def _sparse_backward_deterministic(grad, rois, metadata, spatial_size, crop, spa
         int(sampling_ratio), ptr(d_feats), n_rows, ptr(scratch), int(nbytes), stream_of()))
 
 
+def _sparse_backward_bf16(grad, rois, metadata, spatial_size, crop, spatial_scale, ph, pw, pz, sampling_ratio, shape):
+    """bf16 map gradient [n_active, C] written fresh (not accumulated into): under
+    torch.use_deterministic_algorithms(True) the fixed-order form, else fp32 atomics into a scratch buffer rounded in one
+    launch; the scratch comes from torch's allocator (stream-ordered, released when the call returns)."""
+    n_rows, C = int(shape[0]), int(shape[1])
+    K = rois.shape[0]
+    d_feats = torch.empty((n_rows, C), dtype=torch.bfloat16, device=grad.device)
+    if deterministic():
+        if sampling_ratio > 0:
+            nbytes = lib().d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes(
+                K, C, ph, pw, pz, int(sampling_ratio), n_rows)
+            scratch = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=grad.device)
+            check(lib().d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16(
+                metadata._h, ints(spatial_size), ptr(grad), C, ints(crop), ptr(rois), K, float(spatial_scale), ph, pw,
+                pz, int(sampling_ratio), ptr(d_feats), n_rows, ptr(scratch), int(nbytes), stream_of()))
+            return d_feats
+        alert_not_deterministic("roi_align_rotated_3d_sparse backward with adaptive sampling (sampling_ratio <= 0)")
+    nbytes = lib().d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes(C, n_rows)
+    scratch = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=grad.device)
+    check(lib().d3d_roi_align_rotated_3d_sparse_backward_bf16(
+        metadata._h, ints(spatial_size), ptr(grad), C, ints(crop), ptr(rois), K, float(spatial_scale), ph, pw, pz,
+        int(sampling_ratio), ptr(d_feats), n_rows, ptr(scratch), int(nbytes), stream_of()))
+    return d_feats
+
+
 def roi_align_rotated_3d_sparse(feat_s3d, rois, spatial_scale, pooled_height, pooled_width, pooled_zsize,
                                 sampling_ratio, crop=None):
     """Equals roi_align_rotated_3d_forward(sparse_3d_to_dense_2d(feat_s3d), ...)
@@ -124,7 +164,8 @@ def roi_align_rotated_3d_sparse_into(out, feat_s3d, rois, spatial_scale, samplin
     f = feat_s3d.features.contiguous()
     r = rois.detach().to(torch.float32).contiguous()
     require_gpu(f, r, out)
-    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == r.shape[0]
+    fn = _forward_fn(f)
+    assert out.is_contiguous() and out.dtype == f.dtype and out.shape[0] == r.shape[0]
     if channels_inner:
         _, ph, pw, C, pz = out.shape
     else:
@@ -133,7 +174,7 @@ def roi_align_rotated_3d_sparse_into(out, feat_s3d, rois, spatial_scale, samplin
     if roi_levels is not None:
         assert roi_levels.dtype == torch.int32 and roi_levels.is_contiguous() and roi_levels.shape[0] == r.shape[0]
     # crop None: the library finds the occupied extent of the map on the device (no host read-back)
-    check(lib().d3d_roi_align_rotated_3d_sparse_forward(
+    check(fn(
         feat_s3d.metadata._h, ints(feat_s3d.spatial_size.tolist()), ptr(f), C,
         None if crop is None else ints([int(c) for c in crop]), ptr(r),
         r.shape[0], float(spatial_scale), ph, pw, pz, int(sampling_ratio), ptr(roi_levels), int(level),
@@ -148,17 +189,20 @@ def roi_align_rotated_3d_sparse_levels_into(out, maps, rois, scales, sampling_ra
     fs = [m.features.contiguous() for m in maps]
     r = rois.detach().to(torch.float32).contiguous()
     require_gpu(r, out, *fs)
-    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == r.shape[0]
+    bf16 = fs[0].dtype == torch.bfloat16
+    assert out.is_contiguous() and out.dtype == fs[0].dtype and out.shape[0] == r.shape[0]
     if channels_inner:
         _, ph, pw, C, pz = out.shape
     else:
         _, C, ph, pw, pz = out.shape
-    assert all(f.shape[1] == C and f.dtype == torch.float32 for f in fs) and 1 <= len(fs) <= 4
+    assert all(f.shape[1] == C and f.dtype == out.dtype for f in fs) and 1 <= len(fs) <= 4
+    fn = (lib().d3d_roi_align_rotated_3d_sparse_forward_levels_bf16 if bf16 else
+          lib().d3d_roi_align_rotated_3d_sparse_forward_levels)
     assert all(m.metadata is maps[0].metadata for m in maps)
     if roi_levels is not None:
         assert roi_levels.dtype == torch.int32 and roi_levels.is_contiguous() and roi_levels.shape[0] == r.shape[0]
     sizes = ints(tuple(int(v) for m in maps for v in m.spatial_size.tolist()))
-    check(lib().d3d_roi_align_rotated_3d_sparse_forward_levels(
+    check(fn(
         maps[0].metadata._h, len(fs), sizes, (ctypes.c_void_p * len(fs))(*[f.data_ptr() for f in fs]), C,
         floats(scales), ptr(r), r.shape[0], ph, pw, pz, int(sampling_ratio), ptr(roi_levels),
         1 if channels_inner else 0, ptr(out), stream_of()))

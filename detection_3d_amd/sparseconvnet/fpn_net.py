@@ -43,6 +43,25 @@ def _geometry_stream(main):
     return st
 
 
+class _RowsToBf16(torch.autograd.Function):
+    """fp32 rows -> bf16 rows in one launch (d3d_rows_to_bf16); the gradient goes back widened to fp32"""
+
+    @staticmethod
+    def forward(ctx, f):
+        return scn.SCN.rows_to_bf16(f, f.shape[1])
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad.float()
+
+
+def _rows_to_bf16(f):
+    """an fp32 map's rows for bf16 heads (round to nearest even, as .to(torch.bfloat16))"""
+    if f.is_cuda and f.dim() == 2 and f.shape[1] % 8 == 0:
+        return _RowsToBf16.apply(f)
+    return f.to(torch.bfloat16)
+
+
 class FPN_Net(torch.nn.Module):
     def __init__(self, full_scale, dimension, raw_elements, reps, nPlanesF, nPlaneM, residual_blocks,
                  fpn_scales_from_top, roi_scales_from_top, downsample, rpn_map_sizes,
@@ -62,6 +81,10 @@ class FPN_Net(torch.nn.Module):
         # torch.bfloat16 = BASELINE.json configs[4] (bf16 rows and weights, fp32 accumulation, fp32 statistics); in
         # training the rows' gradients are bf16 too, parameters, their gradients and the BatchNorm statistics fp32
         self.compute_dtype = torch.float32
+        # storage type of the maps handed to RPN / pooler (SparseRCNN.head_dtype, set by the detector before each pass):
+        # float32 = the backbone's maps widened (bf16 storage) or as they are; bfloat16 = bf16 rows, converted once from
+        # an fp32 backbone or passed on as they are from a bf16 one
+        self.head_dtype = torch.float32
         n_scales = len(nPlanesF)
         assert len(self.down_kernels) == n_scales - 1 == len(self.down_strides)
         in_channels = sum({'xyz': 3, 'color': 3, 'normal': 3}[e] for e in raw_elements)
@@ -132,7 +155,19 @@ class FPN_Net(torch.nn.Module):
             net.features = torch.nn.functional.pad(f, (0, width - f.shape[1])).to(self.compute_dtype)
         return net
 
-    def _from_compute(self, maps):
+    def _from_compute(self, maps, converted=None):
+        """maps -> the heads' storage type; `converted` (id -> tensor) shares the conversion of a map that both the RPN
+        and the pooler consume"""
+        if self.head_dtype == torch.bfloat16:
+            converted = {} if converted is None else converted
+            out = []
+            for t in maps:
+                if t is not None and t.features.dtype != torch.bfloat16:
+                    if id(t) not in converted:
+                        converted[id(t)] = scn.SparseConvNetTensor(_rows_to_bf16(t.features), t.metadata, t.spatial_size)
+                    t = converted[id(t)]
+                out.append(t)
+            return out
         if self.compute_dtype == torch.float32:
             return maps
         return [None if t is None else scn.SparseConvNetTensor(t.features.float(), t.metadata, t.spatial_size) for t in maps]
@@ -418,4 +453,5 @@ class FPN_Net(torch.nn.Module):
         roi_maps = [ups[i] for i in self.roi_scales_from_top]
         for i in range(len(rpn_maps_3d)):
             assert rpn_maps_3d[i].spatial_size.tolist() == [int(v) for v in self.rpn_map_sizes[i]]
-        return self._from_compute(rpn_maps), self._from_compute(roi_maps)
+        converted = {}
+        return self._from_compute(rpn_maps, converted), self._from_compute(roi_maps, converted)

@@ -160,6 +160,15 @@ int d3d_anchors_maps(d3d_meta *m, int n_maps, const int *sizes_host, const float
 int d3d_rpn_head(const float *const *maps_host, const int *rows_host, int n_maps, int channels,
                  const float *w1_packed, const float *b1, const float *w2_packed, const float *b2, int a,
                  float *objectness, float *regression, void *stream);
+/* The same head over bf16 rows (bf16 storage of the heads, SparseRCNN.head_dtype): maps_host[m] bf16 [rows_host[m],
+ * channels] (16-byte aligned), channels 128 or 256, and 8a <= channels (one 32-column output tile per wave at most;
+ * wider heads are the caller's library GEMMs).  Weights bf16, packed [channels/8, NOUT, 8] with
+ * packed[g][co][j] = W[co][8g+j] (w1: NOUT = channels; w2: the rows of (Wc; Wr) zero-padded to NOUT = 32*ceil(8a/32)),
+ * 16-byte aligned; b1 / b2 fp32.  Products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the hidden
+ * t = relu(x W1^T + b1) is rounded to bf16 before the second stage; objectness and regression are fp32.           */
+int d3d_rpn_head_bf16(const void *const *maps_host, const int *rows_host, int n_maps, int channels, const void *w1_packed,
+                      const float *b1, const void *w2_packed, const float *b2, int a, float *objectness,
+                      float *regression, void *stream);
 /* a22. The box head behind fc6 at inference (roi_box_feature_extractors.py:110-117, roi_box_predictors.py:33-55) with the
  * same kernel:  t = relu(relu?(x) W1^T + b1)  [rows, channels];  out_a = t Wa^T + ba  [rows, a];  out_7a = t Wb^T + bb
  * [rows, 7a]  (a = classes: cls_score and bbox_pred).  x [rows, channels] fp32, channels 128, 256 or 512; relu_in != 0
@@ -399,6 +408,30 @@ int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const in
                                                            void *stream);
 size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_scratch_bytes(int K, int C, int ph, int pw, int pz,
                                                                            int sampling_ratio, int n_rows);
+/* bf16 forms of the two sparse backwards above: top_diff bf16 [K, C, ph, pw, pz] (the bf16 forward's layout 0), d_feats
+ * bf16 [n_rows, C] with n_rows = the grid's active sites.  Unlike the fp32 forms they WRITE a fresh gradient (every row
+ * of d_feats is written, rows no tap reaches get 0), they do not add to one.
+ * _bf16: the fp32 atomics of d3d_roi_align_rotated_3d_sparse_backward into an fp32 buffer in `scratch` (zeroed by the
+ *   call), then one launch rounds it to d_feats.  scratch: d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes
+ *   (C, n_rows) bytes (0: arguments out of range); d_feats 8-byte aligned.
+ * _deterministic_bf16: the records, sort and chunk order of the fixed-order form with fp32 sums; a row is rounded when
+ *   it is written, so d_feats equals the fp32 fixed-order form run on the widened top_diff into zeros, rounded to bf16,
+ *   bit for bit.  sampling_ratio must be > 0 (adaptive sampling has no record bound before the launch).  scratch:
+ *   d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes(K, C, ph, pw, pz, sampling_ratio, n_rows)
+ *   bytes (0: arguments out of range).                                                                               */
+int d3d_roi_align_rotated_3d_sparse_backward_bf16(d3d_meta *m, const int *spatial_size_host, const void *top_diff, int C,
+                                                  const int *crop_host, const float *rois, int K, float spatial_scale,
+                                                  int ph, int pw, int pz, int sampling_ratio, void *d_feats, int n_rows,
+                                                  void *scratch, size_t scratch_bytes, void *stream);
+size_t d3d_roi_align_rotated_3d_sparse_backward_bf16_scratch_bytes(int C, int n_rows);
+int d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16(d3d_meta *m, const int *spatial_size_host,
+                                                                const void *top_diff, int C, const int *crop_host,
+                                                                const float *rois, int K, float spatial_scale, int ph,
+                                                                int pw, int pz, int sampling_ratio, void *d_feats,
+                                                                int n_rows, void *scratch, size_t scratch_bytes,
+                                                                void *stream);
+size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes(int K, int C, int ph, int pw, int pz,
+                                                                                int sampling_ratio, int n_rows);
 
 /* a8. BatchNormalization_updateOutput (SCN/sparseconvnet.h:21-26; SCN/CPU/BatchNormalization.cpp:12-60).
  * train!=0: batch statistics, running update r = m*r + (1-m)*batch.  train==0: uses
@@ -479,6 +512,18 @@ int d3d_roi_align_rotated_3d_sparse_forward_levels(d3d_meta *m, int n_levels, co
                                                    const float *rois, int K, int ph, int pw, int pz,
                                                    int sampling_ratio, const int *roi_levels, int layout, float *out,
                                                    void *stream);
+/* bf16 forms of the two above: feats bf16 [n_active, C] (4-byte aligned), out bf16 in the same layouts.  The taps are
+ * widened to fp32 and summed in the fp32 kernel's order, and each bin is rounded once when it is stored: the result is
+ * the fp32 op on the widened map, rounded to bf16 (round to nearest even), bit for bit.                              */
+int d3d_roi_align_rotated_3d_sparse_forward_bf16(d3d_meta *m, const int *spatial_size_host, const void *feats, int C,
+                                                 const int *crop_host, const float *rois, int K, float spatial_scale,
+                                                 int ph, int pw, int pz, int sampling_ratio, const int *roi_levels,
+                                                 int level, int layout, void *out, void *stream);
+int d3d_roi_align_rotated_3d_sparse_forward_levels_bf16(d3d_meta *m, int n_levels, const int *sizes_host,
+                                                        const void *const *feats_host, int C, const float *scales_host,
+                                                        const float *rois, int K, int ph, int pw, int pz,
+                                                        int sampling_ratio, const int *roi_levels, int layout, void *out,
+                                                        void *stream);
 
 /* a17. rotate_iou_gpu_eval (second/core/non_max_suppression/nms_gpu.py:614-664) incl.
  * check_same_boxes: boxes [N,5], query [K,5] -> out [N,K].                                   */

@@ -3,7 +3,7 @@ RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + 
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
-        [--deterministic [--seed S]] [--bf16]
+        [--deterministic [--seed S]] [--bf16] [--bf16-heads]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -44,7 +44,10 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of the weights and of the samplers")
     ap.add_argument("--bf16", action="store_true",
                     help="train the sparse backbone in bf16 storage (fp32 accumulation, fp32 weights, statistics and "
-                         "optimizer state; the heads stay fp32)")
+                         "optimizer state; the heads stay fp32 unless --bf16-heads)")
+    ap.add_argument("--bf16-heads", action="store_true",
+                    help="run the RPN head, RoI pooling and box head on bf16 operands (model.head_dtype; fp32 weights, "
+                         "statistics, outputs of the heads and losses); combinable with --bf16")
     return ap.parse_args(argv)
 
 
@@ -91,6 +94,8 @@ def main():
     model = build_detection_model(cfg).to(dev)
     if args.bf16:
         model.backbone.compute_dtype = torch.bfloat16
+    if args.bf16_heads:
+        model.head_dtype = torch.bfloat16
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
                        ims_per_gpu=args.ims_per_gpu)
     if args.verify:
@@ -112,6 +117,7 @@ def main():
             out["gt_per_scene"] = [int(gts[k]["bbox3d"].shape[0]) for k in sorted(gts)]
     if rank == 0:
         out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic, bf16=args.bf16,
+                   bf16_heads=args.bf16_heads,
                    points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
