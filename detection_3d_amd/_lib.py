@@ -23,6 +23,17 @@ class BnPrologue(ctypes.Structure):
 
 bn_p = ctypes.POINTER(BnPrologue)
 
+
+class AugmentParams(ctypes.Structure):
+    """d3d_augment_params (include/d3d_hip.h): one scene's augmentation, host memory."""
+    _fields_ = [("m", ctypes.c_double * 9), ("nrm", ctypes.c_double * 9), ("color", ctypes.c_double * 3),
+                ("u1", ctypes.c_double * 3), ("u2", ctypes.c_double * 3), ("origin_offset", ctypes.c_int),
+                ("color_col", ctypes.c_int), ("normal_col", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+aug_p = ctypes.POINTER(AugmentParams)
+c_double_p = ctypes.POINTER(ctypes.c_double)
+
 _SIGS = {
     "d3d_last_error": (ctypes.c_char_p, []),
     "d3d_abi_version": (ctypes.c_int, []),
@@ -59,6 +70,14 @@ _SIGS = {
     "d3d_voxelize": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_int_p, vp, vp,
                                     c_int_p, vp, ctypes.c_size_t, vp]),
     "d3d_voxelize_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_augment_voxelize": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, aug_p, ctypes.c_double, c_int_p, vp, vp,
+                                            c_int_p, c_double_p, vp, ctypes.c_size_t, vp]),
+    "d3d_augment_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_augment_transform": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, aug_p, vp, c_double_p, vp, ctypes.c_size_t,
+                                             vp]),
+    "d3d_elastic_blur": (ctypes.c_int, [vp, ctypes.c_int, c_int_p, vp, vp]),
+    "d3d_elastic_apply": (ctypes.c_int, [vp, ctypes.c_int, vp, c_int_p, ctypes.c_double, ctypes.c_double, c_double_p,
+                                         vp, ctypes.c_size_t, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

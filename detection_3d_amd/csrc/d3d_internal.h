@@ -60,6 +60,14 @@ struct Arena {
     return D3D_ERR_NOMEM;                                                              \
   }
 
+// per host thread and device: a 64-byte pinned word a kernel stores a count (or a few values) to and the event recorded
+// behind that store (d3d_voxelize, d3d_augment_*: the host waits for the event alone)
+struct VoxWord {
+  int32_t *word = nullptr;
+  hipEvent_t ev = nullptr;
+};
+VoxWord *vox_word();
+
 static constexpr uint64_t kEmptyKey = ~uint64_t(0);
 
 // One 16-byte hash slot: a probe is a single aligned 16-B load.  Initialised to all ones

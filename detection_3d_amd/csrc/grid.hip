@@ -1576,12 +1576,7 @@ __global__ void k_store_word(const int32_t *__restrict__ src, int32_t *__restric
   D3D_SIDE_PRIO();
   __hip_atomic_store(dst, *src, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// per host thread and device: a pinned word a kernel stores a count to and the event recorded behind that store
-struct VoxWord {
-  int32_t *word = nullptr;
-  hipEvent_t ev = nullptr;
-};
-static VoxWord *vox_word() {
+extern "C++" VoxWord *vox_word() {      // (shared with augment.hip)
   static thread_local VoxWord words[16];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {

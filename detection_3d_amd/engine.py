@@ -23,13 +23,18 @@ def _hip_voxelize(pcl, cfg):
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize):
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
-    the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets])."""
+    the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
+    augment (augment.Augment): every example is augmented on its own with its own draws, in place of `voxelize_fn`;
+    its targets must then be in the file's frame (ScenePrefetcher(shift_targets=False))."""
     cs, fs, tgs = [], [], []
     for b, (pcl, tg) in enumerate(scenes):
-        c, f = voxelize_fn(pcl, cfg)
+        if augment is None:
+            c, f = voxelize_fn(pcl, cfg)
+        else:
+            c, f, tg = augment(pcl, tg, cfg)
         cs.append(torch.cat([c, torch.full((c.shape[0], 1), b, dtype=c.dtype, device=c.device)], 1))
         fs.append(f)
         tgs.append(tg)
@@ -102,11 +107,11 @@ def evaluate(cfg, dets, gts):
     return eval_detection_suncg([host(dets[i]) for i in ids], [host(gts[i]) for i in ids], cfg)
 
 
-def _cycled_scenes(files, cfg, device, rank, world, depth):
+def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
     """the rank's buildings, prefetched, cycled epoch after epoch"""
     while True:
         pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank,
-                              world=world, depth=depth)
+                              world=world, depth=depth, shift_targets=shift_targets)
         if len(pre) == 0:
             raise ValueError(f"rank {rank} of {world} has no building: {len(files)} files")
         for pcl, tg, _path in pre:
@@ -114,12 +119,13 @@ def _cycled_scenes(files, cfg, device, rank, world, depth):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1):
+          ims_per_gpu=1, augment=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
-    process group with more than one rank exists.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced
-    losses)."""
+    process group with more than one rank exists.  augment (augment.Augment): every example is augmented on the GPU
+    while it is voxelised, rank r drawing with seed + 1000003 r; None keeps the plain path.  -> dict(buildings_per_s
+    (examples/s), ms_per_step, last reduced losses)."""
     rank, world = _rank_world()
     ims = int(ims_per_gpu)
     if ims < 1:
@@ -135,18 +141,24 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
         sched_cfg = cfg.clone()
         sched_cfg.SOLVER.IMS_PER_BATCH = world * ims
         sched = T.make_lr_scheduler(sched_cfg, opt, examples_per_epoch=max(len(files), 1))
+    aug = None if augment is None else augment.for_rank(rank)
+    if aug is not None:
+        aug.check_classes(cfg.INPUT.CLASSES)
     it, t0, reduced = 0, None, {}
-    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth), ims):
+    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth, aug is None), ims):
         if it == 1:                          # the first iteration pays allocations and the bucket build
             if device is not None:
                 torch.cuda.synchronize(device)
             t0 = time.perf_counter()
         if ims == 1:
             pcl, tg = batch[0]
-            coords, feats = voxelize_fn(pcl, cfg)
+            if aug is None:
+                coords, feats = voxelize_fn(pcl, cfg)
+            else:
+                coords, feats, tg = aug(pcl, tg, cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
         else:
-            points, tgs = collate(batch, cfg, voxelize_fn)
+            points, tgs = collate(batch, cfg, voxelize_fn, aug)
             _, reduced = T.train_step(ddp, opt, sched, points, tgs)
         it += 1
         if log_every and rank == 0 and it % log_every == 0:

@@ -166,15 +166,16 @@ def set_yaw_zero(boxes):
     return b
 
 
-def scene_targets(pcl, boxes_std, classes, scale):
+def scene_targets(pcl, boxes_std, classes, scale, shift=True):
     """Ground truth of one building in the detector's frame (suncg_dataset.py:97-166,235-250):
-    -> {"bbox3d": float32 [M,7] yx_zb shifted like the points, "labels": int64 [M]}."""
+    -> {"bbox3d": float32 [M,7] yx_zb shifted like the points, "labels": int64 [M]}.  shift=False: the boxes stay in the
+    file's frame (augment.Augment moves them with the points)."""
     c2l = class_to_label(classes)
     # min of (xyz * scale) in float64 = (min of xyz) * scale for scale > 0: the product is monotonic and the minimum's
     # product is computed from the same float32 value either way -- without a float64 copy of the whole cloud
     # (column by column: numpy's axis-0 reduction of a strided [N, 3] view is 4x slower than three 1-D ones)
     a_min = (np.array([pcl[:, d].min() for d in range(3)]).astype(np.float64) * float(scale)
-             if pcl.shape[0] else np.zeros(3))
+             if pcl.shape[0] and shift else np.zeros(3))
     offset = -a_min / float(scale)
     bb, ll = [], []
     for obj, b in boxes_std.items():
@@ -183,7 +184,8 @@ def scene_targets(pcl, boxes_std, classes, scale):
         b = standard_to_yx_zb(b)
         if obj in _ZERO_YAW_CLASSES:
             b = set_yaw_zero(b)
-        b[:, 0:3] += offset[None, :].astype(np.float64)            # float32 += float64, as the reference does
+        if shift:
+            b[:, 0:3] += offset[None, :].astype(np.float64)        # float32 += float64, as the reference does
         bb.append(b)
         ll.append(np.full(b.shape[0], c2l[obj], dtype=np.int64))
         assert c2l[obj] > 0, "label 0 is background"
@@ -210,8 +212,10 @@ class ScenePrefetcher(object):
     the copy through an event, never the host.  A 500 k-point building takes ~12 ms to read; three readers deliver one
     every ~5 ms, which is what a rank needs to keep its GPU busy at inference."""
 
-    def __init__(self, files, classes, scale, device=None, rank=0, world=1, depth=6, element_ids=None, workers=3):
+    def __init__(self, files, classes, scale, device=None, rank=0, world=1, depth=6, element_ids=None, workers=3,
+                 shift_targets=True):
         self.files = list(files)[rank::world]
+        self.shift_targets = bool(shift_targets)       # False: boxes in the file's frame, for augment.Augment
         self.classes, self.scale, self.device = list(classes), scale, device
         self.element_ids = None if element_ids is None else sorted(int(i) for i in element_ids)
         self.workers = max(1, min(int(workers), max(1, int(depth))))
@@ -228,7 +232,7 @@ class ScenePrefetcher(object):
         slot's pinned buffer (grown when a building is larger) and copied from there on the side stream."""
         if self.device is None:
             pcl, boxes = load_scene(path)
-            tg = scene_targets(pcl, boxes, self.classes, self.scale)
+            tg = scene_targets(pcl, boxes, self.classes, self.scale, self.shift_targets)
             if self.element_ids is not None:
                 pcl = np.ascontiguousarray(pcl[:, self.element_ids])
             return torch.from_numpy(pcl), {"bbox3d": torch.from_numpy(tg["bbox3d"]), "labels": torch.from_numpy(tg["labels"])}, None
@@ -239,7 +243,7 @@ class ScenePrefetcher(object):
             return pinned["buf"].numpy()
 
         pcl, boxes = load_scene_into(path, take)
-        tg = scene_targets(pcl, boxes, self.classes, self.scale)
+        tg = scene_targets(pcl, boxes, self.classes, self.scale, self.shift_targets)
         host = torch.from_numpy(pcl)                       # a view of the pinned buffer
         if self.element_ids is not None:
             host = host[:, self.element_ids].contiguous().pin_memory()

@@ -109,6 +109,46 @@ int d3d_voxelize(const float *pcl, int n, int nfeat, double scale, const int *fu
                  size_t scratch_bytes, void *stream);
 size_t d3d_voxelize_scratch_bytes(int n);
 
+/* Training-time augmentation of one scene, data3d/suncg_utils/suncg_dataset.py:113-149 (hard-wired off in the reference,
+ * :78-83).  Points are in voxel units: a = xyz . M, a_j = ((x m[0+j] + y m[3+j]) + z m[6+j]) in fp64 without contraction
+ * (m row-major, scale included, :115-122).  nrm: the normals' matrix (row-major, no scale); color: added to the three
+ * colour columns in fp64 (:140-142); u1, u2: the origin-offset draws of :127-132, used when origin_offset != 0.
+ * color_col / normal_col: first of the three colour / normal columns of the features, -1 when absent.             */
+typedef struct d3d_augment_params {
+  double m[9];
+  double nrm[9];
+  double color[3];
+  double u1[3];
+  double u2[3];
+  int origin_offset;
+  int color_col;
+  int normal_col;
+  int reserved;
+} d3d_augment_params;
+/* d3d_voxelize with the augmentation folded in: a = points (fp64 [n,3], from d3d_augment_transform and
+ * d3d_elastic_apply) or xyz . M when points is null; offset = -min(a) (+ the origin offset), :126-133; the bounds filter,
+ * trunc and feats[:,0:3] = (a + offset)/scale of d3d_voxelize; colour and normal columns transformed, other columns
+ * copied.  Identity parameters (m = diag(scale), nothing else) give d3d_voxelize's bits.  Synchronises once;
+ * *n_kept_host = rows written, offset_host[3] = the shift applied (voxel units).  scratch: d3d_augment_scratch_bytes. */
+int d3d_augment_voxelize(const float *pcl, int n, int nfeat, const double *points, const d3d_augment_params *prm_host,
+                         double scale, const int *full_scale_host, int64_t *coords_out, float *feats_out,
+                         int *n_kept_host, double *offset_host, void *scratch, size_t scratch_bytes, void *stream);
+size_t d3d_augment_scratch_bytes(int n);
+/* a = xyz . M into points_out (fp64 [n,3]) for the elastic passes; minmax_host[6] = per-axis min, then max (the grid of
+ * elastic(), :221, needs max |a|).  Synchronises once.  scratch: >= 64 bytes.                                         */
+int d3d_augment_transform(const float *pcl, int n, int nfeat, const d3d_augment_params *prm_host, double *points_out,
+                          double *minmax_host, void *scratch, size_t scratch_bytes, void *stream);
+/* elastic(), :223-228: the 3-tap 1/3 box filter along axes 0, 1, 2, 0, 1, 2 of nfields fp32 fields [nfields][d0][d1][d2]
+ * (dims_host[3]), zero padded, fp64 sums rounded to fp32 after every pass (scipy.ndimage.convolve, mode 'constant'), in
+ * place; tmp: a buffer of the same size.  Asynchronous.                                                               */
+int d3d_elastic_blur(float *fields, int nfields, const int *dims_host, float *tmp, void *stream);
+/* elastic(), :229-233: points += mag * (3 blurred fields [3][d0][d1][d2] sampled trilinearly in fp64 on the axes
+ * linspace(-(d-1) gran, (d-1) gran, d), 0 outside -- RegularGridInterpolator(bounds_error=0, fill_value=0)).
+ * minmax_host: null (asynchronous) or [6], per-axis min and max of the displaced points (synchronises once).
+ * scratch: >= 64 bytes.                                                                                              */
+int d3d_elastic_apply(double *points, int n, const float *fields, const int *dims_host, double gran, double mag,
+                      double *minmax_host, void *scratch, size_t scratch_bytes, void *stream);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with

@@ -3,7 +3,7 @@ RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + 
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
-        [--deterministic [--seed S]] [--bf16] [--bf16-heads]
+        [--deterministic [--seed S]] [--bf16] [--bf16-heads] [--augment flip,rotate[=quarter|free],scale=Z,offset,...]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -48,6 +48,9 @@ def parse_args(argv=None):
     ap.add_argument("--bf16-heads", action="store_true",
                     help="run the RPN head, RoI pooling and box head on bf16 operands (model.head_dtype; fp32 weights, "
                          "statistics, outputs of the heads and losses); combinable with --bf16")
+    ap.add_argument("--augment", default="",
+                    help="augment every training building on the GPU (detection_3d_amd.augment): a comma list of flip, "
+                         "rotate[=quarter|free], scale=Z, offset, elastic, color=S; seeded from --seed (+ 1000003 x rank)")
     return ap.parse_args(argv)
 
 
@@ -90,6 +93,8 @@ def main():
                 if not os.path.exists(f):
                     write_scene_file(f, i, args.points, cfg.INPUT.CLASSES)
         dist.barrier()
+    from detection_3d_amd.augment import parse_augment
+    augment = parse_augment(args.augment, args.seed)
     seed_everything(args)
     model = build_detection_model(cfg).to(dev)
     if args.bf16:
@@ -97,7 +102,7 @@ def main():
     if args.bf16_heads:
         model.head_dtype = torch.bfloat16
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
-                       ims_per_gpu=args.ims_per_gpu)
+                       ims_per_gpu=args.ims_per_gpu, augment=augment)
     if args.verify:
         # (1) the averaged-gradient steps leave every rank with the same weights (fingerprint: sum and sum of squares of
         # every parameter in fp64); (2) the sharded inference loop returns every scene's detections on rank 0
@@ -117,7 +122,7 @@ def main():
             out["gt_per_scene"] = [int(gts[k]["bbox3d"].shape[0]) for k in sorted(gts)]
     if rank == 0:
         out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic, bf16=args.bf16,
-                   bf16_heads=args.bf16_heads,
+                   bf16_heads=args.bf16_heads, augment=repr(augment) if augment is not None else None,
                    points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
