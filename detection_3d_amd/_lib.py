@@ -78,6 +78,11 @@ _SIGS = {
     "d3d_elastic_blur": (ctypes.c_int, [vp, ctypes.c_int, c_int_p, vp, vp]),
     "d3d_elastic_apply": (ctypes.c_int, [vp, ctypes.c_int, vp, c_int_p, ctypes.c_double, ctypes.c_double, c_double_p,
                                          vp, ctypes.c_size_t, vp]),
+    "d3d_estimate_normals_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_estimate_normals": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p, vp,
+                                            vp, vp, ctypes.c_size_t, vp]),
+    "d3d_estimate_normals_phases": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                                   c_float_p, vp, vp, vp, ctypes.c_size_t, vp, c_float_p]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

@@ -15,6 +15,7 @@ import torch.distributed as dist
 
 from . import training as T
 from .distributed import agree_capacity, gather_detections, pack_detections
+from .normals import normals_kwargs, with_normals
 from .scene_io import ScenePrefetcher
 
 
@@ -23,14 +24,24 @@ def _hip_voxelize(pcl, cfg):
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None):
+def _fill_normals(pcl, nkw):
+    """the raw cloud with estimated normal columns (normals.with_normals), on the stream that voxelises it"""
+    return pcl if nkw is None else with_normals(pcl, **nkw)
+
+
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
     the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
     augment (augment.Augment): every example is augmented on its own with its own draws, in place of `voxelize_fn`;
-    its targets must then be in the file's frame (ScenePrefetcher(shift_targets=False))."""
+    its targets must then be in the file's frame (ScenePrefetcher(shift_targets=False)).
+    normals (None, 'estimate' or a dict of estimate_normals keywords): the raw cloud's normal columns are estimated on
+    the GPU first (normals.with_normals), before voxelisation and before `augment`, which then flips and rotates them
+    with the points; its elastic distortion comes after the estimate and does not bend them."""
+    nkw = normals_kwargs(normals)
     cs, fs, tgs = [], [], []
     for b, (pcl, tg) in enumerate(scenes):
+        pcl = _fill_normals(pcl, nkw)
         if augment is None:
             c, f = voxelize_fn(pcl, cfg)
         else:
@@ -63,11 +74,14 @@ def _rank_world():
     return 0, 1
 
 
-def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip_voxelize):
+def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip_voxelize, normals=None):
     """Detections of every building in `files`, sharded over the ranks of the default process group.
     -> on rank 0: ({file index: detections dict}, {file index: targets dict of the building in the detector's frame});
-    None on the other ranks.  Targets travel with the detections so that rank 0 can evaluate without re-reading files."""
+    None on the other ranks.  Targets travel with the detections so that rank 0 can evaluate without re-reading files.
+    normals (None, 'estimate' or a dict of estimate_normals keywords): files that hold xyz, or xyz and colour, get their
+    normal columns estimated on the GPU before they are voxelised."""
     rank, world = _rank_world()
+    nkw = normals_kwargs(normals)
     max_det = max_det or int(cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG) * max(1, len(cfg.MODEL.SEPARATE_CLASSES_ID) + 1)
     pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank, world=world,
                           depth=depth)
@@ -76,7 +90,7 @@ def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip
     results, truths = [], []
     with torch.no_grad():
         for i, (pcl, tg, _path) in enumerate(pre):
-            coords, feats = voxelize_fn(pcl, cfg)
+            coords, feats = voxelize_fn(_fill_normals(pcl, nkw), cfg)
             results.append((rank + i * world, model([coords, feats])))
             truths.append({"bbox3d": tg["bbox3d"], "labels": tg["labels"],
                            "scores": torch.ones(tg["bbox3d"].shape[0], device=tg["bbox3d"].device)})
@@ -119,14 +133,17 @@ def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1, augment=None):
+          ims_per_gpu=1, augment=None, normals=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
     process group with more than one rank exists.  augment (augment.Augment): every example is augmented on the GPU
-    while it is voxelised, rank r drawing with seed + 1000003 r; None keeps the plain path.  -> dict(buildings_per_s
-    (examples/s), ms_per_step, last reduced losses)."""
+    while it is voxelised, rank r drawing with seed + 1000003 r; None keeps the plain path.  normals (None, 'estimate' or
+    a dict of estimate_normals keywords): every raw cloud's normal columns are estimated on the GPU before voxelisation
+    and before `augment`; the augmentation flips and rotates them, and they are not estimated again after its elastic
+    distortion.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
     rank, world = _rank_world()
+    nkw = normals_kwargs(normals)
     ims = int(ims_per_gpu)
     if ims < 1:
         raise ValueError(f"ims_per_gpu {ims_per_gpu} < 1")
@@ -152,13 +169,14 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
             t0 = time.perf_counter()
         if ims == 1:
             pcl, tg = batch[0]
+            pcl = _fill_normals(pcl, nkw)
             if aug is None:
                 coords, feats = voxelize_fn(pcl, cfg)
             else:
                 coords, feats, tg = aug(pcl, tg, cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
         else:
-            points, tgs = collate(batch, cfg, voxelize_fn, aug)
+            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw)
             _, reduced = T.train_step(ddp, opt, sched, points, tgs)
         it += 1
         if log_every and rank == 0 and it % log_every == 0:

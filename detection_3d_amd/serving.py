@@ -24,12 +24,18 @@ import threading
 
 import torch
 
+from .normals import normals_kwargs, with_normals
 from .voxelize import voxelize
 
 
 class BuildingPipeline(object):
-    def __init__(self, model, cfg, in_flight=2, device=None):
+    """normals: None (clouds arrive with every column the config takes), 'estimate' or a dict of estimate_normals
+    keywords: every raw cloud ([N, 3], [N, 6] or [N, 9]) gets its normal columns from normals.with_normals before it is
+    voxelised, on its slot's geometry stream."""
+
+    def __init__(self, model, cfg, in_flight=2, device=None, normals=None):
         self.model, self.cfg = model, cfg
+        self.normals = normals_kwargs(normals)
         self.device = device if device is not None else next(model.parameters()).device
         self.in_flight = max(1, int(in_flight))
         # streams live as long as the pipeline: metadata arenas and scratch buffers are recycled per stream
@@ -84,7 +90,8 @@ class BuildingPipeline(object):
                 hi, lo = slot(i)
                 with torch.cuda.stream(hi):
                     hi.wait_stream(lo)      # the slot's previous building has left its arena and allocator blocks
-                    coords, feats = voxelize(clouds[i], s3d.VOXEL_SCALE, s3d.VOXEL_FULL_SCALE)
+                    pcl = clouds[i] if self.normals is None else with_normals(clouds[i], **self.normals)
+                    coords, feats = voxelize(pcl, s3d.VOXEL_SCALE, s3d.VOXEL_FULL_SCALE)
                     net = self.model.stage_geometry([coords, feats])
                     lo.wait_stream(hi)
                 q_feat.put((i, net))

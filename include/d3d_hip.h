@@ -149,6 +149,24 @@ int d3d_elastic_blur(float *fields, int nfields, const int *dims_host, float *tm
 int d3d_elastic_apply(double *points, int n, const float *fields, const int *dims_host, double gran, double mag,
                       double *minmax_host, void *scratch, size_t scratch_bytes, void *stream);
 
+/* Point normals for a cloud that has none (data3d/indoor_data_util.py:73-76, add_norm: open3d's hybrid search).  For
+ * every point i of xyz (fp32, row i at xyz + i * row_stride_floats, so the xyz columns of an [n, 6] or [n, 9] cloud are
+ * read in place): the candidates are all j, i included, with d2 = (dx dx + dy dy) + dz dz <= radius * radius in fp32 from
+ * the fp32 offset p_j - p_i; more than max_nn candidates are cut to the max_nn smallest by (d2, j); counts[i] = the
+ * number kept.  Fewer than 3, or coincident points: normal (0, 0, 1).  Otherwise the unit eigenvector of the smallest
+ * eigenvalue of the kept points' covariance (fp32 sums about the query, fp64 eigen solve), with its component of
+ * largest magnitude positive (ties: lowest axis) when viewpoint_host is null, else with n . (v - p_i) >= 0.  The same
+ * input gives the same bits.  Asynchronous, no host read-back; scratch: d3d_estimate_normals_scratch_bytes(n, max_nn)
+ * bytes, which depend on n alone and not on the cloud's extent.                                                       */
+size_t d3d_estimate_normals_scratch_bytes(int n, int max_nn);
+int d3d_estimate_normals(const float *xyz, int n, int row_stride_floats, float radius, int max_nn,
+                         const float *viewpoint_host /* NULL: canonical sign */, float *normals /* [n,3] */,
+                         int32_t *counts /* [n] or NULL */, void *scratch, size_t scratch_bytes, void *stream);
+/* The same, timed: phase_ms_host[4] = cell coordinates, sort, cell table, search (events on `stream`).  Synchronises. */
+int d3d_estimate_normals_phases(const float *xyz, int n, int row_stride_floats, float radius, int max_nn,
+                                const float *viewpoint_host, float *normals, int32_t *counts, void *scratch,
+                                size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with

@@ -4,6 +4,7 @@ RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
         [--deterministic [--seed S]] [--bf16] [--bf16-heads] [--augment flip,rotate[=quarter|free],scale=Z,offset,...]
+        [--estimate-normals[=radius,max_nn]]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -51,7 +52,13 @@ def parse_args(argv=None):
     ap.add_argument("--augment", default="",
                     help="augment every training building on the GPU (detection_3d_amd.augment): a comma list of flip, "
                          "rotate[=quarter|free], scale=Z, offset, elastic, color=S; seeded from --seed (+ 1000003 x rank)")
-    return ap.parse_args(argv)
+    ap.add_argument("--estimate-normals", nargs="?", const="", default=None, metavar="RADIUS[,MAX_NN]",
+                    help="estimate the normal columns of every building on the GPU before it is voxelised and augmented "
+                         "(detection_3d_amd.normals; files that hold xyz, or xyz and colour); default 0.1,50")
+    args = ap.parse_args(argv)
+    from detection_3d_amd.normals import parse_estimate_normals
+    args.normals = parse_estimate_normals(args.estimate_normals)
+    return args
 
 
 def seed_everything(args):
@@ -102,7 +109,7 @@ def main():
     if args.bf16_heads:
         model.head_dtype = torch.bfloat16
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
-                       ims_per_gpu=args.ims_per_gpu, augment=augment)
+                       ims_per_gpu=args.ims_per_gpu, augment=augment, normals=args.normals)
     if args.verify:
         # (1) the averaged-gradient steps leave every rank with the same weights (fingerprint: sum and sum of squares of
         # every parameter in fp64); (2) the sharded inference loop returns every scene's detections on rank 0
@@ -114,7 +121,7 @@ def main():
         fps = [torch.empty_like(fp) for _ in range(WORLD)]
         dist.all_gather(fps, fp)
         out["weights_equal"] = bool(all(torch.equal(fps[0], f) for f in fps))
-        res = engine.inference(model, cfg, files, dev)
+        res = engine.inference(model, cfg, files, dev, normals=args.normals)
         if rank == 0:
             dets, gts = res
             out["scenes_gathered"] = sorted(int(k) for k in dets)
@@ -123,6 +130,7 @@ def main():
     if rank == 0:
         out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic, bf16=args.bf16,
                    bf16_heads=args.bf16_heads, augment=repr(augment) if augment is not None else None,
+                   normals=args.normals,
                    points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
