@@ -494,23 +494,6 @@ __global__ void k_conv_insert(const int32_t *__restrict__ loc, long n_entries, C
   atomicMin(&tab[slot].first, (uint32_t)e);
   eslot[e] = slot;
 }
-__global__ void k_conv_assign(const int32_t *__restrict__ loc, long n_entries, ConvGeom g,
-                              const int32_t *__restrict__ eslot, const int32_t *__restrict__ flag,
-                              const int32_t *__restrict__ rank, HashEntry *tab, int32_t *loc_out) {
-  D3D_SIDE_PRIO();
-  long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_entries || !flag[e]) return;
-  int i = (int)(e / g.max_out), j = (int)(e % g.max_out);
-  const int32_t *p = loc + (size_t)i * 4;
-  int o[3], off;
-  conv_entry(g, p, j, o, &off);
-  int id = rank[e];
-  tab[eslot[e]].val = id;
-  loc_out[id * 4 + 0] = o[0];
-  loc_out[id * 4 + 1] = o[1];
-  loc_out[id * 4 + 2] = o[2];
-  loc_out[id * 4 + 3] = p[3];
-}
 // nbr_dec may be null (no deconvolution / backward view of this rulebook will be asked for)
 __global__ void k_conv_fill(const int32_t *__restrict__ loc, long n_entries, ConvGeom g, int K,
                             const int32_t *__restrict__ eslot, const HashEntry *__restrict__ tab,
@@ -531,8 +514,8 @@ __global__ void k_conv_fill(const int32_t *__restrict__ loc, long n_entries, Con
 // First-touch numbering of a strided grid's output sites without a scan over the entries: a tile of kChainTile entries
 // leaves its first-touch flags as 32 ballot words and their number (k_chain_flag); k_chain_assign then sums the counts of
 // the tiles before its own (a few hundred integers, no cross-workgroup waiting), ranks its flags with popcounts and writes
-// site ids, coordinates and -- the last tile -- the site count, all on the device.  Two launches for what k_flag_first,
-// the three scan kernels and k_conv_assign did in five, and nothing the host has to read before the next level starts.
+// site ids, coordinates and -- the last tile -- the site count, all on the device.  Two launches where a flag kernel,
+// a three-kernel scan and an assignment kernel took five, and nothing the host has to read before the next level starts.
 static constexpr int kChainTile = 2048;   // = 256 threads x 8 rounds; word w of a tile = its entries 64 w .. 64 w + 63
 __global__ __launch_bounds__(256) void k_chain_flag(const int32_t *__restrict__ eslot, const HashEntry *__restrict__ tab,
                                                     long n_entries, int max_out, const int32_t *__restrict__ n_in_dev,
@@ -645,41 +628,26 @@ __global__ void k_store_counts(CountPtrs c, int32_t *__restrict__ host) {
   if (i < c.n) __hip_atomic_store(&host[i], *c.p[i], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// The whole strided-grid build of a SMALL level in one single-workgroup launch: table + rulebook initialisation,
-// insertion, first-touch flags, their exclusive scan in entry order, site numbering, and the forward / decoded
-// rulebook fill -- what the large path spreads over 11 launches (3 fills, k_conv_insert, k_flag_first, 3 scan kernels,
-// k_conv_assign, k_conv_fill).  The coarse pyramid levels are pure latency (each launch a dependent step of the chain
-// the host waits on for the site count), so fewer steps is what matters; the results are the large path's, bit for bit.
+// The whole strided-grid build of a SMALL level in one single-workgroup launch: insertion, first-touch flags, their
+// exclusive scan in entry order, site numbering, and the forward / decoded rulebook fill -- what the large path spreads
+// over four launches (k_conv_insert, k_chain_flag, k_chain_assign, k_conv_fill).  The coarse pyramid levels are pure
+// latency (each launch a dependent step of the chain), so fewer steps is what matters; the results are the large
+// path's, bit for bit.  Table and rulebook arrays already hold 0xFF (the chain's one fill launch).
 // Threads keep their entries' slots in registers; table fields other threads wrote are read with agent-scope atomic
 // loads (L2), never through a possibly stale L1 line.
-static constexpr int kSmallGrid = 4096;                        // entries one workgroup takes (16 k: slower than the 11 launches)
+static constexpr int kSmallGrid = 4096;                        // entries one workgroup takes (16 k: slower than the large path)
 static constexpr int kSmallGridThreads = 256;                  // 4 waves: finds a slot on a busy CU (see k_plan_small)
 static constexpr int kSmallGridEPT = kSmallGrid / kSmallGridThreads;
-// n_in_dev (may be null): the input site count on the device (n_entries / n_in are then upper bounds; the grid chain);
-// prefilled: table and rulebook arrays already hold 0xFF (the chain's one fill launch); nbr_dec may be null.
+// n_in_dev (may be null): the input site count on the device (n_entries is then an upper bound); nbr_dec may be null.
 __global__ __launch_bounds__(kSmallGridThreads) void k_conv_grid_small(const int32_t *__restrict__ loc, int n_entries, ConvGeom g,
-                                                          int K, int n_in, HashEntry *tab, int cap,
+                                                          int K, HashEntry *tab, int cap,
                                                           int32_t *__restrict__ loc_out, int32_t *__restrict__ nbr_fwd,
                                                           int32_t *__restrict__ nbr_dec, int32_t *__restrict__ total,
-                                                          const int32_t *__restrict__ n_in_dev, int prefilled) {
+                                                          const int32_t *__restrict__ n_in_dev) {
   D3D_SIDE_PRIO();
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   __shared__ int wsum[kSmallGridThreads / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (n_in_dev) {
-    n_in = *n_in_dev;
-    n_entries = n_in * g.max_out;
-  }
-  if (!prefilled) {
-    const u32x4 ones = {~0u, ~0u, ~0u, ~0u};
-    for (int i = tid; i < cap; i += kSmallGridThreads) *(u32x4 *)&tab[i] = ones;
-    if (nbr_dec)
-      for (int i = tid; i < n_in * K + 1; i += kSmallGridThreads) nbr_dec[i] = -1;
-    for (int i = tid; i < n_entries * K + 1; i += kSmallGridThreads) nbr_fwd[i] = -1;      // n_out <= n_entries rows are read later
-    __syncthreads();   // every wave's stores have reached L2 ...
-    if (tid == 0) __threadfence();   // ... one agent-scope fence for the workgroup (as in k_bn_stats)
-    __syncthreads();
-  }
+  if (n_in_dev) n_entries = *n_in_dev * g.max_out;
   int slot_r[kSmallGridEPT];
 #pragma unroll
   for (int it = 0; it < kSmallGridEPT; it++) {
@@ -1378,13 +1346,7 @@ namespace d3d {
 // while it waits.  The thread builds the listed rulebooks in order on the geometry stream and publishes, per entry,
 // the output site count and an event; the caller picks an entry up when it needs it (d3d_geometry_async_wait).
 // A new strided grid is complete (hash table, coordinates, site count) as soon as its count has been read back, before
-// the strided rulebook that d3d_conv_prepare builds with it: it is entered into the metadata then.
-static void publish_grid(d3d_meta *m, Grid &go, int n_out, const int *out_size) {
-  go.n = n_out;
-  D3D_LOCK(m);
-  m->grids[Size3{out_size[0], out_size[1], out_size[2]}] = go;
-}
-
+// the strided rulebook built with it: run_grid_chain enters it into the metadata then.
 struct GeoAsync {
   std::thread th, th_views;                 // the grids (blocking read-backs) / the views behind them; started with the
   bool threads_up = false, stop = false;    // first chain of this metadata and kept (a handle serves scene after scene)
@@ -1417,7 +1379,7 @@ static int geo_begin(GeoAsync *g) {
   set_error("geometry thread: hipSetDevice(%d) failed", g->device);
   return D3D_ERR_HIP;
 }
-static void geo_run_grids(d3d_meta *m, GeoAsync *g);   // (call d3d_conv_prepare & co, defined with the C entry points)
+static void geo_run_grids(d3d_meta *m, GeoAsync *g);   // (run_grid_chain / d3d_subm_prepare & co, defined with the C entry points)
 static void geo_run_views(d3d_meta *m, GeoAsync *g);
 static void geo_worker(d3d_meta *m, GeoAsync *g, int which) {
   int seen = 0;
@@ -2065,146 +2027,21 @@ int d3d_subm_prepare(d3d_meta *m, const int *size, const int *filt, void *stream
   return D3D_OK;
 }
 
-int d3d_conv_prepare(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                     const int *stride, void *stream, int *n_out_host, long *n_rules_host) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  PlanKey key = make_key(1, in_size, filt, stride);
-  std::map<PlanKey, Plan>::iterator it;
-  bool have;
-  {
-    D3D_LOCK(m);
-    it = m->plans.find(key);
-    have = it != m->plans.end();
-  }
-  if (!have) {
-    if (int rc = check_build_stream(m, s, "strided rulebook")) return rc;
-    Grid *gi = find_grid(m, in_size);
-    if (!gi) {
-      set_error("strided rulebook: no grid of spatial size [%d,%d,%d]", in_size[0], in_size[1], in_size[2]);
-      return D3D_ERR_STATE;
-    }
-    ConvGeom geo;
-    int K = 1, max_out = 1;
-    for (int d = 0; d < 3; d++) {
-      D3D_REQUIRE(filt[d] > 0 && stride[d] > 0 && out_size[d] > 0, "bad filter/stride/size");
-      D3D_REQUIRE((out_size[d] - 1) * stride[d] + filt[d] == in_size[d],
-                  "convolution sizes inconsistent: (out-1)*stride+filter != in (convolution.py:37-38)");
-      geo.filt[d] = filt[d];
-      geo.stride[d] = stride[d];
-      geo.out_size[d] = out_size[d];
-      K *= filt[d];
-      max_out *= std::min((filt[d] + stride[d] - 1) / stride[d], out_size[d]);
-    }
-    geo.max_out = max_out;
-    D3D_REQUIRE(K <= 32, "filter volume %d not supported (<= 32)", K);
-    D3D_REQUIRE(max_out <= 8, "each input site may feed at most 8 outputs");
-    if (find_grid(m, out_size)) {
-      set_error("strided rulebook: output grid [%d,%d,%d] already exists", out_size[0], out_size[1], out_size[2]);
-      return D3D_ERR_STATE;
-    }
-    Arena &A = m->arena;
-    const int n_in = gi->n;
-    const long n_entries = (long)n_in * max_out;
-    Grid go;
-    for (int d = 0; d < 3; d++) go.size[d] = out_size[d];
-    go.cap = next_pow2(2L * n_entries);
-    D3D_ALLOC(tab, HashEntry, A, go.cap);
-    D3D_ALLOC(loc_out, int32_t, A, (size_t)n_entries * 4 + 4);
-    D3D_ALLOC(nbr_dec, int32_t, A, (size_t)n_in * K + 1);
-    go.tab = tab;
-    go.loc = loc_out;
-    const bool small = n_entries > 0 && n_entries <= kSmallGrid;   // one launch does it all (k_conv_grid_small)
-    if (!small) {
-      D3D_HIP_CHECK(fill_ones(tab, sizeof(HashEntry) * go.cap, s));
-      D3D_HIP_CHECK(fill_ones(nbr_dec, sizeof(int32_t) * ((size_t)n_in * K + 1), s));
-    }
-    Plan p;
-    int n_out = 0;
-    if (small) {
-      size_t raw_bytes = ((size_t)n_entries * K + 1) * sizeof(int32_t);
-      if (A.used + raw_bytes + (size_t)(1 << 20) > A.cap) {
-        set_error("metadata arena exhausted while building a strided rulebook");
-        return D3D_ERR_NOMEM;
-      }
-      int32_t *nbr_fwd = (int32_t *)(A.base + ((A.cap - raw_bytes) & ~size_t(255)));
-      CapGuard guard(A, (A.cap - raw_bytes) & ~size_t(255));
-      size_t mark = A.used;
-      D3D_ALLOC(total, int32_t, A, 1);
-      hipLaunchKernelGGL(k_conv_grid_small, dim3(1), dim3(kSmallGridThreads), 0, s, gi->loc, (int)n_entries, geo, K, n_in, tab, go.cap,
-                         loc_out, nbr_fwd, nbr_dec, total, (const int32_t *)nullptr, 0);
-      D3D_LAUNCH_CHECK();
-      D3D_HIP_CHECK(hipMemcpyAsync(&m->host_words[1], total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      D3D_HIP_CHECK(hipStreamSynchronize(s));
-      n_out = (int)*(int32_t *)&m->host_words[1];
-      A.used = mark;
-      publish_grid(m, go, n_out, out_size);
-      int rc = finalize_plan(m, nbr_fwd, n_out, K, p, s, nullptr);
-      if (rc) return rc;
-    } else if (n_entries > 0) {
-      // raw forward table staged at the far end of the arena (size known only after the scan:
-      // bound it by n_entries rows)
-      size_t raw_bytes = ((size_t)n_entries * K + 1) * sizeof(int32_t);
-      if (A.used + raw_bytes + 12 * (size_t)n_entries * sizeof(int32_t) + (size_t)(1 << 20) > A.cap) {
-        set_error("metadata arena exhausted while building a strided rulebook");
-        return D3D_ERR_NOMEM;
-      }
-      int32_t *nbr_fwd = (int32_t *)(A.base + ((A.cap - raw_bytes) & ~size_t(255)));
-      CapGuard guard(A, (A.cap - raw_bytes) & ~size_t(255));
-      size_t mark = A.used;
-      D3D_ALLOC(eslot, int32_t, A, n_entries);
-      D3D_ALLOC(flag, int32_t, A, n_entries);
-      D3D_ALLOC(rank, int32_t, A, n_entries);
-      D3D_ALLOC(total, int32_t, A, 1);
-      hipLaunchKernelGGL(k_conv_insert, grid1d(n_entries), dim3(256), 0, s, gi->loc, n_entries, geo, tab, go.cap, eslot,
-                         (const int32_t *)nullptr);
-      hipLaunchKernelGGL(k_flag_first, grid1d(n_entries), dim3(256), 0, s, eslot, tab, (int)n_entries, flag);
-      int rc = scan_exclusive_i32(flag, rank, (int)n_entries, total, A, s);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_conv_assign, grid1d(n_entries), dim3(256), 0, s, gi->loc, n_entries, geo, eslot, flag, rank, tab, loc_out);
-      D3D_HIP_CHECK(hipMemcpyAsync(&m->host_words[1], total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      D3D_HIP_CHECK(hipStreamSynchronize(s));
-      n_out = (int)*(int32_t *)&m->host_words[1];
-      publish_grid(m, go, n_out, out_size);
-      D3D_HIP_CHECK(fill_ones(nbr_fwd, sizeof(int32_t) * ((size_t)n_out * K + 1), s));
-      hipLaunchKernelGGL(k_conv_fill, grid1d(n_entries), dim3(256), 0, s, gi->loc, n_entries, geo, K, eslot, tab, nbr_fwd, nbr_dec,
-                         (const int32_t *)nullptr);
-      D3D_LAUNCH_CHECK();
-      A.used = mark;
-      rc = finalize_plan(m, nbr_fwd, n_out, K, p, s, nullptr);
-      if (rc) return rc;
-    } else {
-      publish_grid(m, go, 0, out_size);
-      int rc = finalize_plan(m, nullptr, 0, K, p, s, nullptr);
-      if (rc) return rc;
-    }
-    D3D_LOCK(m);   // the raw table and the rulebook become visible together (the grid already is: publish_grid)
-    StridedRaw raw;
-    raw.nbr_dec = nbr_dec;
-    raw.n_in = n_in;
-    raw.out_size = Size3{out_size[0], out_size[1], out_size[2]};
-    m->strided_raw[key] = raw;
-    p.n_in = n_in;
-    it = m->plans.emplace(key, p).first;
-  }
-  if (n_out_host) *n_out_host = it->second.n_rows;
-  if (n_rules_host) return plan_rules(m, it->second, s, n_rules_host);
-  return D3D_OK;
-}
-
 }  // extern "C" (reopened below)
 
 namespace d3d {
 // ------------------------------------------------------------------------------------------------------------------
-// Grid chain: the strided grids (+ raw rule tables) of a whole pyramid enqueued WITHOUT a host read-back between the
-// levels.  d3d_conv_prepare reads every new grid's site count back before it can size the next level's launches and
-// allocations: 11 stream synchronisations per building, each with the GPU idle on that stream for the round trip.  Here
-// every level is sized by an upper bound known ahead of time -- sites(out) <= min(entries(in), cells of the occupied box
-// at that level), from the input grid's site count and coordinate extents, which arrive in ONE read-back -- its kernels
+// Grid chain: the one builder of strided grids (+ raw rule tables) -- a whole pyramid enqueued WITHOUT a host read-back
+// between the levels (the geometry thread), or a single level (d3d_conv_prepare).  Reading every new grid's site count
+// back before the next level is sized costs 11 stream synchronisations per building, each with the GPU idle on that
+// stream for the round trip.  Here every level is sized by an upper bound known ahead of time -- sites(out) <=
+// min(entries(in), cells of the occupied box at that level), from the input grid's site count and coordinate
+// extents, which arrive in ONE read-back (an input grid without known extents: the entry bound alone) -- its kernels
 // read the true count from the device word the level before left, all tables get their 0xFF fill in one launch up
 // front, and the counts of all levels come back together behind the last kernel (k_store_counts -> pinned words, one
 // event).  Only then are the grids published and the rulebooks finalised (exact sizes), in order.
-// Results are those of d3d_conv_prepare bit for bit: same insertion, same first-touch numbering, same tables.
+// Sites are numbered by first touch in entry order (ConvolutionRules.h:12-34), whatever the bounds and however many
+// levels one call takes: tests/test_scn_gpu.py and tests/test_fullsize_gpu.py pin that numbering to the CPU oracle.
 struct ChainSpec {              // one strided rulebook: sizes as d3d_conv_prepare takes them
   int in_size[3], out_size[3], filt[3], stride[3];
   int need_dec;                 // keep the decoded table (deconvolution / backward view will be asked for)
@@ -2321,11 +2158,11 @@ static int run_grid_chain(d3d_meta *m, const std::vector<ChainSpec> &specs, hipS
     v.go.tab = tab;
     v.go.loc = loc_out;
     v.n_out_dev = cnt;
-    if (v.bound_entries > 0) add_fill(tab, sizeof(HashEntry) * (size_t)v.go.cap);
+    add_fill(tab, sizeof(HashEntry) * (size_t)v.go.cap);       // (an empty level too: its grid still answers probes)
     if (sp.need_dec) {
       D3D_ALLOC(dec, int32_t, A, (size_t)v.bound_in * K + 4);
       v.nbr_dec = dec;
-      if (v.bound_entries > 0) add_fill(dec, sizeof(int32_t) * ((size_t)v.bound_in * K + 1));
+      add_fill(dec, sizeof(int32_t) * ((size_t)v.bound_in * K + 1));
     }
     if (v.bound_entries > 0) {
       const size_t fwd_bytes = sizeof(int32_t) * ((size_t)v.bound_out * K + 4);
@@ -2360,6 +2197,7 @@ static int run_grid_chain(d3d_meta *m, const std::vector<ChainSpec> &specs, hipS
       break;
     }
   }
+  if (L_ok == 0) return fail_rc;          // (g_err is still the level's own message)
   // one fill for every table of every level, then the levels back to back
   if (n_seg > 0) {
     size_t most = 0;
@@ -2378,7 +2216,7 @@ static int run_grid_chain(d3d_meta *m, const std::vector<ChainSpec> &specs, hipS
     }
     if (v.small) {
       hipLaunchKernelGGL(k_conv_grid_small, dim3(1), dim3(kSmallGridThreads), 0, s, v.loc_in, (int)v.bound_entries, v.geo, v.K,
-                         (int)v.bound_in, v.go.tab, v.go.cap, v.go.loc, v.nbr_fwd, v.nbr_dec, v.n_out_dev, v.n_in_dev, 1);
+                         v.go.tab, v.go.cap, v.go.loc, v.nbr_fwd, v.nbr_dec, v.n_out_dev, v.n_in_dev);
       continue;
     }
     const long ne = v.bound_entries;
@@ -2534,6 +2372,29 @@ static void geo_run_views(d3d_meta *m, GeoAsync *g) {      // the views: each be
 }  // namespace d3d
 
 extern "C" {
+
+int d3d_conv_prepare(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
+                     const int *stride, void *stream, int *n_out_host, long *n_rules_host) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
+  Plan *p = const_cast<Plan *>(find_plan(m, 1, in_size, filt, stride));
+  if (!p) {                                  // a chain of one level, decoded table kept
+    ChainSpec sp;
+    for (int d = 0; d < 3; d++) {
+      sp.in_size[d] = in_size[d];
+      sp.out_size[d] = out_size[d];
+      sp.filt[d] = filt[d];
+      sp.stride[d] = stride[d];
+    }
+    sp.need_dec = 1;
+    std::vector<int> n_out;
+    if (int rc = run_grid_chain(m, {sp}, s, n_out, nullptr, nullptr, nullptr)) return rc;
+    p = const_cast<Plan *>(find_plan(m, 1, in_size, filt, stride));
+  }
+  if (n_out_host) *n_out_host = p->n_rows;
+  if (n_rules_host) return plan_rules(m, *p, s, n_rules_host);
+  return D3D_OK;
+}
 
 int d3d_geometry_async_start(d3d_meta *m, const int *specs, int n, void *stream, void *view_stream) {
   D3D_REQUIRE(m && (n == 0 || specs) && n >= 0 && n <= 128, "geometry_async_start: bad arguments");

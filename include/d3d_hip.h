@@ -72,10 +72,12 @@ int d3d_conv_split_mode(int mode);
  * epilogue written (0 / 1), row blocks, filter volume.  The record is cleared by the call (out may be null).
  * -> the number of fields the record has.                                                                            */
 int d3d_conv_last_form(int *out, int n);
-/* The chain of strided grids run by a thread of the library (no reference counterpart; every new grid costs one blocking
- * read-back of its site count, during which a caller that builds the chain itself cannot enqueue feature kernels).
+/* The chain of strided grids run by a thread of the library (no reference counterpart; a caller that builds the levels
+ * itself, one d3d_conv_prepare at a time, waits for one blocking read-back of a site count per level, during which it
+ * cannot enqueue feature kernels; the thread builds the levels back to back, sized by bounds, with two read-backs).
  * start: `specs` = n x 13 ints (kind, in_size[3], out_size[3], filter[3], stride[3]), built in order:
- *   kind 1: d3d_conv_prepare (a new grid + strided rulebook) on `stream`, which must be the metadata's geometry stream;
+ *   kind 1: what d3d_conv_prepare builds (a new grid + strided rulebook) on `stream`, which must be the metadata's
+ *           geometry stream; kind 3: the same without the decoded table a deconvolution view needs;
  *   kind 0: d3d_subm_prepare(in_size, filter), kind 2: d3d_deconv_prepare -- views of grids that exist by then, enqueued
  *           on `view_stream` (the metadata's plan stream, d3d_meta_set_plan_stream) behind the newest grid.
  * The caller has already ordered `stream` after whatever built the first input grid and must not build on either stream
@@ -244,7 +246,12 @@ int d3d_subm_prepare(d3d_meta *m, const int *spatial_size_host, const int *filte
 /* a5. Metadata::getRuleBook (Metadata.cpp:485-510; ConvolutionRules.h:12-34): builds the output
  * grid of spatial size `out_size` and the rulebook.  Output sites are numbered by first touch
  * while visiting input sites in id order (canonical; the reference's order is hash-iteration
- * dependent).                                                                                */
+ * dependent).  A rulebook that is not cached yet is built as a grid chain of one level -- the
+ * builder the geometry thread runs for a whole pyramid (d3d_geometry_async_start): same sizing by
+ * bounds, the new grid carries coordinate bounds (dense index for the RoI pooler), one read-back
+ * of the site count.  The call shares that read-back's pinned words and event with the geometry
+ * thread: building on the geometry stream from two threads at once is not supported (it never
+ * was: the arena is unlocked).                                                                 */
 int d3d_conv_prepare(d3d_meta *m, const int *in_size_host, const int *out_size_host,
                      const int *filter_host, const int *stride_host, void *stream,
                      int *n_out_host, long *n_rules_host);
