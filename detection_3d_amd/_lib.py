@@ -83,6 +83,8 @@ _SIGS = {
                                             vp, vp, ctypes.c_size_t, vp]),
     "d3d_estimate_normals_phases": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                                    c_float_p, vp, vp, vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
+                                           ctypes.c_float, vp, vp, vp, vp, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

@@ -16,6 +16,7 @@ import torch.distributed as dist
 from . import training as T
 from .distributed import agree_capacity, gather_detections, pack_detections
 from .normals import normals_kwargs, with_normals
+from .primitives import as_crop, shift_targets
 from .scene_io import ScenePrefetcher
 
 
@@ -29,7 +30,12 @@ def _fill_normals(pcl, nkw):
     return pcl if nkw is None else with_normals(pcl, **nkw)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None):
+def _crop_scene(pcl, tg, crop):
+    """the scene cut to a random window (primitives.RandomCrop); targets in the file's frame"""
+    return (pcl, tg) if crop is None else crop(pcl, tg)
+
+
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
     the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
@@ -37,13 +43,21 @@ def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None):
     its targets must then be in the file's frame (ScenePrefetcher(shift_targets=False)).
     normals (None, 'estimate' or a dict of estimate_normals keywords): the raw cloud's normal columns are estimated on
     the GPU first (normals.with_normals), before voxelisation and before `augment`, which then flips and rotates them
-    with the points; its elastic distortion comes after the estimate and does not bend them."""
+    with the points; its elastic distortion comes after the estimate and does not bend them.
+    crop ((sx, sy) in metres, or a primitives.RandomCrop): every scene is first cut to a random window of that size and
+    its boxes are cropped to the points that remain or dropped (primitives.crop_scene), before the normals, the
+    voxelisation and `augment`.  Like `augment` it needs the targets in the file's frame; without `augment` they are
+    shifted afterwards as scene_targets(shift=True) shifts them."""
     nkw = normals_kwargs(normals)
+    crop = as_crop(crop)
     cs, fs, tgs = [], [], []
     for b, (pcl, tg) in enumerate(scenes):
+        pcl, tg = _crop_scene(pcl, tg, crop)
         pcl = _fill_normals(pcl, nkw)
         if augment is None:
             c, f = voxelize_fn(pcl, cfg)
+            if crop is not None:
+                tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
         else:
             c, f, tg = augment(pcl, tg, cfg)
         cs.append(torch.cat([c, torch.full((c.shape[0], 1), b, dtype=c.dtype, device=c.device)], 1))
@@ -133,7 +147,7 @@ def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1, augment=None, normals=None):
+          ims_per_gpu=1, augment=None, normals=None, crop=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
@@ -141,7 +155,9 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     while it is voxelised, rank r drawing with seed + 1000003 r; None keeps the plain path.  normals (None, 'estimate' or
     a dict of estimate_normals keywords): every raw cloud's normal columns are estimated on the GPU before voxelisation
     and before `augment`; the augmentation flips and rotates them, and they are not estimated again after its elastic
-    distortion.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
+    distortion.  crop ((sx, sy) in metres, or a primitives.RandomCrop): every building is cut to a random window of that
+    size first and its boxes follow the points that remain (primitives.crop_scene), rank r drawing with
+    seed + 1000003 r.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
     rank, world = _rank_world()
     nkw = normals_kwargs(normals)
     ims = int(ims_per_gpu)
@@ -161,22 +177,28 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     aug = None if augment is None else augment.for_rank(rank)
     if aug is not None:
         aug.check_classes(cfg.INPUT.CLASSES)
+    crop = as_crop(crop)
+    if crop is not None:
+        crop = crop.for_rank(rank)
     it, t0, reduced = 0, None, {}
-    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth, aug is None), ims):
+    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth, aug is None and crop is None),
+                               ims):
         if it == 1:                          # the first iteration pays allocations and the bucket build
             if device is not None:
                 torch.cuda.synchronize(device)
             t0 = time.perf_counter()
         if ims == 1:
-            pcl, tg = batch[0]
+            pcl, tg = _crop_scene(*batch[0], crop)
             pcl = _fill_normals(pcl, nkw)
             if aug is None:
                 coords, feats = voxelize_fn(pcl, cfg)
+                if crop is not None:
+                    tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
             else:
                 coords, feats, tg = aug(pcl, tg, cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
         else:
-            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw)
+            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw, crop)
             _, reduced = T.train_step(ddp, opt, sched, points, tgs)
         it += 1
         if log_every and rank == 0 and it % log_every == 0:

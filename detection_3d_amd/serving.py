@@ -25,16 +25,22 @@ import threading
 import torch
 
 from .normals import normals_kwargs, with_normals
+from .primitives import points_in_boxes
 from .voxelize import voxelize
 
 
 class BuildingPipeline(object):
     """normals: None (clouds arrive with every column the config takes), 'estimate' or a dict of estimate_normals
     keywords: every raw cloud ([N, 3], [N, 6] or [N, 9]) gets its normal columns from normals.with_normals before it is
-    voxelised, on its slot's geometry stream."""
+    voxelised, on its slot's geometry stream.
+    point_owner: every result dict gets two more entries, computed on its slot's tail stream with
+    primitives.points_in_boxes(cloud, detections, origin='min'): "point_owner" int32, one entry per row of the input
+    cloud = the index of the first detection (the dict's order: descending score per class group) that holds the point,
+    -1 for none, and "point_count" int32, the number of points in each detection."""
 
-    def __init__(self, model, cfg, in_flight=2, device=None, normals=None):
+    def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False):
         self.model, self.cfg = model, cfg
+        self.point_owner = bool(point_owner)
         self.normals = normals_kwargs(normals)
         self.device = device if device is not None else next(model.parameters()).device
         self.in_flight = max(1, int(in_flight))
@@ -116,7 +122,10 @@ class BuildingPipeline(object):
                     return
                 i, feats = item
                 with torch.cuda.stream(slot(i)[0]):
-                    results[i] = self.model.stage_tail(feats)
+                    results[i] = r = self.model.stage_tail(feats)
+                    if self.point_owner:
+                        r["point_owner"], r["point_count"], _, _ = points_in_boxes(
+                            clouds[i], r["bbox3d"].to(torch.float32), origin="min")
                 del feats, item
                 slots.release()
 

@@ -169,6 +169,27 @@ int d3d_estimate_normals_phases(const float *xyz, int n, int row_stride_floats, 
                                 const float *viewpoint_host, float *normals, int32_t *counts, void *scratch,
                                 size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* The points of each rotated box (Bbox3D.points_in_bbox, utils3d/bbox3d_ops.py:731-755; the counts of split_bbox,
+ * data3d/indoor_data_util.py:244-254; the extents of crop_bbox_by_points, bbox3d_ops.py:873-878), without an [n, k] mask.
+ * Point i = the first three floats of row xyz + i * row_stride_floats (>= 3: an [n, 9] cloud is read in place); with
+ * origin_dev (device, 3 doubles; NULL: none) the point is float(double(x) - origin), which puts a raw cloud into the
+ * detector's min-shifted frame without a host read-back.  boxes [k, 7] yx_zb (xc, yc, z_bot, d3, d4, dz, yaw), BEV
+ * geometry of the IoU kernels: c = cos(yaw), s = sin(yaw) in fp64 rounded to fp32, lx = c (X - xc) - s (Y - yc),
+ * ly = s (X - xc) + c (Y - yc), lz = Z - z_bot in fp32 without contraction.  Member iff |lx| <= max(d3, grow_yx) / 2,
+ * |ly| <= max(d4, grow_yx) / 2 and 0 <= lz <= max(dz, grow_z), all closed (grow 0: the box as given; 0.3, 0.3: split_bbox's
+ * clip); a NaN coordinate is a member of nothing.
+ *   owner int32 [n]:    the lowest box index that holds the point, -1 for none (pass boxes in descending score order);
+ *   count int32 [k]:    all members of each box, owned by it or not;
+ *   lo, hi fp32 [k, 3]: minimum and maximum of (lx, ly, lz) over the members, a zero always as +0; +inf / -inf for an
+ *                       empty box.
+ * The outputs need no initialisation by the caller: the call starts its accumulators itself.  Counts are summed with
+ * integer adds and extents taken with integer min / max of an order-preserving image of the floats; these commute, so
+ * the same input gives the same bits without a fixed-order form, whatever torch's deterministic mode says.
+ * n >= 0, 0 <= k <= 4096; n == 0 or k == 0 touch nothing out of bounds.  Asynchronous, no scratch, no read-back.       */
+int d3d_points_in_boxes(const float *xyz, int n, int row_stride_floats, const double *origin_dev, const float *boxes,
+                        int k, float grow_yx, float grow_z, int32_t *owner, int32_t *count, float *lo, float *hi,
+                        void *stream);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with

@@ -55,6 +55,9 @@ def parse_args(argv=None):
     ap.add_argument("--estimate-normals", nargs="?", const="", default=None, metavar="RADIUS[,MAX_NN]",
                     help="estimate the normal columns of every building on the GPU before it is voxelised and augmented "
                          "(detection_3d_amd.normals; files that hold xyz, or xyz and colour); default 0.1,50")
+    ap.add_argument("--crop", default="", metavar="SX,SY",
+                    help="cut every training building to a random window of SX x SY metres on the GPU and crop or drop its "
+                         "boxes by the points that remain (detection_3d_amd.primitives); seeded from --seed (+ 1000003 x rank)")
     args = ap.parse_args(argv)
     from detection_3d_amd.normals import parse_estimate_normals
     args.normals = parse_estimate_normals(args.estimate_normals)
@@ -102,6 +105,8 @@ def main():
         dist.barrier()
     from detection_3d_amd.augment import parse_augment
     augment = parse_augment(args.augment, args.seed)
+    from detection_3d_amd.primitives import parse_crop
+    crop = parse_crop(args.crop, args.seed)
     seed_everything(args)
     model = build_detection_model(cfg).to(dev)
     if args.bf16:
@@ -109,7 +114,7 @@ def main():
     if args.bf16_heads:
         model.head_dtype = torch.bfloat16
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
-                       ims_per_gpu=args.ims_per_gpu, augment=augment, normals=args.normals)
+                       ims_per_gpu=args.ims_per_gpu, augment=augment, normals=args.normals, crop=crop)
     if args.verify:
         # (1) the averaged-gradient steps leave every rank with the same weights (fingerprint: sum and sum of squares of
         # every parameter in fp64); (2) the sharded inference loop returns every scene's detections on rank 0
@@ -130,7 +135,7 @@ def main():
     if rank == 0:
         out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic, bf16=args.bf16,
                    bf16_heads=args.bf16_heads, augment=repr(augment) if augment is not None else None,
-                   normals=args.normals,
+                   normals=args.normals, crop=repr(crop) if crop is not None else None,
                    points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
