@@ -85,6 +85,13 @@ _SIGS = {
                                                    c_float_p, vp, vp, vp, ctypes.c_size_t, vp, c_float_p]),
     "d3d_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
                                            ctypes.c_float, vp, vp, vp, vp, vp]),
+    "d3d_voxel_downsample_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_voxel_downsample_cells": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, ctypes.c_size_t,
+                                                  c_int_p, vp]),
+    "d3d_voxel_downsample_rows": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, vp,
+                                                 ctypes.c_size_t, vp, vp, vp, vp]),
+    "d3d_sample_rows_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_sample_rows": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, vp, ctypes.c_size_t, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

@@ -15,6 +15,7 @@ import torch.distributed as dist
 
 from . import training as T
 from .distributed import agree_capacity, gather_detections, pack_detections
+from .downsample import apply_downsample, downsample_kwargs
 from .normals import normals_kwargs, with_normals
 from .primitives import as_crop, shift_targets
 from .scene_io import ScenePrefetcher
@@ -30,12 +31,18 @@ def _fill_normals(pcl, nkw):
     return pcl if nkw is None else with_normals(pcl, **nkw)
 
 
+def _prepare(pcl, dkw, nkw):
+    """one raw cloud on the stream that voxelises it: down-sampled and capped (downsample.apply_downsample), then its
+    normal columns estimated"""
+    return _fill_normals(apply_downsample(pcl, dkw), nkw)
+
+
 def _crop_scene(pcl, tg, crop):
     """the scene cut to a random window (primitives.RandomCrop); targets in the file's frame"""
     return (pcl, tg) if crop is None else crop(pcl, tg)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None):
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
     the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
@@ -47,16 +54,22 @@ def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, 
     crop ((sx, sy) in metres, or a primitives.RandomCrop): every scene is first cut to a random window of that size and
     its boxes are cropped to the points that remain or dropped (primitives.crop_scene), before the normals, the
     voxelisation and `augment`.  Like `augment` it needs the targets in the file's frame; without `augment` they are
-    shifted afterwards as scene_targets(shift=True) shifts them."""
+    shifted afterwards as scene_targets(shift=True) shifts them.
+    downsample (None, a voxel size, or a dict with keys among voxel, max_points, seed): every raw cloud is reduced to one
+    point per voxel and capped (downsample.voxel_downsample, cap_points) after the crop and before the normals, so that
+    the order is crop -> down-sample -> cap -> estimated normals -> voxelise or augment.  The detector's frame is the
+    minimum of the cloud that is voxelised, which the raw cloud's minimum misses by up to a voxel: like `crop`,
+    `downsample` needs the targets in the file's frame and shifts them afterwards."""
+    dkw = downsample_kwargs(downsample)
     nkw = normals_kwargs(normals)
     crop = as_crop(crop)
     cs, fs, tgs = [], [], []
     for b, (pcl, tg) in enumerate(scenes):
         pcl, tg = _crop_scene(pcl, tg, crop)
-        pcl = _fill_normals(pcl, nkw)
+        pcl = _prepare(pcl, dkw, nkw)
         if augment is None:
             c, f = voxelize_fn(pcl, cfg)
-            if crop is not None:
+            if crop is not None or dkw is not None:
                 tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
         else:
             c, f, tg = augment(pcl, tg, cfg)
@@ -88,23 +101,31 @@ def _rank_world():
     return 0, 1
 
 
-def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip_voxelize, normals=None):
+def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip_voxelize, normals=None,
+              downsample=None):
     """Detections of every building in `files`, sharded over the ranks of the default process group.
     -> on rank 0: ({file index: detections dict}, {file index: targets dict of the building in the detector's frame});
     None on the other ranks.  Targets travel with the detections so that rank 0 can evaluate without re-reading files.
     normals (None, 'estimate' or a dict of estimate_normals keywords): files that hold xyz, or xyz and colour, get their
-    normal columns estimated on the GPU before they are voxelised."""
-    rank, world = _rank_world()
+    normal columns estimated on the GPU before they are voxelised.
+    downsample (None, a voxel size, or a dict with keys among voxel, max_points, seed): every raw cloud is reduced to one
+    point per voxel and capped first (downsample.apply_downsample); the targets are then read in the file's frame and
+    shifted by the minimum of the cloud that is voxelised."""
+    dkw = downsample_kwargs(downsample)
     nkw = normals_kwargs(normals)
+    rank, world = _rank_world()
     max_det = max_det or int(cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG) * max(1, len(cfg.MODEL.SEPARATE_CLASSES_ID) + 1)
     pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank, world=world,
-                          depth=depth)
+                          depth=depth, shift_targets=dkw is None)
     was_training = model.training
     model.eval()
     results, truths = [], []
     with torch.no_grad():
         for i, (pcl, tg, _path) in enumerate(pre):
-            coords, feats = voxelize_fn(_fill_normals(pcl, nkw), cfg)
+            pcl = _prepare(pcl, dkw, nkw)
+            if dkw is not None:
+                tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
+            coords, feats = voxelize_fn(pcl, cfg)
             results.append((rank + i * world, model([coords, feats])))
             truths.append({"bbox3d": tg["bbox3d"], "labels": tg["labels"],
                            "scores": torch.ones(tg["bbox3d"].shape[0], device=tg["bbox3d"].device)})
@@ -147,7 +168,7 @@ def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1, augment=None, normals=None, crop=None):
+          ims_per_gpu=1, augment=None, normals=None, crop=None, downsample=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
@@ -157,9 +178,13 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     and before `augment`; the augmentation flips and rotates them, and they are not estimated again after its elastic
     distortion.  crop ((sx, sy) in metres, or a primitives.RandomCrop): every building is cut to a random window of that
     size first and its boxes follow the points that remain (primitives.crop_scene), rank r drawing with
-    seed + 1000003 r.  -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
-    rank, world = _rank_world()
+    seed + 1000003 r.  downsample (None, a voxel size, or a dict with keys among voxel, max_points, seed): every raw
+    cloud is reduced to one point per voxel and capped after the crop and before the normals
+    (downsample.apply_downsample); the targets are then read in the file's frame and follow the cloud that is voxelised.
+    -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
+    dkw = downsample_kwargs(downsample)
     nkw = normals_kwargs(normals)
+    rank, world = _rank_world()
     ims = int(ims_per_gpu)
     if ims < 1:
         raise ValueError(f"ims_per_gpu {ims_per_gpu} < 1")
@@ -181,7 +206,8 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     if crop is not None:
         crop = crop.for_rank(rank)
     it, t0, reduced = 0, None, {}
-    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth, aug is None and crop is None),
+    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth,
+                                              aug is None and crop is None and dkw is None),
                                ims):
         if it == 1:                          # the first iteration pays allocations and the bucket build
             if device is not None:
@@ -189,16 +215,16 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
             t0 = time.perf_counter()
         if ims == 1:
             pcl, tg = _crop_scene(*batch[0], crop)
-            pcl = _fill_normals(pcl, nkw)
+            pcl = _prepare(pcl, dkw, nkw)
             if aug is None:
                 coords, feats = voxelize_fn(pcl, cfg)
-                if crop is not None:
+                if crop is not None or dkw is not None:
                     tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
             else:
                 coords, feats, tg = aug(pcl, tg, cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
         else:
-            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw, crop)
+            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw, crop, dkw)
             _, reduced = T.train_step(ddp, opt, sched, points, tgs)
         it += 1
         if log_every and rank == 0 and it % log_every == 0:

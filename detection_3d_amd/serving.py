@@ -24,6 +24,7 @@ import threading
 
 import torch
 
+from .downsample import apply_downsample, downsample_kwargs
 from .normals import normals_kwargs, with_normals
 from .primitives import points_in_boxes
 from .voxelize import voxelize
@@ -36,9 +37,15 @@ class BuildingPipeline(object):
     point_owner: every result dict gets two more entries, computed on its slot's tail stream with
     primitives.points_in_boxes(cloud, detections, origin='min'): "point_owner" int32, one entry per row of the input
     cloud = the index of the first detection (the dict's order: descending score per class group) that holds the point,
-    -1 for none, and "point_count" int32, the number of points in each detection."""
+    -1 for none, and "point_count" int32, the number of points in each detection.
+    downsample: None, a voxel size, or a dict with keys among voxel, max_points, seed: every raw cloud is reduced to one
+    point per voxel and capped (downsample.voxel_downsample, cap_points) on its slot's geometry stream, before the
+    normals.  point_owner keeps one entry per row of the RAW cloud: the owner of the down-sampled point the row went
+    into, -1 for a row that was dropped (position not finite) or capped away; "point_count" then counts the
+    down-sampled points of each detection."""
 
-    def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False):
+    def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None):
+        self.downsample = downsample_kwargs(downsample)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
         self.normals = normals_kwargs(normals)
@@ -65,6 +72,7 @@ class BuildingPipeline(object):
         for st in self.hi:
             st.wait_event(ready)
         results, errors = [None] * n, []
+        reduced = [None] * n        # with downsample and point_owner: (the cloud that was voxelised, raw row -> its row)
         slots = threading.Semaphore(self.in_flight)
         q_feat, q_tail = queue.Queue(), queue.Queue()
         stop = threading.Event()
@@ -96,7 +104,14 @@ class BuildingPipeline(object):
                 hi, lo = slot(i)
                 with torch.cuda.stream(hi):
                     hi.wait_stream(lo)      # the slot's previous building has left its arena and allocator blocks
-                    pcl = clouds[i] if self.normals is None else with_normals(clouds[i], **self.normals)
+                    pcl = clouds[i]
+                    if self.downsample is not None and self.point_owner:
+                        pcl, source = apply_downsample(pcl, self.downsample, return_source=True)
+                        reduced[i] = (pcl, source)
+                    elif self.downsample is not None:
+                        pcl = apply_downsample(pcl, self.downsample)
+                    if self.normals is not None:
+                        pcl = with_normals(pcl, **self.normals)
                     coords, feats = voxelize(pcl, s3d.VOXEL_SCALE, s3d.VOXEL_FULL_SCALE)
                     net = self.model.stage_geometry([coords, feats])
                     lo.wait_stream(hi)
@@ -123,7 +138,14 @@ class BuildingPipeline(object):
                 i, feats = item
                 with torch.cuda.stream(slot(i)[0]):
                     results[i] = r = self.model.stage_tail(feats)
-                    if self.point_owner:
+                    if self.point_owner and reduced[i] is not None:
+                        pcl, source = reduced[i]
+                        reduced[i] = None
+                        owner, r["point_count"], _, _ = points_in_boxes(pcl, r["bbox3d"].to(torch.float32), origin="min")
+                        # entry M of the table: the rows that went nowhere (source -1 indexes it from the end)
+                        table = torch.cat([owner, torch.full((1,), -1, dtype=owner.dtype, device=owner.device)])
+                        r["point_owner"] = table[source.long()]
+                    elif self.point_owner:
                         r["point_owner"], r["point_count"], _, _ = points_in_boxes(
                             clouds[i], r["bbox3d"].to(torch.float32), origin="min")
                 del feats, item

@@ -190,6 +190,50 @@ int d3d_points_in_boxes(const float *xyz, int n, int row_stride_floats, const do
                         int k, float grow_yx, float grow_z, int32_t *owner, int32_t *count, float *lo, float *hi,
                         void *stream);
 
+/* Voxel down-sampling of a raw scan: one row per occupied voxel, every column the mean over the voxel's points
+ * (data3d/suncg_utils/suncg_preprocess.py:748-767, open3d.voxel_down_sample(pcd, voxel_size=0.02)).  A restatement of
+ * open3d's VoxelDownSample that is not pinned against open3d itself.  pcl fp32 [n, ncols], 3 <= ncols <= 16, contiguous,
+ * columns 0:3 the position.
+ *   dropped rows: a row whose position is not finite belongs to no voxel;
+ *   cell of a point: lo_a = double(min over the kept rows of axis a) - 0.5 voxel; cell_a = floor((double(p_a) - lo_a) /
+ *     voxel), fp64 subtraction and IEEE fp64 division, no contraction, no multiplication by a reciprocal;
+ *   output values: per column the fp64 sum over the voxel's points, one fp64 division by the count, one rounding to fp32;
+ *     with normal_col >= 0 the means m of columns normal_col .. normal_col + 2 are divided in fp64 by
+ *     sqrt((m0 m0 + m1 m1) + m2 m2) before the rounding when that is positive, and stay as they are when it is zero;
+ *     a voxel of one point is not scaled, so that its row is that point bit for bit;
+ *   output order: the order of each voxel's first point in the input (the input layer's site numbering);
+ *   summation order, fixed by the data: the points of a voxel in input order when there are at most 64; otherwise in
+ *     chunks of 512 consecutive points, inside a chunk lane l of 64 adds points l, l + 64, ... in order, the lanes are
+ *     added pairwise (l with l ^ 32, then ^ 16, ... ^ 1), and the chunk sums are added in chunk order.  No float atomics:
+ *     the same input gives the same bits, whatever torch's deterministic mode says;
+ *   limit: at most 2^21 cells per axis.  A wider cloud makes _cells return D3D_ERR_ARG, with a message that names the
+ *     limit and the extent, and no output exists yet.
+ * Two calls, because the caller allocates the outputs from the voxel count:
+ *   _cells: everything up to the segments, then the one host read-back: info_host[0] = voxels M, info_host[1] = the
+ *     number of 512-row chunks (both 0 for n == 0); synchronises once.
+ *   _rows:  out fp32 [M, ncols]; inverse int32 [n] or NULL: the output row of every input row, -1 for a dropped row;
+ *     counts int32 [M] or NULL: the points of every voxel.  `scratch` and info_host as _cells left them, same pcl, n and
+ *     ncols, same stream.  Asynchronous.
+ * scratch: d3d_voxel_downsample_scratch_bytes(n, ncols) bytes, linear in n and independent of the extent: 40 bytes per
+ * point for the cells, permutations, keys and segments (eight int32 arrays, one int64), ncols / 8 bytes per point of
+ * chunk sums, and the radix sort's 16.5 bytes per point: 59 bytes per point at ncols = 16, plus a few KiB.            */
+size_t d3d_voxel_downsample_scratch_bytes(int n, int ncols);
+int d3d_voxel_downsample_cells(const float *pcl, int n, int ncols, double voxel, void *scratch, size_t scratch_bytes,
+                               int *info_host /* [2] */, void *stream);
+int d3d_voxel_downsample_rows(const float *pcl, int n, int ncols, int normal_col /* -1: none */, const int *info_host,
+                              const void *scratch, size_t scratch_bytes, float *out, int32_t *inverse, int32_t *counts,
+                              void *stream);
+
+/* A uniform random subset of k of n rows without replacement, the only_reduce form of random_sample_pcl
+ * (data3d/indoor_data_util.py:59-71), in ascending row order (the reference returns it shuffled).  Row i gets the key
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (uint32 arithmetic)
+ *   s0 = mix(uint32(seed) + 0x9e3779b9), s1 = mix(uint32(seed >> 32) ^ s0), key(i) = mix(mix(i ^ s0) + s1)
+ * and the k rows with the smallest (key, i) are kept.  The mix is a bijection of the 32-bit i, so no two rows of one
+ * call tie.  rows int32 [min(k, n)]; k >= n gives 0 .. n - 1.  A pure function of (n, k, seed).  Asynchronous, no
+ * read-back; scratch: d3d_sample_rows_scratch_bytes(n) bytes (8 per row).                                             */
+size_t d3d_sample_rows_scratch_bytes(int n);
+int d3d_sample_rows(int n, int k, uint64_t seed, int32_t *rows, void *scratch, size_t scratch_bytes, void *stream);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with
