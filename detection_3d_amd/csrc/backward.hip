@@ -443,12 +443,24 @@ template <typename S>
 using DwKernel = void (*)(const S *, int, const S *, const int32_t *, int, const int32_t *, const uint32_t *, int, int, int,
                           int, float *);
 
-// grid, run length and scratch of one dW launch; T = output tiles (32 x 32) of the layer, `cin` = Cin of dW
+// d3d_conv_dw_last_form: family (1 fp32, 2 bf16), CP / CS, COUT, cin, T, nz, run, chunk, n_chunks, grid x / y / z, DET,
+// G, scratch (0 none, 1 caller buffer, 2 feature lane, 3 stream-ordered allocation), n_blk, K
+static constexpr int kDwFormFields = 17;
+static thread_local int t_dw_last_form[kDwFormFields] = {};
+enum DwScratch { kDwScratchNone = 0, kDwScratchCaller = 1, kDwScratchLane = 2, kDwScratchAsync = 3 };
+
+// grid, run length and scratch of one dW launch; T = output tiles (32 x 32) of the layer, `cin` = Cin of dW, `cw` = the
+// kernel's channel class (CP of k_conv_dw, CS of k_conv_dw_bf16)
 template <typename S>
-static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomic, DwKernel<S> k_det, const S *in, int cin,
-                          const S *d_out, int cout, float *dW, hipStream_t s) {
+static int launch_dw_with(d3d_meta *m, const Plan &p, int cw, int T, DwKernel<S> k_atomic, DwKernel<S> k_det, const S *in,
+                          int cin, const S *d_out, int cout, float *dW, hipStream_t s) {
   const int TPG = T < 16 ? T : 16;
   const int nz = (T + TPG - 1) / TPG;
+  auto record = [&](int run, int chunk, int n_chunks, dim3 grid, bool det, int G, int scratch) {
+    const int f[kDwFormFields] = {sizeof(S) == 4 ? 1 : 2, cw, cout, cin, T, nz, run, chunk, n_chunks, (int)grid.x,
+                                  (int)grid.y, (int)grid.z, det ? 1 : 0, G, scratch, p.n_blk, p.K};
+    std::copy(f, f + kDwFormFields, t_dw_last_form);
+  };
   if (g_dw_deterministic || t_dw.on) {
     // fixed summation order: run r belongs to workgroup r % G, which adds its runs' blocks in order; the G partial
     // sums are added in order by k_dw_reduce.  Scratch: G x (K, cin, cout) floats, G <= kDwDetPartials and within
@@ -467,6 +479,7 @@ static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomi
     if (t_dw.on && t_dw.scratch) {
       D3D_REQUIRE(t_dw.bytes >= bytes, "deterministic conv backward: scratch %zu < %zu bytes (d3d_conv_dw_scratch_bytes)",
                   t_dw.bytes, bytes);
+      record(run, run, 1, dim3(G, p.K, nz), true, G, kDwScratchCaller);
       launch((float *)t_dw.scratch);
     } else {
       D3D_REQUIRE(m, "deterministic conv backward needs the metadata (its scratch lane)");
@@ -474,12 +487,14 @@ static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomi
       const size_t mark = m->feat_arena.used;
       float *part = m->feat_arena.get<float>((size_t)G * n);
       if (part) {
+        record(run, run, 1, dim3(G, p.K, nz), true, G, kDwScratchLane);
         launch(part);
         m->feat_arena.used = mark;   // stream-ordered scratch
       } else {                       // the lane is too small: a stream-ordered buffer of its own, the same partials
         m->feat_arena.used = mark;
         void *buf = nullptr;
         D3D_HIP_CHECK(hipMallocAsync(&buf, bytes, s));
+        record(run, run, 1, dim3(G, p.K, nz), true, G, kDwScratchAsync);
         launch((float *)buf);
         D3D_HIP_CHECK(hipFreeAsync(buf, s));
       }
@@ -503,6 +518,7 @@ static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomi
   }
   const int n_chunks = (int)((run + chunk - 1) / chunk);
   dim3 grid((unsigned)((p.n_blk + run - 1) / run), p.K, nz * n_chunks);
+  record((int)run, (int)chunk, n_chunks, grid, false, 0, kDwScratchNone);
   hipLaunchKernelGGL(k_atomic, grid, dim3(256), 0, s, in, cin, d_out, p.nbrT, p.n_blk * 32, p.rows,
                      p.blkmask, p.n_blk, (int)run, (int)chunk, nz, dW);
   D3D_LAUNCH_CHECK();
@@ -510,7 +526,7 @@ static int launch_dw_with(d3d_meta *m, const Plan &p, int T, DwKernel<S> k_atomi
 }
 template <int CP, int COUT>
 static int launch_dw_t(d3d_meta *m, const Plan &p, const float *in, int cin, const float *d_out, float *dW, hipStream_t s) {
-  return launch_dw_with<float>(m, p, (CP / 32) * (COUT / 32), k_conv_dw<CP, COUT, false>, k_conv_dw<CP, COUT, true>, in,
+  return launch_dw_with<float>(m, p, CP, (CP / 32) * (COUT / 32), k_conv_dw<CP, COUT, false>, k_conv_dw<CP, COUT, true>, in,
                                cin, d_out, COUT, dW, s);
 }
 template <int CP>
@@ -543,10 +559,10 @@ static int launch_dw_bf16_c(d3d_meta *m, const Plan &p, const bf16_t *in, int ci
                             float *dW, hipStream_t s) {
   constexpr int NTI = CS < 32 ? 1 : CS / 32;
   switch (cout) {
-    case 32: return launch_dw_with<bf16_t>(m, p, NTI, k_conv_dw_bf16<CS, 32, false>, k_conv_dw_bf16<CS, 32, true>, in, cin, d_out, 32, dW, s);
-    case 64: return launch_dw_with<bf16_t>(m, p, NTI * 2, k_conv_dw_bf16<CS, 64, false>, k_conv_dw_bf16<CS, 64, true>, in, cin, d_out, 64, dW, s);
-    case 128: return launch_dw_with<bf16_t>(m, p, NTI * 4, k_conv_dw_bf16<CS, 128, false>, k_conv_dw_bf16<CS, 128, true>, in, cin, d_out, 128, dW, s);
-    case 256: return launch_dw_with<bf16_t>(m, p, NTI * 8, k_conv_dw_bf16<CS, 256, false>, k_conv_dw_bf16<CS, 256, true>, in, cin, d_out, 256, dW, s);
+    case 32: return launch_dw_with<bf16_t>(m, p, CS, NTI, k_conv_dw_bf16<CS, 32, false>, k_conv_dw_bf16<CS, 32, true>, in, cin, d_out, 32, dW, s);
+    case 64: return launch_dw_with<bf16_t>(m, p, CS, NTI * 2, k_conv_dw_bf16<CS, 64, false>, k_conv_dw_bf16<CS, 64, true>, in, cin, d_out, 64, dW, s);
+    case 128: return launch_dw_with<bf16_t>(m, p, CS, NTI * 4, k_conv_dw_bf16<CS, 128, false>, k_conv_dw_bf16<CS, 128, true>, in, cin, d_out, 128, dW, s);
+    case 256: return launch_dw_with<bf16_t>(m, p, CS, NTI * 8, k_conv_dw_bf16<CS, 256, false>, k_conv_dw_bf16<CS, 256, true>, in, cin, d_out, 256, dW, s);
   }
   set_error("bf16 conv backward: Cout=%d not supported", cout);
   return D3D_ERR_UNSUPPORTED;
@@ -1040,6 +1056,12 @@ int d3d_conv_dw_deterministic(int on) {
   const int was = g_dw_deterministic ? 1 : 0;
   if (on >= 0) g_dw_deterministic = on != 0;
   return was;
+}
+
+int d3d_conv_dw_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kDwFormFields; i++) out[i] = t_dw_last_form[i];
+  std::fill(t_dw_last_form, t_dw_last_form + kDwFormFields, 0);
+  return kDwFormFields;
 }
 
 size_t d3d_conv_dw_scratch_bytes(int filter_volume, int cin, int cout) {

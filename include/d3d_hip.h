@@ -492,6 +492,13 @@ int d3d_conv_dw_deterministic(int on);
  * and the layer's size, so the bits are the same in every run.                                                      */
 int d3d_conv_dw_thread_mode(int on, void *scratch, size_t scratch_bytes);
 size_t d3d_conv_dw_scratch_bytes(int filter_volume, int cin, int cout);
+/* The form of the calling thread's most recent dWeight launch, recorded on the host: up to n of the ints family (0 none,
+ * 1 k_conv_dw on fp32 rows, 2 k_conv_dw_bf16), the kernel's channel class (CP of fp32, the stored width CS of bf16), COUT,
+ * Cin of dWeight, T (32 x 32 output tiles), nz (tile groups), run (row blocks per workgroup), chunk (active blocks of a run
+ * per workgroup), n_chunks, grid x / y / z, DET (0 atomic, 1 fixed order), G (partial sums; 0 in the atomic form), scratch
+ * of the partials (0 none, 1 the caller's buffer, 2 the feature lane, 3 a stream-ordered allocation), row blocks, filter
+ * volume.  The record is cleared by the call (out may be null).  -> the number of fields the record has.             */
+int d3d_conv_dw_last_form(int *out, int n);
 /* BatchNormalization_backward (SCN/sparseconvnet.h:27-32; SCN/CPU/BatchNormalization.cpp:62-107). */
 int d3d_bn_backward(const float *in, const float *out, const float *d_out, float *d_in, int rows,
                     int planes, const float *save_mean, const float *save_invstd, const float *weight,

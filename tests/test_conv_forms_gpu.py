@@ -30,7 +30,8 @@ k_conv<CT,1,COUT,1,BPW,true,LATE> CT 16 / 32 / 64 /    test_fp32_forms[cin-cout-
 split) / 64 / 128 / 256 (BPW 1); unsplit, and           16), test_row_structure, test_fp32_auto_threshold,
 offset-split + k_conv_reduce (+ column statistics)      test_stages, test_dinput_exact
 k_conv<..., VEC = false, LATE = false>                  test_fp32_unpadded_cin (Cin 9 / 20 / 48 / 100 / 200)
-dWeight, atomic and fixed-order (backward.hip)          test_dweight
+dWeight, atomic and fixed-order (backward.hip)          test_dweight; every launch form of it in
+                                                        test_dweight_forms_gpu.py (d3d_conv_dw_last_form)
 k_conv_ws<64,64,64,4>, k_conv_ws<128,128,32,4>          test_fp32_ws (d3d_conv_ws_mode 2, unsplit only: the
                                                         split form never takes it)
 k_conv_bf16<CT,NCT,COUT,BPW,RB> RB 1 / 2 / 4            test_bf16_forms[cin-cout-rb-split] (RB 4 falls back to
@@ -43,7 +44,7 @@ and split + k_conv_reduce                               the classes it declines 
 ======================================================  =======================================================
 
 Every forward and dInput launch is asserted through d3d_conv_last_form (family, CT, NCT, COUT, BPW, RB, VEC, LATE,
-n_split, statistics, row blocks, filter volume); the dWeight kernels are no convolution launch and record none.
+n_split, statistics, row blocks, filter volume).
 Not reached: the unsplit fallback of a split launch whose partial sums do not fit the feature arena (it takes GiBs of
 partials; d3d_conv_last_form would report it as n_split 1), and the 4 GiB gather-offset limit (D3D_REQUIRE).  Every
 test that changes a mode restores it in `finally`."""
