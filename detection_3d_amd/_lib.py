@@ -93,6 +93,14 @@ _SIGS = {
                                                  ctypes.c_size_t, vp, vp, vp, vp]),
     "d3d_sample_rows_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "d3d_sample_rows": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, vp, ctypes.c_size_t, vp]),
+    "d3d_unproject_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "d3d_unproject_count": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_size_t,
+                                           c_int_p, vp]),
+    "d3d_unproject_rows": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t,
+                                          vp, vp, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

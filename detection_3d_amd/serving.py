@@ -27,6 +27,7 @@ import torch
 from .downsample import apply_downsample, downsample_kwargs
 from .normals import normals_kwargs, with_normals
 from .primitives import points_in_boxes
+from .unproject import DepthFrames, unproject, unproject_kwargs
 from .voxelize import voxelize
 
 
@@ -42,10 +43,17 @@ class BuildingPipeline(object):
     point per voxel and capped (downsample.voxel_downsample, cap_points) on its slot's geometry stream, before the
     normals.  point_owner keeps one entry per row of the RAW cloud: the owner of the down-sampled point the row went
     into, -1 for a row that was dropped (position not finite) or capped away; "point_count" then counts the
-    down-sampled points of each detection."""
+    down-sampled points of each detection.
+    unproject: None or a dict of unproject.unproject keywords (columns, step, min_depth, max_depth, edge, color_div) for
+    the inputs that are unproject.DepthFrames: such an input becomes a cloud on its slot's geometry stream first, and
+    the steps above follow as for a cloud ("raw cloud" then means the unprojected one).  With point_owner its result also
+    carries "point_pixel" int32, the pixel (f H + v) W + u of every row of that cloud (unproject.pixel_labels paints
+    point_owner into the frames with it)."""
 
-    def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None):
+    def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None,
+                 unproject=None):
         self.downsample = downsample_kwargs(downsample)
+        self.unproject = unproject_kwargs(unproject)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
         self.normals = normals_kwargs(normals)
@@ -59,7 +67,8 @@ class BuildingPipeline(object):
         self.lo = [torch.cuda.Stream(device=self.device) for _ in range(self.in_flight)]
 
     def map(self, clouds):
-        """clouds: list of float32 [N, F] point clouds resident on the device -> list of detection dicts, in order.
+        """clouds: list of float32 [N, F] point clouds resident on the device, or unproject.DepthFrames -> list of
+        detection dicts, in order.
         The caller's stream is made to wait for the results (no device-wide synchronisation)."""
         clouds = list(clouds)
         n = len(clouds)
@@ -72,6 +81,8 @@ class BuildingPipeline(object):
         for st in self.hi:
             st.wait_event(ready)
         results, errors = [None] * n, []
+        pixels = [None] * n         # of a DepthFrames input with point_owner: the pixel of every unprojected row
+        raw = [None] * n            # ... and its unprojected cloud, kept only while the tail needs it (no downsample)
         reduced = [None] * n        # with downsample and point_owner: (the cloud that was voxelised, raw row -> its row)
         slots = threading.Semaphore(self.in_flight)
         q_feat, q_tail = queue.Queue(), queue.Queue()
@@ -105,6 +116,13 @@ class BuildingPipeline(object):
                 with torch.cuda.stream(hi):
                     hi.wait_stream(lo)      # the slot's previous building has left its arena and allocator blocks
                     pcl = clouds[i]
+                    if isinstance(pcl, DepthFrames):
+                        if self.point_owner:
+                            pcl, pixels[i] = unproject(pcl, return_pixels=True, **self.unproject)
+                        else:
+                            pcl = unproject(pcl, **self.unproject)
+                        if self.point_owner and self.downsample is None:
+                            raw[i] = pcl
                     if self.downsample is not None and self.point_owner:
                         pcl, source = apply_downsample(pcl, self.downsample, return_source=True)
                         reduced[i] = (pcl, source)
@@ -146,8 +164,12 @@ class BuildingPipeline(object):
                         table = torch.cat([owner, torch.full((1,), -1, dtype=owner.dtype, device=owner.device)])
                         r["point_owner"] = table[source.long()]
                     elif self.point_owner:
+                        pcl, raw[i] = (raw[i] if raw[i] is not None else clouds[i]), None
                         r["point_owner"], r["point_count"], _, _ = points_in_boxes(
-                            clouds[i], r["bbox3d"].to(torch.float32), origin="min")
+                            pcl, r["bbox3d"].to(torch.float32), origin="min")
+                        del pcl
+                    if pixels[i] is not None:
+                        r["point_pixel"], pixels[i] = pixels[i], None
                 del feats, item
                 slots.release()
 

@@ -234,6 +234,46 @@ int d3d_voxel_downsample_rows(const float *pcl, int n, int ncols, int normal_col
 size_t d3d_sample_rows_scratch_bytes(int n);
 int d3d_sample_rows(int n, int k, uint64_t seed, int32_t *rows, void *scratch, size_t scratch_bytes, void *stream);
 
+/* Posed depth frames -> one cloud with colours and image-space normals: depth_2_pcl of
+ * data3d/suncg_utils/suncg_preprocess.py:790-832 for a batch of frames, and what gen_pcl (:718-764) concatenates.  A
+ * restatement that is not pinned against a run of the reference.  depth [frames, height, width], uint16 or fp32;
+ * color [frames, height, width, 3], uint8 or fp32, or NULL; intrinsics fp64 [frames, 4] (fx, fy, cx, cy) and extrinsics
+ * fp64 [frames, 3, 4] (camera to world, R | t), both on the device.  Every operation below is fp64 in exactly this
+ * order, without contraction; each output value is rounded once to fp32.
+ *   pixel (f, v, u), u the column in 0 .. width - 1, v the row in 0 .. height - 1;
+ *   depth: z = double(d) * depth_scale for uint16, z = double(d) for fp32 (depth_scale is ignored);
+ *   valid: z is finite, z > 0 and min_depth <= z <= max_depth; kept: valid, u % step == 0 and v % step == 0;
+ *   camera frame, x right, y down, z forward (the reference's [r, -u, t, v] extrinsics): zx = z / fx, zy = z / fy,
+ *     C = ((double(u) - cx) * zx, (double(v) - cy) * zy, z);
+ *   world position, columns 0:3: X_k = ((R[k][0] * C.x + R[k][1] * C.y) + R[k][2] * C.z) + t[k];
+ *   colour, columns 3:6 (ncols >= 6): uint8: float(double(c) / color_div) (the reference divides by 256, :828); fp32:
+ *     copied bit for bit; no colour pointer: zeros;
+ *   normal, columns 6:9 (ncols == 9), from the raw neighbours u +- 1 and v +- 1 whatever step is.  A neighbour q of p is
+ *     usable when it is inside the image, valid, and fabs(z_q - z_p) <= edge * z_p.  Horizontal difference a: both
+ *     usable: C(u + 1, v) - C(u - 1, v); only the right one: C(u + 1, v) - C(u, v); only the left one: C(u, v) -
+ *     C(u - 1, v); neither: no normal.  Vertical difference b: the same with v.  m = a x b = (a.y b.z - a.z b.y,
+ *     a.z b.x - a.x b.z, a.x b.y - a.y b.x); l2 = (m.x m.x + m.y m.y) + m.z m.z; not l2 > 0: no normal.  If (m.x C.x +
+ *     m.y C.y) + m.z C.z > 0 then m = -m: the normal faces its camera.  n = m / sqrt(l2) per component; world normal
+ *     per axis k: (R[k][0] * n.x + R[k][1] * n.y) + R[k][2] * n.z.  R is taken as orthonormal, nothing is normalised
+ *     again.  "No normal" is (0, 0, 0), which the voxel mean of d3d_voxel_downsample_rows (normal_col 6) ignores;
+ *   order: the kept pixels in ascending (f * height + v) * width + u; pixel_of_point holds that index.
+ * The same input gives the same bits.  frames * height * width >= 2^31 is an error.
+ * Two calls, because the caller allocates the rows from their number:
+ *   _count: one count of kept pixels per run of 2048 pixels, their scan, and the one host read-back: info_host[0] = N
+ *     (0 for an empty batch); synchronises once.
+ *   _rows:  out fp32 [N, ncols], ncols 3, 6 or 9; pixel_of_point int32 [N] or NULL.  Same depth, shape, step, depth
+ *     range, stream, and `scratch` and info_host as _count left them.  Asynchronous.  Never writes past N rows.
+ * scratch: d3d_unproject_scratch_bytes bytes: 8 per run of 2048 pixels plus a few KiB, whatever step is.              */
+size_t d3d_unproject_scratch_bytes(int frames, int height, int width, int step);
+int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int height, int width, int step,
+                        double depth_scale, double min_depth, double max_depth, void *scratch, size_t scratch_bytes,
+                        int *info_host /* [0] = N */, void *stream);
+int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
+                       const double *intrinsics, const double *extrinsics, int frames, int height, int width, int step,
+                       double depth_scale, double min_depth, double max_depth, double edge, int ncols /* 3, 6 or 9 */,
+                       const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
+                       int32_t *pixel_of_point, void *stream);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with
