@@ -33,6 +33,7 @@ class AugmentParams(ctypes.Structure):
 
 aug_p = ctypes.POINTER(AugmentParams)
 c_double_p = ctypes.POINTER(ctypes.c_double)
+c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
 _SIGS = {
     "d3d_last_error": (ctypes.c_char_p, []),
@@ -101,6 +102,14 @@ _SIGS = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t,
                                           vp, vp, vp]),
+    "d3d_render_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "d3d_render_bin": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, vp, ctypes.c_size_t, c_int64_p, vp]),
+    "d3d_render_fill": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, c_int64_p, vp, ctypes.c_size_t, vp, vp]),
+    "d3d_render_tiles": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                        ctypes.c_double, c_int64_p, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

@@ -274,6 +274,46 @@ int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, i
                        const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
                        int32_t *pixel_of_point, void *stream);
 
+/* Posed depth frames from a triangle mesh: the step between gen_house_obj and gen_pcl of
+ * data3d/suncg_utils/suncg_preprocess.py, which the reference leaves to an external OpenGL tool (scn2img).  vertices fp32
+ * [n_vertices, 3] in world coordinates, triangles int32 [n_triangles, 3], vertex_color fp32 or uint8 [n_vertices, 3] or
+ * NULL; intrinsics fp64 [frames, 4] (fx, fy, cx, cy) and extrinsics fp64 [frames, 3, 4] (camera to world, R | t, the
+ * camera looking along +z with x right and y down) as for d3d_unproject_*, all on the device.  Every operation below is
+ * fp64 in exactly this order, without contraction:
+ *   camera-space vertex p = R^T (x - t): d = double(x) - t, p_k = (R[0][k] * d.x + R[1][k] * d.y) + R[2][k] * d.z, a
+ *     function of (frame, vertex) alone;
+ *   triangle with camera-space vertices a, b, c: n_bc = b x c with (p x q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z,
+ *     p.x q.y - p.y q.x), n_ca = c x a, n_ab = a x b; D = (a.x * n_bc.x + a.y * n_bc.y) + a.z * n_bc.z;
+ *   pixel (f, v, u): d = ((double(u) - cx) / fx, (double(v) - cy) / fy, 1); e0 = (d.x * n_bc.x + d.y * n_bc.y) + n_bc.z,
+ *     e1 likewise from n_ca, e2 from n_ab; S = (e0 + e1) + e2;
+ *   hit: S != 0 and (e0, e1, e2 all >= 0 or all <= 0): two-sided, closed edges; z = D / S, the z-depth of
+ *     d3d_unproject_*; it counts when z is finite, z > 0 and min_depth <= z <= max_depth.  A triangle with a vertex
+ *     index outside [0, n_vertices) or a non-finite vertex never hits (and nothing is read out of bounds);
+ *   winner of a pixel: the smallest z, then the lowest triangle index: independent of any processing order;
+ *   depth [frames, height, width]: fp32: float(z), 0 without a hit; uint16: rint(z / depth_scale), and 0 where that is 0
+ *     or above 65535; tri int32 [frames, height, width] or NULL: the winner, -1 for none; color [frames, height, width, 3]
+ *     (with vertex_color, of its type): (w0 * c_a + w1 * c_b) + w2 * c_c with w_i = e_i / S, fp32: rounded once, uint8:
+ *     rint clamped to [0, 255]; 0 without a hit.
+ * Tiles of 16 x 16 pixels, three calls on one stream with the same mesh, cameras and shape:
+ *   _bin:   a conservative rectangle of tiles per (frame, triangle), the list length of every tile and their scan; the
+ *           one host read-back: info_host[0] = E, all list entries (0 for an empty mesh or no frame); synchronises once.
+ *   _fill:  lists int32 [E], allocated by the caller: every tile's triangles, in no particular order.  Asynchronous.
+ *   _tiles: one workgroup per (frame, tile) writes the images.  Asynchronous.  E >= 2^31 is an error in _fill and _tiles
+ *           (use fewer frames per call), as is frames * height * width >= 2^31 everywhere.
+ * scratch: d3d_render_scratch_bytes bytes, 8 per tile plus a few KiB; the lists take 4 E bytes more.                     */
+size_t d3d_render_scratch_bytes(int frames, int height, int width);
+int d3d_render_bin(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                   const double *intrinsics, const double *extrinsics, int frames, int height, int width, void *scratch,
+                   size_t scratch_bytes, int64_t *info_host /* [0] = E */, void *stream);
+int d3d_render_fill(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                    const double *intrinsics, const double *extrinsics, int frames, int height, int width,
+                    const int64_t *info_host, void *scratch, size_t scratch_bytes, int32_t *lists, void *stream);
+int d3d_render_tiles(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                     const void *vertex_color, int color_is_u8, const double *intrinsics, const double *extrinsics,
+                     int frames, int height, int width, double min_depth, double max_depth, int depth_is_u16,
+                     double depth_scale, const int64_t *info_host, const void *scratch, size_t scratch_bytes,
+                     const int32_t *lists, void *depth, int32_t *tri, void *color, void *stream);
+
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with
