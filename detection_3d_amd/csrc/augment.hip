@@ -15,7 +15,6 @@ namespace d3d {
 
 namespace {
 
-inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 // by value: every kernel gets the scene's matrices in its argument block
 struct AugArgs {
@@ -347,9 +346,7 @@ int d3d_augment_voxelize(const float *pcl, int n, int nfeat, const double *point
   if (n == 0) return D3D_OK;
   const AugArgs g = to_args(prm_host);
   const int fx = full_scale_host[0], fy = full_scale_host[1], fz = full_scale_host[2];
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   D3D_ALLOC(red, unsigned long long, A, 16);       // min[3], max[3], offset[3] (fp64), kept count (int32)
   D3D_ALLOC(flag, int32_t, A, n);
   D3D_ALLOC(rank, int32_t, A, n);

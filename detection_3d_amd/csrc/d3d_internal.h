@@ -51,6 +51,16 @@ struct Arena {
     return static_cast<T *>(alloc(count * sizeof(T)));
   }
 };
+// the arena over a caller's scratch buffer
+inline Arena scratch_arena(const void *scratch, size_t bytes) {
+  Arena A;
+  A.base = (char *)scratch;
+  A.cap = bytes;
+  return A;
+}
+
+// one thread per item in blocks of `block`: the grid that covers n items (empty for n <= 0)
+inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 #define D3D_ALLOC(ptr, T, arena, count)                                                \
   T *ptr = (arena).get<T>(count);                                                      \
@@ -165,6 +175,10 @@ struct StridedRaw {  // kept so that the deconvolution plan can be finalised laz
 __device__ __forceinline__ uint32_t f32_ordered(float v) {
   const uint32_t b = __float_as_uint(v);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// ... and back (host and device: d3d_voxel_downsample_cells reports a cloud's extent with it)
+__host__ __device__ __forceinline__ float ordered_to_f32(uint32_t u) {
+  return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 // BoxCoder3D.decode of one row (box_coder_3d.py:38-65 / box_torch_ops.py:51-88, smooth_dim): e[7] encoding, a[7] anchor
 // (xa, ya, za, wa, la, ha, ra), w[7] the coder's weights, size deltas clamped to `clip`; yaw wrapped to [-pi/2, pi/2).

@@ -32,12 +32,8 @@ constexpr int kChunk = 512;                        // longer ones: chunks of thi
 constexpr int kMaxCols = 16;
 constexpr int kMaxPoints = 1 << 28;
 
-inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)std::max(1l, (n + block - 1) / block)); }
 inline unsigned reduce_blocks(int n) { return std::max(1u, std::min(1024u, (unsigned)((n + 255) / 256))); }
 
-__device__ __forceinline__ float ordered_to_f32(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 __device__ __forceinline__ bool finite3(const float *p) {
   return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;   // false for NaN
 }
@@ -381,9 +377,7 @@ int d3d_voxel_downsample_cells(const float *pcl, int n, int ncols, double voxel,
   if (n == 0) return D3D_OK;
   D3D_REQUIRE(pcl && scratch, "d3d_voxel_downsample_cells: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_voxel_downsample_scratch_bytes(n, ncols), "d3d_voxel_downsample_cells: scratch too small");
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   int rc = carve(A, n, ncols, L);
   if (rc) return rc;
@@ -437,14 +431,8 @@ int d3d_voxel_downsample_cells(const float *pcl, int n, int ncols, double voxel,
   for (int k = 0; k < 16; k++) host[k] = ((volatile int32_t *)w->word)[k];
   if (host[kInfoOverflow]) {
     double ext[3];
-    for (int d = 0; d < 3; d++) {
-      const uint32_t ulo = (uint32_t)host[kInfoMin + d], uhi = (uint32_t)host[kInfoMax + d];
-      uint32_t blo = (ulo & 0x80000000u) ? (ulo & 0x7fffffffu) : ~ulo, bhi = (uhi & 0x80000000u) ? (uhi & 0x7fffffffu) : ~uhi;
-      float flo, fhi;
-      memcpy(&flo, &blo, 4);
-      memcpy(&fhi, &bhi, 4);
-      ext[d] = (double)fhi - (double)flo;
-    }
+    for (int d = 0; d < 3; d++)
+      ext[d] = (double)ordered_to_f32((uint32_t)host[kInfoMax + d]) - (double)ordered_to_f32((uint32_t)host[kInfoMin + d]);
     set_error("d3d_voxel_downsample: the cloud spans %.9g x %.9g x %.9g m, more than the limit of 2^21 = 2097152 cells of "
               "%.9g m per axis (%.9g m)", ext[0], ext[1], ext[2], voxel, voxel * 2097152.0);
     return D3D_ERR_ARG;
@@ -468,9 +456,7 @@ int d3d_voxel_downsample_rows(const float *pcl, int n, int ncols, int normal_col
   D3D_REQUIRE(M >= 0 && M <= n && T >= 0 && (size_t)T <= max_chunks(n), "d3d_voxel_downsample_rows: bad counts %d, %d", M, T);
   D3D_REQUIRE(pcl && scratch && (out || M == 0), "d3d_voxel_downsample_rows: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_voxel_downsample_scratch_bytes(n, ncols), "d3d_voxel_downsample_rows: scratch too small");
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   const int rc = carve(A, n, ncols, L);
   if (rc) return rc;
@@ -506,9 +492,7 @@ int d3d_sample_rows(int n, int k, uint64_t seed, int32_t *rows, void *scratch, s
     return D3D_OK;
   }
   D3D_REQUIRE(scratch && scratch_bytes >= d3d_sample_rows_scratch_bytes(n), "d3d_sample_rows: scratch too small");
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   D3D_ALLOC(hist, uint32_t, A, 4 * 256 + 16);
   uint32_t *sel = hist + 4 * 256;
   D3D_ALLOC(flag, int32_t, A, n);

@@ -348,7 +348,6 @@ static inline int next_pow2(long v) {
   while (c < v) c <<= 1;
   return (int)c;
 }
-static inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 // 0xFF fill of hash tables and rulebook arrays.  hipMemsetAsync's fill kernel reaches ~0.3 TB/s on the 12-16 MB arrays
 // of the fine levels (53 us for a 16 MB table); 16-byte stores from enough workgroups run at HBM speed.
@@ -1566,9 +1565,7 @@ int d3d_voxelize(const float *pcl, int n, int nfeat, double scale, const int *fu
   D3D_REQUIRE(scratch_bytes >= d3d_voxelize_scratch_bytes(n), "d3d_voxelize: scratch too small");
   *n_kept_host = 0;
   if (n == 0) return D3D_OK;
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   D3D_ALLOC(mins, unsigned long long, A, 4);
   D3D_ALLOC(flag, int32_t, A, n);
   D3D_ALLOC(rank, int32_t, A, n);
@@ -1833,9 +1830,7 @@ int d3d_sort_pairs(const uint32_t *keys, const int32_t *vals, int n, int bits, i
   if (n == 0) return D3D_OK;
   D3D_REQUIRE(keys && vals && vals_out && scratch, "d3d_sort_pairs: null pointer");
   D3D_REQUIRE(scratch_bytes >= sort_scratch_bytes(n, bits), "d3d_sort_pairs: scratch too small");
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   return sort_pairs_u32(keys, keys_out, vals, vals_out, n, bits, A, (hipStream_t)stream, descending != 0);
 }
 

@@ -28,12 +28,6 @@ constexpr int kSpan = 64;                         // sorted queries per workgrou
 constexpr int kBudget = 1024;                     // staged candidates (16 KiB of LDS); beyond: read from global memory
 constexpr int kSweeps = 8;                        // cyclic Jacobi on a 3x3: converged to fp64 after 5-6
 
-inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-
-__device__ __forceinline__ float ordered_to_f32(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 // per-axis min: grid-stride, wave shuffle, LDS, one integer atomic per block and axis -- order-independent
 __global__ __launch_bounds__(256) void k_nrm_min(const float *__restrict__ xyz, int n, int stride, uint32_t *red) {
   __shared__ float lds[4][3];
@@ -361,9 +355,7 @@ int estimate(const float *xyz, int n, int stride, float radius, int max_nn, cons
     for (int k = 0; k < 5; k++) D3D_HIP_CHECK(hipEventCreate(&ev[k]));
 #define NRM_MARK(k) \
   if (phase_ms) D3D_HIP_CHECK(hipEventRecord(ev[k], s))
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   const int cap = table_cap(n);
   D3D_ALLOC(red, uint32_t, A, 4);
   D3D_ALLOC(cx, uint32_t, A, n);

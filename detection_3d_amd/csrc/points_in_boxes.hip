@@ -20,30 +20,21 @@ constexpr int kSpan = kThreads * kPointsPerLane;   // points of one workgroup
 constexpr int kTile = 256;                         // boxes staged at a time
 constexpr int kMaxBoxes = 4096;
 
-// order-preserving image of a float: a < b <=> ordered(a) < ordered(b) as unsigned (-0 below +0)
-__device__ __forceinline__ uint32_t ordered(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t v) {
-  return __uint_as_float(v ^ ((v & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
 // count = 0, lo = image(+inf), hi = image(-inf): the accumulators the sweep's atomics start from
 __global__ void k_pib_begin(int k, int32_t *count, uint32_t *lo, uint32_t *hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 3 * k) return;
   if (i < k) count[i] = 0;
-  lo[i] = ordered(__builtin_inff());
-  hi[i] = ordered(-__builtin_inff());
+  lo[i] = f32_ordered(__builtin_inff());
+  hi[i] = f32_ordered(-__builtin_inff());
 }
 
 // the images back to floats, in place
 __global__ void k_pib_end(int k, uint32_t *lo, uint32_t *hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 3 * k) return;
-  reinterpret_cast<float *>(lo)[i] = unordered(lo[i]);
-  reinterpret_cast<float *>(hi)[i] = unordered(hi[i]);
+  reinterpret_cast<float *>(lo)[i] = ordered_to_f32(lo[i]);
+  reinterpret_cast<float *>(hi)[i] = ordered_to_f32(hi[i]);
 }
 
 struct BoxTile {
@@ -126,9 +117,9 @@ __global__ __launch_bounds__(kThreads) void k_pib_sweep(const float *__restrict_
       }
       if ((tid & 63) == 0) {
         atomicAdd(&T.count[bi], hits);
-        atomicMin(&T.lo[0][bi], ordered(mn0)), atomicMax(&T.hi[0][bi], ordered(mx0));
-        atomicMin(&T.lo[1][bi], ordered(mn1)), atomicMax(&T.hi[1][bi], ordered(mx1));
-        atomicMin(&T.lo[2][bi], ordered(mn2)), atomicMax(&T.hi[2][bi], ordered(mx2));
+        atomicMin(&T.lo[0][bi], f32_ordered(mn0)), atomicMax(&T.hi[0][bi], f32_ordered(mx0));
+        atomicMin(&T.lo[1][bi], f32_ordered(mn1)), atomicMax(&T.hi[1][bi], f32_ordered(mx1));
+        atomicMin(&T.lo[2][bi], f32_ordered(mn2)), atomicMax(&T.hi[2][bi], f32_ordered(mx2));
       }
     }
     __syncthreads();

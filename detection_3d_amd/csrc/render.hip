@@ -292,8 +292,7 @@ int open_scratch(const char *who, void *scratch, size_t scratch_bytes, int frame
                  Arena &A, Layout &L) {
   D3D_REQUIRE(scratch, "%s: null pointer", who);
   D3D_REQUIRE(scratch_bytes >= d3d_render_scratch_bytes(frames, height, width), "%s: scratch too small", who);
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  A = scratch_arena(scratch, scratch_bytes);
   return carve(A, n_tiles, L);
 }
 

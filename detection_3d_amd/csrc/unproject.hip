@@ -259,9 +259,7 @@ int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int hei
   D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames, height, width, step),
               "d3d_unproject_count: scratch too small");
   V.depth = depth;
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   rc = carve(A, V.P, L);
   if (rc) return rc;
@@ -301,9 +299,7 @@ int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, i
   D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames, height, width, step),
               "d3d_unproject_rows: scratch too small");
   V.depth = depth;
-  Arena A;
-  A.base = (char *)scratch;
-  A.cap = scratch_bytes;
+  Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   rc = carve(A, V.P, L);
   if (rc) return rc;

@@ -188,7 +188,6 @@ def prepare_cloud(pcl, voxel=DEFAULT_VOXEL, max_points=DEFAULT_MAX_POINTS, seed=
     """A raw scan -> the cloud the detector takes, the three steps of the reference's preparation in its order: one point
     per `voxel` (None: skip), at most max_points of them (None: skip), then, with normals ('estimate' or a dict of
     estimate_normals keywords), normal columns estimated on the down-sampled cloud (normals.with_normals)."""
-    from .normals import normals_kwargs, with_normals
-    nkw = normals_kwargs(normals)
-    pcl = apply_downsample(pcl, downsample_kwargs({"voxel": voxel, "max_points": max_points, "seed": seed}))
-    return pcl if nkw is None else with_normals(pcl, **nkw)
+    from .prepare import Preparation
+    dkw = {"voxel": voxel, "max_points": max_points, "seed": seed}
+    return Preparation(downsample=dkw, normals=normals).cloud(pcl)[0]

@@ -15,31 +15,13 @@ import torch.distributed as dist
 
 from . import training as T
 from .distributed import agree_capacity, gather_detections, pack_detections
-from .downsample import apply_downsample, downsample_kwargs
-from .normals import normals_kwargs, with_normals
-from .primitives import as_crop, shift_targets
+from .prepare import Preparation
 from .scene_io import ScenePrefetcher
 
 
 def _hip_voxelize(pcl, cfg):
     from .voxelize import voxelize          # d3d_voxelize: needs the GPU library
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
-
-
-def _fill_normals(pcl, nkw):
-    """the raw cloud with estimated normal columns (normals.with_normals), on the stream that voxelises it"""
-    return pcl if nkw is None else with_normals(pcl, **nkw)
-
-
-def _prepare(pcl, dkw, nkw):
-    """one raw cloud on the stream that voxelises it: down-sampled and capped (downsample.apply_downsample), then its
-    normal columns estimated"""
-    return _fill_normals(apply_downsample(pcl, dkw), nkw)
-
-
-def _crop_scene(pcl, tg, crop):
-    """the scene cut to a random window (primitives.RandomCrop); targets in the file's frame"""
-    return (pcl, tg) if crop is None else crop(pcl, tg)
 
 
 def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None):
@@ -60,19 +42,14 @@ def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, 
     the order is crop -> down-sample -> cap -> estimated normals -> voxelise or augment.  The detector's frame is the
     minimum of the cloud that is voxelised, which the raw cloud's minimum misses by up to a voxel: like `crop`,
     `downsample` needs the targets in the file's frame and shifts them afterwards."""
-    dkw = downsample_kwargs(downsample)
-    nkw = normals_kwargs(normals)
-    crop = as_crop(crop)
+    return _collate(scenes, cfg, Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment,
+                                             voxelize_fn=voxelize_fn))
+
+
+def _collate(scenes, cfg, chain):
     cs, fs, tgs = [], [], []
     for b, (pcl, tg) in enumerate(scenes):
-        pcl, tg = _crop_scene(pcl, tg, crop)
-        pcl = _prepare(pcl, dkw, nkw)
-        if augment is None:
-            c, f = voxelize_fn(pcl, cfg)
-            if crop is not None or dkw is not None:
-                tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
-        else:
-            c, f, tg = augment(pcl, tg, cfg)
+        c, f, tg = chain.scene(pcl, tg, cfg)
         cs.append(torch.cat([c, torch.full((c.shape[0], 1), b, dtype=c.dtype, device=c.device)], 1))
         fs.append(f)
         tgs.append(tg)
@@ -106,26 +83,19 @@ def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip
     """Detections of every building in `files`, sharded over the ranks of the default process group.
     -> on rank 0: ({file index: detections dict}, {file index: targets dict of the building in the detector's frame});
     None on the other ranks.  Targets travel with the detections so that rank 0 can evaluate without re-reading files.
-    normals (None, 'estimate' or a dict of estimate_normals keywords): files that hold xyz, or xyz and colour, get their
-    normal columns estimated on the GPU before they are voxelised.
-    downsample (None, a voxel size, or a dict with keys among voxel, max_points, seed): every raw cloud is reduced to one
-    point per voxel and capped first (downsample.apply_downsample); the targets are then read in the file's frame and
-    shifted by the minimum of the cloud that is voxelised."""
-    dkw = downsample_kwargs(downsample)
-    nkw = normals_kwargs(normals)
+    normals, downsample: as in `collate` (files that hold xyz, or xyz and colour, get their normal columns estimated);
+    with downsample the targets are read in the file's frame and shifted by the minimum of the cloud that is voxelised."""
+    chain = Preparation(downsample=downsample, normals=normals, voxelize_fn=voxelize_fn)
     rank, world = _rank_world()
     max_det = max_det or int(cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG) * max(1, len(cfg.MODEL.SEPARATE_CLASSES_ID) + 1)
     pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank, world=world,
-                          depth=depth, shift_targets=dkw is None)
+                          depth=depth, shift_targets=not chain.targets_in_file_frame)
     was_training = model.training
     model.eval()
     results, truths = [], []
     with torch.no_grad():
         for i, (pcl, tg, _path) in enumerate(pre):
-            pcl = _prepare(pcl, dkw, nkw)
-            if dkw is not None:
-                tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
-            coords, feats = voxelize_fn(pcl, cfg)
+            coords, feats, tg = chain.scene(pcl, tg, cfg)
             results.append((rank + i * world, model([coords, feats])))
             truths.append({"bbox3d": tg["bbox3d"], "labels": tg["labels"],
                            "scores": torch.ones(tg["bbox3d"].shape[0], device=tg["bbox3d"].device)})
@@ -172,18 +142,11 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
-    process group with more than one rank exists.  augment (augment.Augment): every example is augmented on the GPU
-    while it is voxelised, rank r drawing with seed + 1000003 r; None keeps the plain path.  normals (None, 'estimate' or
-    a dict of estimate_normals keywords): every raw cloud's normal columns are estimated on the GPU before voxelisation
-    and before `augment`; the augmentation flips and rotates them, and they are not estimated again after its elastic
-    distortion.  crop ((sx, sy) in metres, or a primitives.RandomCrop): every building is cut to a random window of that
-    size first and its boxes follow the points that remain (primitives.crop_scene), rank r drawing with
-    seed + 1000003 r.  downsample (None, a voxel size, or a dict with keys among voxel, max_points, seed): every raw
-    cloud is reduced to one point per voxel and capped after the crop and before the normals
-    (downsample.apply_downsample); the targets are then read in the file's frame and follow the cloud that is voxelised.
+    process group with more than one rank exists.  augment, normals, crop, downsample: as in `collate`, for every
+    building (prepare.Preparation), rank r drawing with seed + 1000003 r in `augment` and `crop`; with any of augment,
+    crop and downsample the targets are read in the file's frame and follow the cloud that is voxelised.
     -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
-    dkw = downsample_kwargs(downsample)
-    nkw = normals_kwargs(normals)
+    chain = Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment, voxelize_fn=voxelize_fn)
     rank, world = _rank_world()
     ims = int(ims_per_gpu)
     if ims < 1:
@@ -199,32 +162,19 @@ def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=
         sched_cfg = cfg.clone()
         sched_cfg.SOLVER.IMS_PER_BATCH = world * ims
         sched = T.make_lr_scheduler(sched_cfg, opt, examples_per_epoch=max(len(files), 1))
-    aug = None if augment is None else augment.for_rank(rank)
-    if aug is not None:
-        aug.check_classes(cfg.INPUT.CLASSES)
-    crop = as_crop(crop)
-    if crop is not None:
-        crop = crop.for_rank(rank)
+    chain = chain.for_rank(rank, cfg.INPUT.CLASSES)
     it, t0, reduced = 0, None, {}
-    for batch in group_batches(_cycled_scenes(files, cfg, device, rank, world, depth,
-                                              aug is None and crop is None and dkw is None),
-                               ims):
+    scenes = _cycled_scenes(files, cfg, device, rank, world, depth, not chain.targets_in_file_frame)
+    for batch in group_batches(scenes, ims):
         if it == 1:                          # the first iteration pays allocations and the bucket build
             if device is not None:
                 torch.cuda.synchronize(device)
             t0 = time.perf_counter()
         if ims == 1:
-            pcl, tg = _crop_scene(*batch[0], crop)
-            pcl = _prepare(pcl, dkw, nkw)
-            if aug is None:
-                coords, feats = voxelize_fn(pcl, cfg)
-                if crop is not None or dkw is not None:
-                    tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
-            else:
-                coords, feats, tg = aug(pcl, tg, cfg)
+            coords, feats, tg = chain.scene(*batch[0], cfg)
             _, reduced = T.train_step(ddp, opt, sched, [coords, feats], tg)
         else:
-            points, tgs = collate(batch, cfg, voxelize_fn, aug, nkw, crop, dkw)
+            points, tgs = _collate(batch, cfg, chain)
             _, reduced = T.train_step(ddp, opt, sched, points, tgs)
         it += 1
         if log_every and rank == 0 and it % log_every == 0:

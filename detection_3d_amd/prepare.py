@@ -1,0 +1,86 @@
+"""From a raw input to what the detector takes, the one place that knows the order of the steps:
+
+    unproject (serving, DepthFrames only) | crop (training) -> down-sample -> cap -> estimated normals
+      -> voxelise + targets shifted into the voxelised cloud's frame | augment
+
+engine.collate / inference / train and serving.BuildingPipeline all go through it.  Every step runs on the caller's
+current stream; a step whose option is None issues no kernel, allocates nothing and reads nothing back."""
+import copy
+from collections import namedtuple
+
+import torch
+
+from .downsample import apply_downsample, downsample_kwargs
+from .normals import normals_kwargs, with_normals
+from .primitives import as_crop, points_in_boxes, shift_targets
+from .unproject import DepthFrames, unproject, unproject_kwargs
+
+# what point_ownership needs of one served input: the cloud the owners are found in (None: the input itself), raw row ->
+# its row of that cloud (None: the same rows), the pixel of every unprojected row (None: the input was a cloud)
+Kept = namedtuple("Kept", "cloud source pixels")
+
+
+class Preparation(object):
+    """The keywords of the loops (unproject_kwargs, as_crop, downsample_kwargs, normals_kwargs; an augment.Augment;
+    voxelize_fn(pcl, cfg) -> (coords, feats)), checked here before anything touches a config, a model or a device."""
+
+    def __init__(self, unproject=None, crop=None, downsample=None, normals=None, augment=None, voxelize_fn=None):
+        self.unproject = unproject_kwargs(unproject)
+        self.crop = as_crop(crop)
+        self.downsample = downsample_kwargs(downsample)
+        self.normals = normals_kwargs(normals)
+        self.augment, self.voxelize_fn = augment, voxelize_fn
+
+    @property
+    def targets_in_file_frame(self):
+        """crop, down-sample and augment each move the detector's frame: ScenePrefetcher(shift_targets=False) feeds `scene`"""
+        return self.crop is not None or self.downsample is not None or self.augment is not None
+
+    def for_rank(self, rank, classes):
+        """the same chain drawing with seed + 1000003 rank in `augment` (checked against the classes) and `crop`"""
+        chain = copy.copy(self)
+        if self.augment is not None:
+            chain.augment = self.augment.for_rank(rank)
+            chain.augment.check_classes(classes)
+        if self.crop is not None:
+            chain.crop = self.crop.for_rank(rank)
+        return chain
+
+    def cloud(self, raw, keep=False):
+        """raw: a cloud or a DepthFrames -> (the cloud to voxelise, None); with keep the second entry is the Kept that
+        point_ownership takes.  With every option None the cloud is `raw` itself."""
+        pcl, source, pixels = raw, None, None
+        if isinstance(raw, DepthFrames):
+            pcl = unproject(raw, return_pixels=keep, **self.unproject)
+            if keep:
+                pcl, pixels = pcl
+        pcl = apply_downsample(pcl, self.downsample, return_source=keep)
+        if keep:
+            pcl, source = pcl
+        kept = Kept(None if pcl is raw else pcl, source, pixels) if keep else None
+        if self.normals is not None:
+            pcl = with_normals(pcl, **self.normals)
+        return pcl, kept
+
+    def scene(self, pcl, tg, cfg):
+        """one training or evaluation scene -> (coords, feats, targets in the frame of coords)"""
+        if self.crop is not None:
+            pcl, tg = self.crop(pcl, tg)
+        pcl, _ = self.cloud(pcl)
+        if self.augment is not None:
+            return self.augment(pcl, tg, cfg)
+        coords, feats = self.voxelize_fn(pcl, cfg)
+        if self.targets_in_file_frame:
+            tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
+        return coords, feats, tg
+
+
+def point_ownership(kept, raw, boxes):
+    """-> (point_owner int32, one entry per row of the raw cloud (`raw`, or the unprojected one): the first box that
+    holds the point it went into, -1 for none or for a row that went nowhere; point_count int32 per box)"""
+    owner, count, _, _ = points_in_boxes(raw if kept.cloud is None else kept.cloud, boxes.to(torch.float32), origin="min")
+    if kept.source is not None:
+        # entry M of the table: the rows that went nowhere (source -1 indexes it from the end)
+        table = torch.cat([owner, torch.full((1,), -1, dtype=owner.dtype, device=owner.device)])
+        owner = table[kept.source.long()]
+    return owner, count

@@ -24,10 +24,7 @@ import threading
 
 import torch
 
-from .downsample import apply_downsample, downsample_kwargs
-from .normals import normals_kwargs, with_normals
-from .primitives import points_in_boxes
-from .unproject import DepthFrames, unproject, unproject_kwargs
+from .prepare import Preparation, point_ownership
 from .voxelize import voxelize
 
 
@@ -52,11 +49,9 @@ class BuildingPipeline(object):
 
     def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None,
                  unproject=None):
-        self.downsample = downsample_kwargs(downsample)
-        self.unproject = unproject_kwargs(unproject)
+        self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
-        self.normals = normals_kwargs(normals)
         self.device = device if device is not None else next(model.parameters()).device
         self.in_flight = max(1, int(in_flight))
         # streams live as long as the pipeline: metadata arenas and scratch buffers are recycled per stream
@@ -81,9 +76,7 @@ class BuildingPipeline(object):
         for st in self.hi:
             st.wait_event(ready)
         results, errors = [None] * n, []
-        pixels = [None] * n         # of a DepthFrames input with point_owner: the pixel of every unprojected row
-        raw = [None] * n            # ... and its unprojected cloud, kept only while the tail needs it (no downsample)
-        reduced = [None] * n        # with downsample and point_owner: (the cloud that was voxelised, raw row -> its row)
+        kept = [None] * n           # with point_owner: what prepare.point_ownership needs, only until the tail has run
         slots = threading.Semaphore(self.in_flight)
         q_feat, q_tail = queue.Queue(), queue.Queue()
         stop = threading.Event()
@@ -115,21 +108,7 @@ class BuildingPipeline(object):
                 hi, lo = slot(i)
                 with torch.cuda.stream(hi):
                     hi.wait_stream(lo)      # the slot's previous building has left its arena and allocator blocks
-                    pcl = clouds[i]
-                    if isinstance(pcl, DepthFrames):
-                        if self.point_owner:
-                            pcl, pixels[i] = unproject(pcl, return_pixels=True, **self.unproject)
-                        else:
-                            pcl = unproject(pcl, **self.unproject)
-                        if self.point_owner and self.downsample is None:
-                            raw[i] = pcl
-                    if self.downsample is not None and self.point_owner:
-                        pcl, source = apply_downsample(pcl, self.downsample, return_source=True)
-                        reduced[i] = (pcl, source)
-                    elif self.downsample is not None:
-                        pcl = apply_downsample(pcl, self.downsample)
-                    if self.normals is not None:
-                        pcl = with_normals(pcl, **self.normals)
+                    pcl, kept[i] = self.prepare.cloud(clouds[i], keep=self.point_owner)
                     coords, feats = voxelize(pcl, s3d.VOXEL_SCALE, s3d.VOXEL_FULL_SCALE)
                     net = self.model.stage_geometry([coords, feats])
                     lo.wait_stream(hi)
@@ -156,20 +135,12 @@ class BuildingPipeline(object):
                 i, feats = item
                 with torch.cuda.stream(slot(i)[0]):
                     results[i] = r = self.model.stage_tail(feats)
-                    if self.point_owner and reduced[i] is not None:
-                        pcl, source = reduced[i]
-                        reduced[i] = None
-                        owner, r["point_count"], _, _ = points_in_boxes(pcl, r["bbox3d"].to(torch.float32), origin="min")
-                        # entry M of the table: the rows that went nowhere (source -1 indexes it from the end)
-                        table = torch.cat([owner, torch.full((1,), -1, dtype=owner.dtype, device=owner.device)])
-                        r["point_owner"] = table[source.long()]
-                    elif self.point_owner:
-                        pcl, raw[i] = (raw[i] if raw[i] is not None else clouds[i]), None
-                        r["point_owner"], r["point_count"], _, _ = points_in_boxes(
-                            pcl, r["bbox3d"].to(torch.float32), origin="min")
-                        del pcl
-                    if pixels[i] is not None:
-                        r["point_pixel"], pixels[i] = pixels[i], None
+                    k, kept[i] = kept[i], None
+                    if k is not None:
+                        r["point_owner"], r["point_count"] = point_ownership(k, clouds[i], r["bbox3d"])
+                        if k.pixels is not None:
+                            r["point_pixel"] = k.pixels
+                    del k
                 del feats, item
                 slots.release()
 
