@@ -85,6 +85,15 @@ _SIGS = {
                                             vp, vp, ctypes.c_size_t, vp]),
     "d3d_estimate_normals_phases": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                                    c_float_p, vp, vp, vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_radius_neighbors_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_radius_neighbors": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, ctypes.c_size_t, vp,
+                                            c_float_p]),
+    "d3d_knn_mean_distance_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_knn_mean_distance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_double,
+                                             vp, vp, vp, vp, vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_connected_components_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_connected_components": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp, ctypes.c_size_t,
+                                                vp, c_float_p]),
     "d3d_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
                                            ctypes.c_float, vp, vp, vp, vp, vp]),
     "d3d_voxel_downsample_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -401,4 +401,48 @@ __device__ __forceinline__ void hash_find_n(const HashEntry *__restrict__ tab, i
   }
 }
 
+// The cell list of a raw cloud (built in normals.hip; consumers: normals.hip, clean.hip): the points sorted by cell
+// (cells of edge 1.0001 r about the per-axis minimum, so that a neighbour within r is never two cells away; order
+// (x, y, z, original index)), the 60-bit cell key of every sorted position and an open-addressing table
+// cell -> [first, last) of the sorted positions.  A namespace of its own: downsample.hip has cells of another width.
+namespace celllist {
+
+constexpr int kCellBits = 20;                     // per axis; cells past 2^20 - 1 are merged into the last one, which
+constexpr int kCellMax = (1 << kCellBits) - 1;    // keeps every neighbour within +-1 cell (the clamp is monotonic)
+constexpr int kMaxPoints = 1 << 28;
+
+__device__ __forceinline__ uint64_t cell_key(uint32_t x, uint32_t y, uint32_t z) {
+  return ((uint64_t)x << (2 * kCellBits)) | ((uint64_t)y << kCellBits) | (uint64_t)z;
+}
+
+// [first, last) of a cell, (0, 0) when it holds no point
+__device__ __forceinline__ int2 cell_range(const HashEntry *__restrict__ tab, int cap, uint64_t c) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  uint32_t slot = hash_key(c) & (uint32_t)(cap - 1), round = 0;
+  while (true) {
+    const u32x4 e = *(const u32x4 *)&tab[slot];
+    const uint64_t k = ((uint64_t)e[1] << 32) | e[0];
+    if (k == c) return make_int2((int)e[2], (int)e[3]);
+    if (k == kEmptyKey) return make_int2(0, 0);
+    slot = probe_next(slot, round, cap);
+  }
+}
+
+struct CellList {
+  const float4 *pts = nullptr;     // [n] (x, y, z, bits of the original index) in cell order
+  const uint64_t *key = nullptr;   // [n] cell key of every sorted position
+  const HashEntry *tab = nullptr;  // [cap] key -> (val = first, first = last) of the cell's sorted positions
+  int cap = 0;
+};
+
+int table_cap(int n);
+// what build() takes from its arena at most (n clamped to kMaxPoints): linear in n, independent of the extent
+size_t scratch_bytes(int n);
+// xyz fp32, row i at xyz + i * stride, 1 <= n <= kMaxPoints -> the cell list in `A` (which stays allocated; the sorts'
+// temporaries are released).  ev: null, or four events recorded on `s` before the cell coordinates, the sorts, the
+// table and after it.  Asynchronous.
+int build(const float *xyz, int n, int stride, float radius, Arena &A, hipStream_t s, CellList *out, hipEvent_t *ev);
+
+}  // namespace celllist
+
 }  // namespace d3d

@@ -19,8 +19,7 @@ namespace d3d {
 
 namespace {
 
-constexpr int kCellBits = 20;                     // per axis; cells past 2^20 - 1 are merged into the last one, which
-constexpr int kCellMax = (1 << kCellBits) - 1;    // keeps every neighbour within +-1 cell (the clamp is monotonic)
+using namespace celllist;                         // kCellBits, kCellMax, cell_key, cell_range, table_cap (d3d_internal.h)
 constexpr int kThreads = 128;                     // k_nrm_search: 16 lane groups of 8, one query per group at a time
 constexpr int kGroup = 8;
 constexpr int kGroups = kThreads / kGroup;
@@ -69,10 +68,6 @@ __global__ void k_nrm_gather(const uint32_t *__restrict__ src, const int32_t *__
   if (k < n) dst[k] = src[perm[k]];
 }
 
-__device__ __forceinline__ uint64_t cell_key(uint32_t x, uint32_t y, uint32_t z) {
-  return ((uint64_t)x << (2 * kCellBits)) | ((uint64_t)y << kCellBits) | (uint64_t)z;
-}
-
 // the points in cell order: (x, y, z, original index) and the cell key of every sorted position
 __global__ void k_nrm_sorted(const float *__restrict__ xyz, int n, int stride, const int32_t *__restrict__ perm,
                              const uint32_t *__restrict__ cx, const uint32_t *__restrict__ cy,
@@ -96,19 +91,6 @@ __global__ void k_nrm_table(const uint64_t *__restrict__ key, int n, HashEntry *
   const int slot = hash_insert(tab, cap, c);
   if (head) tab[slot].val = k;
   if (tail) tab[slot].first = (uint32_t)(k + 1);
-}
-
-// [first, last) of a cell, (0, 0) when it holds no point
-__device__ __forceinline__ int2 cell_range(const HashEntry *__restrict__ tab, int cap, uint64_t c) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  uint32_t slot = hash_key(c) & (uint32_t)(cap - 1), round = 0;
-  while (true) {
-    const u32x4 e = *(const u32x4 *)&tab[slot];
-    const uint64_t k = ((uint64_t)e[1] << 32) | e[0];
-    if (k == c) return make_int2((int)e[2], (int)e[3]);
-    if (k == kEmptyKey) return make_int2(0, 0);
-    slot = probe_next(slot, round, cap);
-  }
 }
 
 // smallest eigenvalue's unit eigenvector of the symmetric c = (xx, xy, xz, yy, yz, zz): cyclic Jacobi, fixed sweeps.
@@ -332,14 +314,6 @@ __global__ __launch_bounds__(kThreads) void k_nrm_search(const float4 *__restric
   }
 }
 
-int table_cap(int n) {
-  long c = 1024;
-  while (c < 2l * n) c <<= 1;
-  return (int)c;
-}
-
-constexpr int kMaxPoints = 1 << 28;
-
 int estimate(const float *xyz, int n, int stride, float radius, int max_nn, const float *vp, float *normals,
              int32_t *counts, void *scratch, size_t scratch_bytes, hipStream_t s, float *phase_ms) {
   D3D_REQUIRE(n >= 0 && n <= kMaxPoints && stride >= 3, "d3d_estimate_normals: bad point count or row stride");
@@ -353,9 +327,44 @@ int estimate(const float *xyz, int n, int stride, float radius, int max_nn, cons
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   if (phase_ms)
     for (int k = 0; k < 5; k++) D3D_HIP_CHECK(hipEventCreate(&ev[k]));
-#define NRM_MARK(k) \
-  if (phase_ms) D3D_HIP_CHECK(hipEventRecord(ev[k], s))
   Arena A = scratch_arena(scratch, scratch_bytes);
+  CellList L;
+  const int rc = celllist::build(xyz, n, stride, radius, A, s, &L, phase_ms ? ev : nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_nrm_search, dim3((unsigned)((n + kSpan - 1) / kSpan)), dim3(kThreads), 0, s, L.pts, L.key, n, L.tab,
+                     L.cap, radius * radius, max_nn, vp ? 1 : 0, vp ? vp[0] : 0.f, vp ? vp[1] : 0.f, vp ? vp[2] : 0.f,
+                     normals, counts);
+  D3D_LAUNCH_CHECK();
+  if (phase_ms) {
+    D3D_HIP_CHECK(hipEventRecord(ev[4], s));
+    D3D_HIP_CHECK(hipEventSynchronize(ev[4]));
+    for (int k = 0; k < 4; k++) D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
+    for (int k = 0; k < 5; k++) (void)hipEventDestroy(ev[k]);
+  }
+  return D3D_OK;
+}
+
+}  // namespace
+
+namespace celllist {
+
+int table_cap(int n) {
+  long c = 1024;
+  while (c < 2l * n) c <<= 1;
+  return (int)c;
+}
+
+size_t scratch_bytes(int n) {
+  const size_t N = (size_t)std::max(1, std::min(n, kMaxPoints));
+  // the arrays of build() (256-byte aligned each), the table and one sort's temporaries
+  return 6 * (N * 4 + 256) + (N * 16 + 256) + (N * 8 + 256) + ((size_t)table_cap((int)N) * sizeof(HashEntry) + 256) +
+         sort_scratch_bytes((int)N, kCellBits) + 1024;
+}
+
+int build(const float *xyz, int n, int stride, float radius, Arena &A, hipStream_t s, CellList *out, hipEvent_t *ev) {
+  D3D_REQUIRE(n >= 1 && n <= kMaxPoints && stride >= 3 && xyz && out, "cell list: bad point count, row stride or pointer");
+#define NRM_MARK(k) \
+  if (ev) D3D_HIP_CHECK(hipEventRecord(ev[k], s))
   const int cap = table_cap(n);
   D3D_ALLOC(red, uint32_t, A, 4);
   D3D_ALLOC(cx, uint32_t, A, n);
@@ -395,21 +404,15 @@ int estimate(const float *xyz, int n, int stride, float radius, int max_nn, cons
   hipLaunchKernelGGL(k_nrm_table, grid1d(n), dim3(256), 0, s, (const uint64_t *)key, n, tab, cap);
   D3D_LAUNCH_CHECK();
   NRM_MARK(3);
-  hipLaunchKernelGGL(k_nrm_search, dim3((unsigned)((n + kSpan - 1) / kSpan)), dim3(kThreads), 0, s, (const float4 *)pts,
-                     (const uint64_t *)key, n, (const HashEntry *)tab, cap, radius * radius, max_nn, vp ? 1 : 0,
-                     vp ? vp[0] : 0.f, vp ? vp[1] : 0.f, vp ? vp[2] : 0.f, normals, counts);
-  D3D_LAUNCH_CHECK();
-  NRM_MARK(4);
 #undef NRM_MARK
-  if (phase_ms) {
-    D3D_HIP_CHECK(hipEventSynchronize(ev[4]));
-    for (int k = 0; k < 4; k++) D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
-    for (int k = 0; k < 5; k++) (void)hipEventDestroy(ev[k]);
-  }
+  out->pts = pts;
+  out->key = key;
+  out->tab = tab;
+  out->cap = cap;
   return D3D_OK;
 }
 
-}  // namespace
+}  // namespace celllist
 }  // namespace d3d
 
 using namespace d3d;
@@ -417,10 +420,7 @@ using namespace d3d;
 size_t d3d_estimate_normals_scratch_bytes(int n, int max_nn) {
   (void)max_nn;   // the cut needs no per-query storage
   if (n <= 0) return 256;
-  const size_t N = (size_t)std::min(n, kMaxPoints);
-  // the arrays of estimate() (256-byte aligned each), the table and one sort's temporaries
-  return 6 * (N * 4 + 256) + (N * 16 + 256) + (N * 8 + 256) + ((size_t)table_cap((int)N) * sizeof(HashEntry) + 256) +
-         sort_scratch_bytes((int)N, kCellBits) + 1024;
+  return celllist::scratch_bytes(n);
 }
 
 int d3d_estimate_normals(const float *xyz, int n, int row_stride_floats, float radius, int max_nn,

@@ -24,7 +24,7 @@ def _hip_voxelize(pcl, cfg):
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None):
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None, clean=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
     the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
@@ -41,9 +41,13 @@ def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, 
     point per voxel and capped (downsample.voxel_downsample, cap_points) after the crop and before the normals, so that
     the order is crop -> down-sample -> cap -> estimated normals -> voxelise or augment.  The detector's frame is the
     minimum of the cloud that is voxelised, which the raw cloud's minimum misses by up to a voxel: like `crop`,
-    `downsample` needs the targets in the file's frame and shifts them afterwards."""
+    `downsample` needs the targets in the file's frame and shifts them afterwards.
+    clean (None, or a dict with keys among radius, min_neighbors, statistical, min_component: clean.clean_cloud's
+    keywords): outliers and small detached components are removed after the cap and before the normals
+    (clean.clean_cloud), so that a stray return does not move the frame; the minimum moves, so the targets are treated
+    as with `downsample`."""
     return _collate(scenes, cfg, Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment,
-                                             voxelize_fn=voxelize_fn))
+                                             voxelize_fn=voxelize_fn, clean=clean))
 
 
 def _collate(scenes, cfg, chain):
@@ -79,13 +83,14 @@ def _rank_world():
 
 
 def inference(model, cfg, files, device, depth=2, max_det=None, voxelize_fn=_hip_voxelize, normals=None,
-              downsample=None):
+              downsample=None, clean=None):
     """Detections of every building in `files`, sharded over the ranks of the default process group.
     -> on rank 0: ({file index: detections dict}, {file index: targets dict of the building in the detector's frame});
     None on the other ranks.  Targets travel with the detections so that rank 0 can evaluate without re-reading files.
-    normals, downsample: as in `collate` (files that hold xyz, or xyz and colour, get their normal columns estimated);
-    with downsample the targets are read in the file's frame and shifted by the minimum of the cloud that is voxelised."""
-    chain = Preparation(downsample=downsample, normals=normals, voxelize_fn=voxelize_fn)
+    normals, downsample, clean: as in `collate` (files that hold xyz, or xyz and colour, get their normal columns
+    estimated); with downsample or clean the targets are read in the file's frame and shifted by the minimum of the cloud
+    that is voxelised."""
+    chain = Preparation(downsample=downsample, normals=normals, voxelize_fn=voxelize_fn, clean=clean)
     rank, world = _rank_world()
     max_det = max_det or int(cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG) * max(1, len(cfg.MODEL.SEPARATE_CLASSES_ID) + 1)
     pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank, world=world,
@@ -138,15 +143,16 @@ def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1, augment=None, normals=None, crop=None, downsample=None):
+          ims_per_gpu=1, augment=None, normals=None, crop=None, downsample=None, clean=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
-    process group with more than one rank exists.  augment, normals, crop, downsample: as in `collate`, for every
+    process group with more than one rank exists.  augment, normals, crop, downsample, clean: as in `collate`, for every
     building (prepare.Preparation), rank r drawing with seed + 1000003 r in `augment` and `crop`; with any of augment,
-    crop and downsample the targets are read in the file's frame and follow the cloud that is voxelised.
+    crop, downsample and clean the targets are read in the file's frame and follow the cloud that is voxelised.
     -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
-    chain = Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment, voxelize_fn=voxelize_fn)
+    chain = Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment, voxelize_fn=voxelize_fn,
+                        clean=clean)
     rank, world = _rank_world()
     ims = int(ims_per_gpu)
     if ims < 1:

@@ -1,6 +1,6 @@
 """From a raw input to what the detector takes, the one place that knows the order of the steps:
 
-    unproject (serving, DepthFrames only) | crop (training) -> down-sample -> cap -> estimated normals
+    unproject (serving, DepthFrames only) | crop (training) -> down-sample -> cap -> clean -> estimated normals
       -> voxelise + targets shifted into the voxelised cloud's frame | augment
 
 engine.collate / inference / train and serving.BuildingPipeline all go through it.  Every step runs on the caller's
@@ -10,6 +10,7 @@ from collections import namedtuple
 
 import torch
 
+from .clean import apply_clean, clean_kwargs, compose_sources
 from .downsample import apply_downsample, downsample_kwargs
 from .normals import normals_kwargs, with_normals
 from .primitives import as_crop, points_in_boxes, shift_targets
@@ -21,20 +22,24 @@ Kept = namedtuple("Kept", "cloud source pixels")
 
 
 class Preparation(object):
-    """The keywords of the loops (unproject_kwargs, as_crop, downsample_kwargs, normals_kwargs; an augment.Augment;
+    """The keywords of the loops (unproject_kwargs, as_crop, downsample_kwargs, clean_kwargs, normals_kwargs; an augment.Augment;
     voxelize_fn(pcl, cfg) -> (coords, feats)), checked here before anything touches a config, a model or a device."""
 
-    def __init__(self, unproject=None, crop=None, downsample=None, normals=None, augment=None, voxelize_fn=None):
+    def __init__(self, unproject=None, crop=None, downsample=None, normals=None, augment=None, voxelize_fn=None,
+                 clean=None):
         self.unproject = unproject_kwargs(unproject)
         self.crop = as_crop(crop)
         self.downsample = downsample_kwargs(downsample)
+        self.clean = clean_kwargs(clean)
         self.normals = normals_kwargs(normals)
         self.augment, self.voxelize_fn = augment, voxelize_fn
 
     @property
     def targets_in_file_frame(self):
-        """crop, down-sample and augment each move the detector's frame: ScenePrefetcher(shift_targets=False) feeds `scene`"""
-        return self.crop is not None or self.downsample is not None or self.augment is not None
+        """crop, down-sample, clean and augment each move the detector's frame (the cloud's minimum):
+        ScenePrefetcher(shift_targets=False) feeds `scene`"""
+        return (self.crop is not None or self.downsample is not None or self.clean is not None or
+                self.augment is not None)
 
     def for_rank(self, rank, classes):
         """the same chain drawing with seed + 1000003 rank in `augment` (checked against the classes) and `crop`"""
@@ -57,6 +62,10 @@ class Preparation(object):
         pcl = apply_downsample(pcl, self.downsample, return_source=keep)
         if keep:
             pcl, source = pcl
+        pcl = apply_clean(pcl, self.clean, return_source=keep)
+        if keep:
+            pcl, cleaned = pcl
+            source = compose_sources(source, cleaned)
         kept = Kept(None if pcl is raw else pcl, source, pixels) if keep else None
         if self.normals is not None:
             pcl = with_normals(pcl, **self.normals)

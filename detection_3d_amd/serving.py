@@ -41,6 +41,9 @@ class BuildingPipeline(object):
     normals.  point_owner keeps one entry per row of the RAW cloud: the owner of the down-sampled point the row went
     into, -1 for a row that was dropped (position not finite) or capped away; "point_count" then counts the
     down-sampled points of each detection.
+    clean: None, or a dict of clean.clean_cloud keywords (radius, min_neighbors, statistical, min_component): outliers and
+    small detached components are removed on the slot's geometry stream after the down-sampling and before the normals.
+    point_owner still has one entry per row of the RAW cloud, -1 for a row that was cleaned away.
     unproject: None or a dict of unproject.unproject keywords (columns, step, min_depth, max_depth, edge, color_div) for
     the inputs that are unproject.DepthFrames: such an input becomes a cloud on its slot's geometry stream first, and
     the steps above follow as for a cloud ("raw cloud" then means the unprojected one).  With point_owner its result also
@@ -48,8 +51,8 @@ class BuildingPipeline(object):
     point_owner into the frames with it)."""
 
     def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None,
-                 unproject=None):
-        self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals)
+                 unproject=None, clean=None):
+        self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals, clean=clean)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
         self.device = device if device is not None else next(model.parameters()).device

@@ -169,6 +169,39 @@ int d3d_estimate_normals_phases(const float *xyz, int n, int row_stride_floats, 
                                 const float *viewpoint_host, float *normals, int32_t *counts, void *scratch,
                                 size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* Cleaning a raw scan before it is voxelised (the reference's users call open3d's remove_radius_outlier,
+ * remove_statistical_outlier and a clustering pass on the CPU; restatements that are not pinned against open3d itself).
+ * All three read xyz as d3d_estimate_normals does (fp32, row i at xyz + i * row_stride_floats), use its cell list and
+ * its distances: d2 = (dx dx + dy dy) + dz dz in fp32 from the fp32 offset p_j - p_i, "within radius" iff d2 <= radius *
+ * radius (fp32 product) by comparison of the bits, the point itself included.  0 <= n <= 2^28.  Asynchronous on `stream`,
+ * no host read-back, no float atomics, every sum in an order fixed by the data: the same input gives the same bits.
+ * scratch: the matching _scratch_bytes(n), linear in n and independent of the extent.  phase_ms_host: NULL, or [5] =
+ * milliseconds of the cell coordinates, the sorts, the cell table, the search and what follows it (events on `stream`;
+ * the call then synchronises).
+ *
+ * d3d_radius_neighbors: count[i] = the points within radius of point i (int32 [n], >= 1).                             */
+size_t d3d_radius_neighbors_scratch_bytes(int n);
+int d3d_radius_neighbors(const float *xyz, int n, int row_stride_floats, float radius, int32_t *count, void *scratch,
+                         size_t scratch_bytes, void *stream, float *phase_ms_host);
+/* d3d_knn_mean_distance: the candidates within radius are cut to the k + 1 smallest by (d2, j), the point itself (d2 = 0)
+ * among them; found[i] = the kept candidates - 1 (int32 [n]); mean[i] = (sum of sqrt(double(d2)) over the kept) / k in
+ * fp64 [n], or +inf for a sparse point (found < k).  stats (device, 2 doubles) = the mean of the finite mean[i] and the
+ * square root of their summed squared deviations / (count - 1): per block of 1024 rows the count, the sum and the squared
+ * deviations about the block's own mean, then one block adds the partials in block order (no finite value: (0, 0); one:
+ * deviation 0).  keep (uint8 [n] or NULL): 1 iff the point is not sparse and mean[i] <= stats[0] + std_ratio * stats[1].
+ * k >= 1.  n == 0 zeroes stats.                                                                                        */
+size_t d3d_knn_mean_distance_scratch_bytes(int n);
+int d3d_knn_mean_distance(const float *xyz, int n, int row_stride_floats, float radius, int k, double std_ratio,
+                          double *mean, int32_t *found, double *stats, uint8_t *keep, void *scratch,
+                          size_t scratch_bytes, void *stream, float *phase_ms_host);
+/* d3d_connected_components: the components of the graph whose edges join the points within radius of one another.
+ * label[i] = the smallest row index of i's component, size[i] = its number of points (int32 [n] each).  A lock-free
+ * union-find over the points in cell order (hooking by compare-and-swap on roots, the lower id wins; path halving), a
+ * flatten pass, then integer min and add per root: integers, so the order of arrival does not show.                   */
+size_t d3d_connected_components_scratch_bytes(int n);
+int d3d_connected_components(const float *xyz, int n, int row_stride_floats, float radius, int32_t *label, int32_t *size,
+                             void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* The points of each rotated box (Bbox3D.points_in_bbox, utils3d/bbox3d_ops.py:731-755; the counts of split_bbox,
  * data3d/indoor_data_util.py:244-254; the extents of crop_bbox_by_points, bbox3d_ops.py:873-878), without an [n, k] mask.
  * Point i = the first three floats of row xyz + i * row_stride_floats (>= 3: an [n, 9] cloud is read in place); with

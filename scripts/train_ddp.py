@@ -4,7 +4,7 @@ RCCL gradient all-reduce over xGMI; tools/train_net_sparse3d.py:52-57,170-177 + 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         scripts/train_ddp.py --config 3G6c_Fpn4321 --steps 20 [--data DIR | --scenes 8 --points 500000] [--ims-per-gpu 2]
         [--deterministic [--seed S]] [--bf16] [--bf16-heads] [--augment flip,rotate[=quarter|free],scale=Z,offset,...]
-        [--estimate-normals[=radius,max_nn]] [--downsample V[,MAX_POINTS]]
+        [--estimate-normals[=radius,max_nn]] [--downsample V[,MAX_POINTS]] [--clean SPEC]
 
 Every rank reads its own buildings (files[rank::world]) through scene_io.ScenePrefetcher, runs forward + backward (DDP
 all-reduces ~128 MB of fp32 gradients bucket by bucket during the backward pass; the never-used top-down modules are
@@ -62,11 +62,17 @@ def parse_args(argv=None):
                     help="reduce every raw building to one point per voxel of V metres on the GPU and, with MAX_POINTS, "
                          "to a random subset of at most that many (detection_3d_amd.downsample), before the normals; "
                          "the cap is seeded from --seed")
+    ap.add_argument("--clean", default=None, metavar="SPEC",
+                    help="remove outliers and small detached components of every building on the GPU after the "
+                         "down-sampling and before the normals (detection_3d_amd.clean): comma-separated radius=R, "
+                         "neighbors=M, statistical=K:RATIO, component=C (points, or a share with a decimal point)")
     args = ap.parse_args(argv)
+    from detection_3d_amd.clean import parse_clean
     from detection_3d_amd.downsample import parse_downsample
     from detection_3d_amd.normals import parse_estimate_normals
     args.normals = parse_estimate_normals(args.estimate_normals)
     args.downsample = parse_downsample(args.downsample)
+    args.clean = parse_clean(args.clean)
     if args.downsample is not None:
         args.downsample["seed"] = int(getattr(args, "seed", 0) or 0)
     return args
@@ -123,7 +129,7 @@ def main():
         model.head_dtype = torch.bfloat16
     out = engine.train(model, cfg, files, dev, args.steps, local_rank=local_rank, log_every=args.log_every,
                        ims_per_gpu=args.ims_per_gpu, augment=augment, normals=args.normals, crop=crop,
-                       downsample=args.downsample)
+                       downsample=args.downsample, clean=args.clean)
     if args.verify:
         # (1) the averaged-gradient steps leave every rank with the same weights (fingerprint: sum and sum of squares of
         # every parameter in fp64); (2) the sharded inference loop returns every scene's detections on rank 0
@@ -135,7 +141,8 @@ def main():
         fps = [torch.empty_like(fp) for _ in range(WORLD)]
         dist.all_gather(fps, fp)
         out["weights_equal"] = bool(all(torch.equal(fps[0], f) for f in fps))
-        res = engine.inference(model, cfg, files, dev, normals=args.normals, downsample=args.downsample)
+        res = engine.inference(model, cfg, files, dev, normals=args.normals, downsample=args.downsample,
+                               clean=args.clean)
         if rank == 0:
             dets, gts = res
             out["scenes_gathered"] = sorted(int(k) for k in dets)
@@ -144,7 +151,7 @@ def main():
     if rank == 0:
         out.update(config=args.config, n_gpus=WORLD, deterministic=args.deterministic, bf16=args.bf16,
                    bf16_heads=args.bf16_heads, augment=repr(augment) if augment is not None else None,
-                   normals=args.normals, downsample=args.downsample, crop=repr(crop) if crop is not None else None,
+                   normals=args.normals, downsample=args.downsample, clean=args.clean, crop=repr(crop) if crop is not None else None,
                    points_per_building=args.points if not args.data else None,
                    unit="buildings/s", metric="training buildings/sec (forward + backward + SGD, DDP)")
         print(json.dumps(out), flush=True)
