@@ -24,6 +24,15 @@ class BnPrologue(ctypes.Structure):
 bn_p = ctypes.POINTER(BnPrologue)
 
 
+class ConvDesc(ctypes.Structure):
+    """d3d_conv_desc (include/d3d_hip.h): one member of a grouped convolution call."""
+    _fields_ = [("kind", ctypes.c_int), ("in_size", ctypes.c_int * 3), ("out_size", ctypes.c_int * 3),
+                ("filter", ctypes.c_int * 3), ("stride", ctypes.c_int * 3), ("input", vp), ("cin", ctypes.c_int),
+                ("packed_w", vp), ("cout", ctypes.c_int), ("residual", vp), ("out", vp), ("dtype", ctypes.c_int),
+                ("macs_host", ctypes.POINTER(ctypes.c_double)), ("bn_host", bn_p), ("time_start", vp), ("time_stop", vp),
+                ("form", c_int_p)]
+
+
 class AugmentParams(ctypes.Structure):
     """d3d_augment_params (include/d3d_hip.h): one scene's augmentation, host memory."""
     _fields_ = [("m", ctypes.c_double * 9), ("nrm", ctypes.c_double * 9), ("color", ctypes.c_double * 3),
@@ -258,6 +267,7 @@ _SIGS = {
                                            vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_double), bn_p]),
     "d3d_deconv_forward_dt": (ctypes.c_int, [vp, c_int_p, c_int_p, c_int_p, c_int_p, vp, ctypes.c_int, vp, ctypes.c_int,
                                              vp, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_double), bn_p]),
+    "d3d_conv_group_forward": (ctypes.c_int, [vp, ctypes.POINTER(ConvDesc), ctypes.c_int, vp]),
     "d3d_conv_bf16_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_long]),
     "d3d_bn_stats_from_partials": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                                   vp, vp, vp, ctypes.c_size_t, vp]),

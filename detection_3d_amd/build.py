@@ -25,7 +25,8 @@ def build_library(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "d3d_internal.h"), os.path.join(HERE, "..", "include", "d3d_hip.h")]
+    headers = [os.path.join(CSRC, "d3d_internal.h"), os.path.join(CSRC, "conv_block.inc"),
+               os.path.join(HERE, "..", "include", "d3d_hip.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def compile_one(src):

@@ -10,6 +10,7 @@
 // stay in registers across all offsets; every output row is written exactly once (no atomics,
 // deterministic, independent of how rows are grouped).
 #include <algorithm>
+#include <climits>
 
 #include "d3d_internal.h"
 
@@ -74,326 +75,62 @@ __global__ __launch_bounds__(BPW *(COUT / 32 / NT) * 64) void k_conv(
     const uint32_t *__restrict__ blkmask, int n_blk, const float *__restrict__ residual,
     float *__restrict__ out, int n_split, float *__restrict__ partial, BnPre pre, uint32_t in_bytes,
     double *__restrict__ stat) {
-  constexpr int WPBLK = COUT / 32 / NT;
-  static_assert(WPBLK == 1 || BPW == 1, "row blocks sharing a workgroup must be single-wave");
-  constexpr int TPB = WPBLK * 64;  // threads working on one row block
-  constexpr int LDA = CT + 4;      // +4 dwords: conflict-free ds_read_b128 of 32 rows
-  constexpr int CP = CT * NCT;
-  constexpr int LPR = CT / 4;      // threads per gathered row (16 B each)
-  constexpr int RPP = TPB / LPR;   // rows per gather pass
-  constexpr int NIT = (32 / RPP) > 0 ? (32 / RPP) : 1;
-  constexpr int NQ = CT / 8;       // q-iterations (4 MFMAs per accumulator tile each) of a step
-  // weight fragments in flight (ring): 8 q-iterations = 2048 matrix cycles of lead (4: the 128 -> 128 family 0.91 ms per
-  // building against 0.89, 2: 0.95; D3D_QA at compile time)
-#ifndef D3D_QA
-#define D3D_QA 8
-#endif
-  constexpr int QA = NQ < D3D_QA ? NQ : D3D_QA;
-  static_assert(NQ % QA == 0, "ring depth must divide the q-iterations of a step");
-  __shared__ __attribute__((aligned(16))) float smem[BPW * 32 * LDA];
+  __shared__ __attribute__((aligned(16))) float smem[BPW * 32 * (CT + 4)];
+  const unsigned bx = blockIdx.x, by = blockIdx.y;
+#include "conv_block.inc"
+}
 
-  const int slot = threadIdx.x / TPB, tib = threadIdx.x % TPB;
-  const int blk = blockIdx.x * BPW + slot;
-  if (blk >= n_blk) return;  // BPW > 1 only when waves are independent (no barrier below)
-  float *As = smem + slot * 32 * LDA;
-  const int lane = tib & 63, wib = tib >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int grow = tib / LPR, gc4 = tib % LPR;
-  const int colbase = wib * NT * 32;
+// ---- grouped launches (d3d_conv_group_forward): independent convolutions that resolve to the same instantiation run as
+// ONE launch.  The members' kernel arguments travel as a table in the kernel argument segment; the grid is flat, member
+// i owns the workgroups [first[i], first[i + 1]) = its own (ceil(n_blk / BPW), n_split) grid in x-major order, and a
+// workgroup finds its member by a search over `first` (wave-uniform: the member's arguments stay in SGPRs), then runs
+// k_conv's body (conv_block.inc) with exactly the arguments the member's own k_conv launch would have had.
+struct ConvArgs {   // the arguments of one k_conv launch
+  const float *in, *wp;
+  const int32_t *nbrT, *rows;
+  const uint32_t *blkmask;
+  const float *residual;
+  float *out, *partial;
+  double *stat;
+  BnPre pre;
+  int cin, npos, n_blk, n_split;
+  uint32_t in_bytes;
+};
+static constexpr int kGroupCap = 8;   // members per launch (a 1.1 KiB table); longer groups take several launches
+struct ConvTable {
+  ConvArgs m[kGroupCap];
+  int first[kGroupCap + 1];   // prefix sums of the members' workgroup counts; INT_MAX behind the last member's end
+};
 
-  auto block_sync = [&]() {
-    if constexpr (WPBLK == 1)
-      wave_lds_sync();
-    else
-      __syncthreads();
-  };
-
-  // active offsets of the block; wave-uniform: keep it (and with it k, the weight / index base pointers and the loop
-  // control) in SGPRs
-  uint32_t mask = __builtin_amdgcn_readfirstlane(blkmask[blk]);
-  if (n_split > 1) {
-    // offset-split launch (few rows): this workgroup keeps every n_split-th active offset and
-    // writes a partial tile; k_conv_reduce sums the partials in a fixed order.
-    // by the offset's INDEX, not by its rank among the block's active offsets: which partial sum an offset of a row
-    // lands in then does not depend on the other rows of the block, so the result is independent of how rows are
-    // grouped into blocks (e.g. the same rows reached through plans of different builds)
-    uint32_t keep = 0;
-    for (uint32_t m = mask; m; m &= m - 1) {
-      const int kk = __builtin_ctz(m);
-      if (kk % n_split == (int)blockIdx.y) keep |= 1u << kk;
-    }
-    mask = keep;
-  }
-  const int rowid = rows[blk * 32 + r];
-  f32x16 acc[NT];
+template <int CT, int NCT, int COUT, int NT, int BPW, bool VEC, bool LATE>
+__global__ __launch_bounds__(BPW *(COUT / 32 / NT) * 64) void k_conv_group(const ConvTable t) {
+  __shared__ __attribute__((aligned(16))) float smem[BPW * 32 * (CT + 4)];
+  const int wg = (int)blockIdx.x;
+  int mi = 0;
 #pragma unroll
-  for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-    for (int i = 0; i < 16; i++) acc[nt][i] = 0.f;
-
-  const int32_t *nb = nbrT + (size_t)blk * 32;
-  // Gather of (offset k, Cin tile ct) in two independent waves of loads, both issued ahead of their use:
-  //   load_idx(k)   : the NIT input-row indices this thread needs for offset k   (one step before issue_data)
-  //   issue_data(ct): the 16-byte row pieces, branch-free -- an absent neighbour reads row 0 and is zeroed
-  //                   at commit time, so that no load waits for another one
-  //   commit_gather : registers -> LDS (+ the fused BatchNorm), after the previous step's MFMAs
-  int idx[NIT];
-  f32x4 stage[NIT];
-  float mreal[NIT];  // 1.f for a real row, 0.f for an absent one
-  int stage_ct = 0;
-  // optional fused BatchNorm + leaky ReLU of the producer layer (y = leaky(fma(x, w, b)), applied to real rows
-  // only: a missing neighbour contributes zeros, as a zero row of the normalised tensor would not);
-  // this thread always gathers the same 4 channels of a Cin tile, so w and b are fetched once
-  f32x4 bnw[NCT], bnb[NCT];
-#pragma unroll
-  for (int t = 0; t < NCT; t++) {
-    bnw[t] = {1.f, 1.f, 1.f, 1.f};
-    bnb[t] = {0.f, 0.f, 0.f, 0.f};
-    if (pre.mean) {
-      const int c = t * CT + gc4 * 4;
-      const f32x4 is = *(const f32x4 *)(pre.invstd + c), mu = *(const f32x4 *)(pre.mean + c);
-      const f32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 ga = pre.weight ? *(const f32x4 *)(pre.weight + c) : one;
-      const f32x4 be = pre.bias ? *(const f32x4 *)(pre.bias + c) : zero;
-      bnw[t] = is * ga;
-      bnb[t] = -mu * bnw[t] + be;
-    }
-  }
-  const uint32_t lane_piece = (uint32_t)gc4 * 16u, lane_idx = (uint32_t)grow * 4u;
-  // The gathered tensor as a raw buffer of in_bytes: a row piece of an ABSENT neighbour is requested at an offset past
-  // the end, which the hardware range check answers with zeros -- no branch, no select, and nothing of a real row
-  // (row 0 used to stand in, and its NaN or Inf would have spread through the 0 * x of the commit) reaches the tile.
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)in, 0, (int)in_bytes, 0x00020000);
-  auto load_idx = [&](int k) {
-    const char *kb = (const char *)(nb + (size_t)k * npos);  // wave-uniform
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-      if constexpr (RPP <= 32) {
-        idx[it] = *(const int32_t *)(kb + (lane_idx + (uint32_t)(it * RPP * 4)));
-      } else {  // a pass wider than the block (tiny Cin tile, many waves): threads past row 31 idle
-        idx[it] = grow < 32 ? *(const int32_t *)(kb + lane_idx) : -1;
-      }
-    }
-  };
-  auto issue_data = [&](int ct) {
-    stage_ct = ct;
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-      const int s = idx[it];
-      mreal[it] = s >= 0 ? 1.f : 0.f;
-      if constexpr (VEC) {
-        // rows are CP * 4 bytes (< 4 GiB tensor); 0xfffffff0 + 16 exceeds any buffer size
-        const uint32_t off = s < 0 ? 0xfffffff0u : (uint32_t)s * (uint32_t)(CP * 4) + (uint32_t)(ct * CT * 4) + lane_piece;
-        stage[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)off, 0, 0));
-      } else {
-        const float *p = in + (size_t)(s < 0 ? 0 : s) * cin + ct * CT + gc4 * 4;
-        const int c = ct * CT + gc4 * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (c + 0 < cin) v[0] = p[0];
-        if (c + 1 < cin) v[1] = p[1];
-        if (c + 2 < cin) v[2] = p[2];
-        if (c + 3 < cin) v[3] = p[3];
-        stage[it] = v;
-      }
-    }
-  };
-  auto commit_gather = [&]() {
-    const f32x4 bw = stage_ct == 0 ? bnw[0] : bnw[NCT - 1], bb = stage_ct == 0 ? bnb[0] : bnb[NCT - 1];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-      const int row = it * RPP + grow;
-      f32x4 v = stage[it];
-      if constexpr (VEC) {
-        // an absent row arrived as zeros; only the fused BatchNorm turns them into leaky(beta'), which the row's
-        // multiplier (0 or 1, one VALU instruction per 2 elements) takes out again -- finite times 0
-        if (pre.mean) v = bn_act(v, bw, bb, pre.leak) * mreal[it];
-      } else {
-        if (pre.mean) v = bn_act(v, bw, bb, pre.leak);
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        v = mreal[it] != 0.f ? v : zero;     // a select: row 0 stood in for the absent neighbour
-      }
-      if (row < 32) *(f32x4 *)(As + row * LDA + gc4 * 4) = v;
-    }
-  };
-
-  // step tokens: (offset k, Cin tile ct) in increasing (k, ct) order over the active offsets
-  auto next_k = [&](int k) -> int {
-    const uint32_t m = k >= 31 ? 0u : (mask & ~((2u << k) - 1u));
-    return m ? __builtin_ctz(m) : -1;
-  };
-  int k = mask ? __builtin_ctz(mask) : -1;
-  int ct = 0;
-  // weight fragments (packed weights, L2-resident, shared by every block) come through a ring of QA q-iterations
-  // in flight that runs across step boundaries: the last QA refills of a step fetch the first fragments of the
-  // next one (the compiler alone keeps only ~1 load ahead)
-  f32x4 ring[QA][NT];
-  const uint32_t lane_b = (uint32_t)(h * COUT + r) * 16u;   // this lane's byte offset inside a weight fragment row
-  if (k >= 0) {
-    load_idx(k);
-    issue_data(0);
-    const int k_after = NCT > 1 ? k : next_k(k);   // indices of the step after this one
-    if (k_after >= 0 && k_after != k) load_idx(k_after);
-    const char *wk0 = (const char *)(wp + ((size_t)(k * (CP / 4)) * COUT + colbase) * 4);
-#pragma unroll
-    for (int q = 0; q < QA; q++)
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++)
-        ring[q][nt] = *(const f32x4 *)(wk0 + (lane_b + (uint32_t)((2 * q * COUT + nt * 32) * 16)));
-  }
-  while (k >= 0) {
-    commit_gather();
-    block_sync();
-    // next (offset, tile) step
-    int nk = k, nct = ct + 1;
-    if (nct == NCT) {
-      nct = 0;
-      nk = next_k(k);
-    }
-    const int k2 = nk < 0 ? -1 : ((nct + 1 < NCT) ? nk : next_k(nk));   // the step after that: its indices are requested now
-    if constexpr (!LATE) {
-      if (nk >= 0) {
-        issue_data(nct);  // loads fly while the matrix cores work; idx holds offset nk
-        if (k2 >= 0 && k2 != nk) load_idx(k2);
-      }
-    }
-    __builtin_amdgcn_s_setprio(1);
-    // ---- 32 x (NT*32) += A[32 x CT] * W[k][CT x cols] ----
-    const char *wk = (const char *)(wp + ((size_t)(k * (CP / 4) + ct * (CT / 4)) * COUT + colbase) * 4);
-    const char *wk_next = nk >= 0 ? (const char *)(wp + ((size_t)(nk * (CP / 4) + nct * (CT / 4)) * COUT + colbase) * 4) : wk;
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      f32x4 b[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) b[nt] = ring[q % QA][nt];
-      {
-        const char *src = (q + QA < NQ) ? wk : wk_next;   // wave-uniform base + per-lane byte offset
-        const int qq = (q + QA) % NQ;
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-          ring[q % QA][nt] = *(const f32x4 *)(src + (lane_b + (uint32_t)((2 * qq * COUT + nt * 32) * 16)));
-      }
-      const f32x4 a = *(const f32x4 *)(As + r * LDA + q * 8 + h * 4);
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) {
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], b[nt][0], acc[nt], 0, 0, 0);
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], b[nt][1], acc[nt], 0, 0, 0);
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b[nt][2], acc[nt], 0, 0, 0);
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], b[nt][3], acc[nt], 0, 0, 0);
-      }
-      if constexpr (LATE) {
-        if (q == 0) {
-          // branch-free: without a next step the rows asked for are absent ones (zeros from the range check, never
-          // committed), and the index loads repeat offset k's
-          if (nk < 0) {
-#pragma unroll
-            for (int it = 0; it < NIT; it++) idx[it] = -1;
-          }
-          issue_data(nk >= 0 ? nct : 0);
-          load_idx(k2 >= 0 ? k2 : k);
-        }
-      }
-    }
-    // order of the step's instruction stream: the gather / index loads up front, then per q-iteration one MFMA,
-    // one LDS read (A of the next iteration), one weight load (ring refill QA iterations ahead), the other MFMAs
-    if constexpr (!LATE) {
-      __builtin_amdgcn_sched_group_barrier(0x020, 2 * NIT, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-      for (int q = 0; q < NQ; q++) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT - 1, 0);
-      }
-    } else {
-      // LATE: A of q = 0, its first MFMA, A of q = 1, the ring refill, the other MFMAs of q = 0, THEN the gather and
-      // index loads, then the remaining q-iterations as above
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-      for (int q = 0; q < NQ; q++) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT - 1, 0);
-        if (q == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2 * NIT, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    block_sync();
-    k = nk;
-    ct = nct;
-  }
-  // ---- epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) ----
-  if (n_split > 1) {
-    float *pt = partial + ((size_t)blockIdx.y * npos + (size_t)blk * 32) * COUT;
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-      const int row_in = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) pt[(size_t)row_in * COUT + colbase + nt * 32 + r] = acc[nt][reg];
-    }
-    return;
-  }
-  // four rows at a time: residual reads first (a padded row reads row 0 and is dropped), then adds and stores --
-  // no load waits for another, and the epilogue does not set the kernel's register budget
-  // `stat`: column sums and sums of squares (fp64) of the block's real rows, as they are stored -- the statistics of the
-  // BatchNorm that follows are then a fixed-order sum of n_blk small vectors instead of a second pass over the tensor
-  double cs[NT], css[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; nt++) cs[nt] = css[nt] = 0.0;
-#pragma unroll
-  for (int g4 = 0; g4 < 4; g4++) {
-    int orow[4];
-    float res[4][NT];
-#pragma unroll
-    for (int j = 0; j < 4; j++) orow[j] = __shfl(rowid, j + 8 * g4 + 4 * h, 64);
-    if (residual) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-          res[j][nt] = residual[(size_t)(orow[j] < 0 ? 0 : orow[j]) * COUT + colbase + nt * 32 + r];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) acc[nt][g4 * 4 + j] += res[j][nt];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (orow[j] < 0) continue;
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) out[(size_t)orow[j] * COUT + colbase + nt * 32 + r] = acc[nt][g4 * 4 + j];
-      if (stat) {
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) {
-          const double d = (double)acc[nt][g4 * 4 + j];
-          cs[nt] += d;
-          css[nt] += d * d;
-        }
-      }
-    }
-  }
-  if (stat) {   // rows 0-3, 8-11, .. live in lanes 0-31, the others in lanes 32-63: both halves form the same sum
-    double *sp = stat + (size_t)blk * (2 * COUT);
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) {
-      const double a = cs[nt] + __shfl_xor(cs[nt], 32, 64), b = css[nt] + __shfl_xor(css[nt], 32, 64);
-      if (h == 0) {
-        sp[colbase + nt * 32 + r] = a;
-        sp[COUT + colbase + nt * 32 + r] = b;
-      }
-    }
-  }
+  for (int i = 1; i < kGroupCap; i++) mi += wg >= t.first[i] ? 1 : 0;   // first[] never decreases
+  const ConvArgs &a = t.m[mi];
+  const float *__restrict__ in = a.in, *__restrict__ wp = a.wp, *__restrict__ residual = a.residual;
+  const int32_t *__restrict__ nbrT = a.nbrT, *__restrict__ rows = a.rows;
+  const uint32_t *__restrict__ blkmask = a.blkmask;
+  float *__restrict__ out = a.out, *__restrict__ partial = a.partial;
+  double *__restrict__ stat = a.stat;
+  const BnPre pre = a.pre;
+  const int cin = a.cin, npos = a.npos, n_blk = a.n_blk, n_split = a.n_split;
+  const uint32_t in_bytes = a.in_bytes;
+  const unsigned local = (unsigned)(wg - t.first[mi]), gx = (unsigned)((n_blk + BPW - 1) / BPW);
+  const unsigned by = local / gx, bx = local - by * gx;
+#include "conv_block.inc"
 }
 
 // out[rows[pos]] = sum_y partial[y][pos] (+ residual), y in increasing order.  `stat` (may be null): per-workgroup column
 // sums / sums of squares of the rows it wrote, [gridDim.x][2 * cout] (see k_conv); a workgroup covers 1024 / cout rows.
-__global__ __launch_bounds__(256) void k_conv_reduce(const float *__restrict__ partial, int n_split,
-                                                     int npos, int cout4, const int32_t *__restrict__ rows,
-                                                     const float *__restrict__ residual,
-                                                     float *__restrict__ out, double *__restrict__ stat) {
-  __shared__ double red[2][256][4];
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+// conv_reduce_block: workgroup bx of the member's own grid (blockIdx.x of k_conv_reduce); red = the kernel's 16 KiB of LDS.
+__device__ __forceinline__ void conv_reduce_block(double (*red)[256][4], const unsigned bx,
+                                                  const float *__restrict__ partial, int n_split, int npos, int cout4,
+                                                  const int32_t *__restrict__ rows, const float *__restrict__ residual,
+                                                  float *__restrict__ out, double *__restrict__ stat) {
+  const long t = (long)bx * blockDim.x + threadIdx.x;
   const bool in_range = t < (long)npos * cout4;
   const int pos = in_range ? (int)(t / cout4) : 0, c4 = (int)(t % cout4);
   const int orow = in_range ? rows[pos] : -1;
@@ -413,7 +150,7 @@ __global__ __launch_bounds__(256) void k_conv_reduce(const float *__restrict__ p
   }
   __syncthreads();
   if ((int)threadIdx.x < cout4) {   // (256 is a multiple of cout4: thread c4 of the first row owns channel group c4)
-    double *sp = stat + (size_t)blockIdx.x * (8 * cout4);
+    double *sp = stat + (size_t)bx * (8 * cout4);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       double a = 0.0, b = 0.0;
@@ -425,6 +162,39 @@ __global__ __launch_bounds__(256) void k_conv_reduce(const float *__restrict__ p
       sp[4 * cout4 + c4 * 4 + j] = b;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_conv_reduce(const float *__restrict__ partial, int n_split,
+                                                     int npos, int cout4, const int32_t *__restrict__ rows,
+                                                     const float *__restrict__ residual,
+                                                     float *__restrict__ out, double *__restrict__ stat) {
+  __shared__ double red[2][256][4];
+  conv_reduce_block(red, blockIdx.x, partial, n_split, npos, cout4, rows, residual, out, stat);
+}
+
+// the reductions of a group's offset-split members as one launch: the table idea of k_conv_group
+struct ReduceArgs {   // the arguments of one k_conv_reduce launch
+  const float *partial;
+  const int32_t *rows;
+  const float *residual;
+  float *out;
+  double *stat;
+  int n_split, npos, cout4;
+};
+struct ReduceTable {
+  ReduceArgs m[kGroupCap];
+  int first[kGroupCap + 1];
+};
+
+__global__ __launch_bounds__(256) void k_conv_reduce_group(const ReduceTable t) {
+  __shared__ double red[2][256][4];
+  const int wg = (int)blockIdx.x;
+  int mi = 0;
+#pragma unroll
+  for (int i = 1; i < kGroupCap; i++) mi += wg >= t.first[i] ? 1 : 0;
+  const ReduceArgs &a = t.m[mi];
+  conv_reduce_block(red, (unsigned)(wg - t.first[mi]), a.partial, a.n_split, a.npos, a.cout4, a.rows, a.residual, a.out,
+                    a.stat);
 }
 
 static constexpr int kSplitTargetWaves = 4096;  // below this many waves the launch is offset-split
@@ -464,6 +234,93 @@ struct StatOut {   // d3d_bn_prologue.out_stats*: where the launch leaves the co
   int *rows_host;
 };
 
+// ---- a group being collected (d3d_conv_group_forward): launch_t parks the launches it would have made here, and
+// conv_group_flush issues them, one k_conv_group per instantiation and kGroupCap members, then one k_conv_reduce_group
+typedef void (*GroupLaunchFn)(int variant, const ConvTable &t, unsigned blocks, hipStream_t s);
+struct PendingConv {
+  ConvArgs a;
+  GroupLaunchFn fn;      // launches the member's instantiation family ...
+  int variant;           // ... 0: plain gather, 1: VEC, 2: VEC + LATE
+  int bpw, cout;         // BPW and COUT of the instantiation
+  double *reduce_stat;   // the column statistics of an offset-split member come from its reduction
+};
+static constexpr int kMaxGroup = 32;   // launches parked at a time (d3d_conv_group_forward flushes when full)
+struct ConvGroup {
+  PendingConv conv[kMaxGroup];
+  int n = 0;
+  bool holds_partials = false;
+  size_t mark = 0;    // feat_arena.used in front of the group's first partial buffer
+};
+static thread_local ConvGroup *t_group = nullptr;
+
+// prefix sums of the workgroup counts of a table's n members -> first[]; returns the total
+template <typename Table, typename Count>
+static unsigned group_prefix(Table &t, int n, Count count) {
+  long total = 0;
+  for (int i = 0; i <= kGroupCap; i++) {
+    t.first[i] = i <= n ? (int)total : INT_MAX;
+    if (i < n) total += count(i);
+  }
+  return (unsigned)total;
+}
+
+static int conv_group_flush(d3d_meta *m, hipStream_t s) {
+  ConvGroup *g = t_group;
+  if (!g || g->n == 0) return D3D_OK;
+  bool done[kMaxGroup] = {};
+  for (int i = 0; i < g->n; i++) {
+    if (done[i]) continue;
+    // the members of member i's instantiation, in table order, kGroupCap at a time
+    ConvTable t;
+    int n = 0;
+    for (int j = i; j <= g->n; j++) {
+      const bool same = j < g->n && !done[j] && g->conv[j].fn == g->conv[i].fn && g->conv[j].variant == g->conv[i].variant;
+      if (same) {
+        t.m[n++] = g->conv[j].a;
+        done[j] = true;
+      }
+      if (n == kGroupCap || (j == g->n && n > 0)) {
+        const ConvTable &tc = t;
+        const unsigned blocks = group_prefix(t, n, [&](int q) {
+          return (long)((tc.m[q].n_blk + g->conv[i].bpw - 1) / g->conv[i].bpw) * tc.m[q].n_split;
+        });
+        g->conv[i].fn(g->conv[i].variant, t, blocks, s);
+        n = 0;
+      }
+    }
+  }
+  ReduceTable r;
+  int n = 0;
+  for (int j = 0; j <= g->n; j++) {
+    if (j < g->n && g->conv[j].a.n_split > 1) {
+      const ConvArgs &a = g->conv[j].a;
+      r.m[n++] = {a.partial, a.rows, a.residual, a.out, g->conv[j].reduce_stat, a.n_split, a.npos, g->conv[j].cout / 4};
+    }
+    if (n == kGroupCap || (j == g->n && n > 0)) {
+      const ReduceTable &rc = r;
+      const unsigned blocks = group_prefix(r, n, [&](int q) { return ((long)rc.m[q].npos * rc.m[q].cout4 + 255) / 256; });
+      hipLaunchKernelGGL(k_conv_reduce_group, dim3(blocks), dim3(256), 0, s, r);
+      n = 0;
+    }
+  }
+  if (g->holds_partials) m->feat_arena.used = g->mark;  // stream-ordered scratch
+  g->n = 0;
+  g->holds_partials = false;
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+template <int CT, int NCT, int COUT, int NT, int BPW>
+static void launch_group_t(int variant, const ConvTable &t, unsigned blocks, hipStream_t s) {
+  constexpr int threads = BPW * (COUT / 32 / NT) * 64;
+  if (variant == 2)
+    hipLaunchKernelGGL((k_conv_group<CT, NCT, COUT, NT, BPW, true, true>), dim3(blocks), dim3(threads), 0, s, t);
+  else if (variant == 1)
+    hipLaunchKernelGGL((k_conv_group<CT, NCT, COUT, NT, BPW, true, false>), dim3(blocks), dim3(threads), 0, s, t);
+  else
+    hipLaunchKernelGGL((k_conv_group<CT, NCT, COUT, NT, BPW, false, false>), dim3(blocks), dim3(threads), 0, s, t);
+}
+
 template <int CT, int NCT, int COUT, int NT, int BPW>
 static int launch_t(d3d_meta *m, const Plan &p, const float *in, int cin, const float *wp,
                     const float *residual, float *out, hipStream_t s, BnPre pre, const StatOut &so) {
@@ -471,12 +328,21 @@ static int launch_t(d3d_meta *m, const Plan &p, const float *in, int cin, const 
   constexpr int threads = BPW * WPBLK * 64;
   const int npos = p.n_blk * 32;
   const long waves = (long)p.n_blk * WPBLK;
+  ConvGroup *grp = t_group;   // collecting a group: the launch is parked, not made
   int n_split = conv_n_split(BPW == 1 && m, p.K, waves, kSplitTargetWaves);
   float *partial = nullptr;
   size_t mark = 0;
   if (n_split > 1) {
     mark = m->feat_arena.used;
     partial = m->feat_arena.get<float>((size_t)n_split * npos * COUT);
+    if (!partial && grp && grp->holds_partials) {
+      // the partial buffers of the members parked so far are in the way: launch those first, so that this member splits
+      // exactly where its own call would have
+      const int rc = conv_group_flush(m, s);
+      if (rc) return rc;
+      mark = m->feat_arena.used;
+      partial = m->feat_arena.get<float>((size_t)n_split * npos * COUT);
+    }
     if (!partial) n_split = 1;  // no room: fall back to the unsplit launch
   }
   const dim3 grid((p.n_blk + BPW - 1) / BPW, n_split);
@@ -495,6 +361,21 @@ static int launch_t(d3d_meta *m, const Plan &p, const float *in, int cin, const 
     // (taken by the weight-sharing kernel: same products in the same order; it records its form)
   } else {
     conv_record_form(kFormConv, CT, NCT, COUT, BPW, 1, vec, late, n_split, stat != nullptr, p.n_blk, p.K);
+    if (grp) {
+      if (partial && !grp->holds_partials) {
+        grp->holds_partials = true;
+        grp->mark = mark;
+      }
+      PendingConv &pc = grp->conv[grp->n++];
+      pc.a = {in, wp, p.nbrT, p.rows, p.blkmask, residual, out, partial, n_split > 1 ? nullptr : stat, pre,
+              cin, npos, p.n_blk, n_split, in_bytes};
+      pc.fn = launch_group_t<CT, NCT, COUT, NT, BPW>;
+      pc.variant = late ? 2 : (vec ? 1 : 0);
+      pc.bpw = BPW;
+      pc.cout = COUT;
+      pc.reduce_stat = n_split > 1 ? stat : nullptr;
+      return D3D_OK;
+    }
     if (late)
       hipLaunchKernelGGL((k_conv<CT, NCT, COUT, NT, BPW, true, true>), grid, dim3(threads), 0, s, in, cin, wp, p.nbrT,
                          npos, p.rows, p.blkmask, p.n_blk, residual, out, n_split, partial, pre, in_bytes,
@@ -745,6 +626,71 @@ int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, 
     *macs_host = (double)nr * cin * cout;
   }
   return launch_conv_dt(m, *p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
+}
+
+// One call for n independent convolutions (no member reads what another writes): every member that resolves to the same
+// k_conv instantiation runs in one k_conv_group launch, the reductions of the offset-split members in one
+// k_conv_reduce_group launch.  What does not resolve to k_conv (the weight-sharing kernel, bf16 rows, bf16x3 products)
+// and every member that carries timing events runs at once, as its own call would.
+int d3d_conv_group_forward(d3d_meta *m, const d3d_conv_desc *descs, int n, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && n >= 0 && (descs || n == 0), "conv_group_forward: bad arguments");
+  D3D_REQUIRE(!t_group, "conv_group_forward: a group is already being collected on this thread");
+  // every plan first: building a rulebook takes scratch where the partial buffers of parked members live
+  for (int i = 0; i < n; i++) {
+    const d3d_conv_desc &d = descs[i];
+    D3D_REQUIRE(d.kind >= 0 && d.kind <= 2, "conv_group_forward: member %d has kind %d (0, 1 or 2)", i, d.kind);
+    D3D_REQUIRE(d.dtype == D3D_F32 || d.dtype == D3D_BF16 || d.dtype == D3D_F32_X3, "conv_group_forward: member %d: bad dtype", i);
+    const Plan *p = nullptr;
+    int rc = D3D_OK;
+    if (d.kind == 0) {
+      rc = d3d_subm_prepare(m, d.in_size, d.filter, stream, nullptr);
+      if (!rc) p = find_plan(m, 0, d.in_size, d.filter, nullptr);
+    } else if (d.kind == 1) {
+      rc = d3d_conv_prepare(m, d.in_size, d.out_size, d.filter, d.stride, stream, nullptr, nullptr);
+      if (!rc) p = find_plan(m, 1, d.in_size, d.filter, d.stride);
+    } else {
+      rc = get_deconv_plan(m, d.out_size, d.filter, d.stride, s, &p);
+    }
+    if (rc) return rc;
+    D3D_REQUIRE(p, "conv_group_forward: member %d has no plan", i);
+    if (d.macs_host) {
+      long nr;
+      rc = plan_rules(m, *const_cast<Plan *>(p), s, &nr);
+      if (rc) return rc;
+      *d.macs_host = (double)nr * d.cin * d.cout;
+    }
+  }
+  ConvGroup g;
+  int rc = D3D_OK;
+  for (int i = 0; i < n && !rc; i++) {
+    const d3d_conv_desc &d = descs[i];
+    const Plan *p = nullptr;
+    if (d.kind == 2)
+      rc = get_deconv_plan(m, d.out_size, d.filter, d.stride, s, &p);
+    else
+      p = find_plan(m, d.kind, d.in_size, d.filter, d.kind == 1 ? d.stride : nullptr);
+    if (rc) break;
+    t_group = &g;
+    if (g.n == kMaxGroup) rc = conv_group_flush(m, s);
+    if (rc) break;
+    if (d.time_start || d.time_stop) {   // measured: its events bracket a k_conv launch of its own
+      t_group = nullptr;
+      t_time_start = (hipEvent_t)d.time_start;
+      t_time_stop = (hipEvent_t)d.time_stop;
+    }
+    std::fill(t_last_form, t_last_form + kFormFields, 0);
+    rc = launch_conv_dt(m, *p, d.in, d.cin, d.packed_w, d.cout, d.kind == 1 ? nullptr : d.residual, d.out, s, d.bn_host, d.dtype);
+    if (d.form) std::copy(t_last_form, t_last_form + kFormFields, d.form);
+  }
+  t_group = &g;
+  if (!rc) {
+    rc = conv_group_flush(m, s);
+  } else if (g.holds_partials) {
+    m->feat_arena.used = g.mark;
+  }
+  t_group = nullptr;
+  return rc;
 }
 
 }  // extern "C"

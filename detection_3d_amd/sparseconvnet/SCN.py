@@ -461,6 +461,12 @@ def InputLayer_updateOutput(m, spatial_size, input_coords, input_features, outpu
 def _bn_struct(bn, stats=None):
     """bn = (mean, invstd, weight, bias, leakiness) device tensors and / or stats = (fp64 [cap, 2 Cout] tensor, c_int
     that receives the rows written) -> d3d_bn_prologue (kept alive by caller)."""
+    st = _bn_object(bn, stats)
+    return None if st is None else ctypes.byref(st)
+
+
+def _bn_object(bn, stats=None):
+    """as _bn_struct -> the _lib.BnPrologue itself (or None)"""
     if bn is None and stats is None:
         return None
     st = _lib.BnPrologue()
@@ -473,7 +479,7 @@ def _bn_struct(bn, stats=None):
     if stats is not None:
         st.out_stats, st.out_stats_cap = stats[0].data_ptr(), stats[0].shape[0]
         st.out_stats_rows = ctypes.pointer(stats[1])
-    return ctypes.byref(st)
+    return st
 
 
 def _stats_arg(stats, n_out, cout, out):
@@ -643,6 +649,66 @@ def Deconvolution_updateOutput(input_size, output_size, filter_size, filter_stri
     if prof is not None:
         prof.end(t0, "deconv", fv, cin, cout, input_features.shape[0], n, macs.value, dt)
     return macs.value
+
+
+_CONV_KINDS = ("subm", "conv", "deconv")
+
+
+def conv_group_forward(m, members, forms=None):
+    """Independent convolutions of one metadata in one library call (d3d_conv_group_forward): the members that run the
+    same fp32 kernel instantiation share a launch, bit-identical to the *_updateOutput calls made one by one.
+    members: (kind, in_size, out_size, filter_size, filter_stride, input_features, weight, packed, residual, bn, stats)
+    with kind 0 submanifold (out_size, filter_stride ignored), 1 strided convolution (residual ignored),
+    2 deconvolution; the other entries as the *_updateOutput functions take them.  -> the output tensors, all of them
+    allocated before the first launch.  forms: None, or a list that receives each member's d3d_conv_last_form fields.
+    The profiler sees every member as a call of its own: a member it times runs as a launch of its own."""
+    n = len(members)
+    descs = (_lib.ConvDesc * max(n, 1))()
+    outs, keep, ends = [], [], []
+    prof = PROFILER
+    want_macs = (prof is not None and prof.learn) or COUNT_MACS
+    for d, (kind, in_size, out_size, filter_size, filter_stride, feats, weight, packed, residual, bn, stats) in zip(descs, members):
+        require_gpu(feats, weight, residual)
+        fv, cin, cout, packed, dt = _conv_common(weight, packed, feats)
+        isz, filt = _size3(in_size), _size3(filter_size)
+        osz, st = (isz, (1, 1, 1)) if kind == 0 else (_size3(out_size), _size3(filter_stride))
+        if kind == 1:
+            n_out = ctypes.c_int(0)
+            check(lib().d3d_conv_prepare(m._h, ints(isz), ints(osz), ints(filt), ints(st), stream_of(),
+                                         ctypes.byref(n_out), None))
+            n_out = n_out.value
+        else:
+            n_out = m.getNActive(osz)
+        out = feats.new_empty((n_out, cout))
+        d.kind, d.in_size, d.out_size, d.filter, d.stride = kind, isz, osz, filt, st
+        d.input, d.cin, d.packed_w, d.cout, d.dtype = feats.data_ptr(), cin, packed.data_ptr(), cout, dt
+        d.residual = residual.data_ptr() if (residual is not None and kind != 1) else None
+        d.out = out.data_ptr()
+        macs = ctypes.c_double(0)
+        if want_macs:
+            d.macs_host = ctypes.pointer(macs)
+        bn_obj = _bn_object(bn, _stats_arg(stats, n_out, cout, out))
+        if bn_obj is not None:
+            d.bn_host = ctypes.pointer(bn_obj)
+        pair = None
+        if prof is not None:
+            name = _CONV_KINDS[kind]
+            if prof.wants(name, fv, cin, cout):
+                pair = (prof._event(), prof._event())
+                d.time_start, d.time_stop = pair[0].cuda_event, pair[1].cuda_event
+            ends.append((pair, name, fv, cin, cout, feats.shape[0], n_out, macs, dt))
+        if forms is not None:
+            form = (ctypes.c_int * 12)()
+            d.form = ctypes.cast(form, _lib.c_int_p)
+            forms.append(form)
+        outs.append(out)
+        keep.append((packed, bn_obj, macs, residual))
+    check(lib().d3d_conv_group_forward(m._h, descs, n, stream_of()))
+    for pair, name, fv, cin, cout, rows_in, rows_out, macs, dt in ends:
+        prof.end(pair, name, fv, cin, cout, rows_in, rows_out, macs.value, dt)
+    if forms is not None:
+        forms[:] = [list(f) for f in forms]
+    return outs
 
 
 def BatchNormalization_updateOutput(input_features, output_features, saveMean, saveInvStd, runningMean,

@@ -26,6 +26,11 @@ _GEO_STREAMS = {}   # (device, caller's stream) -> side streams
 # priority buys nothing where it works and costs 8 % where the queue scheduler lets the geometry kernels hold back the
 # caller's stream
 _SIDE_PRIORITY = int(os.environ.get("D3D_SIDE_PRIORITY", "0"))
+# fp32 inference with fuse_adds on the GPU: the convolutions of the top-down path that do not depend on one another --
+# the lateral 1x1x1 shortcuts, the merged maps, the 2-D projections -- run as three grouped calls (scn.conv_group) around
+# the chain BatchNorm statistics -> deconvolution, instead of in line between its links.  Same kernels' bodies on the same
+# data (bit-identical); D3D_CONV_GROUP=0 restores the one-by-one order (A/B runs).
+GROUP_CONVS = os.environ.get("D3D_CONV_GROUP", "1") != "0"
 
 
 def _is_gpu_input(net0):
@@ -428,6 +433,9 @@ class FPN_Net(torch.nn.Module):
         if lane is not None:
             lane(n_scales)
         _tmark("down path done")
+        if (GROUP_CONVS and self.fuse_adds and not self.training and not torch.is_grad_enabled()
+                and net.features.is_cuda and net.features.dtype == torch.float32):
+            return self._top_down_grouped(net, downs)
         net = self.m_shortcuts[-1](net)
         ups = [net]
         needed = max(self.fpn_scales_from_top + self.roi_scales_from_top) if self.skip_unused else n_scales - 1
@@ -448,6 +456,46 @@ class FPN_Net(torch.nn.Module):
         selected_2d = {i - len(rpn_maps_3d) for i in self.rpn_3d_2d_selector if i >= len(rpn_maps_3d)}
         rpn_maps_2d = [self.convs_pro2d[i](rpn_maps_3d[i]) if (i in selected_2d or not self.skip_unused) else None
                        for i in range(len(rpn_maps_3d))]
+        rpn_maps = rpn_maps_3d + rpn_maps_2d
+        rpn_maps = [rpn_maps[i] for i in self.rpn_3d_2d_selector]
+        roi_maps = [ups[i] for i in self.roi_scales_from_top]
+        for i in range(len(rpn_maps_3d)):
+            assert rpn_maps_3d[i].spatial_size.tolist() == [int(v) for v in self.rpn_map_sizes[i]]
+        converted = {}
+        return self._from_compute(rpn_maps, converted), self._from_compute(roi_maps, converted)
+
+    def _top_down_grouped(self, net, downs):
+        """The top-down path of forward_fpn with its independent convolutions grouped: one call for every needed
+        shortcut, the dependent chain (statistics -> deconvolution with the level's shortcut as residual) with nothing in
+        between, one call for the needed merged maps, one for the needed 2-D projections.  Returns what forward_fpn
+        returns, bit for bit."""
+        n_scales = len(self.m_downs)
+        needed = max(self.fpn_scales_from_top + self.roi_scales_from_top) if self.skip_unused else n_scales - 1
+        consumed = set(self.fpn_scales_from_top) | set(self.roi_scales_from_top)
+        levels = min(n_scales - 1, needed)
+        # the top shortcut feeds a BatchNorm (it keeps its column statistics), the others are residuals only
+        laterals = scn.conv_group([(self.m_shortcuts[-1], net, None)]
+                                  + [(self.m_shortcuts[n_scales - 2 - k], downs[n_scales - 2 - k], None)
+                                     for k in range(levels)], want_stats=[True] + [False] * levels)
+        net, laterals = laterals[0], laterals[1:]
+        chain = [net]
+        for k in range(levels):
+            up = self.m_ups[k]
+            net = up[1](up[0](net), residual=laterals[k])
+            chain.append(net)
+        merged = [k for k in range(levels) if not self.skip_unused or (k + 1) in consumed]
+        outs = scn.conv_group([(self.m_mergeds[k], chain[k + 1], None) for k in merged], want_stats=False)
+        ups = [chain[0]] + [None] * levels
+        for k, t in zip(merged, outs):
+            ups[k + 1] = t
+        _tmark("top-down done")
+        rpn_maps_3d = [ups[i] for i in self.fpn_scales_from_top]
+        selected_2d = {i - len(rpn_maps_3d) for i in self.rpn_3d_2d_selector if i >= len(rpn_maps_3d)}
+        pro = [i for i in range(len(rpn_maps_3d)) if (i in selected_2d or not self.skip_unused)]
+        outs = scn.conv_group([(self.convs_pro2d[i], rpn_maps_3d[i], None) for i in pro], want_stats=False)
+        rpn_maps_2d = [None] * len(rpn_maps_3d)
+        for i, t in zip(pro, outs):
+            rpn_maps_2d[i] = t
         rpn_maps = rpn_maps_3d + rpn_maps_2d
         rpn_maps = [rpn_maps[i] for i in self.rpn_3d_2d_selector]
         roi_maps = [ups[i] for i in self.roi_scales_from_top]

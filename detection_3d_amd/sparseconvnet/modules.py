@@ -364,6 +364,42 @@ class Deconvolution(Module, _PackedWeightMixin):
         return (out_size - self.filter_size) // self.filter_stride + 1
 
 
+def conv_group(calls, want_stats=True, forms=None):
+    """calls: [(convolution module, input, residual or None)] of convolutions on one metadata none of which reads what
+    another writes, without gradients -> their outputs, as module(input, residual=residual) returns them, computed by
+    ONE library call (SCN.conv_group_forward) that shares a launch among the members of one kernel instantiation.
+    want_stats: False (or a list with False for a member) = the member does not leave the column statistics of its
+    output, because no BatchNorm consumes it.  forms: None, or a list that receives every member's launch form (the
+    fields of d3d_conv_last_form)."""
+    assert not torch.is_grad_enabled()
+    if not calls:
+        return []
+    members, sizes, all_stats = [], [], []
+    if isinstance(want_stats, bool):
+        want_stats = [want_stats] * len(calls)
+    for (mod, input, residual), want in zip(calls, want_stats):
+        feats, bn = _conv_input(input)
+        assert feats.nelement() == 0 or feats.size(1) == SCN.stored_planes(mod.nIn, feats.dtype), (mod.nIn, mod.nOut)
+        if isinstance(mod, SubmanifoldConvolution):
+            kind, out_size, stride = 0, input.spatial_size, None
+        elif isinstance(mod, Convolution):
+            kind, out_size, stride = 1, mod._out_size(input.spatial_size), mod.filter_stride
+            assert residual is None
+        else:
+            assert isinstance(mod, Deconvolution), type(mod)
+            kind, stride = 2, mod.filter_stride
+            out_size = (input.spatial_size - 1) * mod.filter_stride + mod.filter_size
+        stats = _want_col_stats(feats) if want else None
+        res = None if residual is None else residual.features.contiguous()
+        members.append((kind, input.spatial_size, out_size, mod.filter_size, stride, feats, mod.weight,
+                        mod._packed(feats.dtype), res, bn, stats))
+        sizes.append(out_size)
+        all_stats.append(stats)
+    metadata = calls[0][1].metadata
+    outs = SCN.conv_group_forward(metadata, members, forms)
+    return [_conv_output(f, stats, metadata, size) for f, stats, size in zip(outs, all_stats, sizes)]
+
+
 class BatchNormalization(Module):
     """sparseconvnet/batchNormalization.py:13-68.  `momentum` is the RETENTION factor of the
     running statistics (SCN/CPU/BatchNormalization.cpp:32-36)."""

@@ -531,6 +531,34 @@ int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size_host, const int *out_s
                           const int *stride_host, const void *in, int cin, const void *packed_w, int cout,
                           const void *residual, void *out, int dtype, void *stream, double *macs_host,
                           const d3d_bn_prologue *bn_host);
+/* Grouped launches: n INDEPENDENT convolutions (no member reads what another member writes) in one call.  A descriptor
+ * holds what the member's own call takes -- kind 0: d3d_subm_conv_forward_dt (in_size = the spatial size; out_size and
+ * stride ignored), 1: d3d_conv_forward_dt (residual ignored), 2: d3d_deconv_forward_dt.  Members that resolve to the
+ * same fp32 k_conv instantiation (padded Cin, Cout, gather form) run as ONE launch of at most 8 members (longer groups
+ * take several), whose workgroups find their member in a table passed as a kernel argument; the reductions of all
+ * offset-split members run as one launch as well.  Each member keeps the tiles, the step and summation order, its own
+ * n_split and partial buffer, and the epilogue of its own call: every output, and every column-statistics row, is
+ * bit-identical to the one-by-one calls.  Members served by the weight-sharing kernel, by bf16 rows or by bf16x3
+ * products, and members that carry timing events (time_start / time_stop: recorded around that member's own k_conv
+ * launch, as d3d_conv_time_next arranges for a single call) are launched one by one inside the call.  `form` (may be
+ * NULL) receives the member's 12 form fields as d3d_conv_last_form reports them (zeros: nothing launched).  No
+ * reference counterpart.                                                                                          */
+typedef struct {
+  int kind;
+  int in_size[3], out_size[3], filter[3], stride[3];
+  const void *in;
+  int cin;
+  const void *packed_w;
+  int cout;
+  const void *residual;
+  void *out;
+  int dtype; /* d3d_dtype */
+  double *macs_host;
+  const d3d_bn_prologue *bn_host;
+  void *time_start, *time_stop; /* hipEvent_t or NULL */
+  int *form;
+} d3d_conv_desc;
+int d3d_conv_group_forward(d3d_meta *m, const d3d_conv_desc *descs_host, int n, void *stream);
 /* Tuning / test hook of the bf16 convolution (process-wide): `row_blocks` (1, 2 or 4) consecutive 32-row blocks share
  * every weight fetch in launches that keep at least min_waves * row_blocks waves (min_waves < 0: the default).
  * Results do not depend on it beyond the summation grouping of offset-split launches.                           */
