@@ -851,18 +851,26 @@ static int bn_backward_t(const T *in, const T *out, const T *d_out, T *d_in, int
   hipLaunchKernelGGL(k_bn_bwd_finish, dim3((planes + 31) / 32), dim3(256), 0, s, partial, nblk, rows, planes,
                      save_invstd, grad_mean, kcoef, d_weight, d_bias);
   size_t total = (size_t)rows * planes;
+  int apply_kernel = kBnApplyScalar;
+  unsigned apply_wgs = (unsigned)((total + 255) / 256);
+  bool apply_multi = false;
   if (vec4 && planes / 4 <= 256 && 256 % (planes / 4) == 0) {
     const int rpi = 256 / (planes / 4);
     const long need = ((long)rows + rpi - 1) / rpi;
     const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
+    apply_kernel = kBnApplyRows, apply_wgs = blocks, apply_multi = (long)rows > (long)blocks * rpi;
     hipLaunchKernelGGL(k_bn_bwd_apply_rows<T>, dim3(blocks), dim3(256), 0, s, in, out, d_out, d_in, rows, planes, save_mean,
                        save_invstd, weight, grad_mean, kcoef, leakiness);
-  } else if (vec4)
+  } else if (vec4) {
+    apply_kernel = kBnApplyVec4, apply_wgs = (unsigned)((total / 4 + 255) / 256);
     hipLaunchKernelGGL(k_bn_bwd_apply4<T>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in,
                        total / 4, planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
-  else
+  } else
     hipLaunchKernelGGL(k_bn_bwd_apply<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, d_out, d_in, total,
                        planes, save_mean, save_invstd, weight, grad_mean, kcoef, leakiness);
+  int *f = t_bn_form;
+  f[kBnBwPartial] = vec4 ? 1 : 2, f[kBnBwSlices] = nblk, f[kBnBwApply] = apply_kernel, f[kBnBwWgs] = (int)apply_wgs;
+  f[kBnBwMulti] = apply_multi ? 1 : 0, f[kBnBwType] = bn_form_type<T>();
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

@@ -16,6 +16,22 @@ static constexpr int kStatGroup = 16;     // slices per first-level group
 static constexpr int kStatMaxGroups = kStatBlocks / kStatGroup;
 static constexpr size_t kTicketBytes = 256;  // [0] = groups done, [1 + g] = slices of group g done
 
+thread_local int t_bn_form[kBnFormFields] = {};
+
+// the statistics section of d3d_bn_last_form for a launch of `nblk` slices over `n` rows (of the tensor, or of partials)
+static void bn_record_stats(int src, int type, int mode, int lanes, int row_lanes, int nblk, int n) {
+  int *f = t_bn_form;
+  f[kBnStSrc] = src, f[kBnStType] = type, f[kBnStMode] = mode, f[kBnStLanes] = lanes, f[kBnStRowLanes] = row_lanes;
+  f[kBnStSlices] = nblk;
+  f[kBnStGroups] = (nblk + kStatGroup - 1) / kStatGroup;
+  f[kBnStLastGroup] = nblk - (f[kBnStGroups] - 1) * kStatGroup;
+  f[kBnStPer] = (n + nblk - 1) / nblk;
+}
+static void bn_record_apply(int kernel, int type, unsigned wgs, bool multi) {
+  int *f = t_bn_form;
+  f[kBnApKernel] = kernel, f[kBnApType] = type, f[kBnApWgs] = (int)wgs, f[kBnApMulti] = multi ? 1 : 0;
+}
+
 // sums n rows of src[n][V] column-wise in a fixed order: thread (slice sl, value vi) adds rows sl, sl+SL, ...
 // and slice 0 adds the slices in order; dst[v] receives the result.  All kStatThreads threads must call.
 __device__ __forceinline__ void stat_reduce_rows(const double *__restrict__ src, int n, int V, double *__restrict__ dst,
@@ -278,8 +294,10 @@ static void launch_bn_apply(const float *in, float *out, int rows, int planes, c
     const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
     hipLaunchKernelGGL(k_bn_apply_rows<float>, dim3(blocks), dim3(256), 0, s, in, out, rows, planes, mean, invstd, weight,
                        bias, leakiness);
+    bn_record_apply(kBnApplyRows, kBnTypeF32, blocks, (long)rows > 3L * blocks * rpi);
   } else {
     const size_t total = (size_t)rows * planes;
+    bn_record_apply((planes & 3) == 0 ? kBnApplyVec4 : kBnApplyScalar, kBnTypeF32, (unsigned)((total / 4 + 256) / 256), false);
     hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)((total / 4 + 256) / 256)), dim3(256), 0, s, in, out, total, planes,
                        mean, invstd, weight, bias, leakiness);
   }
@@ -313,6 +331,7 @@ static int run_stats(const T *in, int rows, int C, void *scratch, size_t scratch
   double *total = gpartial + (size_t)kStatMaxGroups * 2 * C;
   hipLaunchKernelGGL(k_bn_stats<T>, dim3(nblk), dim3(kStatThreads), 0, s, in, rows, C, (unsigned int *)scratch, partial,
                      gpartial, total, mode, o0, o1, running_mean, running_var, eps, momentum, rows);
+  bn_record_stats(kBnSrcTensor, bn_form_type<T>(), mode, C4, RL, nblk, rows);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
@@ -321,6 +340,9 @@ static int run_stats(const T *in, int rows, int C, void *scratch, size_t scratch
 static int run_stats_partials(const double *src, int src_rows, int rows, int C, void *scratch, size_t scratch_bytes,
                               hipStream_t s, int mode, float *mean, float *invstd, float eps) {
   D3D_REQUIRE(C > 0 && C <= 4096 && C % 4 == 0, "batch norm: planes=%d must be a multiple of 4, <= 4096", C);
+  // stat_reduce_rows walks the 2 C values in whole passes of kStatThreads threads
+  D3D_REQUIRE(2 * C <= kStatThreads || 2 * C % kStatThreads == 0,
+              "batch norm: statistics from partials need planes=%d <= %d or a multiple of it", C, kStatThreads / 2);
   D3D_REQUIRE(scratch && scratch_bytes >= d3d_bn_scratch_bytes(C), "batch norm: scratch too small");
   const int V = 2 * C, VP = V < kStatThreads ? V : kStatThreads, SL = kStatThreads / VP;
   // >= 8 passes of the row lanes per workgroup and at most 64 slices (four first-level groups): the vectors are
@@ -337,6 +359,7 @@ static int run_stats_partials(const double *src, int src_rows, int rows, int C, 
   double *total = gpartial + (size_t)kStatMaxGroups * 2 * C;
   hipLaunchKernelGGL(k_bn_stats<double>, dim3(nblk), dim3(kStatThreads), 0, s, src, rows, C, (unsigned int *)scratch,
                      partial, gpartial, total, mode, mean, invstd, nullptr, nullptr, eps, 0.f, src_rows);
+  bn_record_stats(kBnSrcPartials, kBnTypeF64, mode, VP, SL, nblk, src_rows);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
@@ -368,6 +391,12 @@ size_t d3d_bn_scratch_bytes(int planes) {
   return kTicketBytes + (size_t)(kStatBlocks + kStatMaxGroups + 1) * 2 * planes * sizeof(double);
 }
 
+int d3d_bn_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kBnFormFields; i++) out[i] = t_bn_form[i];
+  std::fill(t_bn_form, t_bn_form + kBnFormFields, 0);
+  return kBnFormFields;
+}
+
 int d3d_bn_batch_stats(const float *in, int rows, int planes, float *mean, float *var_unbiased,
                        void *scratch, size_t scratch_bytes, void *stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -395,6 +424,8 @@ int d3d_bn_forward(const float *in, float *out, int rows, int planes, float *sav
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL(k_bn_eval_stats, dim3((planes + 63) / 64), dim3(64), 0, s, running_mean, running_var, planes, eps, save_mean, save_invstd);
+    std::fill(t_bn_form + kBnStSrc, t_bn_form + kBnStPer + 1, 0);
+    t_bn_form[kBnStSrc] = kBnSrcRunning;
   }
   launch_bn_apply(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, s);
   D3D_LAUNCH_CHECK();
@@ -444,6 +475,7 @@ int d3d_bn_apply_dt(const void *in, void *out, int rows, int planes, const float
   const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
   hipLaunchKernelGGL(k_bn_apply_rows<unsigned short>, dim3(blocks), dim3(256), 0, s, (const unsigned short *)in,
                      (unsigned short *)out, rows, planes, mean, invstd, weight, bias, leakiness);
+  bn_record_apply(kBnApplyRows, kBnTypeBf16, blocks, (long)rows > 3L * blocks * rpi);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
@@ -467,6 +499,8 @@ int d3d_bn_forward_dt(const void *in, void *out, int rows, int planes, float *sa
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL(k_bn_eval_stats, dim3((planes + 63) / 64), dim3(64), 0, s, running_mean, running_var, planes, eps, save_mean, save_invstd);
+    std::fill(t_bn_form + kBnStSrc, t_bn_form + kBnStPer + 1, 0);
+    t_bn_form[kBnStSrc] = kBnSrcRunning;
   }
   return d3d_bn_apply_dt(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, dtype, stream);
 }

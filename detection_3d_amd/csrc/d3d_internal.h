@@ -290,6 +290,25 @@ int conv_n_split(bool allowed, int K, long waves, long target);
 enum ConvFamily { kFormNone = 0, kFormConv = 1, kFormWs = 2, kFormBf16 = 3, kFormX3 = 4 };
 void conv_record_form(int family, int ct, int nct, int cout, int bpw, int rb, bool vec, bool late, int n_split,
                       bool stats, int n_blk, int K);
+// bn.hip.  d3d_bn_last_form: what the calling thread's BatchNorm launch sequences chose (host side only), one section
+// per stage -- a call writes the sections of the stages it launches, the read clears all of them
+enum BnFormField {
+  // statistics: source (BnFormSource), storage (BnFormType), mode of k_bn_stats, threads across a row (LPR; VP from
+  // partials), concurrent rows (RL; SL), row slices, first-level groups, slices of the last group, rows per slice
+  kBnStSrc = 0, kBnStType, kBnStMode, kBnStLanes, kBnStRowLanes, kBnStSlices, kBnStGroups, kBnStLastGroup, kBnStPer,
+  // apply: kernel (BnFormApply), storage, workgroups, 1 when the 4-rows-in-flight loop can be entered
+  kBnApKernel, kBnApType, kBnApWgs, kBnApMulti,
+  // backward: partial kernel (1 vec4, 2 scalar), slices, apply kernel (BnFormApply), workgroups, 1 when the two-row
+  // loop can be entered, storage
+  kBnBwPartial, kBnBwSlices, kBnBwApply, kBnBwWgs, kBnBwMulti, kBnBwType,
+  kBnFormFields
+};
+enum BnFormSource { kBnSrcNone = 0, kBnSrcTensor = 1, kBnSrcPartials = 2, kBnSrcRunning = 3 };
+enum BnFormType { kBnTypeF32 = 1, kBnTypeBf16 = 2, kBnTypeF64 = 3 };
+enum BnFormApply { kBnApplyNone = 0, kBnApplyRows = 1, kBnApplyVec4 = 2, kBnApplyScalar = 3 };
+extern thread_local int t_bn_form[kBnFormFields];
+template <typename T>
+constexpr int bn_form_type() { return sizeof(T) == 8 ? kBnTypeF64 : sizeof(T) == 4 ? kBnTypeF32 : kBnTypeBf16; }
 // conv_bf16.hip
 // dtype D3D_BF16, or D3D_F32_X3 (fp32 rows, bf16x3 products) for the shapes conv_x3_serves admits
 int launch_conv_bf16(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,

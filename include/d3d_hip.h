@@ -566,10 +566,23 @@ int d3d_conv_bf16_tuning(int row_blocks, long min_waves);
 /* d3d_bn_batch_stats (want_invstd == 0: mean, unbiased var) / d3d_bn_batch_invstd (want_invstd != 0: mean,
  * powf(var + eps, -0.5)) from the column sums a convolution left per row block (d3d_bn_prologue.out_stats: partial_rows
  * rows of [2 * planes] fp64) instead of from the tensor; `rows` = rows of the tensor.  Same arithmetic after the sums,
- * a fixed summation order (deterministic), one launch.                                                              */
+ * a fixed summation order (deterministic), one launch.  planes: a multiple of 4, at most 512 or a multiple of 512 up
+ * to 4096 (the finish walks the 2 * planes values in whole passes of 1024 threads).                                  */
 int d3d_bn_stats_from_partials(const double *partials, int partial_rows, int rows, int planes, float eps,
                                int want_invstd, float *mean, float *var_or_invstd, void *scratch, size_t scratch_bytes,
                                void *stream);
+/* What the calling thread's BatchNorm launch sequences chose since the last read (host side only): up to n of 19 ints,
+ * a section per stage, a section zero when its stage did not run.
+ *   statistics: source (1 tensor, 2 partials, 3 running statistics: nothing else recorded), storage (1 fp32, 2 bf16,
+ *     3 the fp64 partials), mode of the finish (0 mean / unbiased var, 1 train, 2 mean / invstd), threads across a row,
+ *     rows (of the tensor, or of partials) in flight per pass, row slices, first-level groups, slices of the last group,
+ *     rows per slice;
+ *   apply: kernel (1 row-walking, 2 general float4, 3 general scalar), storage, workgroups, 1 when the grid is capped far
+ *     enough that the 4-rows-in-flight loop is entered;
+ *   backward: partial kernel (1 float4, 2 scalar), slices, apply kernel (1 row-walking, 2 float4, 3 scalar), workgroups,
+ *     1 when the two-row loop is entered, storage.
+ * The record is cleared by the call (out may be null).  -> the number of fields the record has.                      */
+int d3d_bn_last_form(int *out, int n);
 /* d3d_bn_batch_invstd / d3d_bn_apply on a tensor of the given storage type (statistics and parameters fp32). */
 int d3d_bn_batch_invstd_dt(const void *in, int rows, int planes, float eps, float *mean, float *invstd,
                            void *scratch, size_t scratch_bytes, int dtype, void *stream);

@@ -83,6 +83,7 @@ def test_first_layer_weight_grad(dev):
 
 
 def test_batchnorm_backward(dev):
+    # every launch form against exact fp64 results, with per-element bounds: tests/test_bn_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     rng = np.random.RandomState(5)
     for C, leak in ((32, 0.0), (128, 0.333), (256, 0.0)):

@@ -162,6 +162,7 @@ def test_conv_backward_bf16_deterministic_dw(dev, cin, cout, n_points):
 @pytest.mark.parametrize("C", [32, 128, 256])
 @pytest.mark.parametrize("leak", [0.0, 0.333])
 def test_batchnorm_train_bf16(dev, C, leak):
+    # every launch form against exact fp64 results, with per-element bounds: tests/test_bn_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     from detection_3d_amd.sparseconvnet import SCN
     rng = np.random.RandomState(C + int(leak * 1000))

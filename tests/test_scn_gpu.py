@@ -149,6 +149,7 @@ def test_conv_ops(dev, cin, cout):
 
 
 def test_batchnorm(dev):
+    # every launch form against exact fp64 results, with per-element bounds: tests/test_bn_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     rng = np.random.RandomState(5)
     for C, rows in ((32, 5000), (64, 5000), (128, 4999), (256, 5000), (8, 37), (512, 3001), (1024, 700)):
