@@ -65,6 +65,7 @@ _SIGS = {
     "d3d_conv_dw_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "d3d_conv_dw_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
     "d3d_bn_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
+    "d3d_roi_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
     "d3d_sort_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_sort_pairs": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
     "d3d_conv_time_next": (ctypes.c_int, [vp, vp]),

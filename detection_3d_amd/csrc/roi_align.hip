@@ -3,6 +3,8 @@
 //  * sparse variant: samples the SparseConvNetTensor through its hash grid, so the 1.07 GB dense
 //    map of sparse_3d_to_dense_2d (sparseconvnet/tools_3d_2d.py:7-48) is never materialised.
 // Both keep the reference's `zsize > zsize` bound quirk (:27): z above the map is clamped.
+#include <algorithm>
+
 #include "d3d_internal.h"
 
 namespace d3d {
@@ -689,6 +691,33 @@ static bool roi_det_layout(int K, int C, int ph, int pw, int pz, int sampling_ra
   return true;
 }
 
+// d3d_roi_last_form: what the calling thread's last RoIAlign call launched (host stores only).  family (1 k_roi_dense,
+// 2 k_roi_sparse, 3 k_roi_dense_bwd, 4 k_roi_sparse_bwd, 5 the fixed-order backward), storage type (1 fp32, 2 bf16),
+// lookup (bit 0: a level probes the hash table, bit 1: a level reads the dense index; 0 for the dense kernels), extent
+// (1 the caller's crop, 2 read on the device, 0 for the dense kernels), grid x / y / z and workgroup size of the family's
+// main kernel (5: k_roi_det_sum), levels with a table, workgroups of k_roi_f32_to_bf16 (4 on bf16 rows), and for 5
+// n_max, n_chunks and the sort's key bits.  A call that launches nothing leaves the record as it is.
+static constexpr int kRoiFormFields = 13;
+static thread_local int t_roi_last_form[kRoiFormFields] = {};
+enum RoiFamily { kRoiFamDense = 1, kRoiFamSparse = 2, kRoiFamDenseBwd = 3, kRoiFamSparseBwd = 4, kRoiFamDet = 5 };
+static void roi_record(int family, size_t type_bytes, int lookup, int extent, dim3 grid, int block, int levels, long cvt = 0,
+                       long n_max = 0, long n_chunks = 0, int bits = 0) {
+  const int f[kRoiFormFields] = {family, type_bytes == 4 ? 1 : 2, lookup, extent, (int)grid.x, (int)grid.y, (int)grid.z,
+                                 block, levels, (int)cvt, (int)n_max, (int)n_chunks, bits};
+  std::copy(f, f + kRoiFormFields, t_roi_last_form);
+}
+// the lookup and extent fields of a forward launch over the levels of lv
+static void roi_record_sparse(const RoiLevels &lv, size_t type_bytes, dim3 grid) {
+  int lookup = 0, extent = 0, levels = 0;
+  for (int l = 0; l < kRoiMaxLevels; l++) {
+    if (!lv.v[l].tab) continue;
+    levels++;
+    lookup |= lv.v[l].dense ? 2 : 1;
+    extent |= lv.v[l].extent ? 2 : 1;
+  }
+  roi_record(kRoiFamSparse, type_bytes, lookup, extent, grid, kRoiWaves * 64, levels);
+}
+
 }  // namespace d3d
 
 using namespace d3d;
@@ -781,6 +810,7 @@ int d3d_roi_align_rotated_3d_forward(const float *input, int B, int C, int H, in
   long nthreads = (long)K * C * ph * pw * pz;
   hipLaunchKernelGGL(k_roi_dense, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, input, C, H, W, Z, rois, nthreads, spatial_scale, ph, pw, pz, sampling_ratio, out);
   D3D_LAUNCH_CHECK();
+  roi_record(kRoiFamDense, 4, 0, 0, dim3((unsigned)((nthreads + 255) / 256)), 256, 0);
   return D3D_OK;
 }
 
@@ -828,6 +858,7 @@ static int roi_sparse_forward(d3d_meta *m, const int *size, const T *feats, int 
   hipLaunchKernelGGL(k_roi_sparse<T>, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
                      roi_levels, ph, pw, pz, sampling_ratio, layout, out);
   D3D_LAUNCH_CHECK();
+  roi_record_sparse(lv, sizeof(T), dim3(K, (C + kRoiCch - 1) / kRoiCch));
   return D3D_OK;
 }
 
@@ -852,6 +883,7 @@ static int roi_sparse_forward_levels(d3d_meta *m, int n_levels, const int *sizes
   hipLaunchKernelGGL(k_roi_sparse<T>, dim3(K, (C + kRoiCch - 1) / kRoiCch), dim3(kRoiWaves * 64), 0, s, lv, C, rois,
                      roi_levels, ph, pw, pz, sampling_ratio, layout, out);
   D3D_LAUNCH_CHECK();
+  roi_record_sparse(lv, sizeof(T), dim3(K, (C + kRoiCch - 1) / kRoiCch));
   return D3D_OK;
 }
 
@@ -906,6 +938,7 @@ int d3d_roi_align_rotated_3d_backward(const float *top_diff, int B, int C, int H
   hipLaunchKernelGGL(k_roi_dense_bwd, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, top_diff, C, H, W, Z,
                      rois, nthreads, spatial_scale, ph, pw, pz, sampling_ratio, bottom_diff);
   D3D_LAUNCH_CHECK();
+  roi_record(kRoiFamDenseBwd, 4, 0, 0, dim3((unsigned)((nthreads + 255) / 256)), 256, 0);
   return D3D_OK;
 }
 
@@ -944,6 +977,7 @@ int d3d_roi_align_rotated_3d_sparse_backward(d3d_meta *m, const int *size, const
   hipLaunchKernelGGL(k_roi_sparse_bwd<float>, dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch), dim3(256), lds, s, g.tab, g.cap,
                      C, crop[0], crop[1], crop[2], rois, spatial_scale, ph, pw, pz, sampling_ratio, top_diff, d_feats);
   D3D_LAUNCH_CHECK();
+  roi_record(kRoiFamSparseBwd, 4, 1, 1, dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch), 256, 1);
   return D3D_OK;
 }
 
@@ -982,6 +1016,8 @@ int d3d_roi_align_rotated_3d_sparse_backward_bf16(d3d_meta *m, const int *size, 
   hipLaunchKernelGGL(k_roi_f32_to_bf16, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, s, acc, total,
                      (unsigned short *)d_feats);
   D3D_LAUNCH_CHECK();
+  roi_record(kRoiFamSparseBwd, 2, 1, 1, K > 0 ? dim3(K, (C + kRoiBwdCch - 1) / kRoiBwdCch) : dim3(0, 0, 0), 256, 1,
+             (total + 1023) / 1024);
   return D3D_OK;
 }
 
@@ -1035,10 +1071,17 @@ static int roi_det_run(const Grid &g, const int *crop, const TT *top_diff, int C
   hipLaunchKernelGGL(k_roi_det_join<TO>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, rbeg, rend, n_rows, part, C,
                      d_feats);
   D3D_LAUNCH_CHECK();
+  roi_record(kRoiFamDet, sizeof(TO), 1, 1, dim3((unsigned)((L.n_chunks + 3) / 4)), 256, 1, 0, L.n_max, L.n_chunks, L.bits);
   return D3D_OK;
 }
 
 extern "C" {
+
+int d3d_roi_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kRoiFormFields; i++) out[i] = t_roi_last_form[i];
+  std::fill(t_roi_last_form, t_roi_last_form + kRoiFormFields, 0);
+  return kRoiFormFields;
+}
 
 int d3d_roi_align_rotated_3d_sparse_backward_deterministic(d3d_meta *m, const int *size, const float *top_diff, int C,
                                                            const int *crop, const float *rois, int K,

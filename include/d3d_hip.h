@@ -723,6 +723,14 @@ int d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16(d3d_meta *m, con
                                                                 void *stream);
 size_t d3d_roi_align_rotated_3d_sparse_backward_deterministic_bf16_scratch_bytes(int K, int C, int ph, int pw, int pz,
                                                                                 int sampling_ratio, int n_rows);
+/* Test hook: what the calling thread's last RoIAlign call launched (host stores only; a call that launches nothing
+ * leaves the record as it is).  Fields: family (1 dense forward, 2 sparse forward, 3 dense backward, 4 sparse backward
+ * with atomics, 5 its fixed-order form), storage type (1 fp32, 2 bf16), lookup (bit 0: a level probes the hash table,
+ * bit 1: a level reads the dense index), extent (1 the caller's crop, 2 read on the device), grid x / y / z and
+ * workgroup size of the family's main kernel (5: the chunk sums), levels with a table, workgroups of the fp32 -> bf16
+ * pass (4 on bf16 rows), and for 5 the record bound n_max, its chunks and the sort's key bits.
+ * The record is cleared by the call (out may be null).  -> the number of fields the record has.                      */
+int d3d_roi_last_form(int *out, int n);
 
 /* a8. BatchNormalization_updateOutput (SCN/sparseconvnet.h:21-26; SCN/CPU/BatchNormalization.cpp:12-60).
  * train!=0: batch statistics, running update r = m*r + (1-m)*batch.  train==0: uses

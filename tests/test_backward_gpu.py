@@ -105,6 +105,7 @@ def test_batchnorm_backward(dev):
 
 
 def test_roi_align_sparse_backward(dev):
+    # every launch form against exact fp64 results, with per-element bounds: tests/test_roi_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     from detection_3d_amd.roi_align_rotated_3d import roi_align_rotated_3d_sparse
     t, ft, x, sop, loc = _sparse_input(dev, 128, seed=8, n_points=9000)

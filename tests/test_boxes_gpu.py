@@ -130,6 +130,7 @@ def test_box_decode(dev):
 
 
 def test_roi_align_dense_and_sparse(dev):
+    # every launch form against exact fp64 results, with per-element bounds: tests/test_roi_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     from detection_3d_amd.roi_align_rotated_3d import roi_align_rotated_3d_forward, roi_align_rotated_3d_sparse
     from tests.helpers import small_scene
