@@ -231,6 +231,8 @@ _SIGS = {
                                                  ctypes.c_float, ctypes.c_float, ctypes.c_int, vp, vp, vp,
                                                  ctypes.c_size_t, vp]),
     "d3d_nms_batched_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_nms_sweep_mode": (ctypes.c_int, [ctypes.c_int]),
+    "d3d_nms_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
     "d3d_rotate_nms_3d": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_float, vp, vp, c_int_p, vp, ctypes.c_size_t, vp]),
     "d3d_rotate_nms_3d_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -7,6 +7,9 @@
 // final ratio (numba promotes `x / 2.0`), cos/sin evaluated in fp64 and rounded to fp32.
 #include "d3d_internal.h"
 
+#include <algorithm>
+#include <cstdlib>
+
 namespace d3d {
 
 struct Quad {
@@ -365,7 +368,8 @@ __global__ void k_nms_prep(const float *__restrict__ boxes, NmsSegs g, float min
   const int i = blockIdx.x * blockDim.x + threadIdx.x, sb = blockIdx.y;
   if (i >= seg_count(g, sb)) return;
   const float *b = boxes + (size_t)seg_box(g, sb, i) * 7;
-  const float d0 = fmaxf(b[3], min_yx), d1 = fmaxf(b[4], min_yx), dz = fmaxf(b[5], min_z);
+  // torch.clamp(min=) of boxlist_nms_3d: a NaN size stays NaN (fmaxf would replace it by the bound)
+  const float d0 = b[3] < min_yx ? min_yx : b[3], d1 = b[4] < min_yx ? min_yx : b[4], dz = b[5] < min_z ? min_z : b[5];
   NmsBox r;
   r.d0 = d0; r.d1 = d1;
   r.z0 = b[2]; r.z1 = b[2] + dz;
@@ -375,11 +379,20 @@ __global__ void k_nms_prep(const float *__restrict__ boxes, NmsSegs g, float min
   r.area = quad_area_f64(r.q.p);
   rec[(size_t)sb * g.n_max + i] = r;
 }
+// overlap of the z intervals as iou_one_dim's torch.min / torch.max give it (rotate_nms_3d_torch.py:18): a NaN bound makes it
+// NaN (fminf / fmaxf would drop the NaN).  z0 = NaN or dz = NaN both leave z1 = NaN, so testing z1 covers the box.
+__device__ __forceinline__ float nms_z_overlap(const NmsBox &cb, const NmsBox &rb) {
+  const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
+  return (cb.z1 != cb.z1 || rb.z1 != rb.z1) ? __builtin_nanf("") : overlap;
+}
 // Suppression masks in two passes so that the expensive geometry runs with full lanes:
 //  k_nms_pairs  -- 256 threads per 64 x 64 tile (wave w: rows 16w..16w+15, lanes = candidate boxes j):
 //                  cheap exact early-outs, survivors appended to a pair list (wave64 ballot + one atomic
 //                  per wave).  The early-outs cannot change the decision:
-//                   * z intervals do not overlap -> iou_z <= 0 (or NaN) -> gate `iou3d > 0` is false;
+//                   * z intervals do not overlap and their hull is finite and not a point -> iou_z = overlap / common
+//                     <= 0 -> the gate skips the pair.  A NaN iou_z (a NaN bound, 0 / 0 of two equal point intervals,
+//                     inf / inf) is NOT skipped: the gate of spconv's rotate_non_max_suppression_cpu is
+//                     `iou3d <= 0 -> skip`, which a NaN passes -- k_nms_eval then decides on the polygon alone;
 //                   * BEV circumscribed circles disjoint, or rectangles separated along an edge normal (margin
 //                     ~1e-3 of the box size, far above fp32 rounding of metre-sized boxes) -> no corner inside
 //                     the other box, no edges cross -> area 0 -> gate false.
@@ -411,10 +424,12 @@ __global__ __launch_bounds__(256) void k_nms_pairs(const NmsBox *__restrict__ re
     bool cand = false;
     if (ii < nrow && j < n && j > i) {
       const NmsBox &rb = srow[ii];
-      const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
+      const float overlap = nms_z_overlap(cb, rb);
+      const float common = fmaxf(cb.z1, rb.z1) - fminf(cb.z0, rb.z0);
+      const bool z_apart = overlap <= 0.f && common > 0.f && common < __builtin_inff();   // -> iou_z <= 0, whatever it rounds to
       const float dx = cb.raw[0] - rb.raw[0], dy = cb.raw[1] - rb.raw[1];
       const float rr = (cb.radius + rb.radius) * 1.001f + 1e-4f;
-      cand = overlap > 0.f && dx * dx + dy * dy <= rr * rr &&
+      cand = !z_apart && dx * dx + dy * dy <= rr * rr &&
              !quads_separated(rb.q.p, cb.q.p, 1e-3f * (1.f + cb.radius + rb.radius));
     }
     bal[u] = __ballot(cand);
@@ -457,10 +472,10 @@ __global__ __launch_bounds__(kEvalThreads) void k_nms_eval(const NmsBox *__restr
 #pragma unroll
     for (int d = 0; d < 5; d++) same = same && (fabsf(rb.raw[d] - cb.raw[d]) < (float)1e-6);
     if (same) v = 1.f;
-    const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
+    const float overlap = nms_z_overlap(cb, rb);
     const float common = fmaxf(cb.z1, rb.z1) - fminf(cb.z0, rb.z0);
     v = v * (overlap / common);
-    if (!(v > 0.0f)) continue;
+    if (v <= 0.0f) continue;   // a NaN gate goes on to the polygon test, as in the reference
     const double ia = quad_inter_f64(rb.q.p, cb.q.p, clip, 64);
     if (!(ia > 0)) continue;
     const double ua = rb.area + cb.area - ia;
@@ -695,6 +710,11 @@ __global__ __launch_bounds__(kSwThreads) void k_nms_sweep_lds(const unsigned lon
         if (cnt >= max_keep && lane == 0) stop_s = 1;
       }
       __syncthreads();
+      // stop_s is one word for all chunks: the sweeper may set it for chunk c + 1 before a slow loader wave has read it
+      // for chunk c.  That loader then leaves one chunk early.  The result does not depend on it: keep, cnt and n_keep are
+      // the sweeper's alone, and the sweeper itself stops behind the barrier of chunk c + 1, so the slot the early leaver
+      // did not fill (chunk c + 2) is never read.  The barrier count does not either: a wave that has ended no longer
+      // counts towards the workgroup barrier, so the waves still at the barrier of chunk c + 1 are released by the rest.
       if (stop_s) {
         stop = true;
         break;
@@ -1020,6 +1040,36 @@ int d3d_match_segments(const float *gt, const int *gt_off_host, int S, const flo
   return D3D_OK;
 }
 
+// d3d_nms_sweep_mode: 0 default (the LDS form), 1 the single-wave register form, 2 the LDS form.  Starts from
+// D3D_NMS_SWEEP (r...: the register form), so that A/B runs of a whole process keep working.
+static int g_nms_sweep = -1;
+static int nms_sweep_mode() {
+  if (g_nms_sweep < 0) {
+    const char *e = getenv("D3D_NMS_SWEEP");
+    g_nms_sweep = (e && e[0] == 'r') ? 1 : 0;
+  }
+  return g_nms_sweep;
+}
+int d3d_nms_sweep_mode(int mode) {
+  const int was = nms_sweep_mode();
+  if (mode >= 0 && mode <= 2) g_nms_sweep = mode;
+  return was;
+}
+// d3d_nms_last_form: what the calling thread's last d3d_rotate_nms_3d_batched launch chose (host stores only): sweep
+// family (1 k_nms_sweep, 2 k_nms_sweep_lds), NCBMAX (0 for the register form), ncb, segments, n_max, the resolved
+// max_keep, dynamic LDS bytes.  A call that launches nothing (no segments, n_max 0) leaves the record as it is.
+static constexpr int kNmsFormFields = 7;
+static thread_local int t_nms_last_form[kNmsFormFields] = {};
+static void nms_record(int family, int ncbmax, int ncb, int segments, int n_max, int max_keep, int lds) {
+  const int f[kNmsFormFields] = {family, ncbmax, ncb, segments, n_max, max_keep, lds};
+  std::copy(f, f + kNmsFormFields, t_nms_last_form);
+}
+int d3d_nms_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kNmsFormFields; i++) out[i] = t_nms_last_form[i];
+  std::fill(t_nms_last_form, t_nms_last_form + kNmsFormFields, 0);
+  return kNmsFormFields;
+}
+
 size_t d3d_nms_batched_scratch_bytes(int segments, int n_max) {
   const size_t B = segments > 0 ? segments : 0, n = n_max > 0 ? n_max : 0, ncb = (n + 63) / 64;
   return B * n * ncb * 8 + B * n * sizeof(NmsBox) + (B * n * n / 2 + 64) * sizeof(int2) + 2048;
@@ -1055,20 +1105,23 @@ int d3d_rotate_nms_3d_batched(const float *boxes, const int32_t *order, int stri
   hipLaunchKernelGGL(k_nms_pairs, dim3(ncb, ncb, B), dim3(256), 0, s, rec, g, pairs, n_pairs);
   hipLaunchKernelGGL(k_nms_eval, dim3(1024), dim3(kEvalThreads), 0, s, rec, pairs, n_pairs, n, ncb, thresh, mask);
   const int mk = max_keep > 0 ? max_keep : n;
-  static const bool lds_sweep = [] {      // D3D_NMS_SWEEP=regs: the single-wave form (A/B runs)
-    const char *e = getenv("D3D_NMS_SWEEP");
-    return !(e && e[0] == 'r');
-  }();
+  const bool lds_sweep = nms_sweep_mode() != 1;
   if (lds_sweep) {
     const size_t lds = (size_t)2 * 64 * (ncb + 1) * sizeof(unsigned long long);
-    if (ncb <= 16)
+    const int ncbmax = ncb <= 16 ? 16 : ncb <= 32 ? 32 : 64;
+    if (ncb <= 16) {
       hipLaunchKernelGGL(k_nms_sweep_lds<16>, dim3(B), dim3(kSwThreads), lds, s, mask, g, ncb, mk, keep, n_keep);
-    else if (ncb <= 32)
+    } else if (ncb <= 32) {
       hipLaunchKernelGGL(k_nms_sweep_lds<32>, dim3(B), dim3(kSwThreads), lds, s, mask, g, ncb, mk, keep, n_keep);
-    else
+    } else {
+      // 4033..4096 candidates: two slots of 64 rows x 65 words are 66,560 B, above 64 KiB.  A gfx950 workgroup may use
+      // 160 KiB and the launch is accepted as it is (tests/test_nms_forms_gpu.py, n = 4033 and 4096)
       hipLaunchKernelGGL(k_nms_sweep_lds<64>, dim3(B), dim3(kSwThreads), lds, s, mask, g, ncb, mk, keep, n_keep);
+    }
+    nms_record(2, ncbmax, ncb, B, n, mk, (int)lds);
   } else {
     hipLaunchKernelGGL(k_nms_sweep, dim3(B), dim3(64), 0, s, mask, g, ncb, mk, keep, n_keep);
+    nms_record(1, 0, ncb, B, n, mk, 0);
   }
   D3D_LAUNCH_CHECK();
   return D3D_OK;

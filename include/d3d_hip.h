@@ -899,6 +899,17 @@ int d3d_topk_segments(const float *vals, int n, int elem_stride, int group_strid
 size_t d3d_topk_scratch_bytes(int n, int segments);
 int d3d_topk_max(void);
 size_t d3d_nms_batched_scratch_bytes(int segments, int n_max);
+/* Measurement / test switch of the greedy sweep behind d3d_rotate_nms_3d_batched (and the two entries built on it),
+ * process-wide: 0 (default) = the LDS-staged sweep k_nms_sweep_lds, 1 = the single-wave register sweep k_nms_sweep,
+ * 2 = the LDS-staged sweep.  Same survivor lists.  mode < 0: query only.  -> the previous setting.
+ * Environment: D3D_NMS_SWEEP (r...: starts at 1).                                                                   */
+int d3d_nms_sweep_mode(int mode);
+/* The form of the calling thread's most recent d3d_rotate_nms_3d_batched launch, recorded on the host: up to n of the
+ * ints sweep family (0 none, 1 k_nms_sweep, 2 k_nms_sweep_lds), NCBMAX of the LDS form (16 / 32 / 64; 0 for the register
+ * form), ncb (64-bit words per mask row), segments, n_max, the resolved max_keep (n_max when the caller passed <= 0),
+ * dynamic LDS bytes of the sweep.  A call that launches nothing (no segments, n_max == 0) does not touch the record.
+ * The record is cleared by the call (out may be null).  -> the number of fields the record has.                     */
+int d3d_nms_last_form(int *out, int n);
 /* Box-head post-processing glue around the batched NMS (roi_heads/box_head_3d/inference.py:113-148), one launch each:
  * post_scores: sc[(nc-1), K] = prob[i][j+1] if > thresh else -1 (class-major), counts[nc-1] = candidates per class
  *              (`inds = scores[:, j] > score_thresh`, :118);

@@ -257,6 +257,18 @@ def rotate_nms_3d(boxes, scores, thresh):
     return keep[:nk].astype(np.int64)
 
 
+def nms_pair(a, b):
+    """Per pair (a[p] scored before b[p], both [7] yx_zb, clamped): the gate value and the fp64 polygon IoU that
+    rotate_nms_3d's sweep uses; it suppresses b[p] iff not (gate <= 0) and iou >= thresh."""
+    a, b = _f32(a), _f32(b)
+    n = a.shape[0]
+    gate = np.zeros(n, np.float32)
+    iou = np.zeros(n, np.float64)
+    if n:
+        lib().orc_nms_pair(_p(a), _p(b), n, _p(gate), _p(iou))
+    return gate, iou
+
+
 def box_decode(enc, anchors, weights=(1.0,) * 7, clip=10000.0):
     enc = _f32(enc)
     anchors = _f32(anchors)

@@ -311,6 +311,9 @@ void orc_boxes_iou_3d(const float *targets, int M, const float *anchors, int N, 
     for (int j = 0; j < N; j++) {
       float overlap = std::min(az[2 * j + 1], tz[2 * i + 1]) - std::max(az[2 * j], tz[2 * i]);
       float common = std::max(az[2 * j + 1], tz[2 * i + 1]) - std::min(az[2 * j], tz[2 * i]);
+      // torch.min / torch.max (:18-19) give NaN when either bound is NaN; std::min / std::max return their first argument
+      if (std::isnan(az[2 * j + 1]) || std::isnan(tz[2 * i + 1]) || std::isnan(az[2 * j]) || std::isnan(tz[2 * i]))
+        overlap = common = std::nanf("");
       out[(size_t)i * N + j] = out[(size_t)i * N + j] * (overlap / common);
     }
 }
@@ -379,6 +382,34 @@ int orc_rotate_nms_3d(const float *boxes, const float *scores, int n, float thre
   }
   orc_bev_corners(xy.data(), dims.data(), ang.data(), n, corners.data());
   return orc_rotate_nms_cpu(corners.data(), order.data(), iou.data(), n, thresh, keep);
+}
+
+// One candidate pair of orc_rotate_nms_3d, n pairs at a time: a[p] is the earlier (higher-scored) box, b[p] the later one,
+// both [7] yx_zb and already clamped.  gate[p] = boxes_iou_3d(dets, dets)[a, b] as the sweep reads it; iou[p] = the fp64
+// polygon IoU the sweep compares with thresh, 0 where it skips the comparison (area <= 0 or NaN, union <= 0 or NaN).
+// The sweep suppresses b iff !(gate <= 0) && iou >= thresh.
+void orc_nms_pair(const float *a, const float *b, int n, float *gate, double *iou) {
+#pragma omp parallel for schedule(static)
+  for (int p = 0; p < n; p++) {
+    float two[14], g[4];
+    std::memcpy(two, a + 7 * p, 7 * sizeof(float));
+    std::memcpy(two + 7, b + 7 * p, 7 * sizeof(float));
+    const float aug[4] = {0, 0, 0, 0};
+    // (the serial inner loops of orc_boxes_iou_3d: a 2 x 2 matrix)
+    orc_boxes_iou_3d(two, 2, two, 2, aug, -1, 0, g);
+    gate[p] = g[1];
+    float xy[4] = {two[0], two[1], two[7], two[8]}, dims[4] = {two[3], two[4], two[10], two[11]};
+    float ang[2] = {two[6], two[13]}, corners[16];
+    orc_bev_corners(xy, dims, ang, 2, corners);
+    double pa[8], pb[8];
+    for (int k = 0; k < 8; k++) {
+      pa[k] = corners[k];
+      pb[k] = corners[8 + k];
+    }
+    const double ia = quad_inter_area(corners, corners + 8);
+    const double ua = shoelace(pa, 4) + shoelace(pb, 4) - ia;
+    iou[p] = (!(ia <= 0) && ua > 0) ? ia / ua : 0.0;
+  }
 }
 
 // BoxCoder3D.decode (maskrcnn_benchmark/modeling/box_coder_3d.py:38-65) =

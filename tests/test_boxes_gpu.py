@@ -70,6 +70,7 @@ def test_boxes_iou_3d_flags(dev):
 
 @pytest.mark.parametrize("n,thr,aug", [(2000, 0.5, (0.3, 0.3)), (1000, 0.45, (0.2, 0.2)), (333, 0.3, (0, 0))])
 def test_nms_survivor_sets_exact(dev, n, thr, aug):
+    # every sweep form, size edge, cap position and hard pair geometry: tests/test_nms_forms_gpu.py
     from detection_3d_amd import box_ops
     b, s = make_boxes(10 + n, n)
     s[::7] = s[3]                                                # score ties -> lower index first
