@@ -110,14 +110,21 @@ __global__ __launch_bounds__(256) void k_roi_dense(const float *__restrict__ inp
 // Sparse variant.  Block = one RoI x one chunk of 128 channels (lane = 2 adjacent channels); a wave owns
 // groups of kRoiG consecutive bins.  Per group and per step of 8 sub-samples the 64 lanes first resolve
 // (sub-sample, corner) -> (row, weight) through the hash grid for all kRoiG bins at once (kRoiG independent
-// probes in flight per lane), compact the taps that exist into a per-bin LDS list, and then every lane
-// accumulates its two channels over the lists with 8 independent feature-row loads in flight (each a
-// coalesced 512-B read of the wave).  Everything is latency-bound L2 traffic: the feature map of a pyramid
-// level is a few MB; what matters is the number of loads in flight, not bytes.
+// probes in flight per lane), merge the taps that fall into one cell into a per-bin list in LDS (cells in
+// order of their first lane; the cells are found with v_readlane, their weights summed in batches of kRoiB
+// independent register-only butterflies, roi_cells4_sum), and then every lane accumulates its two channels
+// over the lists with 8 independent feature-row loads in flight (each a coalesced 512-B read of the wave).
+// Everything is latency-bound L2 traffic: the feature map of a pyramid level is a few MB; what matters is the
+// number of loads in flight, not bytes.
 // layout 0: out[n][c][ph][pw][pz] (the reference's); layout 1: out[n][ph][pw][c][pz] (rows of the box head's
 // [1,1,pz] convolution seen as a GEMM).  roi_levels (optional): only RoIs with roi_levels[i] == level are pooled.
-static constexpr int kRoiG = 4;   // 4 bins per group and 4 waves per SIMD (128 VGPRs, 4 spilled): 286 us for the bench's 1000 RoIs;
-                                 // 8 bins at 3 waves (164 VGPRs) 368 us, 4 bins at 3 waves 357 us, 4 bins at 5 waves: 32 spills
+// kRoiG: 4 bins per group and 4 waves per SIMD (128 VGPRs, 4 spilled).  Measured on the bench's 1000 RoIs (4.98 merged
+// cells per bin and step on average, 231 ... 1952 per RoI): the launch takes 0.64 of the cycles it took
+// with the merge as one loop per cell of seven dependent ds_bpermute round trips (about 70 cycles each, a third of a
+// wave's life).  What is left: a wave waits 39 % of its cycles (probes, row loads) and issues VALU instructions in
+// 27 %, and the launch lasts twice the mean life of its waves -- a single round of workgroups over RoIs of unequal
+// size.
+static constexpr int kRoiG = 4;
 static constexpr int kRoiCch = 128;
 __device__ __forceinline__ void roi_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -125,6 +132,39 @@ __device__ __forceinline__ void roi_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 static constexpr int kRoiWaves = 4;  // waves per RoI (8 measured the same; what helps is waves per SIMD, see kRoiG)
+static constexpr int kRoiB = 8;      // merged cells whose weight sums run as independent chains (two roi_cells4_sum)
+
+// The wave-wide sums of four lane vectors a, b, c, d, each added in the pairing of the xor butterfly
+// `for (d = 32; d >= 1; d >>= 1) w += __shfl_xor(w, d)` (lane i with lane i ^ 32, then ^ 16, ... ^ 1; fp32 addition is
+// commutative, so the pairing alone fixes the bits), without LDS and with one chain for the four:
+//  * level 32: v_permlane32_swap exchanges the upper half of a with the lower half of b, so the sum of the two results
+//    holds a's level in lanes 0-31 and b's in lanes 32-63 (a lane's partner at this level holds the same number);
+//  * level 16: v_permlane16_swap exchanges the odd rows (of 16 lanes) of the first operand with the even rows of the
+//    second: the sum holds a, c, b, d in rows 0, 1, 2, 3;
+//  * levels 8, 4, 2, 1 stay inside a row: DPP row_ror:8 is lane ^ 8, row_half_mirror (lane ^ 7) followed by quad_perm
+//    [3,2,1,0] (lane ^ 3) is lane ^ 4, quad_perm [2,3,0,1] and [1,0,3,2] are lane ^ 2 and lane ^ 1.
+// Every lane of row 0 returns the sum of a, of row 1 that of c, of row 2 that of b, of row 3 that of d.  All 64 lanes
+// must be active.
+template <int CTRL>
+__device__ __forceinline__ float roi_dpp(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float roi_pack32(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float roi_pack16(float p, float q) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(q), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float roi_cells4_sum(float a, float b, float c, float d) {
+  float v = roi_pack16(roi_pack32(a, b), roi_pack32(c, d));
+  v += roi_dpp<0x128>(v);                  // row_ror:8
+  v += roi_dpp<0x1B>(roi_dpp<0x141>(v));   // row_half_mirror, then quad_perm [3,2,1,0]
+  v += roi_dpp<0x4E>(v);                   // quad_perm [2,3,0,1]
+  v += roi_dpp<0xB1>(v);                   // quad_perm [1,0,3,2]
+  return v;
+}
 // One launch serves every pyramid level: a RoI's workgroup picks the map of roi_levels[n] (a launch per level leaves
 // the workgroups of the other levels' RoIs to exit at once -- with two levels each launch fills half the wave slots).
 struct RoiLevel {
@@ -167,7 +207,7 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
     Z = L.extent[2];
   }
   typedef float f32x2 __attribute__((ext_vector_type(2)));
-  __shared__ int2 list[kRoiWaves][kRoiG][64];  // (row, weight bits) of the taps that exist
+  __shared__ int2 list[kRoiWaves][kRoiG * 64];  // (row, weight bits) of a step's merged cells, bin after bin
   const int NB = PH * PW * PZ;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const RoiGeom g = roi_geom(rois + (size_t)n * 8, spatial_scale, PH, PW, PZ, sampling_ratio);
@@ -194,6 +234,11 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
     }
     return v;
   };
+  // layout 1 with PZ == kRoiG, a whole chunk of channels and an aligned result: a lane's kRoiG bins of a channel are
+  // consecutive, 16 bytes of fp32 or 8 of bf16 (the offset of a group is a multiple of that: kRoiG elements per channel)
+  static_assert(kRoiG == 4, "the wide store writes four bins per channel");
+  const bool wide = layout == 1 && PZ == kRoiG && (cc + 1) * kRoiCch <= C &&
+                    ((uintptr_t)out & (kRoiG * sizeof(T) - 1)) == 0;
   const int ngroups = (NB + kRoiG - 1) / kRoiG;
   for (int grp = wave; grp < ngroups; grp += kRoiWaves) {
     const int b0 = grp * kRoiG;
@@ -253,30 +298,60 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
         for (int j = 0; j < 4; j++) row[g0 + j] = r4[j];
       }
       // the 64 taps of a bin fall into a handful of cells (its sub-samples are a fraction of a cell apart): merge
-      // the taps of one cell (weights summed by a wave butterfly) so that each feature row is fetched once per bin
-      // and step -- the kernel is bound by the L2 -> L1 bytes of those 512-B rows, not by instructions
-      int cnt[kRoiG];
+      // the taps of one cell (weights summed in the pairing of a wave butterfly) so that each feature row is fetched
+      // once per bin and step.
+      // Leader pass (no LDS): the cells of a bin in order of their first lane.  The leader's row comes through a
+      // scalar-indexed v_readlane; every lane learns the index of its cell in the step's list (the kRoiG bins' cells
+      // one after another: bin gi owns [base[gi], base[gi] + cnt[gi])), lane j of cellrow[gi] the row of the bin's cell j.
+      int2 *lst = list[wave];
+      int cnt[kRoiG], base[kRoiG], flat[kRoiG];
+      int total = 0;
 #pragma unroll
       for (int gi = 0; gi < kRoiG; gi++) {
         unsigned long long m = __ballot(row[gi] >= 0);
-        int c = 0;
+        int c = 0, fl = -1, cellrow = 0;
         while (m) {
-          const int rl = __shfl(row[gi], __builtin_ctzll(m), 64);   // wave-uniform cell
+          const int rl = __builtin_amdgcn_readlane(row[gi], __builtin_ctzll(m));   // wave-uniform cell
           const bool mine = row[gi] == rl;
-          float w = mine ? wgt[gi] : 0.f;
-#pragma unroll
-          for (int d = 32; d >= 1; d >>= 1) w += __shfl_xor(w, d, 64);
-          if (lane == 0) list[wave][gi][c] = make_int2(rl, __float_as_int(w));
+          fl = mine ? total + c : fl;
+          cellrow = lane == c ? rl : cellrow;
           c++;
           m &= ~__ballot(mine);
         }
+        if (lane < c) lst[total + lane].x = cellrow;
+        flat[gi] = fl;
+        base[gi] = total;
         cnt[gi] = c;
+        total += c;
+      }
+      // Weight sums, kRoiB cells of the list per batch: every cell's sum is the xor butterfly of the serial form (levels
+      // 32 ... 1 over `mine ? wgt : 0`), but the chains of a batch are independent and none of them goes through LDS
+      // (roi_cells4_sum).  A batch may straddle bins; only the bins it touches are looked at.
+      for (int f0 = 0; f0 < total; f0 += kRoiB) {
+        float sm[kRoiB];
+#pragma unroll
+        for (int k = 0; k < kRoiB; k++) sm[k] = 0.f;
+#pragma unroll
+        for (int gi = 0; gi < kRoiG; gi++) {
+          if (base[gi] < f0 + kRoiB && base[gi] + cnt[gi] > f0) {   // wave-uniform
+            const int e = flat[gi] - f0;
+#pragma unroll
+            for (int k = 0; k < kRoiB; k++) sm[k] = e == k ? wgt[gi] : sm[k];
+          }
+        }
+#pragma unroll
+        for (int h = 0; h < kRoiB; h += 4) {
+          const float w = roi_cells4_sum(sm[h], sm[h + 1], sm[h + 2], sm[h + 3]);
+          const int q = lane >> 4;                                  // rows of 16 lanes hold cells h + 0, 2, 1, 3
+          const int f = f0 + h + (((q & 1) << 1) | (q >> 1));
+          if ((lane & 15) == 0 && f < total) lst[f].y = __float_as_int(w);
+        }
       }
       roi_wave_sync();
       // ---- lanes = channel pairs: one entry per cell, batches of independent row loads ----
 #pragma unroll
       for (int gi = 0; gi < kRoiG; gi++) {
-        const int2 *L = list[wave][gi];
+        const int2 *L = lst + base[gi];
         const int nc = cnt[gi];
         int i = 0;
         for (; i + 8 <= nc; i += 8) {
@@ -313,6 +388,25 @@ __global__ __launch_bounds__(kRoiWaves * 64) __attribute__((amdgpu_waves_per_eu(
         }
       }
       roi_wave_sync();  // the lists are rewritten by the next step
+    }
+    if (wide) {   // the group is the pz run of one (ph, pw) cell: kRoiG consecutive outputs per channel, one store each
+      f32x2 r[kRoiG];
+#pragma unroll
+      for (int gi = 0; gi < kRoiG; gi++) r[gi] = acc[gi] / count;
+      T *o = out + ((n_out * (size_t)(PH * PW) + grp) * C + c0) * kRoiG;
+#pragma unroll
+      for (int ch = 0; ch < 2; ch++) {
+        if constexpr (sizeof(T) == 4) {
+          const d3d_f32x4 v = {r[0][ch], r[1][ch], r[2][ch], r[3][ch]};
+          *(d3d_f32x4 *)(o + ch * kRoiG) = v;
+        } else {
+          unsigned short h[kRoiG];
+#pragma unroll
+          for (int gi = 0; gi < kRoiG; gi++) st1(&h[gi], r[gi][ch]);
+          *(uint2 *)(o + ch * kRoiG) = make_uint2(h[0] | (unsigned)h[1] << 16, h[2] | (unsigned)h[3] << 16);
+        }
+      }
+      continue;
     }
 #pragma unroll
     for (int gi = 0; gi < kRoiG; gi++) {
