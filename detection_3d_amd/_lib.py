@@ -260,6 +260,9 @@ _SIGS = {
     "d3d_box_decode_rows": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_float,
                                            vp, vp]),
     "d3d_gather_kept": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp, vp]),
+    "d3d_plan_export": (ctypes.c_int, [vp, ctypes.c_int, c_int_p, c_int_p, c_int_p, vp, vp, vp, c_int_p, vp]),
+    "d3d_plan_last_form": (ctypes.c_int, [c_int_p, ctypes.c_int]),
+    "d3d_subm_probe_mode": (ctypes.c_int, [ctypes.c_int]),
     "d3d_plan_stats": (ctypes.c_int, [vp, ctypes.c_int, c_int_p, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_long),
                                       ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long), vp]),
     # storage-type aware forms (d3d_dtype: 0 fp32, 1 bf16)

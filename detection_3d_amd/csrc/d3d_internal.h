@@ -240,6 +240,7 @@ struct d3d_meta {
   // ... and, sized by the point count like the table, the rest of that rulebook (sort by mask, transpose): enqueued
   // behind the probes before the host has the site count; registered as a plan once the count is back
   bool pre_plan_built = false;
+  bool pre_sym = false;            // that table was probed in the half-probe form
   d3d::Plan pre_plan;              // (rows / blocks / gathered rows are filled in when the count is back)
   void *pre_tab = nullptr;         // the input grid's hash table (known before the grid is registered)
   // the input layer's point lists, built on a stream of the library's own right behind the grid (no count needed:

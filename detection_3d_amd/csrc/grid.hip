@@ -134,21 +134,24 @@ int scan_exclusive_i32(const int32_t *in, int32_t *out, int n, int32_t *total_de
 // rocPRIM's device sort takes ~20 dependent launches of 5-7 us (block sort + merge passes) for the 10^4 .. 5*10^5 rows of
 // a rulebook -- 110-190 us, almost all launch latency -- and its Onesweep variant 25-33 us per pass at these sizes (the
 // look-back chain over a few dozen tiles is serial); this one is bound by its 3 launches per pass (~17 us).
-// Descending order sorts the complemented digits, so it is stable too.
+// Descending order sorts the complemented digits, so it is stable too.  The digits of the last pass are cut to the bits
+// that remain (dmask): key bits above `bits` never take part, also where the digits cover more than `bits` (4 bits: one
+// 8-bit digit; 19 bits: 2 x 10).  finalize_plan relies on it: its keys carry the rows' popcounts above the offset mask.
 static constexpr int kRsThreads = 256;
 static constexpr int kRsItems = 8;
 static constexpr int kRsTile = kRsThreads * kRsItems;
 
 template <int DB>
-__device__ __forceinline__ uint32_t rs_digit(uint32_t k, int shift, bool desc) {
-  return ((desc ? ~k : k) >> shift) & ((1u << DB) - 1u);
+__device__ __forceinline__ uint32_t rs_digit(uint32_t k, int shift, bool desc, uint32_t dmask) {
+  static_assert(DB >= 8 && DB <= 10, "digit width");
+  return ((desc ? ~k : k) >> shift) & dmask;
 }
 
 // hist[digit][tile] of one pass
 // n_dev (may be null): the element count on the device, for a sort enqueued with an upper bound `n` (and its n_tiles)
 template <int DB>
 __global__ __launch_bounds__(kRsThreads) void k_rs_count(const uint32_t *__restrict__ keys, int n, int n_tiles, int shift,
-                                                         int desc, uint32_t *__restrict__ hist,
+                                                         int desc, uint32_t dmask, uint32_t *__restrict__ hist,
                                                          const int32_t *__restrict__ n_dev) {
   D3D_SIDE_PRIO();
   constexpr int BINS = 1 << DB;
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_count(const uint32_t *__restr
 #pragma unroll
   for (int j = 0; j < kRsItems; j++) {
     const int i = base + j * kRsThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[rs_digit<DB>(keys[i], shift, desc != 0)], 1u);
+    if (i < n) atomicAdd(&h[rs_digit<DB>(keys[i], shift, desc != 0, dmask)], 1u);
   }
   __syncthreads();
   for (int b = threadIdx.x; b < BINS; b += kRsThreads) hist[(size_t)b * n_tiles + blockIdx.x] = h[b];
@@ -199,7 +202,8 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scan(uint32_t *__restrict__ h
 template <int DB>
 __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const uint32_t *__restrict__ keys_in,
                                                            const int32_t *__restrict__ vals_in, int n, int n_tiles,
-                                                           int shift, int desc, const uint32_t *__restrict__ hist,
+                                                           int shift, int desc, uint32_t dmask,
+                                                           const uint32_t *__restrict__ hist,
                                                            const uint32_t *__restrict__ totals,
                                                            uint32_t *__restrict__ keys_out,
                                                            int32_t *__restrict__ vals_out,
@@ -220,7 +224,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const uint32_t *__res
     const int i = base + r * 64 + lane;
     const bool ok = i < n;
     key[r] = ok ? keys_in[i] : 0u;
-    const uint32_t d = rs_digit<DB>(key[r], shift, desc != 0);
+    const uint32_t d = rs_digit<DB>(key[r], shift, desc != 0, dmask);
     dig[r] = d;
     unsigned long long m = __ballot(ok);
 #pragma unroll
@@ -277,13 +281,14 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const uint32_t *__res
 }
 
 template <int DB>
-static void rs_pass(const uint32_t *ksrc, const int32_t *vsrc, int n, int n_tiles, int shift, bool desc, uint32_t *hist,
-                    uint32_t *totals, uint32_t *kdst, int32_t *vdst, hipStream_t s, const int32_t *n_dev) {
-  hipLaunchKernelGGL(k_rs_count<DB>, dim3(n_tiles), dim3(kRsThreads), 0, s, ksrc, n, n_tiles, shift, desc ? 1 : 0, hist,
-                     n_dev);
+static void rs_pass(const uint32_t *ksrc, const int32_t *vsrc, int n, int n_tiles, int shift, int bits, bool desc,
+                    uint32_t *hist, uint32_t *totals, uint32_t *kdst, int32_t *vdst, hipStream_t s, const int32_t *n_dev) {
+  const uint32_t dmask = (1u << std::min(DB, bits - shift)) - 1u;   // the digit, cut to the key bits that remain
+  hipLaunchKernelGGL(k_rs_count<DB>, dim3(n_tiles), dim3(kRsThreads), 0, s, ksrc, n, n_tiles, shift, desc ? 1 : 0, dmask,
+                     hist, n_dev);
   hipLaunchKernelGGL(k_rs_scan, dim3(1 << DB), dim3(kRsThreads), 0, s, hist, n_tiles, totals);
   hipLaunchKernelGGL(k_rs_scatter<DB>, dim3(n_tiles), dim3(kRsThreads), 0, s, ksrc, vsrc, n, n_tiles, shift, desc ? 1 : 0,
-                     hist, totals, kdst, vdst, n_dev);
+                     dmask, hist, totals, kdst, vdst, n_dev);
 }
 static inline void rs_layout(int bits, int &passes, int &db) {
   passes = std::max(1, (bits + 9) / 10);
@@ -321,9 +326,9 @@ int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *v
     const bool last = p == passes - 1;
     uint32_t *kdst = last ? keys_out : ktmp[p & 1];
     int32_t *vdst = last ? vals_out : vtmp[p & 1];
-    if (db == 8) rs_pass<8>(ksrc, vsrc, n, n_tiles, db * p, descending, hist, totals, kdst, vdst, s, n_dev);
-    else if (db == 9) rs_pass<9>(ksrc, vsrc, n, n_tiles, db * p, descending, hist, totals, kdst, vdst, s, n_dev);
-    else rs_pass<10>(ksrc, vsrc, n, n_tiles, db * p, descending, hist, totals, kdst, vdst, s, n_dev);
+    if (db == 8) rs_pass<8>(ksrc, vsrc, n, n_tiles, db * p, bits, descending, hist, totals, kdst, vdst, s, n_dev);
+    else if (db == 9) rs_pass<9>(ksrc, vsrc, n, n_tiles, db * p, bits, descending, hist, totals, kdst, vdst, s, n_dev);
+    else rs_pass<10>(ksrc, vsrc, n, n_tiles, db * p, bits, descending, hist, totals, kdst, vdst, s, n_dev);
     ksrc = kdst;
     vsrc = vdst;
   }
@@ -717,8 +722,10 @@ __global__ __launch_bounds__(kSmallGridThreads) void k_conv_grid_small(const int
 // a4. Submanifold neighbour probes (SubmanifoldConvolutionRules.h:13-45).  A 256-thread block owns 64
 // output sites; its 64*K probes are spread over the threads (independent loads in flight), the [site][k]
 // table is written coalesced, and the per-site offset masks are assembled in LDS.
-// sort key of a plan row: (number of offsets << K) | offset mask -- rows with equal masks stay together and blocks come
-// out ordered by weight (sorted descending: the heaviest blocks are dispatched first); the mask is its low K bits
+// sort key of a plan row: (number of offsets << K) | offset mask (K > 27: the mask alone); the mask is its low K bits.
+// The radix form of finalize_plan sorts ONLY those low K bits, descending and stable: rows come out by descending mask
+// VALUE (rows with equal masks together, in site order), not by number of offsets -- the bits above the mask are carried
+// but never sorted.  (The single-workgroup form has a key of its own, k_plan_small.)
 __device__ __forceinline__ uint32_t plan_key(uint32_t m, int K) { return K <= 27 ? (((uint32_t)__popc(m) << K) | m) : m; }
 __device__ __forceinline__ uint32_t plan_key_mask(uint32_t key, int K) { return K <= 27 ? (key & ((1u << K) - 1u)) : key; }
 
@@ -749,7 +756,7 @@ __global__ __launch_bounds__(256) void k_subm_nbr(const int32_t *__restrict__ lo
     if (v >= 0) atomicOr(&smask[ls], 1u << k);
   }
   __syncthreads();
-  // the row's SORT KEY (popcount above the mask, plan_key): finalize_plan sorts it as it is
+  // the row's SORT KEY (popcount above the mask, plan_key): finalize_plan sorts its low K bits, the mask
   if (threadIdx.x < ns) mask[s0 + threadIdx.x] = plan_key(smask[threadIdx.x], K);
 }
 
@@ -800,9 +807,12 @@ __global__ __launch_bounds__(256) void k_subm_nbr_sym(const int32_t *__restrict_
 // The half-probe form pays two fills: measured rulebook builds 0.285 -> 0.230 ms at 462 k sites, 0.245 -> 0.208 at 371 k,
 // 0.113 -> 0.130 at 193 k, 0.084 -> 0.104 at 57 k.
 static constexpr int kSymMinSites = 262144;
+// d3d_subm_probe_mode: 0 automatic (the site threshold above), 1 never the half-probe form, 2 wherever the filter allows
+static int g_subm_probe_mode = 0;
 static bool subm_nbr_is_sym(int n_bound, const int *filt) {
   const int K = filt[0] * filt[1] * filt[2];
-  return (filt[0] & 1) && (filt[1] & 1) && (filt[2] & 1) && K > 1 && n_bound >= kSymMinSites;
+  if (!((filt[0] & 1) && (filt[1] & 1) && (filt[2] & 1) && K > 1) || g_subm_probe_mode == 1) return false;
+  return g_subm_probe_mode == 2 || n_bound >= kSymMinSites;
 }
 // the two fills the half-probe form needs (table -1, masks 0); a caller may run them ahead of time on another stream
 static int subm_nbr_prefill(int n_bound, const int *filt, int32_t *nbr, uint32_t *mask, hipStream_t s) {
@@ -811,11 +821,11 @@ static int subm_nbr_prefill(int n_bound, const int *filt, int32_t *nbr, uint32_t
   D3D_HIP_CHECK(hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)n_bound, s));
   return D3D_OK;
 }
+// sym: the caller's subm_nbr_is_sym decision (taken once per build: a prefill made ahead of time must match the launch)
 static int launch_subm_nbr(const int32_t *loc, int n_bound, const int *filt, const HashEntry *tab, int cap, int32_t *nbr,
-                           uint32_t *mask, const int32_t *n_dev, hipStream_t s, bool prefilled = false) {
+                           uint32_t *mask, const int32_t *n_dev, hipStream_t s, bool sym, bool prefilled = false) {
   if (n_bound <= 0) return D3D_OK;
-  const int K = filt[0] * filt[1] * filt[2];
-  if (subm_nbr_is_sym(n_bound, filt)) {
+  if (sym) {
     if (!prefilled)
       if (int rc = subm_nbr_prefill(n_bound, filt, nbr, mask, s)) return rc;
     hipLaunchKernelGGL(k_subm_nbr_sym, grid1d(n_bound, kNbrSites), dim3(256), 0, s, loc, n_bound, filt[0], filt[1], filt[2],
@@ -829,6 +839,21 @@ static int launch_subm_nbr(const int32_t *loc, int n_bound, const int *filt, con
 }
 
 // ------------------------------------------------------------------------------------------
+// d3d_plan_last_form: how the calling thread's most recently ENQUEUED plan was built (host stores only).  family 1
+// identity, 2 single-workgroup sort, 3 radix sort, 4 radix sort enqueued by an upper bound with the count on the device
+// (0: an empty plan, nothing launched); masks 0 computed in the finalisation / 1 handed in by the probes; probe 0 none,
+// 1 plain, 2 half-probe; K, n_rows, n_bound, n_blk; passes and digit bits of the radix layout; grid 0 no grid build,
+// 1 k_conv_grid_small, 2 the tiled chain, 3 an empty level.  Probe and grid are what the caller of finalize_plan did
+// before it: left in t_plan_ctx and consumed by the record.
+static constexpr int kPlanFormFields = 10;
+static thread_local int t_plan_last_form[kPlanFormFields] = {};
+static thread_local int t_plan_ctx[2] = {0, 0};   // probe, grid of the plan about to be finalised
+static void plan_record(int family, int masks, int probe, int K, int n_rows, int n_bound, int n_blk, int passes, int db,
+                        int grid) {
+  const int f[kPlanFormFields] = {family, masks, probe, K, n_rows, n_bound, n_blk, passes, db, grid};
+  std::copy(f, f + kPlanFormFields, t_plan_last_form);
+}
+
 // Plan finalisation: per-row offset masks, sort rows by mask, transpose, block masks.
 __global__ void k_row_mask(const int32_t *__restrict__ nbr, int n, int K, uint32_t *mask) {
   D3D_SIDE_PRIO();
@@ -984,6 +1009,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_plan_small(const int32_t *__r
 // rule count in plan.n_rules_dev.  The rule count stays on the device until somebody asks for it.
 int finalize_plan(d3d_meta *m, const int32_t *nbr, int n_rows, int K, Plan &plan, hipStream_t s,
                   uint32_t *mask_in) {
+  const int probe = t_plan_ctx[0], grid = t_plan_ctx[1];   // consumed whatever happens below
+  t_plan_ctx[0] = t_plan_ctx[1] = 0;
   D3D_REQUIRE(K >= 1 && K <= 32, "filter volume %d not supported (1..32)", K);
   Arena &A = lane_arena(m, s);
   plan.K = K;
@@ -997,8 +1024,12 @@ int finalize_plan(d3d_meta *m, const int32_t *nbr, int n_rows, int K, Plan &plan
   plan.nbrT = nbrT;
   plan.blkmask = blkmask;
   plan.n_rules = n_rows == 0 ? 0 : -1;
-  if (n_rows == 0) return D3D_OK;
+  if (n_rows == 0) {
+    plan_record(0, 0, probe, K, 0, 0, 0, 0, 0, grid);
+    return D3D_OK;
+  }
   if (n_rows <= kSmallMax) {
+    plan_record(2, mask_in ? 1 : 0, probe, K, n_rows, n_rows, plan.n_blk, 0, 0, grid);
     hipLaunchKernelGGL(k_plan_small, dim3(1), dim3(kSmallThreads), 0, s, nbr, mask_in, n_rows, K, rows);
     hipLaunchKernelGGL(k_plan_finish, dim3((npos + kTP - 1) / kTP), dim3(256), (size_t)kTP * (K | 1) * sizeof(int32_t),
                        s, nbr, rows, n_rows, npos, K, nbrT, blkmask, (const int32_t *)nullptr);
@@ -1015,13 +1046,19 @@ int finalize_plan(d3d_meta *m, const int32_t *nbr, int n_rows, int K, Plan &plan
     }
     hipLaunchKernelGGL(k_row_mask, grid1d(n_rows), dim3(256), 0, s, nbr, n_rows, K, mask);
   }
-  // Exact, STABLE sort by (popcount, mask): rows of a mask class stay in site-id order, i.e. consecutive positions
-  // of a block read (centre offset) and write nearly consecutive feature rows.  Measured alternative: grouping the rows
+  // Exact, STABLE sort by the mask value alone (descending; the popcount above it in the key is not sorted): rows of a
+  // mask class are contiguous and stay in site-id order, i.e. consecutive positions of a block read (centre offset) and
+  // write nearly consecutive feature rows.  Measured alternative: grouping the rows
   // by hashing their masks into a class table (4 launches instead of ~19, same executed / useful steps within 10 %)
   // hands out positions by atomics, loses that order, and made the 64 -> 64 convolutions 29 % slower.  Leaving the
   // k = s = 2 plans unsorted (absent gathers cost no memory traffic) saves four sorts per building and costs the
   // strided convolutions 0.25 ms of zero tiles: 6.45 against 6.37 ms per building.
   D3D_REQUIRE(m->iota && n_rows <= m->iota_n, "finalize_plan: %d rows exceed the input layer's %d points", n_rows, m->iota_n);
+  {
+    int passes, db;
+    rs_layout(std::min(K, 32), passes, db);
+    plan_record(3, mask_in ? 1 : 0, probe, K, n_rows, n_rows, plan.n_blk, passes, db, grid);
+  }
   int rc = sort_pairs_u32(mask, nullptr, m->iota, rows, n_rows, std::min(K, 32), A, s, true, nullptr);   // low K bits: the mask
   if (rc) return rc;
   hipLaunchKernelGGL(k_plan_finish, dim3((npos + kTP - 1) / kTP), dim3(256), (size_t)kTP * (K | 1) * sizeof(int32_t),
@@ -1475,6 +1512,7 @@ int d3d_meta_clear(d3d_meta *m) {
   m->pre_nbr = nullptr;
   m->pre_mask = nullptr;
   m->pre_plan_built = false;
+  m->pre_sym = false;
   m->pre_tab = nullptr;
   m->lists_on_aux = false;
   m->feat_arena.used = 0;
@@ -1718,7 +1756,7 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
       D3D_HIP_CHECK(hipEventRecord(m->count_ev, s));          // the host waits for the count, not for what follows
       // 1. the probes (the longest kernel of the start) ...
       if (sym) D3D_HIP_CHECK(hipStreamWaitEvent(s, m->fill_ev, 0));
-      if (int rc2 = launch_subm_nbr(loc, n, prefetch_filter, tab, g.cap, m->pre_nbr, m->pre_mask, total, s, sym)) return rc2;
+      if (int rc2 = launch_subm_nbr(loc, n, prefetch_filter, tab, g.cap, m->pre_nbr, m->pre_mask, total, s, sym, sym)) return rc2;
       prefetched = true;
       // 2. ... beside them the point lists, behind the grid (count_ev marks it) ...
       D3D_HIP_CHECK(hipStreamWaitEvent(m->aux_stream, m->count_ev, 0));
@@ -1739,6 +1777,7 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
                          s, m->pre_nbr, p.rows, n, npos_b, pre_K, p.nbrT, p.blkmask, (const int32_t *)total);
       D3D_LAUNCH_CHECK();
       m->pre_plan_built = true;
+      m->pre_sym = sym;
     }
     if (prefetched) D3D_HIP_CHECK(hipEventSynchronize(m->count_ev));
     else D3D_HIP_CHECK(hipStreamSynchronize(s));
@@ -1760,6 +1799,9 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
       p.n_blk = (n_active + 31) / 32;
       p.n_rules = n_active == 0 ? 0 : -1;
       m->plans.emplace(make_key(0, size, m->pre_filt, nullptr), p);
+      int passes, db;
+      rs_layout(std::min(p.K, 32), passes, db);
+      plan_record(4, 1, m->pre_sym ? 2 : 1, p.K, n_active, n, p.n_blk, passes, db, 0);
     }
   }
   *n_active_host = n_active;
@@ -1997,16 +2039,20 @@ int d3d_subm_prepare(d3d_meta *m, const int *size, const int *filt, void *stream
       p.blkmask = blkmask;
       if (npos) hipLaunchKernelGGL(k_identity_plan, grid1d(npos), dim3(256), 0, s, rows, nbrT, blkmask, g->n, npos, p.n_blk);
       D3D_LAUNCH_CHECK();
+      plan_record(1, 0, 0, 1, g->n, g->n, p.n_blk, 0, 0, 0);
     } else if (m->pre_nbr && s == m->pre_stream && g->size[0] == m->in_size[0] && g->size[1] == m->in_size[1] &&
                g->size[2] == m->in_size[2] && filt[0] == m->pre_filt[0] && filt[1] == m->pre_filt[1] &&
                filt[2] == m->pre_filt[2]) {
       // the table d3d_input_layer_build_prefetch started on this stream
+      t_plan_ctx[0] = m->pre_sym ? 2 : 1;
       int rc = finalize_plan(m, m->pre_nbr, g->n, K, p, s, m->pre_mask);
       if (rc) return rc;
     } else {
       int32_t *nbr = (int32_t *)(A.base + ((A.cap - raw_bytes) & ~size_t(255)));
       uint32_t *mask = (uint32_t *)((char *)nbr - (((size_t)g->n * 4 + 511) & ~size_t(255)));
-      if (int rc2 = launch_subm_nbr(g->loc, g->n, filt, g->tab, g->cap, nbr, mask, nullptr, s)) return rc2;
+      const bool sym = subm_nbr_is_sym(g->n, filt);
+      if (int rc2 = launch_subm_nbr(g->loc, g->n, filt, g->tab, g->cap, nbr, mask, nullptr, s, sym)) return rc2;
+      t_plan_ctx[0] = sym ? 2 : 1;
       int rc;
       {
         CapGuard guard(A, (size_t)((char *)mask - A.base) & ~size_t(255));
@@ -2249,6 +2295,7 @@ static int run_grid_chain(d3d_meta *m, const std::vector<ChainSpec> &specs, hipS
     const ChainSpec &sp = specs[i];
     const int n_in = v.src >= 0 ? n_out[v.src] : v.n_in_host;
     Plan p;
+    t_plan_ctx[1] = v.bound_entries == 0 ? 3 : v.small ? 1 : 2;
     int rc = finalize_plan(m, v.nbr_fwd, n_out[i], v.K, p, s, nullptr);
     if (rc) return rc;
     {
@@ -2524,6 +2571,39 @@ int d3d_plan_stats(d3d_meta *m, int kind, const int *in_size, const int *filt, c
   for (uint32_t v : bm) ex += 32L * __builtin_popcount(v);
   *executed_host = ex;
   return D3D_OK;
+}
+
+int d3d_plan_export(d3d_meta *m, int kind, const int *in_size, const int *filt, const int *stride, int32_t *rows,
+                    int32_t *nbrT, uint32_t *blkmask, int *dims_host, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && in_size && filt && dims_host && (kind == 0 || kind == 1 || kind == 2), "bad arguments");
+  const Plan *p = find_plan(m, kind, in_size, filt, kind == 0 ? nullptr : stride);
+  if (!p) {
+    set_error("export: rulebook not built");
+    return D3D_ERR_STATE;
+  }
+  dims_host[0] = p->K;
+  dims_host[1] = p->n_rows;
+  dims_host[2] = p->n_in;
+  dims_host[3] = p->n_blk;
+  const size_t npos = (size_t)p->n_blk * 32;
+  if (npos == 0) return D3D_OK;
+  if (rows) D3D_HIP_CHECK(hipMemcpyAsync(rows, p->rows, sizeof(int32_t) * npos, hipMemcpyDeviceToDevice, s));
+  if (nbrT) D3D_HIP_CHECK(hipMemcpyAsync(nbrT, p->nbrT, sizeof(int32_t) * npos * p->K, hipMemcpyDeviceToDevice, s));
+  if (blkmask) D3D_HIP_CHECK(hipMemcpyAsync(blkmask, p->blkmask, sizeof(uint32_t) * p->n_blk, hipMemcpyDeviceToDevice, s));
+  return D3D_OK;
+}
+
+int d3d_plan_last_form(int *out, int n) {
+  for (int i = 0; out && i < n && i < kPlanFormFields; i++) out[i] = t_plan_last_form[i];
+  std::fill(t_plan_last_form, t_plan_last_form + kPlanFormFields, 0);
+  return kPlanFormFields;
+}
+
+int d3d_subm_probe_mode(int mode) {
+  const int was = g_subm_probe_mode;
+  if (mode >= 0 && mode <= 2) g_subm_probe_mode = mode;
+  return was;
 }
 
 int d3d_sparse_to_dense_forward(d3d_meta *m, const int *size, const float *in, int planes, int batch,

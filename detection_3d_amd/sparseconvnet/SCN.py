@@ -293,6 +293,21 @@ class Metadata_3(object):
                                      ptr(trip), capacity, ctypes.byref(n), stream_of()))
         return trip[:n.value]
 
+    def export_plan(self, kind, in_size, filter_size, stride=None):
+        """The raw tables of a built rulebook (d3d_plan_export; kind as export_rules) -> dict: K, n_rows, n_in, n_blk and
+        the device tensors rows int32 [n_blk*32], nbrT int32 [K, n_blk*32], blkmask int32 [n_blk] (the uint32 words)."""
+        dev = torch.device("cuda", self._dev)
+        sz, fs = ints(_size3(in_size)), ints(_size3(filter_size))
+        st = ints(_size3(stride)) if stride is not None else ints([0, 0, 0])
+        dims = (ctypes.c_int * 4)()
+        check(lib().d3d_plan_export(self._h, kind, sz, fs, st, None, None, None, dims, stream_of()))
+        K, n_rows, n_in, n_blk = list(dims)
+        rows = torch.empty(n_blk * 32, dtype=torch.int32, device=dev)
+        nbrT = torch.empty((K, n_blk * 32), dtype=torch.int32, device=dev)
+        blkmask = torch.empty(n_blk, dtype=torch.int32, device=dev)
+        check(lib().d3d_plan_export(self._h, kind, sz, fs, st, ptr(rows), ptr(nbrT), ptr(blkmask), dims, stream_of()))
+        return dict(K=K, n_rows=n_rows, n_in=n_in, n_blk=n_blk, rows=rows, nbrT=nbrT, blkmask=blkmask)
+
 
 F32, BF16, F32_X3 = 0, 1, 2        # d3d_dtype
 

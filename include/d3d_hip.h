@@ -450,6 +450,31 @@ int d3d_export_rules(d3d_meta *m, int kind, const int *in_size_host, const int *
 int d3d_plan_stats(d3d_meta *m, int kind, const int *in_size_host, const int *filter_host, const int *stride_host,
                    long *n_blocks_host, long *executed_host, long *rules_host, void *stream);
 
+/* debug exporter: the raw tables of a built rulebook, copied on `stream` (kind, sizes as d3d_export_rules):
+ *   rows    int32 [n_blk*32]     output row of every position, -1 in the padding behind n_rows
+ *   nbrT    int32 [K][n_blk*32]  input row feeding position p through filter offset k, or -1
+ *   blkmask uint32 [n_blk]       the offsets each block of 32 positions executes
+ * dims_host[4] receives K, n_rows, n_in, n_blk; any of the three buffers may be NULL (all NULL: the sizes only).      */
+int d3d_plan_export(d3d_meta *m, int kind, const int *in_size_host, const int *filter_host, const int *stride_host,
+                    int32_t *rows, int32_t *nbrT, uint32_t *blkmask, int *dims_host, void *stream);
+/* How the calling thread's most recently enqueued rulebook was built, recorded on the host by the call that enqueues it
+ * (d3d_subm_prepare, d3d_conv_prepare / the grid chain, d3d_deconv_prepare, d3d_input_layer_build_prefetch; a cached
+ * rulebook records nothing): up to n of the ints
+ *   family      0 empty (nothing launched), 1 identity (1x1x1), 2 single-workgroup sort, 3 radix sort, 4 radix sort
+ *               enqueued by an upper bound of the row count, the count read on the device (the prefetched rulebook)
+ *   masks       0 computed in the finalisation, 1 handed in by the neighbour probes
+ *   probe       0 none (strided / decoded table), 1 plain probes, 2 half-probe form
+ *   K, n_rows, n_bound (what the launches were sized by), n_blk
+ *   passes, digit_bits of the radix sort (0 otherwise)
+ *   grid        0 no grid built with it, 1 single-workgroup grid build, 2 tiled chain, 3 empty level
+ * The record is cleared by the call (out may be null).  -> the number of fields the record has.                       */
+int d3d_plan_last_form(int *out, int n);
+/* Test hook of the submanifold neighbour probes (process-wide; d3d_subm_prepare and the prefetch of
+ * d3d_input_layer_build_prefetch): 0 (default) = the half-probe form from 262144 sites on, 1 = never, 2 = wherever the
+ * filter allows it (odd in every dimension, volume > 1) at any site count.  Same tables.  mode < 0: query only.
+ * -> the previous setting.                                                                                           */
+int d3d_subm_probe_mode(int mode);
+
 /* Measurement hook (bench.py's roofline leg; no reference counterpart): the next sparse-convolution launch made by
  * the calling thread records the two HIP events (hipEvent_t, created with timing) on its stream immediately before
  * and after the k_conv kernel itself -- not the k_conv_reduce of an offset-split launch -- so that the live average

@@ -50,7 +50,8 @@ def test_sort_pairs_is_the_stable_sort(dev, n, bits, distinct, desc):
 @pytest.mark.parametrize("K", [8, 27, 32])
 def test_rulebook_row_order(dev, K):
     """finalize_plan sorts the rows' keys (popcount << K | offset mask) by their low K bits, descending: rows of one mask
-    end up contiguous and in their original (site) order, whatever sits above the mask in the key."""
+    end up contiguous and in their original (site) order, whatever sits above the mask in the key.  The order of real
+    plans, in every build form, is checked in tests/test_plan_forms_gpu.py."""
     n = 50000
     rng = np.random.RandomState(K)
     masks = rng.randint(1, 1 << min(K, 31), 300, dtype=np.int64).astype(np.uint32)
