@@ -107,6 +107,9 @@ _SIGS = {
                                                 vp, c_float_p]),
     "d3d_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
                                            ctypes.c_float, vp, vp, vp, vp, vp]),
+    "d3d_fit_boxes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_fit_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, ctypes.c_size_t, vp, c_float_p]),
     "d3d_voxel_downsample_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_voxel_downsample_cells": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, ctypes.c_size_t,
                                                   c_int_p, vp]),

@@ -8,6 +8,7 @@ pieces so that one process per GPU feeds itself:
 
 There is no collective on the inference data path; training adds DistributedDataParallel's bucketed gradient all-reduce
 (RCCL over xGMI) and the small loss `reduce` for logging."""
+import os
 import time
 
 import torch
@@ -24,7 +25,8 @@ def _hip_voxelize(pcl, cfg):
     return voxelize(pcl, cfg.SPARSE3D.VOXEL_SCALE, cfg.SPARSE3D.VOXEL_FULL_SCALE)
 
 
-def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None, clean=None):
+def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, crop=None, downsample=None, clean=None,
+            fit=None):
     """data3d/data.py:15,23-35 (batch collation) for the detector: every scene [(pcl, targets), ...] is voxelised on its own
     (shifted by its own minimum, as the dataset does per scene), gets its example index as a 4th coordinate column, and
     the examples are listed one after the other.  -> (points = [coords int64 [N, 4], feats [N, F], B], [targets]).
@@ -45,9 +47,13 @@ def collate(scenes, cfg, voxelize_fn=_hip_voxelize, augment=None, normals=None, 
     clean (None, or a dict with keys among radius, min_neighbors, statistical, min_component: clean.clean_cloud's
     keywords): outliers and small detached components are removed after the cap and before the normals
     (clean.clean_cloud), so that a stray return does not move the frame; the minimum moves, so the targets are treated
-    as with `downsample`."""
+    as with `downsample`.
+    A scene whose targets are {"instance": int [N], "instance_labels": int64 [K]} (an instance id per point and a label id
+    per instance, no boxes) gets its boxes fitted on the GPU first, before the crop (primitives.targets_from_labels); they
+    are in the file's frame and are shifted like those of `crop`.  fit (None or a dict with keys among min_points,
+    min_size): that function's keywords."""
     return _collate(scenes, cfg, Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment,
-                                             voxelize_fn=voxelize_fn, clean=clean))
+                                             voxelize_fn=voxelize_fn, clean=clean, fit=fit))
 
 
 def _collate(scenes, cfg, chain):
@@ -132,7 +138,15 @@ def evaluate(cfg, dets, gts):
 
 
 def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
-    """the rank's buildings, prefetched, cycled epoch after epoch"""
+    """the rank's buildings, prefetched, cycled epoch after epoch; `files` may also hold scenes that are already in
+    memory, (pcl, targets) pairs on the device, which are cycled as they are"""
+    if len(files) and not isinstance(files[0], (str, os.PathLike)):
+        mine = list(files)[rank::world]
+        if not mine:
+            raise ValueError(f"rank {rank} of {world} has no building: {len(files)} scenes")
+        while True:
+            for pcl, tg in mine:
+                yield pcl, tg
     while True:
         pre = ScenePrefetcher(files, cfg.INPUT.CLASSES, cfg.SPARSE3D.VOXEL_SCALE, device=device, rank=rank,
                               world=world, depth=depth, shift_targets=shift_targets)
@@ -143,16 +157,19 @@ def _cycled_scenes(files, cfg, device, rank, world, depth, shift_targets=True):
 
 
 def train(model, cfg, files, device, steps, local_rank=None, log_every=0, depth=2, voxelize_fn=_hip_voxelize,
-          ims_per_gpu=1, augment=None, normals=None, crop=None, downsample=None, clean=None):
+          ims_per_gpu=1, augment=None, normals=None, crop=None, downsample=None, clean=None, fit=None):
     """`steps` iterations of data-parallel training over `files[rank::world]` (cycled): `ims_per_gpu` consecutive
     buildings per rank and step (one batch through `collate` when > 1; the global batch world x ims_per_gpu is the
     reference's IMS_PER_BATCH).  `model` must already sit on `device`; it is wrapped in DistributedDataParallel when a
     process group with more than one rank exists.  augment, normals, crop, downsample, clean: as in `collate`, for every
     building (prepare.Preparation), rank r drawing with seed + 1000003 r in `augment` and `crop`; with any of augment,
-    crop, downsample and clean the targets are read in the file's frame and follow the cloud that is voxelised.
+    crop, downsample and clean the targets are read in the file's frame and follow the cloud that is voxelised.  fit: as
+    in `collate`, for scenes that carry instance ids instead of boxes; such scenes are given in memory: `files` may be a
+    list of (pcl, targets) pairs on `device` in place of paths (with augment, crop, downsample or clean their boxes, if
+    they have any, must be in the file's frame).
     -> dict(buildings_per_s (examples/s), ms_per_step, last reduced losses)."""
     chain = Preparation(crop=crop, downsample=downsample, normals=normals, augment=augment, voxelize_fn=voxelize_fn,
-                        clean=clean)
+                        clean=clean, fit=fit)
     rank, world = _rank_world()
     ims = int(ims_per_gpu)
     if ims < 1:

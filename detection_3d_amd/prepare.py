@@ -13,7 +13,8 @@ import torch
 from .clean import apply_clean, clean_kwargs, compose_sources
 from .downsample import apply_downsample, downsample_kwargs
 from .normals import normals_kwargs, with_normals
-from .primitives import as_crop, points_in_boxes, shift_targets
+from .primitives import (as_crop, fit_kwargs, is_labelled, points_in_boxes, shift_targets,
+                         targets_from_labels)
 from .unproject import DepthFrames, unproject, unproject_kwargs
 
 # what point_ownership needs of one served input: the cloud the owners are found in (None: the input itself), raw row ->
@@ -22,11 +23,13 @@ Kept = namedtuple("Kept", "cloud source pixels")
 
 
 class Preparation(object):
-    """The keywords of the loops (unproject_kwargs, as_crop, downsample_kwargs, clean_kwargs, normals_kwargs; an augment.Augment;
-    voxelize_fn(pcl, cfg) -> (coords, feats)), checked here before anything touches a config, a model or a device."""
+    """The keywords of the loops (unproject_kwargs, as_crop, downsample_kwargs, clean_kwargs, normals_kwargs, fit_kwargs; an
+    augment.Augment; voxelize_fn(pcl, cfg) -> (coords, feats)), checked here before anything touches a config, a model or a
+    device."""
 
     def __init__(self, unproject=None, crop=None, downsample=None, normals=None, augment=None, voxelize_fn=None,
-                 clean=None):
+                 clean=None, fit=None):
+        self.fit = fit_kwargs(fit)
         self.unproject = unproject_kwargs(unproject)
         self.crop = as_crop(crop)
         self.downsample = downsample_kwargs(downsample)
@@ -72,14 +75,19 @@ class Preparation(object):
         return pcl, kept
 
     def scene(self, pcl, tg, cfg):
-        """one training or evaluation scene -> (coords, feats, targets in the frame of coords)"""
+        """one training or evaluation scene -> (coords, feats, targets in the frame of coords).  Targets of the form
+        {"instance", "instance_labels"} (a scan with an id per point) become boxes first (primitives.targets_from_labels,
+        `fit`): in the file's frame, whatever the other options say, so they are shifted after voxelisation."""
+        fitted = is_labelled(tg)
+        if fitted:
+            tg = targets_from_labels(pcl, tg["instance"], tg["instance_labels"], classes=cfg.INPUT.CLASSES, **self.fit)
         if self.crop is not None:
             pcl, tg = self.crop(pcl, tg)
         pcl, _ = self.cloud(pcl)
         if self.augment is not None:
             return self.augment(pcl, tg, cfg)
         coords, feats = self.voxelize_fn(pcl, cfg)
-        if self.targets_in_file_frame:
+        if self.targets_in_file_frame or fitted:
             tg = shift_targets(pcl, tg, cfg.SPARSE3D.VOXEL_SCALE)
         return coords, feats, tg
 

@@ -6,6 +6,8 @@ bbox3d_ops.py:850-926).
 
 `points_in_boxes` is one call on the GPU (libd3d_hip, points_in_boxes.hip) that builds no [N, K] mask; `point_lists`,
 `crop_boxes` and `random_window` are plain torch on small tensors and run on CPU tensors too; `crop_scene` composes them.
+`fit_boxes` is the inverse (box_fit.hip): the box of the points of every labelled instance, which `targets_from_labels`
+turns into training targets for scans that come with an instance id per point and no boxes.
 
 Boxes are yx_zb (xc, yc, z_bot, d3, d4, dz, yaw) with the BEV geometry of the IoU kernels: in the box frame
 lx = c (X - xc) - s (Y - yc) runs along the thickness d3, ly = s (X - xc) + c (Y - yc) along the length d4 (c, s = cos, sin
@@ -13,9 +15,12 @@ of yaw: a wall along the world's x axis has yaw +-pi/2), lz = Z - z_bot upwards.
 min-shifted frame (voxelize, scene_targets): pass origin='min' with a raw cloud."""
 import math
 
+import numpy as np
 import torch
 
 from ._lib import D3DError, check, lib, ptr, stream_of
+from .config import class_to_label
+from .scene_io import _ZERO_YAW_CLASSES
 
 MAX_BOXES = 4096
 THICKNESS_AUG = 0.3            # split_bbox's thickness_aug: the clip of the box sizes its counts are taken with
@@ -23,6 +28,8 @@ MIN_POINTS_PER_M2 = 10.0       # split_bbox: min_point_num_per1sm
 MIN_POINTS_CAP = 200.0
 MIN_POINTS_ANY = 10            # crop_bbox_by_points: fewer grown-box points than this, no box
 MIN_LENGTH = 0.2               # split_bbox step (4): min_wall_size_x
+FIT_CHUNK = 1024               # box_fit.hip kChunk: the sorted rows one workgroup of fit_boxes' sweep takes
+FIT_Q = math.pi / 65536        # fit_boxes' fine step of yaw
 
 
 def _grow(grow):
@@ -96,6 +103,191 @@ def points_in_boxes(xyz, boxes, grow=(0.0, 0.0), origin=None):
     check(lib().d3d_points_in_boxes(ptr(xyz), n, stride, ptr(o), ptr(boxes), k, g[0], g[1], ptr(owner), ptr(count),
                                     ptr(lo), ptr(hi), stream_of(dev)))
     return owner, count, lo, hi
+
+
+_FIT_TABLES = {}     # device -> (coarse, fine) fp64 [256, 2]
+
+
+def _fit_tables(dev):
+    """(cos, sin) of the 256 coarse directions a 128 Q and of the 256 fine turns (i - 128) Q, in numpy on the host: the
+    library takes them as they are, so that no device cos / sin enters a fitted box"""
+    t = _FIT_TABLES.get(dev)
+    if t is None:
+        a = np.arange(256, dtype=np.float64)
+        coarse = np.stack([np.cos(a * 128 * FIT_Q), np.sin(a * 128 * FIT_Q)], 1)
+        fine = np.stack([np.cos((a - 128) * FIT_Q), np.sin((a - 128) * FIT_Q)], 1)
+        t = _FIT_TABLES[dev] = (torch.from_numpy(coarse).to(dev), torch.from_numpy(fine).to(dev))
+    return t
+
+
+def _fit_lists(xyz, inst, k, o):
+    """the point lists of fit_boxes: a stable sort of the masked ids (k: belongs to nothing, sorts last) and the first
+    sorted position of every id -> (order int32 [N], sorted ids int32 [N], offsets int32 [k + 1]); no read-back"""
+    pos = xyz[:, :3]
+    if o is not None:
+        pos = (pos.to(torch.float64) - o).to(torch.float32)        # the kernel's own shift, for the finite test
+    ok = (inst >= 0) & (inst < k) & torch.isfinite(pos).all(1)
+    srt, order = torch.sort(torch.where(ok, inst, torch.full_like(inst, k)), stable=True)
+    offsets = torch.searchsorted(srt, torch.arange(k + 1, dtype=torch.int64, device=xyz.device)).to(torch.int32)
+    return order.to(torch.int32), srt.to(torch.int32), offsets
+
+
+def _fit_call(xyz, o, order, srt, offsets, k, yaw_free, phase_ms=None):
+    """d3d_fit_boxes on the lists of _fit_lists -> boxes, count, choice, extent; phase_ms: a ctypes float [2] that takes
+    the milliseconds of the two passes (the call then synchronises)"""
+    n, dev = xyz.shape[0], xyz.device
+    if n > 1 and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
+        xyz = xyz[:, :3].contiguous()
+    stride = xyz.stride(0) if n > 1 else max(3, xyz.stride(0))
+    free = None if yaw_free is None else yaw_free.to(dev).to(torch.uint8).contiguous()
+    boxes = torch.empty((k, 7), dtype=torch.float32, device=dev)
+    count = torch.empty((k,), dtype=torch.int32, device=dev)
+    choice = torch.empty((k, 2), dtype=torch.int32, device=dev)
+    extent = torch.empty((k, 6), dtype=torch.float32, device=dev)
+    if k > 0:
+        coarse, fine = _fit_tables(dev)
+        nbytes = lib().d3d_fit_boxes_scratch_bytes(k)
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        check(lib().d3d_fit_boxes(ptr(xyz), n, stride, ptr(o), ptr(order), ptr(srt), ptr(offsets), k, ptr(free),
+                                  ptr(coarse), ptr(fine), ptr(boxes), ptr(count), ptr(choice), ptr(extent), ptr(scratch),
+                                  nbytes, stream_of(dev), phase_ms))
+    return boxes, count, choice, extent
+
+
+def fit_boxes(xyz, instance, k=None, yaw_free=None, origin=None, return_details=False):
+    """The yx_zb box of the points of every instance: xyz fp32 [N, >= 3] on the GPU (read in place like points_in_boxes,
+    `origin` as there), instance an integer tensor [N] on the same GPU with an id in [0, k) per row; a row with a
+    negative id, an id >= k or a non-finite coordinate belongs to nothing.  k=None takes max(instance) + 1 with one host
+    read-back, an explicit k (<= 4096) issues none.  yaw_free: bool [k], None for all free; an instance that is not free
+    (floor, ceiling, room) gets yaw 0 and its sizes along the world's x and y.
+    Per instance the call sweeps 256 coarse directions over a quarter turn, then 256 fine ones around the best, and
+    keeps the one whose extents u = c x - s y, v = s x + c y enclose the smallest area (the lowest index among equals):
+    the best of 256 + 256 candidates to pi / 65536 = 0.00275 degrees, not the rotating-calipers optimum of a hull.  A free
+    box has d3 <= d4 and yaw in [-pi/2, pi/2); z_bot and dz are the points' own.  The exact arithmetic: include/d3d_hip.h,
+    d3d_fit_boxes.
+    -> boxes fp32 [k, 7], count int32 [k]; with return_details also choice int32 [k, 2] (coarse, fine index) and extent
+    fp32 [k, 6] (umin, umax, vmin, vmax, zmin, zmax of the chosen direction).  An instance without points: a zero row,
+    count 0, choice (-1, -1), extents +inf / -inf.  Only min, max and integer arithmetic: the bits depend on the set of
+    points alone, not on the order of the rows.  Runs on the current stream."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] < 3:
+        raise ValueError("xyz must be a tensor [N, >= 3]")
+    n = xyz.shape[0]
+    if (not isinstance(instance, torch.Tensor) or instance.dim() != 1 or instance.dtype.is_floating_point or
+            instance.dtype.is_complex or instance.dtype == torch.bool):
+        raise ValueError("instance must be an integer tensor [N]")
+    if instance.shape[0] != n:
+        raise ValueError(f"instance holds {instance.shape[0]} ids, xyz {n} rows")
+    if k is not None:
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"k {k} < 0")
+        if k > MAX_BOXES:
+            raise ValueError(f"{k} instances: at most {MAX_BOXES} in one call")
+    if yaw_free is not None:
+        yaw_free = torch.as_tensor(yaw_free)
+        if yaw_free.dtype != torch.bool or yaw_free.dim() != 1 or (k is not None and yaw_free.shape[0] != k):
+            raise ValueError(f"yaw_free must be a bool tensor [k], got {yaw_free.dtype} {tuple(yaw_free.shape)}")
+    if xyz.dtype != torch.float32:
+        raise ValueError(f"xyz must be float32, got {xyz.dtype}")
+    if isinstance(origin, str) and origin != "min":
+        raise ValueError(f"origin must be None, a 3-vector or 'min', got {origin!r}")
+    o = origin if origin is None or isinstance(origin, str) else _origin(origin, torch.empty(0))
+    for t in (xyz, instance):
+        if not t.is_cuda:
+            raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % t.device)
+    if instance.device != xyz.device:
+        raise ValueError(f"xyz is on {xyz.device}, instance on {instance.device}")
+    xyz, inst = xyz.detach(), instance.detach().to(torch.int64)
+    dev = xyz.device
+    if k is None:
+        k = max(int(inst.max()) + 1, 0) if n else 0
+        if k > MAX_BOXES:
+            raise ValueError(f"{k} instances: at most {MAX_BOXES} in one call")
+        if yaw_free is not None and yaw_free.shape[0] != k:
+            raise ValueError(f"yaw_free must be a bool tensor [{k}], got {tuple(yaw_free.shape)}")
+    o = _origin(o, xyz) if isinstance(o, str) else (None if o is None else o.to(dev))
+    order, srt, offsets = _fit_lists(xyz, inst, k, o)
+    boxes, count, choice, extent = _fit_call(xyz, o, order, srt, offsets, k, yaw_free)
+    return (boxes, count, choice, extent) if return_details else (boxes, count)
+
+
+def _min_size(min_size):
+    try:
+        m = [float(v) for v in min_size]
+    except TypeError:
+        raise ValueError(f"min_size must be (d3, d4, dz) in metres, got {min_size!r}") from None
+    if len(m) != 3 or not all(0.0 <= v < float("inf") for v in m):
+        raise ValueError(f"min_size must be three finite values >= 0 (d3, d4, dz), got {min_size!r}")
+    return m
+
+
+def fit_kwargs(fit):
+    """The `fit=` keyword of the loops: None -> targets_from_labels' defaults; a dict with keys among min_points,
+    min_size -> a checked copy."""
+    kw = {"min_points": MIN_POINTS_ANY, "min_size": (0.0, 0.0, 0.0)}
+    if fit is None:
+        return kw
+    if not isinstance(fit, dict):
+        raise ValueError(f"fit must be None or a dict with keys among min_points, min_size, got {fit!r}")
+    bad = sorted(set(fit) - set(kw))
+    if bad:
+        raise ValueError(f"fit: unknown keywords {bad} (min_points, min_size)")
+    kw.update(fit)
+    kw["min_points"] = int(kw["min_points"])
+    if kw["min_points"] < 0:
+        raise ValueError(f"fit: min_points {kw['min_points']} < 0")
+    kw["min_size"] = tuple(_min_size(kw["min_size"]))
+    return kw
+
+
+def is_labelled(targets):
+    """targets of the form {"instance": int [N], "instance_labels": int64 [K]}: a scan with an instance id per point
+    instead of boxes"""
+    return isinstance(targets, dict) and "instance" in targets and "instance_labels" in targets
+
+
+def targets_from_labels(pcl, instance, instance_labels, min_points=MIN_POINTS_ANY, min_size=(0, 0, 0), classes=None):
+    """Training targets of a scan that carries an instance id per point: pcl fp32 [N, >= 3] on the GPU, instance an integer
+    tensor [N] (fit_boxes), instance_labels int64 [K], the label id (config.class_to_label) of every instance, 0 for one
+    that is not a target.  classes: the config's class list (cfg.INPUT.CLASSES); the instances of its floor, ceiling and
+    room classes (scene_io._ZERO_YAW_CLASSES, which scene_targets passes through set_yaw_zero) are fitted with yaw 0;
+    None: every instance is free.  An instance is dropped when its label is 0 or it has fewer than min_points points.
+    min_size = (d3, d4, dz): smaller sizes are widened to these about the box's middle (a wall scanned from one side has no
+    thickness of its own).
+    -> {"bbox3d" fp32 [M, 7] yx_zb, "labels" int64 [M]} on the cloud's device and in the cloud's own frame."""
+    ms = _min_size(min_size)
+    min_points = int(min_points)
+    if min_points < 0:
+        raise ValueError(f"min_points {min_points} < 0")
+    labels = torch.as_tensor(instance_labels)
+    if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError("instance_labels must be an integer tensor [K]")
+    k = labels.shape[0]
+    if k > MAX_BOXES:
+        raise ValueError(f"{k} instances: at most {MAX_BOXES} in one call")
+    labels = labels.to(torch.int64)
+    fixed = []
+    if classes is not None:
+        c2l = class_to_label(classes)
+        fixed = [c2l[c] for c in _ZERO_YAW_CLASSES if c in c2l]
+    free = torch.ones(k, dtype=torch.bool, device=labels.device)
+    for f in fixed:
+        free &= labels != f
+    if isinstance(instance, torch.Tensor) and isinstance(pcl, torch.Tensor) and instance.device != pcl.device:
+        instance = instance.to(pcl.device)
+    boxes, count = fit_boxes(pcl, instance, k=k, yaw_free=free)
+    labels = labels.to(boxes.device)
+    keep = (labels > 0) & (count >= min_points)
+    if any(v > 0 for v in ms):
+        b = boxes.to(torch.float64)
+        want = torch.tensor(ms, dtype=torch.float64, device=boxes.device)
+        size = torch.maximum(b[:, 3:6], want)
+        zb = b[:, 2] + (b[:, 5] - size[:, 2]) * 0.5
+        wide = boxes.clone()
+        wide[:, 3:6] = size.to(boxes.dtype)
+        wide[:, 2] = torch.where(size[:, 2] > b[:, 5], zb.to(boxes.dtype), boxes[:, 2])
+        boxes = wide
+    return {"bbox3d": boxes[keep], "labels": labels[keep]}
 
 
 def point_lists(owner, k):

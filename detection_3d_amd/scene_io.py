@@ -152,6 +152,16 @@ def standard_to_yx_zb(boxes):
     return b
 
 
+def yx_zb_to_standard(boxes):
+    """The inverse of standard_to_yx_zb: swap the two horizontal sizes back, bottom z -> centre z, yaw + pi/2 (a yx_zb yaw
+    in [-pi/2, pi/2) lands in [0, pi)), all in float32 like the forward direction.  x, y and the sizes come back bit for
+    bit; z and yaw pass two float32 additions on the round trip."""
+    b = np.array(boxes, dtype=np.float32).reshape(-1, 7)[:, [0, 1, 2, 4, 3, 5, 6]]
+    b[:, 2] = b[:, 2] + b[:, 5] * 0.5
+    b[:, 6] += np.float32(np.pi * 0.5)
+    return b
+
+
 def set_yaw_zero(boxes):
     """Bbox3D.set_yaw_zero (utils3d/bbox3d_ops.py:178-195) for ceiling / floor / room."""
     b = np.array(boxes, dtype=np.float32).reshape(-1, 7)

@@ -223,6 +223,34 @@ int d3d_points_in_boxes(const float *xyz, int n, int row_stride_floats, const do
                         int k, float grow_yx, float grow_z, int32_t *owner, int32_t *count, float *lo, float *hi,
                         void *stream);
 
+/* Rotated boxes fitted to labelled points: per instance the yx_zb box of its points, the inverse of d3d_points_in_boxes.
+ * The best of 256 coarse and then 256 fine candidate directions by a defined sweep (to pi / 65536 = 0.00275 degrees), not
+ * the rotating-calipers optimum of a hull.  Point i as in d3d_points_in_boxes (row stride, origin_dev).  The caller lists
+ * the rows by instance: order int32 [n] (row of every sorted position), sorted_id int32 [n] (its instance), offsets int32
+ * [k + 1] (instance g owns the sorted positions offsets[g] .. offsets[g + 1] - 1; positions from offsets[k] on belong to
+ * nothing).  Rows with a non-finite coordinate must not be listed.  coarse_dev, fine_dev: device fp64 [256, 2] (cos, sin)
+ * of a 128 Q and of (i - 128) Q, Q = M_PI / 65536, made on the host, so that no device cos / sin enters the result.
+ *   direction: coarse a: c = float(C[a].cos), s = float(C[a].sin); fine (a, i): c = float(Ca Fc - Sa Fs),
+ *     s = float(Sa Fc + Ca Fs), products and sums separate fp64 operations;
+ *   extents: u = c x - s y, v = s x + c y in fp32 without contraction, a zero always as +0; umin, umax, vmin, vmax over
+ *     the instance's rows; area = (double(umax) - double(umin)) (double(vmax) - double(vmin));
+ *   choice: the coarse a of the smallest area, then the fine i around it, the lowest index among equals; an instance with
+ *     yaw_free[g] == 0 (uint8 [k]; NULL: all free) takes a = 0, i = 128;
+ *   box, in fp64 and rounded once: t = 128 a + i - 128, theta = t Q; eu, ev the extents' lengths, mu, mv their middles;
+ *     xc = c mu + s mv, yc = -s mu + c mv; free and eu > ev: d3 = ev, d4 = eu, yaw = theta + pi / 2, otherwise d3 = eu,
+ *     d4 = ev, yaw = theta; yaw >= pi / 2 loses pi; z_bot = zmin, dz = zmax - zmin.
+ * Outputs: boxes fp32 [k, 7], count int32 [k], choice int32 [k, 2] (a, i), extent fp32 [k, 6] (umin, umax, vmin, vmax,
+ * zmin, zmax of the chosen direction).  An instance without rows: a zero box, count 0, choice (-1, -1), extents +inf / -inf.
+ * Only min, max and integer arithmetic touch shared memory, so the result depends on the set of rows alone, not on their
+ * order.  0 <= k <= 4096 (k == 0 touches nothing), n >= 0; scratch of d3d_fit_boxes_scratch_bytes(k) bytes (0 for a k out
+ * of range).  Asynchronous, no read-back.  phase_ms_host (NULL: none): two floats, the milliseconds of pass 1 and of pass 2
+ * (accumulator fill, sweep and pick each) between device events; the call then synchronises.                          */
+size_t d3d_fit_boxes_scratch_bytes(int k);
+int d3d_fit_boxes(const float *xyz, int n, int row_stride_floats, const double *origin_dev, const int32_t *order,
+                  const int32_t *sorted_id, const int32_t *offsets, int k, const uint8_t *yaw_free,
+                  const double *coarse_dev, const double *fine_dev, float *boxes, int32_t *count, int32_t *choice,
+                  float *extent, void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* Voxel down-sampling of a raw scan: one row per occupied voxel, every column the mean over the voxel's points
  * (data3d/suncg_utils/suncg_preprocess.py:748-767, open3d.voxel_down_sample(pcd, voxel_size=0.02)).  A restatement of
  * open3d's VoxelDownSample that is not pinned against open3d itself.  pcl fp32 [n, ncols], 3 <= ncols <= 16, contiguous,
