@@ -421,7 +421,7 @@ __device__ __forceinline__ void hash_find_n(const HashEntry *__restrict__ tab, i
   }
 }
 
-// The cell list of a raw cloud (built in normals.hip; consumers: normals.hip, clean.hip): the points sorted by cell
+// The cell list of a raw cloud (built in normals.hip; consumers: normals.hip, clean.hip, planes.hip): the points sorted by cell
 // (cells of edge 1.0001 r about the per-axis minimum, so that a neighbour within r is never two cells away; order
 // (x, y, z, original index)), the 60-bit cell key of every sorted position and an open-addressing table
 // cell -> [first, last) of the sorted positions.  A namespace of its own: downsample.hip has cells of another width.

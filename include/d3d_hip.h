@@ -202,6 +202,43 @@ size_t d3d_connected_components_scratch_bytes(int n);
 int d3d_connected_components(const float *xyz, int n, int row_stride_floats, float radius, int32_t *label, int32_t *size,
                              void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* Planar patches of a cloud that carries normals, and the plane of every patch: what lies between "a cloud with normals"
+ * and "an instance id per point" for the planar classes.  Pairwise region growing, not RANSAC: a smoothly curved surface
+ * chains into one patch, and the points on the crease between two planes carry mixed normals and fall into small patches.
+ *
+ * d3d_segment_planes: d3d_connected_components with a narrower edge.  xyz, n, radius, scratch, phase_ms_host[5] as there;
+ * normals fp32 [n, 3] contiguous.  Points P and C are joined iff all three hold, d = C - P, everything in fp32 without
+ * contraction:
+ *   (dx dx + dy dy) + dz dz <= radius * radius, by comparison of the bits;
+ *   |(nPx nCx + nPy nCy) + nPz nCz| >= cos_min (the caller rounds cos(angle) from fp64 once; a normal's sign is free);
+ *   |(nPx dx + nPy dy) + nPz dz| <= offset and |(nCx dx + nCy dy) + nCz dz| <= offset.
+ * Each test is bitwise symmetric in P and C (products commute, d negates exactly, the absolute values are equal), so the
+ * components are those of an undirected graph.  Each is a "passes if": a zero or non-finite normal and a NaN position
+ * fail it and leave the point a patch of its own.  label[i] = the smallest row index of i's patch, size[i] = its number
+ * of points.  0 <= cos_min <= 1, 0 <= offset < inf.  The same input gives the same bits.                               */
+size_t d3d_segment_planes_scratch_bytes(int n);
+int d3d_segment_planes(const float *xyz, int n, int row_stride_floats, const float *normals, float radius, float cos_min,
+                       float offset, int32_t *label, int32_t *size, void *scratch, size_t scratch_bytes, void *stream,
+                       float *phase_ms_host);
+/* d3d_fit_planes: the least-squares plane of every patch.  plane_of_point int32 [n]: the plane of every row in [0, k), or
+ * -1; the caller lists the rows by (plane, row) as for d3d_fit_boxes: order int32 [n], offsets int32 [k + 1]; a listed row
+ * whose plane_of_point is not the list's plane is skipped.  Per plane, in fp64: the origin o is its first listed row;
+ * q = p - o; the count m, sum q and sum q q^T are taken over chunks of 1024 listed rows (thread t of 256 adds rows t,
+ * t + 256, ... of the chunk, the lanes are added pairwise, the waves in order), then over the chunks in order: no float
+ * atomics, the same input gives the same bits.  centroid = o + sum q / m; C = sum q q^T / m - mean mean^T; normal = the
+ * unit eigenvector of C's smallest eigenvalue (cyclic Jacobi, as d3d_estimate_normals), its component of largest
+ * magnitude positive (ties: lowest axis); d = (nx cx + ny cy) + nz cz; eigenvalues ascending: the normal's Rayleigh
+ * quotient and the two of C restricted to the plane across it; rms = sqrt(max(smallest, 0)).  A plane whose largest
+ * eigenvalue is not positive (one point, coincident points): normal, d, rms and eigenvalues 0.  A plane without rows:
+ * count 0 and zeros.  Outputs fp64: normal [k, 3], d [k], centroid [k, 3], rms [k], eigenvalues [k, 3]; count int32 [k].
+ * 0 <= k <= 4096 (k == 0 touches nothing), 0 <= n <= 2^28; scratch of d3d_fit_planes_scratch_bytes(n, k) bytes (0 when
+ * out of range).  Asynchronous, no read-back.  phase_ms_host (NULL: none): two floats, the milliseconds of the moments
+ * and of the solve; the call then synchronises.                                                                        */
+size_t d3d_fit_planes_scratch_bytes(int n, int k);
+int d3d_fit_planes(const float *xyz, int n, int row_stride_floats, const int32_t *plane_of_point, const int32_t *order,
+                   const int32_t *offsets, int k, double *normal, double *d, double *centroid, int32_t *count, double *rms,
+                   double *eigenvalues, void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* The points of each rotated box (Bbox3D.points_in_bbox, utils3d/bbox3d_ops.py:731-755; the counts of split_bbox,
  * data3d/indoor_data_util.py:244-254; the extents of crop_bbox_by_points, bbox3d_ops.py:873-878), without an [n, k] mask.
  * Point i = the first three floats of row xyz + i * row_stride_floats (>= 3: an [n, 9] cloud is read in place); with
