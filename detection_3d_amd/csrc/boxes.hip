@@ -260,8 +260,9 @@ __device__ __forceinline__ void load_box(const IouArgs &a, const float *base, in
   } else {
     const float *b = base + (size_t)idx * 7;
     const float cy = is_row ? a.aug[0] : a.aug[2], cz = is_row ? a.aug[1] : a.aug[3];
-    xc = b[0]; yc = b[1]; d0 = fmaxf(b[3], cy); d1 = b[4]; ang = b[6];
-    const float dz = fmaxf(b[5], cz);
+    // torch.clamp(min=) of boxes_iou_3d: a NaN size stays NaN (fmaxf would replace it by the bound)
+    xc = b[0]; yc = b[1]; d0 = b[3] < cy ? cy : b[3]; d1 = b[4]; ang = b[6];
+    const float dz = b[5] < cz ? cz : b[5];
     r.z0 = b[2];
     r.z1 = b[2] + dz;  // rotate_nms_3d_torch.py:15-16
   }
@@ -273,13 +274,19 @@ __device__ __forceinline__ void load_box(const IouArgs &a, const float *base, in
     r.lo[d] = fminf(fminf(r.q.p[d], r.q.p[2 + d]), fminf(r.q.p[4 + d], r.q.p[6 + d]));
     r.hi[d] = fmaxf(fmaxf(r.q.p[d], r.q.p[2 + d]), fmaxf(r.q.p[4 + d], r.q.p[6 + d]));
   }
+  // point_in_quad takes a point as inside when its projections on the edges AB and AD fall within them.  An edge without
+  // length (a size of 0) bounds nothing: corners of a box far away count as inside, and inter() of such a pair is not 0.
+  // A box with such an edge gets a NaN bounding box, so that iou_pair's early-out never applies to it.
+  const float ab0 = r.q.p[2] - r.q.p[0], ab1 = r.q.p[3] - r.q.p[1], ad0 = r.q.p[6] - r.q.p[0], ad1 = r.q.p[7] - r.q.p[1];
+  if (!(ab0 * ab0 + ab1 * ab1 > 0.f && ad0 * ad0 + ad1 * ad1 > 0.f))
+    r.lo[0] = r.lo[1] = r.hi[0] = r.hi[1] = __builtin_nanf("");
 }
 
 // one entry of the matrix: row box rb (target / "boxes"), column box cb (anchor / "query")
 __device__ __forceinline__ float iou_pair(const IouArgs &a, const BoxRec &rb, const BoxRec &cb) {
   // kernel order (nms_gpu.py:605-611): rbox1 = query (col), rbox2 = box (row).  Most pairs of an anchors x targets
-  // matrix are far apart: their bounding boxes do not touch and the intersection is exactly 0 (NaN corners compare
-  // false and take the full path)
+  // matrix are far apart: their bounding boxes do not touch and the intersection is exactly 0 (NaN corners and the NaN
+  // bounds of a box with a zero size compare false and take the full path)
   const bool apart = cb.hi[0] < rb.lo[0] || rb.hi[0] < cb.lo[0] || cb.hi[1] < rb.lo[1] || rb.hi[1] < cb.lo[1];
   float v = iou_eval(cb.q, cb.d0, cb.d1, rb.q, rb.d0, rb.d1, a.criterion, PrivatePts(), apart);
   bool same = true;  // check_same_boxes, nms_gpu.py:653-664
@@ -287,9 +294,12 @@ __device__ __forceinline__ float iou_pair(const IouArgs &a, const BoxRec &rb, co
   for (int d = 0; d < 5; d++) same = same && (fabsf(rb.raw[d] - cb.raw[d]) < (float)1e-6);
   if (same) v = 1.f;
   if (a.mode == 1 && !a.only_xy) {
+    // iou_one_dim's torch.min / torch.max (rotate_nms_3d_torch.py:18-19): a NaN bound makes overlap and common NaN (fminf /
+    // fmaxf would drop it).  z0 = NaN or dz = NaN both leave z1 = NaN, so testing z1 covers the box.
+    const bool znan = cb.z1 != cb.z1 || rb.z1 != rb.z1;
     const float overlap = fminf(cb.z1, rb.z1) - fmaxf(cb.z0, rb.z0);
     const float common = fmaxf(cb.z1, rb.z1) - fminf(cb.z0, rb.z0);
-    v = v * (overlap / common);
+    v = v * (znan ? __builtin_nanf("") : overlap / common);
   }
   return v;
 }
@@ -785,8 +795,11 @@ struct MatchArgs {
   int off[kMatchMaxSeg + 1];  // GT rows of segment s: [off[s], off[s + 1])
 };
 
-__device__ __forceinline__ unsigned f2ord(float f) {    // order-preserving float -> unsigned (NaN with sign 0 on top)
+// order-preserving float -> unsigned; a NaN of either sign is the top value (q.max(1) is NaN if any quality of the row is),
+// which ord2f gives back as a NaN
+__device__ __forceinline__ unsigned f2ord(float f) {
   const unsigned u = __float_as_uint(f);
+  if (f != f) return 0xffffffffu;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float ord2f(unsigned u) {

@@ -4,7 +4,9 @@ images; data3d/data.py:15,23-35 collation).
 (1)-(2) d3d_match_segments -- IoU + Matcher + box_encode of every (example, class group) segment in one launch set --
 against the same steps in tensor ops (boxes_iou_3d + Matcher + box_encode, tests/helpers.py) once per segment;
 (3) the sparse RoI backward with example ids against the dense backward of the B-example map;
-(4) a duplicated batch [A, A] against the single example A; (5) heterogeneous batches train; (6) the driver."""
+(4) a duplicated batch [A, A] against the single example A; (5) heterogeneous batches train; (6) the driver.
+d3d_match_segments against results that do not come from the library's own IoU (exact qualities, every Matcher rule, tie
+order, size edges of the launch): tests/test_match_forms_gpu.py."""
 import math
 
 import numpy as np

@@ -53,6 +53,7 @@ def test_empty_and_ragged_shapes(dev):
 
 
 def test_boxes_iou_3d_flags(dev):
+    # exact values at the tile edges, on touching / clamped / z-disjoint pairs and non-finite fields: tests/test_match_forms_gpu.py
     from detection_3d_amd import box_ops
     t, _ = make_boxes(2, 97)
     a, _ = make_boxes(3, 1030)
