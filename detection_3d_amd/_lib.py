@@ -111,6 +111,13 @@ _SIGS = {
     "d3d_fit_planes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_fit_planes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp,
                                       ctypes.c_size_t, vp, c_float_p]),
+    "d3d_nearest_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_nearest": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp,
+                                   ctypes.c_size_t, vp, c_float_p]),
+    "d3d_icp_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "d3d_icp": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int,
+                               ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp, vp, vp, vp, vp,
+                               ctypes.c_size_t, vp, c_float_p]),
     "d3d_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
                                            ctypes.c_float, vp, vp, vp, vp, vp]),
     "d3d_fit_boxes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),

@@ -435,16 +435,41 @@ __device__ __forceinline__ uint64_t cell_key(uint32_t x, uint32_t y, uint32_t z)
   return ((uint64_t)x << (2 * kCellBits)) | ((uint64_t)y << kCellBits) | (uint64_t)z;
 }
 
+// The table slot of a cell key: all 60 bits mixed, linear probing.  hash_key is made for the grids' packed key: it
+// keeps bits 0, 16 and 32 out of the mix and uses them as the position inside a group of 8 slots.  In a cell key those
+// are z's bit 0 and bits of y and z that a building never sets, so its cells share two of the eight positions; a scan
+// of 500 k points in 329 k cells puts 229 k keys into the 131 k slots of one position, and every key past that and
+// every lookup of an empty cell then walks a whole round of 131 k probes.
+__device__ __forceinline__ uint32_t cell_slot(uint64_t c, int cap) {
+  c ^= c >> 33;
+  c *= 0xff51afd7ed558ccdULL;
+  c ^= c >> 33;
+  c *= 0xc4ceb9fe1a85ec53ULL;
+  c ^= c >> 33;
+  return (uint32_t)c & (uint32_t)(cap - 1);
+}
+
+// the slot that holds cell `c`, inserted if absent (the table has at least twice as many slots as there are cells)
+__device__ __forceinline__ int cell_insert(HashEntry *tab, int cap, uint64_t c) {
+  uint32_t slot = cell_slot(c, cap);
+  while (true) {
+    unsigned long long prev = atomicCAS((unsigned long long *)&tab[slot].key, (unsigned long long)kEmptyKey,
+                                        (unsigned long long)c);
+    if (prev == kEmptyKey || prev == c) return (int)slot;
+    slot = (slot + 1) & (uint32_t)(cap - 1);
+  }
+}
+
 // [first, last) of a cell, (0, 0) when it holds no point
 __device__ __forceinline__ int2 cell_range(const HashEntry *__restrict__ tab, int cap, uint64_t c) {
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  uint32_t slot = hash_key(c) & (uint32_t)(cap - 1), round = 0;
+  uint32_t slot = cell_slot(c, cap);
   while (true) {
     const u32x4 e = *(const u32x4 *)&tab[slot];
     const uint64_t k = ((uint64_t)e[1] << 32) | e[0];
     if (k == c) return make_int2((int)e[2], (int)e[3]);
     if (k == kEmptyKey) return make_int2(0, 0);
-    slot = probe_next(slot, round, cap);
+    slot = (slot + 1) & (uint32_t)(cap - 1);
   }
 }
 
@@ -453,6 +478,9 @@ struct CellList {
   const uint64_t *key = nullptr;   // [n] cell key of every sorted position
   const HashEntry *tab = nullptr;  // [cap] key -> (val = first, first = last) of the cell's sorted positions
   int cap = 0;
+  // what a point of another cloud needs to find its cell, floor((q - min) / h) per axis in fp64 (register.hip)
+  const uint32_t *red = nullptr;   // [3] f32_ordered image of the per-axis minimum (device)
+  double h = 0.0;                  // cell edge, (double)radius * 1.0001
 };
 
 int table_cap(int n);

@@ -88,7 +88,7 @@ __global__ void k_nrm_table(const uint64_t *__restrict__ key, int n, HashEntry *
   const uint64_t c = key[k];
   const bool head = k == 0 || key[k - 1] != c, tail = k == n - 1 || key[k + 1] != c;
   if (!head && !tail) return;
-  const int slot = hash_insert(tab, cap, c);
+  const int slot = cell_insert(tab, cap, c);
   if (head) tab[slot].val = k;
   if (tail) tab[slot].first = (uint32_t)(k + 1);
 }
@@ -369,6 +369,8 @@ int build(const float *xyz, int n, int stride, float radius, Arena &A, hipStream
   out->key = key;
   out->tab = tab;
   out->cap = cap;
+  out->red = red;
+  out->h = (double)radius * 1.0001;
   return D3D_OK;
 }
 

@@ -1,0 +1,264 @@
+"""Aligning overlapping scans.  Every other step from raw sensor data to the detector's input (unproject, scan_mesh,
+voxel_downsample, clean_cloud, estimate_normals, segment_planes, fit_boxes) takes a cloud that is already in one frame,
+while a building is scanned from many stations whose poses are good to a few centimetres and degrees: enough to double
+every wall.  The reference's users align the stations with open3d's registration_icp on the CPU; here it is a call on
+the GPU (libd3d_hip, register.hip), built on a query of one cloud's cell list by the points of another.
+
+Semantics (include/d3d_hip.h), restatements that are not pinned against open3d itself.  nearest: the cloud
+row with the smallest (d2, row) among those with d2 = (dx dx + dy dy) + dz dz <= radius^2 in fp32, estimate_normals'
+test.  icp: Gauss-Newton steps on the point-to-plane (or point-to-point) residuals of the pairs nearest finds within
+max_dist, sums in fp64 in a fixed order, a 6 x 6 Cholesky solve on the device; pose = [R t; 0 1] with x' = R x + t
+mapping source into the target's frame.  The same input gives the same bits, whatever torch's deterministic mode says."""
+import ctypes
+import math
+import warnings
+
+import torch
+
+from ._lib import D3DError, check, lib, ptr, stream_of
+from .clean import _as_int, _check_radius, _scratch, _xyz
+from .clean import PHASES as NEAREST_PHASES
+from .downsample import _normal_col
+
+ICP_PHASES = ("cells", "sort", "table", "transform", "nearest", "accumulate", "solve")
+METHODS = {"plane": 0, "point": 1}
+HISTORY_COLS = 20
+SYSTEM_SIZE = 29
+MAX_ITERATIONS = 10000
+STATUS = {0: "iterations exhausted", 1: "converged", 2: "degenerate"}
+
+
+def nearest(query_xyz, cloud_xyz, radius=0.1, return_dist2=False, phases=False):
+    """query_xyz fp32 [M, >= 3], cloud_xyz fp32 [N, >= 3] on the GPU (column slices of wider clouds are read in place)
+    -> index int32 [M]: the row of the cloud nearest to every query among those within `radius`, ties to the lowest row,
+    -1 when there is none or the query is not finite; with return_dist2 also that squared distance, fp32 [M], +inf for
+    none.  Current stream, no read-back.  phases: also a dict of milliseconds (cells, sort, table, search, tail), timed
+    with events inside the library; synchronises."""
+    radius = _check_radius(radius)
+    query, m, qstride = _xyz(query_xyz)
+    cloud, n, cstride = _xyz(cloud_xyz)
+    if query.device != cloud.device:
+        raise ValueError(f"nearest: query on {query.device}, cloud on {cloud.device}")
+    dev = query.device
+    index = torch.empty((m,), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((m,), dtype=torch.float32, device=dev) if return_dist2 else None
+    ms = (ctypes.c_float * len(NEAREST_PHASES))() if phases else None
+    if m > 0:
+        nbytes = lib().d3d_nearest_scratch_bytes(n, m)
+        scratch = _scratch(nbytes, dev)
+        with torch.cuda.device(dev):
+            check(lib().d3d_nearest(ptr(cloud), n, cstride, ptr(query), m, qstride, radius, ptr(index), ptr(dist2),
+                                    ptr(scratch), nbytes, stream_of(dev), ms))
+    res = (index,) + ((dist2,) if return_dist2 else ())
+    if phases:
+        res += (dict(zip(NEAREST_PHASES, (float(v) for v in ms))),)
+    return res[0] if len(res) == 1 else res
+
+
+def _check_pose(pose, what):
+    """-> fp64 [4, 4] on the CPU, finite, last row (0, 0, 0, 1)"""
+    try:
+        p = torch.as_tensor(pose).detach().to("cpu", torch.float64)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: a 4 x 4 matrix, got {pose!r}")
+    if p.shape != (4, 4):
+        raise ValueError(f"{what}: a 4 x 4 matrix, got shape {tuple(p.shape)}")
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError(f"{what}: entries must be finite")
+    if p[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+        raise ValueError(f"{what}: the last row must be (0, 0, 0, 1), got {p[3].tolist()}")
+    return p
+
+
+def apply_pose(pcl, pose, normal_col="auto"):
+    """pcl [N, C >= 3], columns 0:3 the position; pose 4 x 4, x' = R x + t -> a copy of the cloud with the position moved
+    and the normal columns rotated (normal_col as voxel_downsample takes it: 'auto' is 6 when C == 9, else none).  fp64
+    arithmetic, one rounding to the cloud's type.  Plain torch: it also runs on CPU tensors."""
+    if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2 or pcl.shape[1] < 3:
+        raise ValueError("apply_pose: a tensor [N, >= 3]")
+    if not pcl.dtype.is_floating_point:
+        raise ValueError(f"apply_pose: a floating-point cloud, got {pcl.dtype}")
+    if isinstance(pose, torch.Tensor) and pose.is_cuda and pose.shape == (4, 4):
+        T = pose.detach().to(pcl.device, torch.float64)          # a registration's pose: no read-back
+    else:
+        T = _check_pose(pose, "apply_pose: pose").to(pcl.device)
+    nc = _normal_col(normal_col, pcl.shape[1])
+    R, t = T[:3, :3], T[:3, 3]
+    out = pcl.detach().clone()
+    out[:, :3] = (pcl[:, :3].to(torch.float64) @ R.T + t).to(pcl.dtype)
+    if nc >= 0:
+        out[:, nc:nc + 3] = (pcl[:, nc:nc + 3].to(torch.float64) @ R.T).to(pcl.dtype)
+    return out
+
+
+def inverse_pose(pose):
+    """the inverse of a rigid pose [R t; 0 1]: [R^T, -R^T t; 0 1], fp64, on the pose's device"""
+    T = pose.detach().to(torch.float64) if isinstance(pose, torch.Tensor) else _check_pose(pose, "inverse_pose")
+    out = torch.eye(4, dtype=torch.float64, device=T.device)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return out
+
+
+class Registration:
+    """What icp returns.  pose fp64 [4, 4], state int32 [2] = (steps, status) and history fp64 [iterations, 20] (per
+    executed step the pose after it, the pairs c, the squared error e, |w|, |v|; NaN past `steps`) stay on the device;
+    the properties read them back on first use.  With return_details also last_index int32 [M] (the target row of every
+    source row in the last executed step, -1: none) and last_system fp64 [29] (its A, b, e, c); phases: the dict of
+    milliseconds, when asked for."""
+
+    def __init__(self, pose, state, history, last_index=None, last_system=None, phases=None):
+        self.pose, self.state, self.history = pose, state, history
+        self.last_index, self.last_system, self.phases = last_index, last_system, phases
+        self._host = None
+
+    def _read(self):
+        if self._host is None:
+            steps, status = (int(v) for v in self.state.cpu())
+            last = self.history[steps - 1].cpu().tolist() if steps > 0 else None
+            self._host = (steps, status, last)
+        return self._host
+
+    @property
+    def steps(self):
+        return self._read()[0]
+
+    @property
+    def status(self):
+        """0: the iterations ran out, 1: converged, 2: degenerate (fewer than 6 pairs, or a vanished pivot)"""
+        return self._read()[1]
+
+    @property
+    def converged(self):
+        return self._read()[1] == 1
+
+    @property
+    def inliers(self):
+        """the pairs of the last executed step"""
+        last = self._read()[2]
+        return int(last[16]) if last else 0
+
+    @property
+    def rmse(self):
+        """sqrt(e / c) of the last executed step, at the pose before it; NaN without a pair"""
+        last = self._read()[2]
+        return math.sqrt(last[17] / last[16]) if last and last[16] > 0 else float("nan")
+
+    def __repr__(self):
+        steps, status, _ = self._read()
+        return f"Registration(steps={steps}, status={status} ({STATUS.get(status)}), inliers={self.inliers}, rmse={self.rmse:.6g})"
+
+
+def _check_icp(max_dist, iterations, tol, method, init):
+    max_dist = _check_radius(max_dist)
+    iterations = _as_int(iterations, "iterations")
+    if iterations > MAX_ITERATIONS:
+        raise ValueError(f"iterations {iterations} > {MAX_ITERATIONS}")
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"tol {tol!r} must be a number")
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError(f"tol {tol} must be finite and not negative")
+    if method not in METHODS:
+        raise ValueError(f"method {method!r}: 'plane' or 'point'")
+    pose = torch.eye(4, dtype=torch.float64) if init is None else _check_pose(init, "init")
+    return max_dist, iterations, tol, method, pose
+
+
+def icp(source, target, target_normals=None, init=None, max_dist=0.1, iterations=30, tol=1e-6, method="plane",
+        normal_radius=0.1, max_nn=50, return_details=False, phases=False):
+    """source fp32 [M, >= 3], target fp32 [N, >= 3] on the GPU -> Registration: the pose that maps source onto target,
+    from `init` (4 x 4, default identity) by at most `iterations` Gauss-Newton steps over the pairs within max_dist;
+    stops when the step's rotation vector and translation are both at most `tol` long (status 1) or the system is
+    degenerate (status 2, the pose stays).  method 'plane' needs the target's normals: target_normals fp32 [N, >= 3], or
+    columns 6:9 of a nine-column target, or estimate_normals(target, normal_radius, max_nn).  All steps are enqueued on
+    the current stream at once and nothing is read back.  Bad arguments raise ValueError before any GPU work."""
+    max_dist, iterations, tol, method, pose = _check_icp(max_dist, iterations, tol, method, init)
+    if method == "plane" and target_normals is None:
+        from .normals import _check_args
+        _check_args(normal_radius, max_nn, None)
+    if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[1] < 3:
+        raise ValueError("xyz must be a tensor [N, >= 3]")
+    own_normals = method == "plane" and target_normals is None and target.shape[1] == 9
+    src, m, sstride = _xyz(source)
+    tgt, n, tstride = _xyz(target)
+    if src.device != tgt.device:
+        raise ValueError(f"icp: source on {src.device}, target on {tgt.device}")
+    dev = src.device
+    nrm, nstride = None, 3
+    if method == "plane":
+        if target_normals is not None:
+            nrm, nn, nstride = _xyz(target_normals)
+            if nn != n or nrm.device != dev:
+                raise ValueError(f"icp: target_normals [{nn}, ..] on {nrm.device} for a target of {n} rows on {dev}")
+        elif own_normals:
+            nrm, _, nstride = _xyz(target[:, 6:9])
+        else:
+            from .normals import estimate_normals
+            nrm = estimate_normals(tgt, normal_radius, max_nn)
+    pose = pose.to(dev)
+    state = torch.zeros((2,), dtype=torch.int32, device=dev)
+    history = torch.full((iterations, HISTORY_COLS), float("nan"), dtype=torch.float64, device=dev)
+    last_index = torch.full((m,), -1, dtype=torch.int32, device=dev) if return_details else None
+    last_system = torch.zeros((SYSTEM_SIZE,), dtype=torch.float64, device=dev) if return_details else None
+    ms = (ctypes.c_float * len(ICP_PHASES))() if phases else None
+    nbytes = lib().d3d_icp_scratch_bytes(n, m)
+    scratch = _scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        check(lib().d3d_icp(ptr(src), m, sstride, ptr(tgt), n, tstride, ptr(nrm), nstride, max_dist, METHODS[method],
+                            iterations, tol, ptr(pose), ptr(history), ptr(state), ptr(last_index), ptr(last_system),
+                            ptr(scratch), nbytes, stream_of(dev), ms))
+    return Registration(pose, state, history, last_index, last_system,
+                        dict(zip(ICP_PHASES, (float(v) for v in ms))) if phases else None)
+
+
+def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=None, seed=0, **icp_kw):
+    """clouds: fp32 [N_i, C] GPU tensors of one width, each in its own frame; init_poses: None or one 4 x 4 (or None) per
+    cloud, its rough pose in the reference's frame -> (cloud, poses).  The scans are taken in order; each one is
+    registered (icp, **icp_kw) to the voxel-down-sampled union of the reference and the scans placed so far, moved with
+    apply_pose and added to the union.  cloud: the union through apply_downsample(voxel, max_points, seed), ready for
+    prepare_cloud / BuildingPipeline.map; poses: fp64 [4, 4] device tensors, the identity for the reference.  One
+    read-back per registration (its state); a registration that does not converge raises a warning and its pose is
+    used as it stands."""
+    from .downsample import apply_downsample, downsample_kwargs
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError("merge_scans: no clouds")
+    try:
+        ok = not isinstance(reference, bool) and int(reference) == reference and 0 <= int(reference) < len(clouds)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"merge_scans: reference {reference!r} is not one of the {len(clouds)} clouds")
+    reference = int(reference)
+    if init_poses is None:
+        init_poses = [None] * len(clouds)
+    init_poses = list(init_poses)
+    if len(init_poses) != len(clouds):
+        raise ValueError(f"merge_scans: {len(init_poses)} poses for {len(clouds)} clouds")
+    init_poses = [None if p is None else _check_pose(p, "merge_scans: init_poses") for p in init_poses]
+    for c in clouds:
+        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != clouds[0].shape[1] or c.shape[1] < 3:
+            raise ValueError("merge_scans: tensors [N, C >= 3] of one width")
+    bad = sorted(set(icp_kw) - {"max_dist", "iterations", "tol", "method", "normal_radius", "max_nn"})
+    if bad:                           # target_normals and init among them: the target and the start differ per scan
+        raise ValueError(f"merge_scans: unknown icp keywords {bad}")
+    _check_icp(icp_kw.get("max_dist", 0.1), icp_kw.get("iterations", 30), icp_kw.get("tol", 1e-6),
+               icp_kw.get("method", "plane"), None)
+    model_kw = downsample_kwargs({"voxel": voxel})
+    final_kw = downsample_kwargs({"voxel": voxel, "max_points": max_points, "seed": seed})
+    union = clouds[reference]
+    dev = union.device
+    poses = [None] * len(clouds)
+    poses[reference] = torch.eye(4, dtype=torch.float64, device=dev)
+    for i, scan in enumerate(clouds):
+        if i == reference:
+            continue
+        reg = icp(scan, apply_downsample(union, model_kw), init=init_poses[i], **icp_kw)
+        if not reg.converged:
+            warnings.warn(f"merge_scans: scan {i} did not converge ({STATUS.get(reg.status)} after {reg.steps} steps, "
+                          f"{reg.inliers} pairs)")
+        poses[i] = reg.pose
+        union = torch.cat([union, apply_pose(scan, reg.pose)])
+    return apply_downsample(union, final_kw), poses

@@ -239,6 +239,51 @@ int d3d_fit_planes(const float *xyz, int n, int row_stride_floats, const int32_t
                    const int32_t *offsets, int k, double *normal, double *d, double *centroid, int32_t *count, double *rms,
                    double *eigenvalues, void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* Aligning overlapping scans (the reference's users call open3d's compute_point_cloud_distance and registration_icp on
+ * the CPU; restatements that are not pinned against open3d itself).
+ *
+ * d3d_nearest: for every query row the nearest row of another cloud within radius.  cloud and query are read as
+ * d3d_estimate_normals reads xyz (fp32, row i at base + i * stride floats, stride >= 3).  The cloud's cell list is
+ * queried by the foreign points: the query's cell is floor((double(q) - min) / h) per axis, the list's own arithmetic,
+ * clamped to [-1, 2^20 - 1], and the 27 cells around it are searched.  A cloud row competes with
+ * d2 = (dx dx + dy dy) + dz dz, dx = C.x - Q.x, in fp32 without contraction, iff d2 <= radius * radius (fp32 product) by
+ * comparison of the bits as unsigned integers; the winner is the minimum of (bits of d2, row), so a tie goes to the lowest
+ * row.  index int32 [m]: that row, or -1; dist2 fp32 [m] (or NULL): that d2, or +inf.  A query with a non-finite
+ * coordinate gets -1 / +inf; a cloud row with a non-finite coordinate is never a neighbour.  0 <= n, m <= 2^28; n == 0
+ * gives -1 / +inf throughout, m == 0 touches nothing.  Asynchronous, no read-back, no atomics: numpy in fp32 reproduces
+ * every bit.  scratch: d3d_nearest_scratch_bytes(n, m).  phase_ms_host: NULL, or [5] as d3d_radius_neighbors (the last
+ * one 0); the call then synchronises.                                                                                 */
+size_t d3d_nearest_scratch_bytes(int n_cloud, int n_query);
+int d3d_nearest(const float *cloud, int n, int row_stride_floats, const float *query, int m, int query_stride_floats,
+                float radius, int32_t *index, float *dist2, void *scratch, size_t scratch_bytes, void *stream,
+                float *phase_ms_host);
+/* d3d_icp: up to `iterations` Gauss-Newton steps of ICP from the pose in pose_inout_dev (device, 16 doubles, row-major
+ * 4 x 4; x' = R x + t maps source into the target's frame; the last row is carried along untouched), without a host
+ * read-back in between.  The target's cell list (cells of max_dist) is built once.  Per step and source row, p the row
+ * widened to fp64:
+ *   p'_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k; the query is fp32(p'), j = d3d_nearest(query, target, max_dist);
+ *   method 0 (point to plane), q = target[j], n = target_normals[j] widened: r = ((p'_0 - q_0) n_0 + (p'_1 - q_1) n_1) +
+ *     (p'_2 - q_2) n_2, J = (p' x n, n); a normal that is not finite or is zero contributes nothing;
+ *   method 1 (point to point): the residuals p' - q with the rows (-[p']x, I); target_normals may be NULL;
+ *   A += J^T J (21 entries, upper triangle by rows), b += J^T r, e += r r, c += 1 per contributing row: 29 fp64 sums, per
+ *   block of 4096 rows (thread t of 256 adds rows t, t + 256, ... in order, lanes pairwise, waves in order), then the
+ *   blocks in order: no float atomics, the same input gives the same bits.
+ * A xi = -b by Cholesky, xi = (w, v).  Degenerate (c < 6, or a pivot <= 1e-12 of A's largest diagonal entry): the pose
+ * stays, status 2.  Otherwise dR = Rodrigues(w), R <- dR R, t <- dR t + v; |w| <= tol and |v| <= tol: status 1.  Once
+ * the status is non-zero the remaining steps' kernels return at once.
+ *   history_dev fp64 [iterations, 20]: one row per executed step: the 16 pose entries after it, c, e, |w|, |v| (0, 0 for a
+ *     degenerate step); the other rows are not touched;
+ *   state_dev int32 [2] = (steps executed, status 0 running out of iterations / 1 converged / 2 degenerate);
+ *   last_index int32 [m] or NULL, last_system fp64 [29] or NULL: j (-1: none) and the 29 sums of the last executed step.
+ * 0 <= iterations <= 10000, tol >= 0.  scratch: d3d_icp_scratch_bytes(n, m).  phase_ms_host: NULL, or [7] = milliseconds
+ * of the list's cell coordinates, sorts and table, then of the transform, nearest, accumulate and solve kernels summed
+ * over the steps; the call then synchronises.                                                                         */
+size_t d3d_icp_scratch_bytes(int n_target, int n_source);
+int d3d_icp(const float *source, int m, int source_stride_floats, const float *target, int n, int target_stride_floats,
+            const float *target_normals, int normal_stride_floats, float max_dist, int method, int iterations, double tol,
+            double *pose_inout_dev, double *history_dev, int32_t *state_dev, int32_t *last_index, double *last_system,
+            void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* The points of each rotated box (Bbox3D.points_in_bbox, utils3d/bbox3d_ops.py:731-755; the counts of split_bbox,
  * data3d/indoor_data_util.py:244-254; the extents of crop_bbox_by_points, bbox3d_ops.py:873-878), without an [n, k] mask.
  * Point i = the first three floats of row xyz + i * row_stride_floats (>= 3: an [n, 9] cloud is read in place); with
