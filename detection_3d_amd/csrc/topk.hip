@@ -7,7 +7,8 @@
 //
 // torch.topk / numpy's argsort leave the order among EQUAL scores to the implementation (and sigmoid saturates to exactly
 // 1.0 for large logits, so ties are not exotic).  Here it is defined -- descending score, lower index first -- and
-// oracle/detector_port.py follows the same rule.  One 1024-thread workgroup per segment:
+// oracle/detector_port.py follows the same rule (the stable argsort of -scores: -0.0 and +0.0 are equal scores, a NaN of
+// either sign comes last; topk_key below).  One 1024-thread workgroup per segment:
 //   1. radix select (11 + 11 + 10 bits, histograms in LDS) of the k-th largest order-preserving key T;
 //   2. every element above T, and of those equal to T the ones with the lowest indices, collected into LDS as
 //      (key << 32 | ~index) words;
@@ -47,6 +48,17 @@ struct TopkArgs {
                             // and re-read by the later ones with 16-byte loads (elements of other examples: key 0)
   int n4;
 };
+
+// The selection key of a value: its order-preserving image, canonical where the defined order (the stable argsort of
+// -scores) does not follow the bits -- a zero of either sign takes +0.0's key (-0.0 == +0.0: the index decides), a NaN of
+// either sign takes key 1 and sorts last, behind -inf (key 0x007fffff, the smallest of all other keys).  Key 0 stays
+// "element of another example".  Integer tests: no float mode can fold a denormal into the zero test.
+__device__ __forceinline__ uint32_t topk_key(float v) {
+  const uint32_t mag = __float_as_uint(v) & 0x7fffffffu;
+  if (mag > 0x7f800000u) return 1u;
+  if (mag == 0u) return 0x80000000u;
+  return f32_ordered(v);
+}
 
 __device__ __forceinline__ float topk_value(const TopkArgs &a, int i, int g) {
   float x = a.vals[(size_t)g * a.group_stride + (size_t)i * a.elem_stride];
@@ -98,14 +110,14 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_select(TopkArgs a) {
   const int n = a.n;
   auto valid = [&](int i) { return a.example == nullptr || a.example[i] == b; };
 
-  // Key of element i: the order-preserving image of its value, at least 1; 0 marks an element of another example.
+  // Key of element i: topk_key of its value, at least 1; 0 marks an element of another example.
   // With key scratch the values are read (and the sigmoid evaluated) ONCE: the first pass stores the keys, the later
   // ones re-read them four per 16-byte load with 16 loads in flight per thread -- one workgroup walking ~10^5 elements
   // one dependent load at a time is bound by that load's latency (measured: 100 us for 150 k anchors, all four passes).
   uint32_t *const kbuf = a.keys ? a.keys + (size_t)seg * a.n4 : nullptr;
   auto key_of = [&](int i) -> uint32_t {
     if (!valid(i)) return 0u;
-    return max(f32_ordered(topk_value(a, i, g)), 1u);
+    return topk_key(topk_value(a, i, g));
   };
   // f(key, index) over all elements, in batches of independent loads
   auto for_each_key = [&](auto f) {
@@ -193,7 +205,7 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_select(TopkArgs a) {
           for (int j = 0; j < 4; j++) {
             float v = x[u][j];
             if (a.apply_sigmoid) v = 1.0f / (1.0f + expf(-v));
-            kv[j] = ok[u][j] ? max(f32_ordered(v), 1u) : 0u;
+            kv[j] = ok[u][j] ? topk_key(v) : 0u;
           }
           if (q < nq) *(u32x4 *)(kbuf + (size_t)q * 4) = kv;
 #pragma unroll
@@ -321,7 +333,9 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_select(TopkArgs a) {
     const unsigned long long w = sel[r];
     const int i = (int)(~(uint32_t)w);
     const size_t o = (size_t)seg * a.k + r;
-    if (a.use_min) {          // the list is sorted: the elements above min_value are a prefix
+    // the list is sorted and NaN sorts last (topk_key): the elements above min_value are a prefix, so exactly one row
+    // sees its end (or row 0 sees that it is empty) and counts[seg] has a single writer
+    if (a.use_min) {
       const float v = topk_value(a, i, g);
       const bool in = v > a.min_value;
       bool next_in = false;

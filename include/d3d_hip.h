@@ -1004,7 +1004,8 @@ int d3d_rotate_nms_3d_batched(const float *boxes, const int32_t *order, int stri
  * boxlist_nms_3d, structures/boxlist_ops_3d.py:14-62, with its size clamp): boxes [n,7] yx_zb and scores [n] in any order.
  * Candidates = the pre_max_size best scores (<= 0: all; at most d3d_topk_max()); descending score, and among EQUAL scores
  * the lower index first -- torch.topk / numpy argsort (nms_cpu.py:37) leave that order open, here and in the oracle port
- * it is defined.  Sizes clamped for the IoU only (dy, dx >= aug_yx, dz >= aug_z); greedy rotated NMS at `thresh`; at
+ * it is defined: the stable argsort of -scores, under which -0.0 and +0.0 are EQUAL scores (the index decides) and a NaN
+ * of either sign comes last, behind -inf.  Sizes clamped for the IoU only (dy, dx >= aug_yx, dz >= aug_z); greedy rotated NMS at `thresh`; at
  * most post_max_size survivors (<= 0: all).  keep_out int64 [min(n, pre_max_size)] = indices into the input in selection
  * order (the LongTensor the reference returns); n_keep_dev device int32 [1]; n_keep_host (NULL: no read-back) receives
  * the count after one stream synchronisation.  scratch >= d3d_rotate_nms_3d_scratch_bytes(pre_max_size, 0); with
@@ -1018,7 +1019,8 @@ size_t d3d_rotate_nms_3d_scratch_bytes(int pre_max_size, int n);   /* n = input 
  * n_examples x n_groups segments in ONE launch.  Segment s = example * n_groups + group reads element i at
  * vals[group * group_stride + i * elem_stride] (apply_sigmoid: 1 / (1 + exp(-x)) first, inference_3d.py:105) over the
  * elements with example[i] == its example (example NULL when n_examples == 1), keeps the k best (k <= d3d_topk_max();
- * descending, equal scores: lower index first) and writes rows [s * k, s * k + min(k, elements)) of the outputs: element
+ * descending, equal scores: lower index first; -0.0 and +0.0 are equal scores, a NaN of either sign sorts last, behind
+ * -inf, and is never > min_value) and writes rows [s * k, s * k + min(k, elements)) of the outputs: element
  * indices (idx32_out = i * idx_map[0] + idx_map[1] + group * idx_map[2], idx_map_host NULL: i; idx64_out = i), scores
  * and -- when props_out is given -- the decoded boxes BoxCoder3D.decode(reg[i * reg_stride + 7 group .. + 7],
  * anchors[i]) with unit weights (box_coder_3d.py:38-65, inference_3d.py:123).  counts_out int32 [segments] =
