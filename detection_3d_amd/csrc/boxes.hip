@@ -1187,7 +1187,12 @@ __global__ __launch_bounds__(256) void k_post_gather(const int32_t *__restrict__
 // `keep = cls_scores >= image_thresh`, ties at the threshold all stay.  For every selected t: the box, the score and
 // the label (box index % nc).  The D-th largest is found by a 4 x 8-bit radix select on the order-preserving integer
 // image of the floats (exact), the compaction by a workgroup scan.
+// The keys follow the tensor spelling of the same cut (torch.sort, clamp_min(0), >=) on every float: -0.0 ranks and
+// compares as 0.0 (it stays), a NaN of either sign ranks above +inf and is never selected, and when the D-th largest is a
+// NaN nothing is (`s >= NaN`).
 static constexpr int kSelMax = 8192, kSelThreads = 1024;
+static constexpr uint32_t kSelNanKey = 0xffffffffu;
+__device__ __forceinline__ uint32_t post_key(float v) { return v != v ? kSelNanKey : f32_ordered(v + 0.f); }
 __global__ __launch_bounds__(kSelThreads) void k_post_select(const int32_t *__restrict__ keep,
                                                              const int32_t *__restrict__ nk, int nseg, int n_max,
                                                              const float *__restrict__ prob_flat,
@@ -1202,7 +1207,7 @@ __global__ __launch_bounds__(kSelThreads) void k_post_select(const int32_t *__re
   const int N = nseg * n_max;
   for (int t = tid; t < N; t += kSelThreads) {
     const bool valid = (t % n_max) < nk[t / n_max];
-    key[t] = f32_ordered(valid ? prob_flat[keep[t]] : -1.f);
+    key[t] = post_key(valid ? prob_flat[keep[t]] : -1.f);
   }
   uint32_t thresh_key = f32_ordered(0.f);     // s >= 0: every survivor
   if (D > 0 && D < N) {
@@ -1240,7 +1245,7 @@ __global__ __launch_bounds__(kSelThreads) void k_post_select(const int32_t *__re
   const int per = (N + kSelThreads - 1) / kSelThreads;
   const int t0 = min(N, tid * per), t1 = min(N, t0 + per);
   uint32_t mine = 0;
-  for (int t = t0; t < t1; t++) mine += key[t] >= thresh_key;
+  for (int t = t0; t < t1; t++) mine += key[t] >= thresh_key && key[t] != kSelNanKey;
   uint32_t incl = mine;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -1254,7 +1259,7 @@ __global__ __launch_bounds__(kSelThreads) void k_post_select(const int32_t *__re
   if (tid == kSelThreads - 1)   // out_n may be a pinned host word: system-scope release, like k_gather_kept's count
     __hip_atomic_store(out_n, (int32_t)(pos + mine), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   for (int t = t0; t < t1; t++) {
-    if (key[t] < thresh_key) continue;
+    if (key[t] < thresh_key || key[t] == kSelNanKey) continue;
     const int f = keep[t];
 #pragma unroll
     for (int j = 0; j < 7; j++) out_boxes[(size_t)pos * 7 + j] = boxes[(size_t)f * 7 + j];

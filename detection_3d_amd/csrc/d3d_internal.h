@@ -187,7 +187,7 @@ __device__ __forceinline__ void box_decode_one(const float *e, const float *a, c
 #pragma unroll
   for (int k = 0; k < 7; k++) t[k] = e[k] / w[k];
 #pragma unroll
-  for (int k = 3; k < 6; k++) t[k] = fminf(t[k], clip);
+  for (int k = 3; k < 6; k++) t[k] = t[k] > clip ? clip : t[k];   // torch.clamp(max=): a NaN stays (fminf drops it)
   const float xa = a[0], ya = a[1], za = a[2], wa = a[3], la = a[4], ha = a[5], ra = a[6];
   const float diagonal = sqrtf(la * la + wa * wa);
   o[0] = t[0] * diagonal + xa;
