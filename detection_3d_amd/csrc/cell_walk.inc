@@ -1,6 +1,7 @@
-// The walk over the cell list of normals.hip with the query left open, and the lock-free union-find over the sorted
-// positions with its labelling tail (consumers: clean.hip, planes.hip).  Included inside namespace d3d's anonymous
-// namespace, after `using namespace celllist`: every translation unit gets its own instantiations.
+// The one walk over a cloud's cell list (celllist.hip) with the query left open, the nearest-k cut that the queries
+// share and the host-side phase timer (consumers: normals.hip, clean.hip, planes.hip; register.hip takes the constants
+// and helpers for a walk of its own).  Included inside namespace d3d's anonymous namespace, after
+// `using namespace celllist`: every translation unit gets its own instantiations.
 
 constexpr int kThreads = 128;                     // 16 lane groups of 8, one query per group at a time
 constexpr int kGroup = 8;
@@ -13,16 +14,19 @@ struct Ranges {     // the 27 neighbour cells' candidates: positions in `pts` an
 };
 
 // f(C, pos) for the candidates of one query that lane gl of its group takes: l, l + 8, ... of every cell, cells in a
-// fixed order; pos is the candidate's sorted position
+// fixed order; pos is the candidate's sorted position.  The inner loop runs over the index that it loads from (the LDS
+// copy's or the sorted points'), with pos as an offset from it: counted from 0 with two bases added, the compiler puts a
+// longer dispatch between the unrolled loop and its remainder in front of every cell, and the normals at 1 M points
+// took 3 % longer (DESIGN 6d)
 template <bool STAGED, class F>
 __device__ __forceinline__ void for_candidates(const float4 *__restrict__ pts, const float4 *cand, const Ranges &R, int gl,
                                                F f) {
 #pragma unroll 1                      // unrolled 27-fold, the count query took 255 registers and one wave per SIMD
   for (int r = 0; r < 27; r++) {
-    const int len = R.ge[r] - R.gb[r];
-    for (int t = gl; t < len; t += kGroup) {
-      const float4 C = STAGED ? cand[R.lb[r] + t] : pts[R.gb[r] + t];
-      f(C, R.gb[r] + t);
+    const int b = STAGED ? R.lb[r] : R.gb[r], e = b + (R.ge[r] - R.gb[r]), shift = R.gb[r] - b;
+    for (int t = b + gl; t < e; t += kGroup) {
+      const float4 C = STAGED ? cand[t] : pts[t];
+      f(C, t + shift);
     }
   }
 }
@@ -32,39 +36,63 @@ __device__ __forceinline__ uint32_t dist2_bits(float4 C, float4 P) {
   return __float_as_uint((dx * dx + dy * dy) + dz * dz);
 }
 
-// Lock-free union-find over the sorted positions.  par[x] <= x always and only ever decreases, every value it takes is a
-// member of x's component, and every access inside the linking kernel is a device-scope atomic, so that no CU works on
-// a cached copy.  Nothing here waits for another thread's store: a failed compare-and-swap returns the value that beat
-// it, and the loop goes on from that value, strictly downwards.
-__device__ __forceinline__ int uf_load(int32_t *par, int x) {
-  return __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int uf_find(int32_t *par, int x) {
-  while (true) {                        // path halving; x strictly decreases
-    const int p = uf_load(par, x);
-    if (p == x) return x;
-    const int g = uf_load(par, p);
-    if (g == p) return p;
-    atomicMin(par + x, g);
-    x = g;
-  }
-}
-__device__ __forceinline__ void uf_unite(int32_t *par, int a, int b) {
-  while (true) {                        // a + b strictly decreases
-    a = uf_find(par, a);
-    b = uf_find(par, b);
-    if (a == b) return;
-    const int hi = max(a, b), lo = min(a, b);
-    const int old = atomicCAS(par + hi, hi, lo);      // hook a root under the lower id
-    if (old == hi) return;
-    a = old;                            // hi had been hooked meanwhile: go on from its parent
-    b = lo;
-  }
+__device__ __forceinline__ int group_sum(int c) {
+#pragma unroll
+  for (int o = kGroup / 2; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+  return c;
 }
 
-// k_nrm_search's walk with the query left open.  One workgroup per kSpan sorted queries.  The span is walked cell by
-// cell: the 27 neighbour cells' ranges come from the table, their points are staged into LDS once (when they fit) and
-// every query of the cell in the span reuses them.
+// The nearest-`want` cut of one query's candidates by (d2, j), j the original index, for its whole lane group:
+//   keep(d2, j) = d2 < T or (d2 == T and j <= J): T the want-th smallest d2 (bits of a non-negative float order like
+//   the float), J the cut among the candidates tied at T.
+// T enters as the bits of r2 and J leaves as 0x7fffffff unless ties had to be cut; returns the number kept,
+// min(candidates within r, want).  d2 <= r2 <=> bits(d2) <= bits(r2); a NaN distance has larger bits than any finite r2
+// and is never kept.  The counts do not depend on scheduling, so every lane of the group takes the same path.
+template <bool STAGED>
+__device__ __forceinline__ int nearest_cut(const float4 *__restrict__ pts, const float4 *cand, const Ranges &R, float4 P,
+                                           int gl, int want, int n, uint32_t &T, int &J) {
+  auto count_kept = [&](uint32_t t, int j) {
+    int c = 0;
+    for_candidates<STAGED>(pts, cand, R, gl, [&](float4 C, int) {
+      const uint32_t u = dist2_bits(C, P);
+      c += (u < t || (u == t && __float_as_int(C.w) <= j)) ? 1 : 0;
+    });
+    return group_sum(c);
+  };
+  J = 0x7fffffff;
+  int m = count_kept(T, J);
+  if (m > want) {
+    uint32_t lo = 0, hi = T;          // invariant: count(d2 <= hi) = m_hi >= want
+    int m_hi = m;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      const int c = count_kept(mid, J);
+      if (c >= want) {
+        hi = mid;
+        m_hi = c;
+      } else {
+        lo = mid + 1;
+      }
+    }
+    T = hi;
+    if (m_hi > want) {                // ties at T: the smallest J with count(.., J) >= want, then exactly `want`
+      int jl = 0, jh = n - 1;
+      while (jl < jh) {
+        const int mid = jl + (jh - jl) / 2;
+        if (count_kept(T, mid) >= want) jh = mid;
+        else jl = mid + 1;
+      }
+      J = jh;
+    }
+    m = want;
+  }
+  return m;
+}
+
+// The walk, with the query left open: Q::run<STAGED>(pts, cand, R, q, P, gl) is one query (sorted position q, point P)
+// by lane gl of one lane group.  One workgroup per kSpan sorted queries.  The span is walked cell by cell: the 27
+// neighbour cells' ranges come from the table, their points are staged into LDS once (when they fit) and every query of
+// the cell in the span reuses them.
 template <class Q>
 __global__ __launch_bounds__(kThreads) void k_cln_walk(const float4 *__restrict__ pts, const uint64_t *__restrict__ key,
                                                        int n, const HashEntry *__restrict__ tab, int cap, Q query) {
@@ -121,59 +149,6 @@ __global__ __launch_bounds__(kThreads) void k_cln_walk(const float4 *__restrict_
     __syncthreads();
     k = e;
   }
-}
-
-// ---- connected components: after the linking ----
-__global__ void k_cln_iota(int32_t *par, int n) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) par[k] = k;
-}
-
-// root of every sorted position (par is only read here), and per root the smallest original index and the point count:
-// integer min and add, which commute.  A wave first gathers the lanes that share a root, so that a component of a
-// whole building does not send one atomic per point to one address.
-__global__ __launch_bounds__(256) void k_cln_roots(const int32_t *__restrict__ par, const float4 *__restrict__ pts, int n,
-                                                   int32_t *root, int32_t *min_index, int32_t *size) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  bool active = k < n;
-  int r = -1, idx = 0x7fffffff;
-  if (active) {
-    r = k;
-    while (true) {
-      const int p = par[r];
-      if (p == r) break;
-      r = p;
-    }
-    root[k] = r;
-    idx = __float_as_int(pts[k].w);
-  }
-  unsigned long long todo = __ballot(active);
-  while (todo) {                      // uniform over the wave; every round retires at least its leader
-    const int leader = __ffsll((long long)todo) - 1;
-    const int lr = __shfl(r, leader, 64);
-    const bool same = active && r == lr;
-    const unsigned long long m = __ballot(same);
-    int v = same ? idx : 0x7fffffff;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s, 64));
-    if (lane == leader) {
-      atomicAdd(size + lr, __popcll(m));
-      atomicMin(min_index + lr, v);
-    }
-    todo &= ~m;
-    active = active && !same;
-  }
-}
-
-__global__ void k_cln_labels(const int32_t *__restrict__ root, const float4 *__restrict__ pts, int n,
-                             const int32_t *__restrict__ min_index, const int32_t *__restrict__ csize, int32_t *label,
-                             int32_t *size) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const int i = __float_as_int(pts[k].w), r = root[k];
-  label[i] = min_index[r];
-  size[i] = csize[r];
 }
 
 // ---- host side ----

@@ -3,11 +3,11 @@
 // three of open3d's remove_radius_outlier, remove_statistical_outlier (on a hybrid search) and a clustering pass that
 // the reference's users run on the CPU; restatements, not pinned against open3d.
 //
-// All three are consumers of the cell list of normals.hip (celllist::build, d3d_internal.h) and walk it as
-// k_nrm_search does: one workgroup per kSpan sorted queries, the span cell by cell, the 27 neighbour cells staged into
-// LDS when they hold at most kBudget points and read from global memory otherwise, one query per lane group of 8 (the
-// walk, the union-find and its labelling tail: cell_walk.inc, shared with planes.hip).
-// Distances are one_query's: d2 = (dx dx + dy dy) + dz dz in fp32 from the fp32 offset, d2 <= r2 by bit comparison.
+// All three are consumers of the cell list (celllist::build, celllist.hip) and queries of the one walk over it
+// (cell_walk.inc): one workgroup per kSpan sorted queries, the span cell by cell, the 27 neighbour cells staged into
+// LDS when they hold at most kBudget points and read from global memory otherwise, one query per lane group of 8.  The
+// union-find and its labelling tail: union_find.inc, shared with planes.hip.
+// Distances are dist2_bits': d2 = (dx dx + dy dy) + dz dz in fp32 from the fp32 offset, d2 <= r2 by bit comparison.
 // No float atomics, every sum in an order fixed by the data: the same input gives the same bits.
 #include "d3d_internal.h"
 
@@ -19,15 +19,10 @@ namespace {
 
 using namespace celllist;
 #include "cell_walk.inc"
+#include "union_find.inc"
 
 constexpr int kStatRows = 1024;                   // rows per block of the statistics' first launch
 constexpr int kStatThreads = 256;
-
-__device__ __forceinline__ int group_sum(int c) {
-#pragma unroll
-  for (int o = kGroup / 2; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-  return c;
-}
 
 // count[i] = the points within r of point i, itself included
 struct CountQuery {
@@ -45,8 +40,7 @@ struct CountQuery {
 };
 
 // mean[i] = (sum of sqrt(double(d2)) over the k + 1 nearest candidates by (d2, j), the point itself among them) / k,
-// found[i] = the kept candidates - 1; found < k: mean = +inf.  The cut is one_query's (normals.hip):
-//   keep(d2, j) = d2 < T or (d2 == T and j <= J): T the (k+1)-th smallest d2, J the cut among the candidates tied at T.
+// found[i] = the kept candidates - 1; found < k: mean = +inf.  The cut is nearest_cut's (cell_walk.inc), want = k + 1.
 struct KnnQuery {
   uint32_t r2_bits;
   int k, n;
@@ -55,43 +49,9 @@ struct KnnQuery {
   template <bool STAGED>
   __device__ __forceinline__ void run(const float4 *__restrict__ pts, const float4 *cand, const Ranges &R, int q, float4 P,
                                       int gl) const {
-    auto count_kept = [&](uint32_t T, int J) {
-      int c = 0;
-      for_candidates<STAGED>(pts, cand, R, gl, [&](float4 C, int) {
-        const uint32_t u = dist2_bits(C, P);
-        c += (u < T || (u == T && __float_as_int(C.w) <= J)) ? 1 : 0;
-      });
-      return group_sum(c);
-    };
-    const int want = k + 1;
     uint32_t T = r2_bits;
-    int J = 0x7fffffff;
-    int m = count_kept(T, J);
-    if (m > want) {
-      uint32_t lo = 0, hi = T;          // invariant: count(d2 <= hi) = m_hi >= want
-      int m_hi = m;
-      while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        const int c = count_kept(mid, J);
-        if (c >= want) {
-          hi = mid;
-          m_hi = c;
-        } else {
-          lo = mid + 1;
-        }
-      }
-      T = hi;
-      if (m_hi > want) {                // ties at T: the smallest J with count(.., J) >= want, then exactly `want`
-        int jl = 0, jh = n - 1;
-        while (jl < jh) {
-          const int mid = jl + (jh - jl) / 2;
-          if (count_kept(T, mid) >= want) jh = mid;
-          else jl = mid + 1;
-        }
-        J = jh;
-      }
-      m = want;
-    }
+    int J;
+    const int m = nearest_cut<STAGED>(pts, cand, R, P, gl, k + 1, n, T, J);
     double s = 0.0;                     // lane order, then the lanes pairwise: fixed by the data
     for_candidates<STAGED>(pts, cand, R, gl, [&](float4 C, int) {
       const uint32_t u = dist2_bits(C, P);

@@ -421,8 +421,16 @@ __device__ __forceinline__ void hash_find_n(const HashEntry *__restrict__ tab, i
   }
 }
 
-// The cell list of a raw cloud (built in normals.hip; consumers: normals.hip, clean.hip, planes.hip): the points sorted by cell
-// (cells of edge 1.0001 r about the per-axis minimum, so that a neighbour within r is never two cells away; order
+// Stable radix sorts by the z, the y and then the x digit of a cell coordinate (celllist.hip; callers: celllist::build,
+// downsample.hip): the order (x, y, z, index).  perm_a holds 0, 1, 2, ... on entry; cz and cy are sorted over `bits`
+// bits, cx over `x_bits`; ktmp [n] takes the gathered digits.  The final order is left in perm_b (d3d_voxel_downsample_rows
+// finds it there again); perm_a is free afterwards.  Every sort's temporaries come from `A` and are released again:
+// `A.used` is on return what it was.
+int sort_cells_zyx(const uint32_t *cx, const uint32_t *cy, const uint32_t *cz, int32_t *perm_a, int32_t *perm_b,
+                   uint32_t *ktmp, int n, int bits, int x_bits, Arena &A, hipStream_t s);
+
+// The cell list of a raw cloud (built in celllist.hip; consumers: normals.hip, clean.hip, planes.hip, register.hip): the
+// points sorted by cell (cells of edge 1.0001 r about the per-axis minimum, so that a neighbour within r is never two cells away; order
 // (x, y, z, original index)), the 60-bit cell key of every sorted position and an open-addressing table
 // cell -> [first, last) of the sorted positions.  A namespace of its own: downsample.hip has cells of another width.
 namespace celllist {

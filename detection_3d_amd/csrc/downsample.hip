@@ -92,11 +92,6 @@ __global__ void k_ds_cells(const float *__restrict__ pcl, int n, int C, const ui
   iota[i] = i;
 }
 
-__global__ void k_ds_gather(const uint32_t *__restrict__ src, const int32_t *__restrict__ perm, int n, uint32_t *dst) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) dst[k] = src[perm[k]];
-}
-
 __global__ void k_ds_keys(const int32_t *__restrict__ perm, const uint32_t *__restrict__ cx,
                           const uint32_t *__restrict__ cy, const uint32_t *__restrict__ cz, int n, uint64_t *key) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -389,18 +384,9 @@ int d3d_voxel_downsample_cells(const float *pcl, int n, int ncols, double voxel,
   hipLaunchKernelGGL(k_ds_cells, grid1d(n), dim3(256), 0, s, pcl, n, ncols, (const uint32_t *)info_u, voxel, L.cx, L.cy,
                      L.cz, L.perm_a, L.info);
   D3D_LAUNCH_CHECK();
-  // least significant digit first; every sort is stable and starts from 0, 1, 2, ...: the final order is (x, y, z, index)
-  rc = sort_pairs_u32(L.cz, nullptr, L.perm_a, L.perm_b, n, kCellBits, A, s, false);
+  // the order (x, y, z, index) into perm_b; the x digit is one bit wider: a dropped row carries kDropX
+  rc = sort_cells_zyx(L.cx, L.cy, L.cz, L.perm_a, L.perm_b, L.ktmp, n, kCellBits, kCellBits + 1, A, s);
   if (rc) return rc;
-  A.used = mark;
-  hipLaunchKernelGGL(k_ds_gather, grid1d(n), dim3(256), 0, s, (const uint32_t *)L.cy, (const int32_t *)L.perm_b, n, L.ktmp);
-  rc = sort_pairs_u32(L.ktmp, nullptr, L.perm_b, L.perm_a, n, kCellBits, A, s, false);
-  if (rc) return rc;
-  A.used = mark;
-  hipLaunchKernelGGL(k_ds_gather, grid1d(n), dim3(256), 0, s, (const uint32_t *)L.cx, (const int32_t *)L.perm_a, n, L.ktmp);
-  rc = sort_pairs_u32(L.ktmp, nullptr, L.perm_a, L.perm_b, n, kCellBits + 1, A, s, false);
-  if (rc) return rc;
-  A.used = mark;
   hipLaunchKernelGGL(k_ds_keys, grid1d(n), dim3(256), 0, s, (const int32_t *)L.perm_b, (const uint32_t *)L.cx,
                      (const uint32_t *)L.cy, (const uint32_t *)L.cz, n, L.key);
   // cx, cy, cz, ktmp and perm_a are free from here on

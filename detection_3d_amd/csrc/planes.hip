@@ -1,7 +1,7 @@
 // Planar patches of a cloud that carries normals, and the plane of every patch (include/d3d_hip.h).
 //
 // d3d_segment_planes is d3d_connected_components (clean.hip) with a narrower edge: the same cell list, the same walk
-// (cell_walk.inc) and the same lock-free union-find, but two points within r are joined only when their normals agree
+// (cell_walk.inc) and the same lock-free union-find (union_find.inc), but two points within r are joined only when their normals agree
 // and each lies in the other's tangent plane.  Pairwise region growing, not RANSAC: a smoothly curved surface chains into
 // one patch.  The three tests are bitwise symmetric in the two points (products commute, C - P = -(P - C) exactly,
 // the absolute values are equal), so linking only towards lower sorted positions gives the components of an undirected
@@ -25,6 +25,7 @@ namespace {
 
 using namespace celllist;
 #include "cell_walk.inc"
+#include "union_find.inc"
 #include "eigen3.inc"
 
 constexpr int kMaxPlanes = 4096;      // box_fit.hip's kMaxBoxes: label_planes hands the patches to d3d_fit_boxes

@@ -2,9 +2,9 @@
 // (what the reference's users do with open3d's compute_point_cloud_distance and registration_icp on the CPU;
 // restatements that are not pinned against open3d itself).
 //
-// k_reg_nearest queries the cell list of normals.hip (celllist::build) by the points of ANOTHER cloud, in the queries'
-// own order: the query's cell is floor((q - min) / h) per axis in fp64, the build's arithmetic, clamped to
-// [-1, kCellMax]; the 27 cells around it hold every cloud point within the radius.  Distances are one_query's:
+// k_reg_nearest queries a cloud's cell list (celllist::build, celllist.hip) by the points of ANOTHER cloud, in the
+// queries' own order: the query's cell is floor((q - min) / h) per axis in fp64, the build's arithmetic, clamped to
+// [-1, kCellMax]; the 27 cells around it hold every cloud point within the radius.  Distances are dist2_bits':
 // d2 = (dx dx + dy dy) + dz dz in fp32 from the fp32 offset C - Q, compared as unsigned integers; the minimum is taken
 // over (bits of d2, original row), so a tie goes to the lowest row and the order of the candidates does not show.
 //

@@ -123,6 +123,22 @@ def test_dense_cell_beyond_the_staging_budget(dev):
     _check(got_n, got_c, _ref("dense", xyz, tie_scale="cut"), what="dense cell + scene(4000, 0)")
 
 
+@pytest.mark.parametrize("k", [7, 49])
+def test_normals_and_cleaning_keep_the_same_neighbours(dev, k):
+    """The three cell-list queries share one notion of "kept": the normals' count at max_nn = k + 1 is the k nearest
+    neighbours that knn_mean_distance found plus the point itself, and both are the radius count capped at k + 1, on
+    the staged path (the scene) and the unstaged one (the dense cell)."""
+    from detection_3d_amd.clean import knn_mean_distance, radius_neighbors
+    xyz = np.concatenate([_scene(4000, 0), dense_patch(3000, 5)])
+    t = torch.from_numpy(xyz).to(dev)
+    counts = _run(dev, xyz, max_nn=k + 1)[1]
+    found = knn_mean_distance(t, k=k, radius=0.1)[1].cpu().numpy()
+    within = radius_neighbors(t, radius=0.1).cpu().numpy()
+    assert (within < k + 1).any() and (within > k + 1).any() and (within[4000:] > 1024).all()
+    assert np.array_equal(counts, found + 1)
+    assert np.array_equal(counts, np.minimum(within, k + 1))
+
+
 def test_two_copies_500_m_apart(dev):
     from detection_3d_amd._lib import lib
     a = _scene(4000, 0)
