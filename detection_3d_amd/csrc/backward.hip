@@ -34,6 +34,10 @@ __global__ void k_pack_weight_t(const float *__restrict__ w, int fv, int cin, in
   packed[t] = co < cout ? w[((size_t)k * cin + ci) * cout + co] : 0.f;
 }
 
+void launch_pack_weight_t(const float *w, int fv, int cin, int cout, int cp, int flip, float *packed, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_weight_t, grid1d((long)fv * cp * cin), dim3(256), 0, s, w, fv, cin, cout, cp, flip, packed);
+}
+
 static constexpr int kDwBlocksPerWg = 64;
 static constexpr int kDwTargetWgs = 1024;
 static constexpr int kDwMaxChunk = 8;
@@ -823,7 +827,7 @@ __global__ void k_input_backward(const float *__restrict__ d_out, int planes, co
   for (int j = b; j < e; j++) d_in[(size_t)idx[j] * planes + c] = g;
 }
 
-// d3d_bn_backward / _dt for storage type T (float, or bf16 as raw 16-bit words): fp32 arithmetic, fp64 partial sums
+// d3d_bn_backward_dt for storage type T (float, or bf16 as raw 16-bit words): fp32 arithmetic, fp64 partial sums
 template <typename T>
 static int bn_backward_t(const T *in, const T *out, const T *d_out, T *d_in, int rows, int planes, const float *save_mean,
                          const float *save_invstd, const float *weight, float *d_weight, float *d_bias, float leakiness,
@@ -881,183 +885,64 @@ using namespace d3d;
 
 extern "C" {
 
-int d3d_pack_conv_weight_transposed(const float *w, int fv, int cin, int cout, int flip, float *packed,
-                                    void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  size_t n = d3d_packed_weight_floats(fv, cout, cin);
-  D3D_REQUIRE(w && packed && n > 0, "pack_conv_weight_transposed: bad arguments (Cin=%d Cout=%d)", cin, cout);
-  int cp = (int)(n / ((size_t)fv * cin));
-  long total = (long)n;
-  hipLaunchKernelGGL(k_pack_weight_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout, cp,
-                     flip, packed);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
-}
-
-// fp32 rows (D3D_F32, or D3D_F32_X3: dInput through launch_conv_dt, dWeight exact either way)
-static int subm_backward_f32(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
-                             const void *packed_wt_flipped, int cout, const float *d_out, float *d_in, float *d_weight,
-                             int dtype, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && size && filt, "null argument");
-  for (int d = 0; d < 3; d++) D3D_REQUIRE(filt[d] % 2 == 1, "submanifold backward needs odd filter sizes");
-  int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
-  if (rc) return rc;
-  const Plan *p = find_plan(m, 0, size, filt, nullptr);
-  if (d_in) {
-    rc = launch_conv_dt(m, *p, d_out, cout, packed_wt_flipped, cin, nullptr, d_in, s, nullptr, dtype);
-    if (rc) return rc;
-  }
-  if (d_weight) return launch_dw(m, *p, in, cin, d_out, cout, d_weight, s);
-  return D3D_OK;
-}
-
-static int conv_backward_f32(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
-                             const float *in, int cin, const void *packed_wt, int cout, const float *d_out, float *d_in,
-                             float *d_weight, int dtype, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  const Plan *fwd = find_plan(m, 1, in_size, filt, stride);
-  if (!fwd) {
-    set_error("conv backward: forward rulebook not built");
+// The backward pass of a convolution of kind 0 submanifold (`in_size` is its spatial size, no out_size / stride), 1 strided
+// or 2 deconvolution, rows of any d3d_dtype: d_in [rows_in, cs] (overwritten), d_weight [fv, cin, cout] fp32 (accumulated
+// into; pre-zero it).  `cs` = stored width of `in` (and of d_in), `cin` = Cin of the weight / d_weight: equal for fp32
+// rows (D3D_F32, or D3D_F32_X3: dInput as bf16x3 where it is served, dWeight exact either way).  dInput is a forward
+// launch over the opposite view of the rulebook with W^T, dWeight runs over the view the forward pass used.
+static int conv_backward(d3d_meta *m, int kind, const char *name, const int *in_size, const int *out_size,
+                         const int *filt, const int *stride, const void *in, int cs, int cin, const void *packed_wt,
+                         int cout, const void *d_out, void *d_in, float *d_weight, int dtype, hipStream_t s) {
+  D3D_REQUIRE(is_conv_dtype(dtype), "%s: dtype %d is not a d3d_dtype", name, dtype);
+  if (dtype != D3D_BF16)
+    D3D_REQUIRE(cs == cin, "%s: fp32 rows are stored %d channels wide, not %d", name, cin, cs);
+  else if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr))
+    return rc;
+  D3D_REQUIRE(m && in_size && filt && (kind == 0 || (out_size && stride)), "null argument");
+  const int *fine = kind == 2 ? out_size : in_size;
+  const Plan *fwd = nullptr;   // the submanifold rulebook, or fine -> coarse of a strided pair
+  const Plan *dec = nullptr;   // coarse -> fine of a strided pair, finalised where it is first needed
+  if (kind == 0) {
+    for (int d = 0; d < 3; d++) D3D_REQUIRE(filt[d] % 2 == 1, "submanifold backward needs odd filter sizes");
+    if (int rc = d3d_subm_prepare(m, in_size, filt, s, nullptr)) return rc;
+    fwd = find_plan(m, 0, in_size, filt, nullptr);
+  } else if (!(fwd = find_plan(m, 1, fine, filt, stride))) {
+    set_error(kind == 1 ? "conv backward: forward rulebook not built" : "deconv backward: strided rulebook not built");
     return D3D_ERR_STATE;
   }
   if (d_in) {
-    const Plan *dec = nullptr;
-    int rc = get_deconv_plan(m, in_size, filt, stride, s, &dec);
-    if (rc) return rc;
-    rc = launch_conv_dt(m, *dec, d_out, cout, packed_wt, cin, nullptr, d_in, s, nullptr, dtype);
-    if (rc) return rc;
+    if (kind == 1)
+      if (int rc = get_deconv_plan(m, fine, filt, stride, s, &dec)) return rc;
+    if (int rc = launch_conv_dt(m, kind == 1 ? *dec : *fwd, d_out, cout, packed_wt, cs, nullptr, d_in, s, nullptr, dtype))
+      return rc;
   }
-  if (d_weight) return launch_dw(m, *fwd, in, cin, d_out, cout, d_weight, s);
-  return D3D_OK;
+  if (!d_weight) return D3D_OK;
+  if (kind == 2)
+    if (int rc = get_deconv_plan(m, fine, filt, stride, s, &dec)) return rc;
+  const Plan &own = kind == 2 ? *dec : *fwd;
+  if (dtype == D3D_BF16) return launch_dw_bf16(m, own, in, cs, cin, d_out, cout, d_weight, s);
+  return launch_dw(m, own, (const float *)in, cin, (const float *)d_out, cout, d_weight, s);
 }
 
-static int deconv_backward_f32(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
-                               const float *in, int cin, const void *packed_wt, int cout, const float *d_out, float *d_in,
-                               float *d_weight, int dtype, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  const Plan *conv = find_plan(m, 1, out_size, filt, stride);  // fine -> coarse rulebook
-  if (!conv) {
-    set_error("deconv backward: strided rulebook not built");
-    return D3D_ERR_STATE;
-  }
-  if (d_in) {
-    int rc = launch_conv_dt(m, *conv, d_out, cout, packed_wt, cin, nullptr, d_in, s, nullptr, dtype);
-    if (rc) return rc;
-  }
-  if (d_weight) {
-    const Plan *dec = nullptr;
-    int rc = get_deconv_plan(m, out_size, filt, stride, s, &dec);
-    if (rc) return rc;
-    return launch_dw(m, *dec, in, cin, d_out, cout, d_weight, s);
-  }
-  return D3D_OK;
-}
-
-// d_in [rows_in, cin] (overwritten), d_weight [fv, cin, cout] (accumulated into; pre-zero it)
-int d3d_subm_conv_backward(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
-                           const float *packed_wt_flipped, int cout, const float *d_out, float *d_in,
-                           float *d_weight, void *stream) {
-  return subm_backward_f32(m, size, filt, in, cin, packed_wt_flipped, cout, d_out, d_in, d_weight, D3D_F32, stream);
-}
-
-int d3d_conv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                      const int *stride, const float *in, int cin, const float *packed_wt, int cout,
-                      const float *d_out, float *d_in, float *d_weight, void *stream) {
-  return conv_backward_f32(m, in_size, out_size, filt, stride, in, cin, packed_wt, cout, d_out, d_in, d_weight, D3D_F32,
-                           stream);
-}
-
-int d3d_deconv_backward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                        const int *stride, const float *in, int cin, const float *packed_wt, int cout,
-                        const float *d_out, float *d_in, float *d_weight, void *stream) {
-  return deconv_backward_f32(m, in_size, out_size, filt, stride, in, cin, packed_wt, cout, d_out, d_in, d_weight, D3D_F32,
-                             stream);
-}
-
-// bf16 storage: `cs` = stored width of `in` (and of d_in), `cin` = Cin of the weight / d_weight
 int d3d_subm_conv_backward_dt(d3d_meta *m, const int *size, const int *filt, const void *in, int cs, int cin,
                               const void *packed_wt_flipped, int cout, const void *d_out, void *d_in, float *d_weight,
                               int dtype, void *stream) {
-  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
-    D3D_REQUIRE(cs == cin, "subm_conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return subm_backward_f32(m, size, filt, (const float *)in, cin, packed_wt_flipped, cout,
-                             (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
-  }
-  D3D_REQUIRE(dtype == D3D_BF16, "subm_conv_backward_dt: dtype %d is not a d3d_dtype", dtype);
-  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && size && filt, "null argument");
-  for (int d = 0; d < 3; d++) D3D_REQUIRE(filt[d] % 2 == 1, "submanifold backward needs odd filter sizes");
-  int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
-  if (rc) return rc;
-  const Plan *p = find_plan(m, 0, size, filt, nullptr);
-  if (d_in) {
-    rc = launch_conv_bf16(m, *p, d_out, cout, packed_wt_flipped, cs, nullptr, d_in, s, nullptr);
-    if (rc) return rc;
-  }
-  if (d_weight) return launch_dw_bf16(m, *p, in, cs, cin, d_out, cout, d_weight, s);
-  return D3D_OK;
+  return conv_backward(m, 0, "subm_conv_backward_dt", size, nullptr, filt, nullptr, in, cs, cin, packed_wt_flipped, cout,
+                       d_out, d_in, d_weight, dtype, (hipStream_t)stream);
 }
 
 int d3d_conv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                          const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out, void *d_in,
                          float *d_weight, int dtype, void *stream) {
-  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
-    D3D_REQUIRE(cs == cin, "conv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return conv_backward_f32(m, in_size, out_size, filt, stride, (const float *)in, cin, packed_wt, cout,
-                             (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
-  }
-  D3D_REQUIRE(dtype == D3D_BF16, "conv_backward_dt: dtype %d is not a d3d_dtype", dtype);
-  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  const Plan *fwd = find_plan(m, 1, in_size, filt, stride);
-  if (!fwd) {
-    set_error("conv backward: forward rulebook not built");
-    return D3D_ERR_STATE;
-  }
-  if (d_in) {
-    const Plan *dec = nullptr;
-    int rc = get_deconv_plan(m, in_size, filt, stride, s, &dec);
-    if (rc) return rc;
-    rc = launch_conv_bf16(m, *dec, d_out, cout, packed_wt, cs, nullptr, d_in, s, nullptr);
-    if (rc) return rc;
-  }
-  if (d_weight) return launch_dw_bf16(m, *fwd, in, cs, cin, d_out, cout, d_weight, s);
-  return D3D_OK;
+  return conv_backward(m, 1, "conv_backward_dt", in_size, out_size, filt, stride, in, cs, cin, packed_wt, cout, d_out,
+                       d_in, d_weight, dtype, (hipStream_t)stream);
 }
 
 int d3d_deconv_backward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                            const void *in, int cs, int cin, const void *packed_wt, int cout, const void *d_out,
                            void *d_in, float *d_weight, int dtype, void *stream) {
-  if (dtype == D3D_F32 || dtype == D3D_F32_X3) {   // X3: dInput as bf16x3 where it is served, dWeight exact
-    D3D_REQUIRE(cs == cin, "deconv_backward_dt: fp32 rows are stored %d channels wide, not %d", cin, cs);
-    return deconv_backward_f32(m, in_size, out_size, filt, stride, (const float *)in, cin, packed_wt, cout,
-                               (const float *)d_out, (float *)d_in, d_weight, dtype, stream);
-  }
-  D3D_REQUIRE(dtype == D3D_BF16, "deconv_backward_dt: dtype %d is not a d3d_dtype", dtype);
-  if (int rc = check_bwd_bf16(cs, cin, cout, d_in != nullptr)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  const Plan *conv = find_plan(m, 1, out_size, filt, stride);  // fine -> coarse rulebook
-  if (!conv) {
-    set_error("deconv backward: strided rulebook not built");
-    return D3D_ERR_STATE;
-  }
-  if (d_in) {
-    int rc = launch_conv_bf16(m, *conv, d_out, cout, packed_wt, cs, nullptr, d_in, s, nullptr);
-    if (rc) return rc;
-  }
-  if (d_weight) {
-    const Plan *dec = nullptr;
-    int rc = get_deconv_plan(m, out_size, filt, stride, s, &dec);
-    if (rc) return rc;
-    return launch_dw_bf16(m, *dec, in, cs, cin, d_out, cout, d_weight, s);
-  }
-  return D3D_OK;
+  return conv_backward(m, 2, "deconv_backward_dt", in_size, out_size, filt, stride, in, cs, cin, packed_wt, cout, d_out,
+                       d_in, d_weight, dtype, (hipStream_t)stream);
 }
 
 int d3d_conv_dw_deterministic(int on) {
@@ -1092,19 +977,13 @@ size_t d3d_bn_backward_scratch_bytes(int planes) {
   return (size_t)kBnBwdBlocks * 2 * planes * sizeof(double) + 2 * (size_t)planes * sizeof(float) + 512;
 }
 
-int d3d_bn_backward(const float *in, const float *out, const float *d_out, float *d_in, int rows, int planes,
-                    const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
-                    float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, void *stream) {
-  return bn_backward_t(in, out, d_out, d_in, rows, planes, save_mean, save_invstd, weight, d_weight, d_bias, leakiness,
-                       scratch, scratch_bytes, (hipStream_t)stream);
-}
-
 int d3d_bn_backward_dt(const void *in, const void *out, const void *d_out, void *d_in, int rows, int planes,
                        const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
                        float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, int dtype, void *stream) {
   if (dtype == D3D_F32)
-    return d3d_bn_backward((const float *)in, (const float *)out, (const float *)d_out, (float *)d_in, rows, planes,
-                           save_mean, save_invstd, weight, d_weight, d_bias, leakiness, scratch, scratch_bytes, stream);
+    return bn_backward_t((const float *)in, (const float *)out, (const float *)d_out, (float *)d_in, rows, planes,
+                         save_mean, save_invstd, weight, d_weight, d_bias, leakiness, scratch, scratch_bytes,
+                         (hipStream_t)stream);
   D3D_REQUIRE(dtype == D3D_BF16, "bn_backward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
   typedef unsigned short bf16_t;
   return bn_backward_t((const bf16_t *)in, (const bf16_t *)out, (const bf16_t *)d_out, (bf16_t *)d_in, rows, planes,

@@ -285,22 +285,47 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float *__restrict__ x, f
   }
 }
 
+// k_bn_apply_rows takes rows whose channel quads divide a 256-thread workgroup
+static bool bn_apply_rows_serves(int planes) {
+  const int C4 = planes >> 2;
+  return (planes & 3) == 0 && C4 >= 1 && C4 <= 256 && 256 % C4 == 0;
+}
+
+template <typename T>
+static void launch_bn_apply_rows(const T *in, T *out, int rows, int planes, const float *mean, const float *invstd,
+                                 const float *weight, const float *bias, float leakiness, hipStream_t s) {
+  const int rpi = 256 / (planes >> 2);
+  const long need = ((long)rows + rpi - 1) / rpi;
+  const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
+  hipLaunchKernelGGL(k_bn_apply_rows<T>, dim3(blocks), dim3(256), 0, s, in, out, rows, planes, mean, invstd, weight, bias,
+                     leakiness);
+  bn_record_apply(kBnApplyRows, bn_form_type<T>(), blocks, (long)rows > 3L * blocks * rpi);
+}
+
 static void launch_bn_apply(const float *in, float *out, int rows, int planes, const float *mean, const float *invstd,
                             const float *weight, const float *bias, float leakiness, hipStream_t s) {
-  const int C4 = planes >> 2;
-  if ((planes & 3) == 0 && C4 >= 1 && C4 <= 256 && 256 % C4 == 0) {
-    const int rpi = 256 / C4;
-    const long need = ((long)rows + rpi - 1) / rpi;
-    const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
-    hipLaunchKernelGGL(k_bn_apply_rows<float>, dim3(blocks), dim3(256), 0, s, in, out, rows, planes, mean, invstd, weight,
-                       bias, leakiness);
-    bn_record_apply(kBnApplyRows, kBnTypeF32, blocks, (long)rows > 3L * blocks * rpi);
+  if (bn_apply_rows_serves(planes)) {
+    launch_bn_apply_rows(in, out, rows, planes, mean, invstd, weight, bias, leakiness, s);
   } else {
     const size_t total = (size_t)rows * planes;
     bn_record_apply((planes & 3) == 0 ? kBnApplyVec4 : kBnApplyScalar, kBnTypeF32, (unsigned)((total / 4 + 256) / 256), false);
     hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)((total / 4 + 256) / 256)), dim3(256), 0, s, in, out, total, planes,
                        mean, invstd, weight, bias, leakiness);
   }
+}
+
+// the apply on rows of either storage type: fp32 rows of any width, bf16 rows of the widths the row kernel serves
+static int bn_apply_dt(const void *in, void *out, int rows, int planes, const float *mean, const float *invstd,
+                       const float *weight, const float *bias, float leakiness, int dtype, hipStream_t s) {
+  if (dtype == D3D_F32) {
+    launch_bn_apply((const float *)in, (float *)out, rows, planes, mean, invstd, weight, bias, leakiness, s);
+  } else {
+    D3D_REQUIRE(bn_apply_rows_serves(planes), "batch norm apply: bf16 rows of %d planes are not built", planes);
+    launch_bn_apply_rows((const unsigned short *)in, (unsigned short *)out, rows, planes, mean, invstd, weight, bias,
+                         leakiness, s);
+  }
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
 }
 
 __global__ __launch_bounds__(256) void k_add(const float *__restrict__ a, const float *__restrict__ b,
@@ -381,6 +406,19 @@ __global__ __launch_bounds__(256) void k_rows_to_bf16(const float *__restrict__ 
   *(uint4 *)(out + row * width + c0) = __builtin_bit_cast(uint4, b);
 }
 
+// BatchNorm on rows of storage type D3D_F32 or D3D_BF16: statistics and parameters are fp32 either way
+static bool is_bn_dtype(int dtype) { return dtype == D3D_F32 || dtype == D3D_BF16; }
+
+// k_bn_stats over the tensor in `mode` (0 mean / unbiased variance, 1 training step, 2 mean / invstd)
+static int bn_stats_dt(const void *in, int rows, int planes, void *scratch, size_t scratch_bytes, hipStream_t s, int mode,
+                       float *o0, float *o1, float *running_mean, float *running_var, float eps, float momentum, int dtype) {
+  if (dtype == D3D_F32)
+    return run_stats((const float *)in, rows, planes, scratch, scratch_bytes, s, mode, o0, o1, running_mean, running_var, eps,
+                     momentum);
+  return run_stats((const unsigned short *)in, rows, planes, scratch, scratch_bytes, s, mode, o0, o1, running_mean,
+                   running_var, eps, momentum);
+}
+
 }  // namespace d3d
 
 using namespace d3d;
@@ -404,44 +442,6 @@ int d3d_bn_batch_stats(const float *in, int rows, int planes, float *mean, float
   return run_stats(in, rows, planes, scratch, scratch_bytes, s, 0, mean, var_unbiased, nullptr, nullptr, 0.f, 0.f);
 }
 
-int d3d_bn_batch_invstd(const float *in, int rows, int planes, float eps, float *mean, float *invstd,
-                        void *scratch, size_t scratch_bytes, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(in && mean && invstd && rows > 0, "bn_batch_invstd: bad arguments");
-  return run_stats(in, rows, planes, scratch, scratch_bytes, s, 2, mean, invstd, nullptr, nullptr, eps, 0.f);
-}
-
-int d3d_bn_forward(const float *in, float *out, int rows, int planes, float *save_mean,
-                   float *save_invstd, float *running_mean, float *running_var, const float *weight,
-                   const float *bias, float eps, float momentum, int train, float leakiness,
-                   void *scratch, size_t scratch_bytes, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(save_mean && save_invstd && running_mean && running_var && planes > 0 && rows >= 0, "bn_forward: bad arguments");
-  if (rows == 0) return D3D_OK;
-  D3D_REQUIRE(in && out, "bn_forward: null features");
-  if (train) {
-    int rc = run_stats(in, rows, planes, scratch, scratch_bytes, s, 1, save_mean, save_invstd, running_mean, running_var, eps, momentum);
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(k_bn_eval_stats, dim3((planes + 63) / 64), dim3(64), 0, s, running_mean, running_var, planes, eps, save_mean, save_invstd);
-    std::fill(t_bn_form + kBnStSrc, t_bn_form + kBnStPer + 1, 0);
-    t_bn_form[kBnStSrc] = kBnSrcRunning;
-  }
-  launch_bn_apply(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, s);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
-}
-
-int d3d_bn_apply(const float *in, float *out, int rows, int planes, const float *mean, const float *invstd,
-                 const float *weight, const float *bias, float leakiness, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (rows == 0) return D3D_OK;
-  D3D_REQUIRE(in && out && mean && invstd && planes > 0 && rows > 0, "bn_apply: bad arguments");
-  launch_bn_apply(in, out, rows, planes, mean, invstd, weight, bias, leakiness, s);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
-}
-
 int d3d_bn_stats_from_partials(const double *partials, int partial_rows, int rows, int planes, float eps,
                                int want_invstd, float *mean, float *var_or_invstd, void *scratch, size_t scratch_bytes,
                                void *stream) {
@@ -450,59 +450,40 @@ int d3d_bn_stats_from_partials(const double *partials, int partial_rows, int row
                             want_invstd ? 2 : 0, mean, var_or_invstd, eps);
 }
 
-/* storage-type aware forms (d3d_dtype) of the two inference-side BatchNorm entry points */
 int d3d_bn_batch_invstd_dt(const void *in, int rows, int planes, float eps, float *mean, float *invstd, void *scratch,
                            size_t scratch_bytes, int dtype, void *stream) {
-  if (dtype == D3D_F32)
-    return d3d_bn_batch_invstd((const float *)in, rows, planes, eps, mean, invstd, scratch, scratch_bytes, stream);
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(dtype == D3D_BF16 && in && mean && invstd && rows > 0, "bn_batch_invstd_dt: bad arguments");
-  return run_stats((const unsigned short *)in, rows, planes, scratch, scratch_bytes, s, 2, mean, invstd, nullptr, nullptr,
-                   eps, 0.f);
+  D3D_REQUIRE(is_bn_dtype(dtype) && in && mean && invstd && rows > 0, "bn_batch_invstd_dt: bad arguments");
+  return bn_stats_dt(in, rows, planes, scratch, scratch_bytes, (hipStream_t)stream, 2, mean, invstd, nullptr, nullptr, eps,
+                     0.f, dtype);
 }
 
 int d3d_bn_apply_dt(const void *in, void *out, int rows, int planes, const float *mean, const float *invstd,
                     const float *weight, const float *bias, float leakiness, int dtype, void *stream) {
-  if (dtype == D3D_F32)
-    return d3d_bn_apply((const float *)in, (float *)out, rows, planes, mean, invstd, weight, bias, leakiness, stream);
-  hipStream_t s = (hipStream_t)stream;
   if (rows == 0) return D3D_OK;
-  const int C4 = planes >> 2;
-  D3D_REQUIRE(dtype == D3D_BF16 && in && out && mean && invstd && (planes & 3) == 0 && C4 >= 1 && C4 <= 256 &&
-              256 % C4 == 0, "bn_apply_dt: bad arguments (planes=%d)", planes);
-  const int rpi = 256 / C4;
-  const long need = ((long)rows + rpi - 1) / rpi;
-  const unsigned blocks = (unsigned)std::max<long>(1, std::min<long>(need, 256 * 8));
-  hipLaunchKernelGGL(k_bn_apply_rows<unsigned short>, dim3(blocks), dim3(256), 0, s, (const unsigned short *)in,
-                     (unsigned short *)out, rows, planes, mean, invstd, weight, bias, leakiness);
-  bn_record_apply(kBnApplyRows, kBnTypeBf16, blocks, (long)rows > 3L * blocks * rpi);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
+  D3D_REQUIRE(is_bn_dtype(dtype) && in && out && mean && invstd && planes > 0 && rows > 0,
+              "bn_apply_dt: bad arguments (planes=%d)", planes);
+  return bn_apply_dt(in, out, rows, planes, mean, invstd, weight, bias, leakiness, dtype, (hipStream_t)stream);
 }
 
 int d3d_bn_forward_dt(const void *in, void *out, int rows, int planes, float *save_mean, float *save_invstd,
                       float *running_mean, float *running_var, const float *weight, const float *bias, float eps,
                       float momentum, int train, float leakiness, void *scratch, size_t scratch_bytes, int dtype,
                       void *stream) {
-  if (dtype == D3D_F32)
-    return d3d_bn_forward((const float *)in, (float *)out, rows, planes, save_mean, save_invstd, running_mean, running_var,
-                          weight, bias, eps, momentum, train, leakiness, scratch, scratch_bytes, stream);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(dtype == D3D_BF16, "bn_forward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
+  D3D_REQUIRE(is_bn_dtype(dtype), "bn_forward_dt: dtype %d is neither D3D_F32 nor D3D_BF16", dtype);
   D3D_REQUIRE(save_mean && save_invstd && running_mean && running_var && planes > 0 && rows >= 0, "bn_forward_dt: bad arguments");
   if (rows == 0) return D3D_OK;
-  const int C4 = planes >> 2;
-  D3D_REQUIRE(in && out && (planes & 3) == 0 && C4 <= 256 && 256 % C4 == 0, "bn_forward_dt: bad arguments (planes=%d)", planes);
+  D3D_REQUIRE(in && out && (dtype == D3D_F32 || bn_apply_rows_serves(planes)), "bn_forward_dt: bad arguments (planes=%d)", planes);
   if (train) {
-    int rc = run_stats((const unsigned short *)in, rows, planes, scratch, scratch_bytes, s, 1, save_mean, save_invstd,
-                       running_mean, running_var, eps, momentum);
+    int rc = bn_stats_dt(in, rows, planes, scratch, scratch_bytes, s, 1, save_mean, save_invstd, running_mean, running_var,
+                         eps, momentum, dtype);
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL(k_bn_eval_stats, dim3((planes + 63) / 64), dim3(64), 0, s, running_mean, running_var, planes, eps, save_mean, save_invstd);
     std::fill(t_bn_form + kBnStSrc, t_bn_form + kBnStPer + 1, 0);
     t_bn_form[kBnStSrc] = kBnSrcRunning;
   }
-  return d3d_bn_apply_dt(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, dtype, stream);
+  return bn_apply_dt(in, out, rows, planes, save_mean, save_invstd, weight, bias, leakiness, dtype, s);
 }
 
 int d3d_rows_to_bf16(const float *in, long rows, int cin, int width, void *out, void *stream) {

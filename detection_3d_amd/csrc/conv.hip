@@ -27,15 +27,6 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-static inline int padded_cin(int cin) {
-  if (cin <= 16) return 16;
-  if (cin <= 32) return 32;
-  if (cin <= 64) return 64;
-  if (cin <= 128) return 128;
-  if (cin <= 256) return 256;
-  return -1;
-}
-
 // packed[k][g][co][j] = w[k][4g+j][co]  (zero for 4g+j >= cin)
 __global__ void k_pack_weight(const float *__restrict__ w, int fv, int cin, int cout, int cp,
                               float *__restrict__ packed) {
@@ -50,6 +41,10 @@ __global__ void k_pack_weight(const float *__restrict__ w, int fv, int cin, int 
   int k = (int)(u / (cp / 4));
   int ci = 4 * g + j;
   packed[t] = ci < cin ? w[((size_t)k * cin + ci) * cout + co] : 0.f;
+}
+
+void launch_pack_weight(const float *w, int fv, int cin, int cout, int cp, float *packed, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_weight, grid1d((long)fv * cp * cout), dim3(256), 0, s, w, fv, cin, cout, cp, packed);
 }
 
 // CT   = Cin tile staged in LDS per step (multiple of 8, <= 128); NCT tiles cover Cin
@@ -493,138 +488,64 @@ int d3d_conv_time_next(void *start_event, void *stop_event) {
   return D3D_OK;
 }
 
-size_t d3d_packed_weight_floats(int fv, int cin, int cout) {
-  int cp = padded_cin(cin);
-  if (cp < 0 || fv <= 0 || cout <= 0) return 0;
-  return (size_t)fv * cp * cout;
-}
-
-int d3d_pack_conv_weight(const float *w, int fv, int cin, int cout, float *packed, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  int cp = padded_cin(cin);
-  D3D_REQUIRE(w && packed && fv > 0 && cout > 0 && cp > 0, "pack_conv_weight: bad arguments (Cin=%d)", cin);
-  long total = (long)fv * cp * cout;
-  hipLaunchKernelGGL(k_pack_weight, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout, cp, packed);
-  D3D_LAUNCH_CHECK();
-  return D3D_OK;
-}
-
-int d3d_subm_conv_forward(d3d_meta *m, const int *size, const int *filt, const float *in, int cin,
-                          const float *packed_w, int cout, const float *residual, float *out,
-                          void *stream, double *macs_host, const d3d_bn_prologue *bn) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && size && filt, "null argument");
-  int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
-  if (rc) return rc;
-  Plan *p = const_cast<Plan *>(find_plan(m, 0, size, filt, nullptr));
-  if (macs_host) {
-    long nr;
-    rc = plan_rules(m, *p, s, &nr);
-    if (rc) return rc;
-    *macs_host = (double)nr * cin * cout;
-  }
-  return launch_conv(m, *p, in, cin, packed_w, cout, residual, out, s, bn);
-}
-
-int d3d_conv_forward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                     const int *stride, const float *in, int cin, const float *packed_w, int cout,
-                     float *out, void *stream, double *macs_host, const d3d_bn_prologue *bn) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
-  int rc = d3d_conv_prepare(m, in_size, out_size, filt, stride, stream, nullptr, nullptr);
-  if (rc) return rc;
-  Plan *p = const_cast<Plan *>(find_plan(m, 1, in_size, filt, stride));
-  if (macs_host) {
-    long nr;
-    rc = plan_rules(m, *p, s, &nr);
-    if (rc) return rc;
-    *macs_host = (double)nr * cin * cout;
-  }
-  return launch_conv(m, *p, in, cin, packed_w, cout, nullptr, out, s, bn);
-}
-
-// Deconvolution: in = coarse features, out = fine features; reuses the strided rulebook of the
-// matching convolution with the roles swapped (SCN/CPU/Deconvolution.cpp:17,33-37).
-int d3d_deconv_forward(d3d_meta *m, const int *in_size, const int *out_size, const int *filt,
-                       const int *stride, const float *in, int cin, const float *packed_w, int cout,
-                       const float *residual, float *out, void *stream, double *macs_host,
-                       const d3d_bn_prologue *bn) {
-  hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(m && in_size && out_size && filt && stride, "null argument");
+// The plan of a forward call, built on first use: kind 0 submanifold (`in_size` is its spatial size, no out_size / stride),
+// 1 strided convolution, 2 deconvolution (in = coarse, out = fine features; reuses the strided rulebook of the matching
+// convolution with the roles swapped, SCN/CPU/Deconvolution.cpp:17,33-37).  With `macs_host`, the multiply-accumulates
+// of a cin -> cout layer over that plan are counted too.
+static int forward_plan(d3d_meta *m, int kind, const int *in_size, const int *out_size, const int *filt,
+                        const int *stride, hipStream_t s, int cin, int cout, double *macs_host, const Plan **out) {
   const Plan *p = nullptr;
-  int rc = get_deconv_plan(m, out_size, filt, stride, s, &p);
+  int rc;
+  if (kind == 0) {
+    rc = d3d_subm_prepare(m, in_size, filt, s, nullptr);
+    if (!rc) p = find_plan(m, 0, in_size, filt, nullptr);
+  } else if (kind == 1) {
+    rc = d3d_conv_prepare(m, in_size, out_size, filt, stride, s, nullptr, nullptr);
+    if (!rc) p = find_plan(m, 1, in_size, filt, stride);
+  } else {
+    rc = get_deconv_plan(m, out_size, filt, stride, s, &p);
+  }
   if (rc) return rc;
-  if (macs_host) {
+  if (macs_host && p) {
     long nr;
     rc = plan_rules(m, *const_cast<Plan *>(p), s, &nr);
     if (rc) return rc;
     *macs_host = (double)nr * cin * cout;
   }
-  return launch_conv(m, *p, in, cin, packed_w, cout, residual, out, s, bn);
+  *out = p;
+  return D3D_OK;
 }
 
-// ---- storage-type aware forms (d3d_dtype): D3D_F32 forwards to the functions above, D3D_BF16 runs conv_bf16.hip,
-// D3D_F32_X3 runs conv_bf16.hip's bf16x3 form where conv_x3_serves(K, cin, cout) and k_conv elsewhere (launch_conv_dt).
+// Storage types (d3d_dtype, launch_conv_dt): D3D_F32 runs k_conv, D3D_BF16 runs conv_bf16.hip, D3D_F32_X3 runs
+// conv_bf16.hip's bf16x3 form where conv_x3_serves(K, cin, cout) and k_conv elsewhere.
 // For bf16, `cin` is the stored row width (16, 32, 64, 128 or 256 channels; narrower inputs are zero padded).
 int d3d_subm_conv_forward_dt(d3d_meta *m, const int *size, const int *filt, const void *in, int cin,
                              const void *packed_w, int cout, const void *residual, void *out, int dtype, void *stream,
                              double *macs_host, const d3d_bn_prologue *bn) {
-  if (dtype == D3D_F32)
-    return d3d_subm_conv_forward(m, size, filt, (const float *)in, cin, (const float *)packed_w, cout,
-                                 (const float *)residual, (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && size && filt, "subm_conv_forward_dt: bad arguments");
-  int rc = d3d_subm_prepare(m, size, filt, stream, nullptr);
-  if (rc) return rc;
-  Plan *p = const_cast<Plan *>(find_plan(m, 0, size, filt, nullptr));
-  if (macs_host) {
-    long nr;
-    rc = plan_rules(m, *p, s, &nr);
-    if (rc) return rc;
-    *macs_host = (double)nr * cin * cout;
-  }
+  D3D_REQUIRE(is_conv_dtype(dtype) && m && size && filt, "subm_conv_forward_dt: bad arguments");
+  const Plan *p = nullptr;
+  if (int rc = forward_plan(m, 0, size, nullptr, filt, nullptr, s, cin, cout, macs_host, &p)) return rc;
   return launch_conv_dt(m, *p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
 }
 
 int d3d_conv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                         const void *in, int cin, const void *packed_w, int cout, void *out, int dtype, void *stream,
                         double *macs_host, const d3d_bn_prologue *bn) {
-  if (dtype == D3D_F32)
-    return d3d_conv_forward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_w, cout,
-                            (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && in_size && out_size && filt && stride,
-              "conv_forward_dt: bad arguments");
-  int rc = d3d_conv_prepare(m, in_size, out_size, filt, stride, stream, nullptr, nullptr);
-  if (rc) return rc;
-  Plan *p = const_cast<Plan *>(find_plan(m, 1, in_size, filt, stride));
-  if (macs_host) {
-    long nr;
-    rc = plan_rules(m, *p, s, &nr);
-    if (rc) return rc;
-    *macs_host = (double)nr * cin * cout;
-  }
+  D3D_REQUIRE(is_conv_dtype(dtype) && m && in_size && out_size && filt && stride, "conv_forward_dt: bad arguments");
+  const Plan *p = nullptr;
+  if (int rc = forward_plan(m, 1, in_size, out_size, filt, stride, s, cin, cout, macs_host, &p)) return rc;
   return launch_conv_dt(m, *p, in, cin, packed_w, cout, nullptr, out, s, bn, dtype);
 }
 
 int d3d_deconv_forward_dt(d3d_meta *m, const int *in_size, const int *out_size, const int *filt, const int *stride,
                           const void *in, int cin, const void *packed_w, int cout, const void *residual, void *out,
                           int dtype, void *stream, double *macs_host, const d3d_bn_prologue *bn) {
-  if (dtype == D3D_F32)
-    return d3d_deconv_forward(m, in_size, out_size, filt, stride, (const float *)in, cin, (const float *)packed_w, cout,
-                              (const float *)residual, (float *)out, stream, macs_host, bn);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && m && in_size && out_size && filt && stride,
-              "deconv_forward_dt: bad arguments");
+  D3D_REQUIRE(is_conv_dtype(dtype) && m && in_size && out_size && filt && stride, "deconv_forward_dt: bad arguments");
   const Plan *p = nullptr;
-  int rc = get_deconv_plan(m, out_size, filt, stride, s, &p);
-  if (rc) return rc;
-  if (macs_host) {
-    long nr;
-    rc = plan_rules(m, *const_cast<Plan *>(p), s, &nr);
-    if (rc) return rc;
-    *macs_host = (double)nr * cin * cout;
-  }
+  if (int rc = forward_plan(m, 2, in_size, out_size, filt, stride, s, cin, cout, macs_host, &p)) return rc;
   return launch_conv_dt(m, *p, in, cin, packed_w, cout, residual, out, s, bn, dtype);
 }
 
@@ -640,36 +561,18 @@ int d3d_conv_group_forward(d3d_meta *m, const d3d_conv_desc *descs, int n, void 
   for (int i = 0; i < n; i++) {
     const d3d_conv_desc &d = descs[i];
     D3D_REQUIRE(d.kind >= 0 && d.kind <= 2, "conv_group_forward: member %d has kind %d (0, 1 or 2)", i, d.kind);
-    D3D_REQUIRE(d.dtype == D3D_F32 || d.dtype == D3D_BF16 || d.dtype == D3D_F32_X3, "conv_group_forward: member %d: bad dtype", i);
+    D3D_REQUIRE(is_conv_dtype(d.dtype), "conv_group_forward: member %d: bad dtype", i);
     const Plan *p = nullptr;
-    int rc = D3D_OK;
-    if (d.kind == 0) {
-      rc = d3d_subm_prepare(m, d.in_size, d.filter, stream, nullptr);
-      if (!rc) p = find_plan(m, 0, d.in_size, d.filter, nullptr);
-    } else if (d.kind == 1) {
-      rc = d3d_conv_prepare(m, d.in_size, d.out_size, d.filter, d.stride, stream, nullptr, nullptr);
-      if (!rc) p = find_plan(m, 1, d.in_size, d.filter, d.stride);
-    } else {
-      rc = get_deconv_plan(m, d.out_size, d.filter, d.stride, s, &p);
-    }
-    if (rc) return rc;
+    if (int rc = forward_plan(m, d.kind, d.in_size, d.out_size, d.filter, d.stride, s, d.cin, d.cout, d.macs_host, &p))
+      return rc;
     D3D_REQUIRE(p, "conv_group_forward: member %d has no plan", i);
-    if (d.macs_host) {
-      long nr;
-      rc = plan_rules(m, *const_cast<Plan *>(p), s, &nr);
-      if (rc) return rc;
-      *d.macs_host = (double)nr * d.cin * d.cout;
-    }
   }
   ConvGroup g;
   int rc = D3D_OK;
   for (int i = 0; i < n && !rc; i++) {
     const d3d_conv_desc &d = descs[i];
     const Plan *p = nullptr;
-    if (d.kind == 2)
-      rc = get_deconv_plan(m, d.out_size, d.filter, d.stride, s, &p);
-    else
-      p = find_plan(m, d.kind, d.in_size, d.filter, d.kind == 1 ? d.stride : nullptr);
+    rc = forward_plan(m, d.kind, d.in_size, d.out_size, d.filter, d.stride, s, d.cin, d.cout, nullptr, &p);   // a lookup now
     if (rc) break;
     t_group = &g;
     if (g.n == kMaxGroup) rc = conv_group_flush(m, s);

@@ -34,15 +34,6 @@ __device__ __forceinline__ void wave_lds_sync_b() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-static inline int padded_cin_bf16(int cin) {
-  if (cin <= 16) return 16;
-  if (cin <= 32) return 32;
-  if (cin <= 64) return 64;
-  if (cin <= 128) return 128;
-  if (cin <= 256) return 256;
-  return -1;
-}
-
 // bf16x3 split of one value: hi = x truncated to bf16 (a finite x never gives an infinite hi), lo = bf16(x - hi), the
 // difference exact in fp32.  A non-finite x splits as (x, 0): x - hi is NaN exactly then, and the select drops it; the
 // canonicalisation quiets a signalling NaN, so that its upper half stays a NaN.  Returns hi's bits in the upper half.
@@ -554,7 +545,7 @@ int launch_conv_bf16(d3d_meta *m, const Plan &p, const void *in_, int cin, const
   }
   const bf16_t *wp = (const bf16_t *)packed_w;
   D3D_REQUIRE(in_ && wp && out_, "bf16 convolution: null pointer");
-  D3D_REQUIRE(x3 ? conv_x3_serves(p.K, cin, cout) : padded_cin_bf16(cin) == cin,
+  D3D_REQUIRE(x3 ? conv_x3_serves(p.K, cin, cout) : padded_cin(cin) == cin,
               "bf16 convolution: feature rows must be stored with 16, 32, 64, 128 or 256 channels (got %d; bf16x3: "
               "32 .. 256); pad narrower inputs with zero channels", cin);
   D3D_REQUIRE((size_t)p.n_in * (size_t)cin * es < ((size_t)1 << 32),
@@ -603,51 +594,46 @@ int d3d_conv_bf16_tuning(int row_blocks, long min_waves) {
 }
 
 size_t d3d_packed_weight_bytes(int fv, int cin, int cout, int dtype) {
-  if (dtype == D3D_F32 || dtype == D3D_F32_X3) return d3d_packed_weight_floats(fv, cin, cout) * sizeof(float);
-  const int cp = padded_cin_bf16(cin);
-  if (dtype != D3D_BF16 || cp < 0 || fv <= 0 || cout <= 0) return 0;
-  return (size_t)fv * cp * cout * 2;
+  if (!is_conv_dtype(dtype)) return 0;
+  return packed_weight_floats(fv, cin, cout) * (dtype == D3D_BF16 ? 2 : sizeof(float));   // X3: a hi and a lo bf16 plane
 }
 
 int d3d_pack_conv_weight_dt(const float *w, int fv, int cin, int cout, void *packed, int dtype, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int cp = padded_cin(cin);
+  D3D_REQUIRE(is_conv_dtype(dtype) && w && packed && fv > 0 && cout > 0 && cp > 0,
+              "pack_conv_weight_dt: bad arguments (Cin=%d, dtype %d)", cin, dtype);
+  const dim3 grid = grid1d((long)fv * cp * cout);
   // D3D_F32_X3: hi / lo planes for the shapes the bf16x3 kernel serves, the fp32 layout (same bytes) for the others
   if (dtype == D3D_F32 || (dtype == D3D_F32_X3 && !conv_x3_serves(fv, cin, cout)))
-    return d3d_pack_conv_weight(w, fv, cin, cout, (float *)packed, stream);
-  hipStream_t s = (hipStream_t)stream;
-  const int cp = padded_cin_bf16(cin);
-  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && w && packed && fv > 0 && cout > 0 && cp > 0,
-              "pack_conv_weight_dt: bad arguments (Cin=%d, dtype %d)", cin, dtype);
-  const long total = (long)fv * cp * cout;
-  if (dtype == D3D_F32_X3)
-    hipLaunchKernelGGL(k_pack_weight_bf16<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout,
-                       cp, (__bf16 *)packed);
+    launch_pack_weight(w, fv, cin, cout, cp, (float *)packed, s);
+  else if (dtype == D3D_F32_X3)
+    hipLaunchKernelGGL(k_pack_weight_bf16<true>, grid, dim3(256), 0, s, w, fv, cin, cout, cp, (__bf16 *)packed);
   else
-    hipLaunchKernelGGL(k_pack_weight_bf16<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin, cout,
-                       cp, (__bf16 *)packed);
+    hipLaunchKernelGGL(k_pack_weight_bf16<false>, grid, dim3(256), 0, s, w, fv, cin, cout, cp, (__bf16 *)packed);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
 
 int d3d_pack_conv_weight_transposed_dt(const float *w, int fv, int cin, int cout, int flip, void *packed, int dtype,
                                        void *stream) {
-  // W^T is a weight with Cin' = cout, Cout' = cin: D3D_F32_X3 packs it as the dInput launch will read it
-  if (dtype == D3D_F32 || (dtype == D3D_F32_X3 && !conv_x3_serves(fv, cout, cin)))
-    return d3d_pack_conv_weight_transposed(w, fv, cin, cout, flip, (float *)packed, stream);
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE((dtype == D3D_BF16 || dtype == D3D_F32_X3) && w && packed && fv > 0,
+  D3D_REQUIRE(is_conv_dtype(dtype) && w && packed && fv > 0,
               "pack_conv_weight_transposed_dt: bad arguments (dtype %d)", dtype);
-  const int cp = padded_cin_bf16(cout);
-  if (cp < 0 || !(cin == 32 || cin == 64 || cin == 128 || cin == 256)) {   // Cout' = cin: a width launch_cb dispatches
+  const int cp = padded_cin(cout);   // W^T is a weight with Cin' = cout, Cout' = cin
+  const dim3 grid = grid1d((long)fv * cp * cin);
+  // D3D_F32_X3 packs it as the dInput launch will read it
+  if (dtype == D3D_F32 || (dtype == D3D_F32_X3 && !conv_x3_serves(fv, cout, cin))) {
+    D3D_REQUIRE(cp > 0 && cin > 0, "pack_conv_weight_transposed_dt: bad arguments (Cin=%d Cout=%d)", cin, cout);
+    launch_pack_weight_t(w, fv, cin, cout, cp, flip, (float *)packed, s);
+  } else if (cp < 0 || !(cin == 32 || cin == 64 || cin == 128 || cin == 256)) {   // Cout' = cin: a width launch_cb dispatches
     set_error("pack_conv_weight_transposed_dt: bf16 W^T for Cin=%d Cout=%d is not built", cin, cout);
     return D3D_ERR_UNSUPPORTED;
+  } else if (dtype == D3D_F32_X3) {
+    hipLaunchKernelGGL(k_pack_weight_t_bf16<true>, grid, dim3(256), 0, s, w, fv, cin, cout, cp, flip, (__bf16 *)packed);
+  } else {
+    hipLaunchKernelGGL(k_pack_weight_t_bf16<false>, grid, dim3(256), 0, s, w, fv, cin, cout, cp, flip, (__bf16 *)packed);
   }
-  const long total = (long)fv * cp * cin;
-  if (dtype == D3D_F32_X3)
-    hipLaunchKernelGGL(k_pack_weight_t_bf16<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin,
-                       cout, cp, flip, (__bf16 *)packed);
-  else
-    hipLaunchKernelGGL(k_pack_weight_t_bf16<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, fv, cin,
-                       cout, cp, flip, (__bf16 *)packed);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

@@ -313,11 +313,31 @@ constexpr int bn_form_type() { return sizeof(T) == 8 ? kBnTypeF64 : sizeof(T) ==
 // conv_bf16.hip
 // dtype D3D_BF16, or D3D_F32_X3 (fp32 rows, bf16x3 products) for the shapes conv_x3_serves admits
 int launch_conv_bf16(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,
-                     const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype = D3D_BF16);
+                     const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype);
 bool conv_x3_serves(int fv, int cin, int cout);   // filter volume (Plan::K), Cin, Cout
 // conv.hip: k_conv_reduce of fp32 partials [n_split][npos][cout] (no column statistics)
 void launch_conv_reduce(const float *partial, int n_split, int npos, int cout, const int32_t *rows, const float *residual,
                         float *out, hipStream_t s);
+inline bool is_conv_dtype(int dtype) { return dtype == D3D_F32 || dtype == D3D_BF16 || dtype == D3D_F32_X3; }
+// Cin as the packed weights (and bf16 rows) store it; -1: wider than any kernel takes
+inline int padded_cin(int cin) {
+  if (cin <= 16) return 16;
+  if (cin <= 32) return 32;
+  if (cin <= 64) return 64;
+  if (cin <= 128) return 128;
+  if (cin <= 256) return 256;
+  return -1;
+}
+// elements of a packed weight of any d3d_dtype (0: no such weight)
+inline size_t packed_weight_floats(int fv, int cin, int cout) {
+  const int cp = padded_cin(cin);
+  if (cp < 0 || fv <= 0 || cout <= 0) return 0;
+  return (size_t)fv * cp * cout;
+}
+// the fp32 packings (conv.hip: k_pack_weight, backward.hip: k_pack_weight_t) of fv * cp * cout / fv * cp * cin elements,
+// cp = padded_cin(cin) / padded_cin(cout); d3d_pack_conv_weight[_transposed]_dt checks the arguments
+void launch_pack_weight(const float *w, int fv, int cin, int cout, int cp, float *packed, hipStream_t s);
+void launch_pack_weight_t(const float *w, int fv, int cin, int cout, int cp, int flip, float *packed, hipStream_t s);
 // a launch of any d3d_dtype: D3D_F32 and the D3D_F32_X3 shapes conv_x3_serves declines run launch_conv
 int launch_conv_dt(d3d_meta *m, const Plan &p, const void *in, int cin, const void *packed_w, int cout,
                    const void *residual, void *out, hipStream_t s, const d3d_bn_prologue *bn, int dtype);

@@ -1462,7 +1462,7 @@ static void geo_async_free(d3d_meta *m) {
 extern "C" {
 
 const char *d3d_last_error(void) { return d3d::g_err; }
-int d3d_abi_version(void) { return 1; }
+int d3d_abi_version(void) { return 2; }
 
 int d3d_meta_create(d3d_meta **out, size_t arena_bytes) {
   D3D_REQUIRE(out && arena_bytes >= (1u << 20), "d3d_meta_create: bad arguments");

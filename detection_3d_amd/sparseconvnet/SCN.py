@@ -343,9 +343,18 @@ def conv_dtype_code(dtype):
     raise _lib.D3DError(f"unsupported feature dtype {dtype} (float32 or bfloat16)")
 
 
+_PACKED_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32_X3: torch.int16}   # F32_X3: raw words, 4 bytes per weight
+_PACKED_CODE = {v: k for k, v in _PACKED_DTYPE.items()}
+
+
 def _packed_code(packed):
-    """d3d_dtype a packed weight was made for (pack_weight: F32 float32, BF16 bfloat16, F32_X3 raw int16 words)"""
-    return {torch.float32: F32, torch.bfloat16: BF16, torch.int16: F32_X3}.get(packed.dtype)
+    """d3d_dtype a packed weight was made for (the element type of its buffer)"""
+    return _PACKED_CODE.get(packed.dtype)
+
+
+def _packed_buffer(nbytes, code, device):
+    dtype = _PACKED_DTYPE[code]
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=device)
 
 
 def stored_planes(planes, dtype):
@@ -379,27 +388,12 @@ def pack_weight(weight, dtype=torch.float32, code=None):
         raise _lib.D3DError("groups != 1 is not supported")
     if code is None:
         code = conv_dtype_code(dtype)
-    if code == F32_X3:
-        nbytes = lib().d3d_packed_weight_bytes(fv, cin, cout, F32_X3)
-        if nbytes == 0:
-            raise _lib.D3DError(f"unsupported conv shape fv={fv} Cin={cin} Cout={cout}")
-        packed = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-        check(lib().d3d_pack_conv_weight_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout, ptr(packed),
-                                            F32_X3, stream_of()))
-        return packed
-    if dtype == torch.bfloat16:
-        nbytes = lib().d3d_packed_weight_bytes(fv, cin, cout, BF16)
-        if nbytes == 0:
-            raise _lib.D3DError(f"unsupported bf16 conv shape fv={fv} Cin={cin} Cout={cout}")
-        packed = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
-        check(lib().d3d_pack_conv_weight_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout, ptr(packed), BF16,
-                                            stream_of()))
-        return packed
-    n = lib().d3d_packed_weight_floats(fv, cin, cout)
-    if n == 0:
-        raise _lib.D3DError(f"unsupported conv shape fv={fv} Cin={cin} Cout={cout}")
-    packed = torch.empty(n, dtype=torch.float32, device=weight.device)
-    check(lib().d3d_pack_conv_weight(ptr(weight.detach()), fv, cin, cout, ptr(packed), stream_of()))
+    nbytes = lib().d3d_packed_weight_bytes(fv, cin, cout, code)
+    if nbytes == 0:
+        raise _lib.D3DError(f"unsupported conv shape fv={fv} Cin={cin} Cout={cout} (d3d_dtype {code})")
+    packed = _packed_buffer(nbytes, code, weight.device)
+    check(lib().d3d_pack_conv_weight_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout, ptr(packed), code,
+                                        stream_of()))
     return packed
 
 
@@ -736,13 +730,7 @@ def BatchNormalization_updateOutput(input_features, output_features, saveMean, s
     b = bias if (bias is not None and bias.numel()) else None
     nbytes = _bn_scratch_bytes(planes)
     scratch = _bn_scratch(input_features.device, nbytes)
-    if input_features.dtype == torch.float32:
-        check(lib().d3d_bn_forward(ptr(input_features), ptr(output_features), rows, planes, ptr(saveMean),
-                                   ptr(saveInvStd), ptr(runningMean), ptr(runningVar), ptr(w), ptr(b),
-                                   float(eps), float(momentum), int(bool(train)), float(leakiness),
-                                   ptr(scratch), scratch.numel(), stream_of()))
-        return
-    dt = dtype_code(input_features)      # bf16 rows; statistics, parameters and running stats fp32
+    dt = dtype_code(input_features)      # statistics, parameters and running stats are fp32 whatever the rows are
     _require_f32(saveMean, saveInvStd, runningMean, runningVar)
     check(lib().d3d_bn_forward_dt(ptr(input_features), ptr(output_features), rows, planes, ptr(saveMean),
                                   ptr(saveInvStd), ptr(runningMean), ptr(runningVar), ptr(w), ptr(b),
@@ -780,28 +768,12 @@ def pack_weight_transposed(weight, flip, dtype=torch.float32, code=None):
     fv, groups, cin, cout = weight.shape
     if code is None:
         code = conv_dtype_code(dtype)
-    if code == F32_X3:
-        nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, F32_X3)
-        if nbytes == 0:
-            raise _lib.D3DError(f"unsupported conv shape for backward fv={fv} Cin={cin} Cout={cout}")
-        packed = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-        check(lib().d3d_pack_conv_weight_transposed_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout,
-                                                       int(bool(flip)), ptr(packed), F32_X3, stream_of()))
-        return packed
-    if dtype == torch.bfloat16:
-        nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, BF16)
-        if nbytes == 0:
-            raise _lib.D3DError(f"unsupported bf16 conv shape for backward fv={fv} Cin={cin} Cout={cout}")
-        packed = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
-        check(lib().d3d_pack_conv_weight_transposed_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout,
-                                                       int(bool(flip)), ptr(packed), BF16, stream_of()))
-        return packed
-    n = lib().d3d_packed_weight_floats(fv, cout, cin)
-    if n == 0:
-        raise _lib.D3DError(f"unsupported conv shape for backward fv={fv} Cin={cin} Cout={cout}")
-    packed = torch.empty(n, dtype=torch.float32, device=weight.device)
-    check(lib().d3d_pack_conv_weight_transposed(ptr(weight.detach()), fv, cin, cout, int(bool(flip)), ptr(packed),
-                                                stream_of()))
+    nbytes = lib().d3d_packed_weight_bytes(fv, cout, cin, code)
+    if nbytes == 0:
+        raise _lib.D3DError(f"unsupported conv shape for backward fv={fv} Cin={cin} Cout={cout} (d3d_dtype {code})")
+    packed = _packed_buffer(nbytes, code, weight.device)
+    check(lib().d3d_pack_conv_weight_transposed_dt(ptr(weight.detach().float().contiguous()), fv, cin, cout,
+                                                   int(bool(flip)), ptr(packed), code, stream_of()))
     return packed
 
 
@@ -851,77 +823,46 @@ class _dw_fixed_order:
         return False
 
 
-def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features, d_input_features,
-                                    d_output_features, weight, d_weight, d_bias, want_d_input=True):
-    """sparseconvnet.h:106-111.  d_input_features is resized and overwritten, d_weight (pre-zeroed by the
-    caller, submanifoldConvolution.py backward) is accumulated into."""
+def _conv_backward(entry, sizes, m, input_features, d_input_features, d_output_features, weight, d_weight, want_d_input,
+                   flip):
+    """One d3d_*_backward_dt call: `entry` names the kind, `sizes` are its size / filter / stride triples.
+    d_input_features is resized and overwritten, d_weight (pre-zeroed by the caller) is accumulated into."""
     require_gpu(input_features, d_output_features, weight, d_weight)
     fv, _, cin, cout = weight.shape
     dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
-    size, filt = _size3(spatial_size), _size3(filter_size)
     do = d_output_features.contiguous()
-    din = None
-    packed_t = None
+    din = packed_t = None
     if want_d_input:
         if not _dinput_supported(cin):
             raise _lib.D3DError(f"dInput for Cin={cin} is not built (only the first layer has such a Cin)")
         d_input_features.resize_(input_features.shape[0], cin)
         din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=True, dtype=input_features.dtype, code=dt)
+        packed_t = pack_weight_transposed(weight, flip=flip, dtype=input_features.dtype, code=dt)
     with _dw_fixed_order(d_weight, fv, cin, cout):
-        if dt == F32:
-            check(lib().d3d_subm_conv_backward(m._h, ints(size), ints(filt), ptr(input_features), cin, ptr(packed_t),
-                                               cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
-        else:
-            check(lib().d3d_subm_conv_backward_dt(m._h, ints(size), ints(filt), ptr(input_features),
-                                                  input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
-                                                  ptr(d_weight), dt, stream_of()))
+        check(getattr(lib(), entry)(m._h, *(ints(_size3(s)) for s in sizes), ptr(input_features),
+                                    stored_planes(cin, input_features.dtype), cin, ptr(packed_t), cout, ptr(do), ptr(din),
+                                    ptr(d_weight), dt, stream_of()))
+
+
+def SubmanifoldConvolution_backward(spatial_size, filter_size, m, input_features, d_input_features,
+                                    d_output_features, weight, d_weight, d_bias, want_d_input=True):
+    """sparseconvnet.h:106-111 (d_weight is pre-zeroed by submanifoldConvolution.py backward)."""
+    _conv_backward("d3d_subm_conv_backward_dt", (spatial_size, filter_size), m, input_features, d_input_features,
+                   d_output_features, weight, d_weight, want_d_input, flip=True)
 
 
 def Convolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
                          d_input_features, d_output_features, weight, d_weight, d_bias, want_d_input=True):
     """sparseconvnet.h:92-98."""
-    require_gpu(input_features, d_output_features, weight, d_weight)
-    fv, _, cin, cout = weight.shape
-    dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
-    isz, osz, filt, st = _size3(input_size), _size3(output_size), _size3(filter_size), _size3(filter_stride)
-    do = d_output_features.contiguous()
-    din = packed_t = None
-    if want_d_input:
-        d_input_features.resize_(input_features.shape[0], cin)
-        din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype, code=dt)
-    with _dw_fixed_order(d_weight, fv, cin, cout):
-        if dt == F32:
-            check(lib().d3d_conv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                          ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
-        else:
-            check(lib().d3d_conv_backward_dt(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features),
-                                             input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
-                                             ptr(d_weight), dt, stream_of()))
+    _conv_backward("d3d_conv_backward_dt", (input_size, output_size, filter_size, filter_stride), m, input_features,
+                   d_input_features, d_output_features, weight, d_weight, want_d_input, flip=False)
 
 
 def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, m, input_features,
                            d_input_features, d_output_features, weight, d_weight, d_bias, want_d_input=True):
     """sparseconvnet.h:153-158."""
-    require_gpu(input_features, d_output_features, weight, d_weight)
-    fv, _, cin, cout = weight.shape
-    dt = _backward_dtype(input_features, d_output_features, d_weight, cin)
-    isz, osz, filt, st = _size3(input_size), _size3(output_size), _size3(filter_size), _size3(filter_stride)
-    do = d_output_features.contiguous()
-    din = packed_t = None
-    if want_d_input:
-        d_input_features.resize_(input_features.shape[0], cin)
-        din = d_input_features
-        packed_t = pack_weight_transposed(weight, flip=False, dtype=input_features.dtype, code=dt)
-    with _dw_fixed_order(d_weight, fv, cin, cout):
-        if dt == F32:
-            check(lib().d3d_deconv_backward(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features), cin,
-                                            ptr(packed_t), cout, ptr(do), ptr(din), ptr(d_weight), stream_of()))
-        else:
-            check(lib().d3d_deconv_backward_dt(m._h, ints(isz), ints(osz), ints(filt), ints(st), ptr(input_features),
-                                               input_features.shape[1], cin, ptr(packed_t), cout, ptr(do), ptr(din),
-                                               ptr(d_weight), dt, stream_of()))
+    _conv_backward("d3d_deconv_backward_dt", (input_size, output_size, filter_size, filter_stride), m, input_features,
+                   d_input_features, d_output_features, weight, d_weight, want_d_input, flip=False)
 
 
 def BatchNormalization_backward(input_features, d_input_features, output_features, d_output_features,
@@ -938,12 +879,6 @@ def BatchNormalization_backward(input_features, d_input_features, output_feature
     w = weight if (weight is not None and weight.numel()) else None
     nbytes = lib().d3d_bn_backward_scratch_bytes(planes)
     scratch = _scratch(input_features.device, nbytes)
-    if input_features.dtype == torch.float32 and d_output_features.dtype == torch.float32:
-        check(lib().d3d_bn_backward(ptr(input_features), ptr(output_features), ptr(d_output_features.contiguous()),
-                                    ptr(d_input_features), rows, planes, ptr(saveMean), ptr(saveInvStd), ptr(w),
-                                    ptr(d_weight), ptr(d_bias), float(leakiness), ptr(scratch), scratch.numel(),
-                                    stream_of()))
-        return
     check(lib().d3d_bn_backward_dt(ptr(input_features), ptr(output_features), ptr(d_output_features.contiguous()),
                                    ptr(d_input_features), rows, planes, ptr(saveMean), ptr(saveInvStd), ptr(w),
                                    ptr(d_weight), ptr(d_bias), float(leakiness), ptr(scratch), scratch.numel(),

@@ -592,10 +592,8 @@ int d3d_subm_probe_mode(int mode);
 int d3d_conv_time_next(void *start_event, void *stop_event);
 /* Conv weights: reference layout [filter_volume, groups=1, Cin, Cout]
  * (sparseconvnet/submanifoldConvolution.py:24-26).  The kernels read a k-interleaved copy
- * [fv][ceil(Cin/8)*2][Cout][4]; pack once per weight update.                                 */
-size_t d3d_packed_weight_floats(int filter_volume, int cin, int cout);
-int d3d_pack_conv_weight(const float *w, int filter_volume, int cin, int cout, float *packed,
-                         void *stream);
+ * [fv][ceil(Cin/8)*2][Cout][4] (Cin padded to 16, 32, 64, 128 or 256); pack once per weight update
+ * (d3d_packed_weight_bytes / d3d_pack_conv_weight_dt below).                                 */
 
 /* a6. SubmanifoldConvolution_updateOutput (SCN/sparseconvnet.h:99-105), Convolution_updateOutput
  * (:85-91), Deconvolution_updateOutput (:147-152): out[r_out] = sum_k in[r_in(k)] @ W[k],
@@ -604,7 +602,7 @@ int d3d_pack_conv_weight(const float *w, int filter_volume, int cin, int cout, f
  * receives rules*Cin*Cout like the reference's return value.                                 */
 /* Optional fusion of the PRODUCER's BatchNormalization (+ leaky ReLU) into the gather of a convolution:
  * the conv reads the un-normalised rows and applies y = leaky(x * (invstd*weight) + (bias - mean*invstd*weight))
- * on the fly (same arithmetic as d3d_bn_forward), which removes one full read+write of the tensor.  Host
+ * on the fly (same arithmetic as d3d_bn_forward_dt), which removes one full read+write of the tensor.  Host
  * struct with device pointers; pass NULL (or mean == NULL) for none.                                 */
 typedef struct {
   const float *mean, *invstd, *weight, *bias; /* [Cin]; weight / bias may be NULL */
@@ -620,24 +618,13 @@ typedef struct {
   int out_stats_cap;
   int *out_stats_rows;
 } d3d_bn_prologue;
-int d3d_subm_conv_forward(d3d_meta *m, const int *spatial_size_host, const int *filter_host,
-                          const float *in, int cin, const float *packed_w, int cout,
-                          const float *residual, float *out, void *stream, double *macs_host,
-                          const d3d_bn_prologue *bn_host);
-int d3d_conv_forward(d3d_meta *m, const int *in_size_host, const int *out_size_host,
-                     const int *filter_host, const int *stride_host, const float *in, int cin,
-                     const float *packed_w, int cout, float *out, void *stream, double *macs_host,
-                     const d3d_bn_prologue *bn_host);
-int d3d_deconv_forward(d3d_meta *m, const int *in_size_host, const int *out_size_host,
-                       const int *filter_host, const int *stride_host, const float *in, int cin,
-                       const float *packed_w, int cout, const float *residual, float *out,
-                       void *stream, double *macs_host, const d3d_bn_prologue *bn_host);
 
-/* ---- bf16 storage (BASELINE.json configs[4]; the reference dispatches on the tensor type in
+/* ---- Storage types.  D3D_F32: fp32 rows, packed weights and outputs, `cin` <= 256 channels as they are.
+ * D3D_BF16: bf16 storage (BASELINE.json configs[4]; the reference dispatches on the tensor type in
  * SCN/CUDA/Convolution.cu:444-521 and sparseconvnet_cuda.cpp).  Feature rows, packed weights and outputs are bf16
  * (raw 16-bit words), accumulation is fp32 on v_mfma_f32_32x32x16_bf16, BatchNorm statistics stay fp64/fp32.
  * For D3D_BF16 `cin` is the STORED row width: 16, 32, 64, 128 or 256 channels (narrower inputs are zero padded by
- * the caller; d3d_pack_conv_weight_dt pads the weights to match).  D3D_F32 forwards to the fp32 entry points.      */
+ * the caller; d3d_pack_conv_weight_dt pads the weights to match).                                               */
 typedef enum { D3D_F32 = 0, D3D_BF16 = 1, D3D_F32_X3 = 2 } d3d_dtype;
 /* D3D_F32_X3: fp32 rows, residual and outputs, as D3D_F32, with bf16x3 products -- what torch's
  * set_float32_matmul_precision('high') / matmul.fp32_precision = 'tf32' permits (gfx950 has no xf32 MFMA).  Each fp32
@@ -698,7 +685,7 @@ int d3d_conv_group_forward(d3d_meta *m, const d3d_conv_desc *descs_host, int n, 
  * every weight fetch in launches that keep at least min_waves * row_blocks waves (min_waves < 0: the default).
  * Results do not depend on it beyond the summation grouping of offset-split launches.                           */
 int d3d_conv_bf16_tuning(int row_blocks, long min_waves);
-/* d3d_bn_batch_stats (want_invstd == 0: mean, unbiased var) / d3d_bn_batch_invstd (want_invstd != 0: mean,
+/* d3d_bn_batch_stats (want_invstd == 0: mean, unbiased var) / d3d_bn_batch_invstd_dt (want_invstd != 0: mean,
  * powf(var + eps, -0.5)) from the column sums a convolution left per row block (d3d_bn_prologue.out_stats: partial_rows
  * rows of [2 * planes] fp64) instead of from the tensor; `rows` = rows of the tensor.  Same arithmetic after the sums,
  * a fixed summation order (deterministic), one launch.  planes: a multiple of 4, at most 512 or a multiple of 512 up
@@ -718,7 +705,11 @@ int d3d_bn_stats_from_partials(const double *partials, int partial_rows, int row
  *     1 when the two-row loop is entered, storage.
  * The record is cleared by the call (out may be null).  -> the number of fields the record has.                      */
 int d3d_bn_last_form(int *out, int n);
-/* d3d_bn_batch_invstd / d3d_bn_apply on a tensor of the given storage type (statistics and parameters fp32). */
+/* The two halves of an inference BatchNorm on a tensor of storage type D3D_F32 or D3D_BF16 (statistics and parameters
+ * fp32).  d3d_bn_batch_invstd_dt: mean(0) and invstd = powf(var_unbiased(0) + eps, -0.5), what the eval path with
+ * track_running_stats=False feeds the normalisation with; use with d3d_bn_prologue.  d3d_bn_apply_dt: the normalisation
+ * alone, y = leaky(x * (invstd*gamma) + (beta - mean*invstd*gamma)) (BatchNormalization.cpp:46-59), for a consumer of a
+ * deferred BatchNorm that is not a convolution (bf16 rows: planes / 4 a divisor of 256).                             */
 int d3d_bn_batch_invstd_dt(const void *in, int rows, int planes, float eps, float *mean, float *invstd,
                            void *scratch, size_t scratch_bytes, int dtype, void *stream);
 int d3d_bn_apply_dt(const void *in, void *out, int rows, int planes, const float *mean, const float *invstd,
@@ -732,26 +723,14 @@ int d3d_rows_to_bf16(const float *in, long rows, int cin, int width, void *out, 
 /* a7. Backward (training).  SubmanifoldConvolution_backward / Convolution_backward / Deconvolution_backward
  * (SCN/sparseconvnet.h:92-98,106-111,153-158; SCN/CUDA/Convolution.cu:249-442): d_in is overwritten,
  * d_weight [fv, Cin, Cout] is accumulated into (the caller pre-zeroes it, as the reference's Python does).
- * `packed_wt*` is the transposed packing of d3d_pack_conv_weight_transposed (flip=1 for submanifold).
- * Either gradient pointer may be null to skip it.  dWeight uses fp32 atomics (like the reference).     */
-int d3d_pack_conv_weight_transposed(const float *w, int filter_volume, int cin, int cout, int flip,
-                                    float *packed, void *stream);   /* size d3d_packed_weight_floats(fv, cout, cin) */
-int d3d_subm_conv_backward(d3d_meta *m, const int *spatial_size_host, const int *filter_host,
-                           const float *in, int cin, const float *packed_wt_flipped, int cout,
-                           const float *d_out, float *d_in, float *d_weight, void *stream);
-int d3d_conv_backward(d3d_meta *m, const int *in_size_host, const int *out_size_host,
-                      const int *filter_host, const int *stride_host, const float *in, int cin,
-                      const float *packed_wt, int cout, const float *d_out, float *d_in,
-                      float *d_weight, void *stream);
-int d3d_deconv_backward(d3d_meta *m, const int *in_size_host, const int *out_size_host,
-                        const int *filter_host, const int *stride_host, const float *in, int cin,
-                        const float *packed_wt, int cout, const float *d_out, float *d_in,
-                        float *d_weight, void *stream);
-/* bf16 storage (d3d_dtype; D3D_F32 forwards to the functions above).  `in`, `d_out` and `d_in` are bf16 rows; `cs` is
- * the STORED width of `in` and `d_in` (16, 32, 64, 128 or 256, as for the forward _dt functions) and `cin` the Cin of
+ * `packed_wt*` is the transposed packing of d3d_pack_conv_weight_transposed_dt (flip=1 for submanifold).
+ * Either gradient pointer may be null to skip it.  dWeight uses fp32 atomics (like the reference).
+ * fp32 rows (D3D_F32, D3D_F32_X3): `in`, `d_out` and `d_in` are fp32 and cs == cin.
+ * bf16 storage (D3D_BF16): `in`, `d_out` and `d_in` are bf16 rows; `cs` is the STORED width of `in` and `d_in` (16, 32, 64,
+ * 128 or 256, as for the forward _dt functions) and `cin` the Cin of
  * the weight and of d_weight [fv, cin, cout], which stays fp32 (cs is cin padded to the next stored width: the first
  * layer stores 9 channels as 16 and its d_weight keeps 9).  dWeight is fp32-accumulated on v_mfma_f32_32x32x16_bf16
- * (atomic or fixed-order form as above); dInput is the bf16 forward convolution with the W^T packing of
+ * (atomic or fixed-order form, see below); dInput is the bf16 forward convolution with the W^T packing of
  * d3d_pack_conv_weight_transposed_dt(..., D3D_BF16) and needs cin = cs >= 32.  Other shapes: D3D_ERR_UNSUPPORTED before
  * any launch.                                                                                                     */
 int d3d_pack_conv_weight_transposed_dt(const float *w, int filter_volume, int cin, int cout, int flip, void *packed,
@@ -788,14 +767,10 @@ size_t d3d_conv_dw_scratch_bytes(int filter_volume, int cin, int cout);
  * of the partials (0 none, 1 the caller's buffer, 2 the feature lane, 3 a stream-ordered allocation), row blocks, filter
  * volume.  The record is cleared by the call (out may be null).  -> the number of fields the record has.             */
 int d3d_conv_dw_last_form(int *out, int n);
-/* BatchNormalization_backward (SCN/sparseconvnet.h:27-32; SCN/CPU/BatchNormalization.cpp:62-107). */
-int d3d_bn_backward(const float *in, const float *out, const float *d_out, float *d_in, int rows,
-                    int planes, const float *save_mean, const float *save_invstd, const float *weight,
-                    float *d_weight, float *d_bias, float leakiness, void *scratch,
-                    size_t scratch_bytes, void *stream);
+/* BatchNormalization_backward (SCN/sparseconvnet.h:27-32; SCN/CPU/BatchNormalization.cpp:62-107) on fp32 or bf16 rows
+ * `in`, `out` (the forward's output, for the activation's mask), `d_out` and `d_in`: fp32 arithmetic and fp64 partial
+ * sums either way; save_mean / save_invstd / weight and d_weight / d_bias stay fp32. */
 size_t d3d_bn_backward_scratch_bytes(int planes);
-/* the same for bf16 rows `in`, `out` (the forward's output, for the activation's mask), `d_out` and `d_in`: fp32 arithmetic,
- * the same fp64 partial sums; save_mean / save_invstd / weight and d_weight / d_bias stay fp32. */
 int d3d_bn_backward_dt(const void *in, const void *out, const void *d_out, void *d_in, int rows, int planes,
                        const float *save_mean, const float *save_invstd, const float *weight, float *d_weight,
                        float *d_bias, float leakiness, void *scratch, size_t scratch_bytes, int dtype, void *stream);
@@ -870,28 +845,16 @@ int d3d_roi_last_form(int *out, int n);
 /* a8. BatchNormalization_updateOutput (SCN/sparseconvnet.h:21-26; SCN/CPU/BatchNormalization.cpp:12-60).
  * train!=0: batch statistics, running update r = m*r + (1-m)*batch.  train==0: uses
  * running_mean / running_var.  d3d_bn_batch_stats computes mean(0) and the UNBIASED var(0)
- * that sparseconvnet/batchNormalization.py:51-56 feeds in when track_running_stats=False.    */
-int d3d_bn_forward(const float *in, float *out, int rows, int planes, float *save_mean,
-                   float *save_invstd, float *running_mean, float *running_var,
-                   const float *weight, const float *bias, float eps, float momentum, int train,
-                   float leakiness, void *scratch, size_t scratch_bytes, void *stream);
-/* d3d_bn_forward on rows of the given storage type (bf16: statistics in fp64 / fp32 as for fp32 rows, y rounded once;
- * save_mean, save_invstd and the running statistics fp32, same semantics). */
+ * that sparseconvnet/batchNormalization.py:51-56 feeds in when track_running_stats=False.
+ * d3d_bn_forward_dt takes rows of storage type D3D_F32 or D3D_BF16 (bf16: statistics in fp64 / fp32 as for fp32 rows,
+ * y rounded once; save_mean, save_invstd and the running statistics fp32, same semantics).  */
 int d3d_bn_forward_dt(const void *in, void *out, int rows, int planes, float *save_mean, float *save_invstd,
                       float *running_mean, float *running_var, const float *weight, const float *bias, float eps,
                       float momentum, int train, float leakiness, void *scratch, size_t scratch_bytes, int dtype,
                       void *stream);
 int d3d_bn_batch_stats(const float *in, int rows, int planes, float *mean, float *var_unbiased,
                        void *scratch, size_t scratch_bytes, void *stream);
-/* mean(0) and invstd = powf(var_unbiased(0) + eps, -0.5): what the eval path with track_running_stats=False
- * feeds the normalisation with; use with d3d_bn_prologue.                                            */
-int d3d_bn_batch_invstd(const float *in, int rows, int planes, float eps, float *mean, float *invstd,
-                        void *scratch, size_t scratch_bytes, void *stream);
-/* the normalisation alone, y = leaky(x * (invstd*gamma) + (beta - mean*invstd*gamma)) (BatchNormalization.cpp:46-59),
- * for a consumer of a deferred BatchNorm that is not a convolution.                                   */
-int d3d_bn_apply(const float *in, float *out, int rows, int planes, const float *mean, const float *invstd,
-                 const float *weight, const float *bias, float leakiness, void *stream);
-/* scratch of d3d_bn_forward / d3d_bn_batch_stats / d3d_bn_batch_invstd: device memory of this many bytes whose
+/* scratch of d3d_bn_forward_dt / d3d_bn_batch_stats / d3d_bn_batch_invstd_dt: device memory of this many bytes whose
  * first 256 bytes (ticket counters) are ZERO before the first call; the library leaves them zero.  planes must
  * be a multiple of 4 with planes/4 dividing 1024 (planes = 4, 8, ..., 4096).                                     */
 size_t d3d_bn_scratch_bytes(int planes);

@@ -121,7 +121,7 @@ def expect_backward(rows, planes, typ, aligned16=True):
 
 def expect_bn(rows, planes, typ, stats=None, apply=False, backward=False, aligned16=True):
     """The whole record after one call.  stats: None, ("tensor", mode), ("partials", mode, partial_rows) or "running"
-    (eval mode of d3d_bn_forward: running statistics, nothing else recorded); apply / backward: that stage ran."""
+    (eval mode of d3d_bn_forward_dt: running statistics, nothing else recorded); apply / backward: that stage ran."""
     f = _zero()
     if rows == 0:
         return f                              # every entry point returns before its first launch

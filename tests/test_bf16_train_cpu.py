@@ -64,15 +64,117 @@ def test_bf16_entry_points_refuse_before_launch(lib):
     assert lib.d3d_bn_backward_dt(p, p, p, p, 10, 32, p, p, None, None, None, 0.0, p, 1 << 20, 2, None) == -1
 
 
+def test_fp32_rows_refused_as_by_the_fp32_only_forms(lib):
+    """dtype 0 (D3D_F32) through the _dt entry points: what the removed fp32-only twins refused with D3D_ERR_ARG (-1) is
+    still refused with it, and their empty calls still return D3D_OK, all before any launch"""
+    from detection_3d_amd import _lib
+    ints = _lib.ints
+    p = 0x1000          # placeholder: never dereferenced
+    size, filt = ints([8, 8, 8]), ints([3, 3, 3])
+    # convolutions, forward and backward: null metadata, null sizes
+    assert lib.d3d_subm_conv_forward_dt(None, size, filt, p, 32, p, 32, None, p, 0, None, None, None) == -1
+    assert lib.d3d_subm_conv_forward_dt(p, None, filt, p, 32, p, 32, None, p, 0, None, None, None) == -1
+    assert lib.d3d_conv_forward_dt(None, size, size, filt, filt, p, 32, p, 32, p, 0, None, None, None) == -1
+    assert lib.d3d_conv_forward_dt(p, size, size, filt, None, p, 32, p, 32, p, 0, None, None, None) == -1
+    assert lib.d3d_deconv_forward_dt(None, size, size, filt, filt, p, 32, p, 32, None, p, 0, None, None, None) == -1
+    assert lib.d3d_deconv_forward_dt(p, size, None, filt, filt, p, 32, p, 32, None, p, 0, None, None, None) == -1
+    assert lib.d3d_subm_conv_backward_dt(None, size, filt, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    assert lib.d3d_subm_conv_backward_dt(p, size, None, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    assert lib.d3d_conv_backward_dt(None, size, size, filt, filt, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    assert lib.d3d_conv_backward_dt(p, size, size, filt, None, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    assert lib.d3d_deconv_backward_dt(None, size, size, filt, filt, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    assert lib.d3d_deconv_backward_dt(p, size, None, filt, filt, p, 32, 32, p, 32, p, p, p, 0, None) == -1
+    # packing: null pointers, no filter, no output channel, Cin (W^T: Cout) past 256
+    assert lib.d3d_pack_conv_weight_dt(None, 27, 32, 32, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_dt(p, 27, 32, 32, None, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_dt(p, 0, 32, 32, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_dt(p, 27, 32, 0, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_dt(p, 27, 300, 32, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_transposed_dt(None, 27, 32, 32, 1, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_transposed_dt(p, 27, 32, 32, 1, None, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_transposed_dt(p, 0, 32, 32, 1, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_transposed_dt(p, 27, 0, 32, 1, p, 0, None) == -1
+    assert lib.d3d_pack_conv_weight_transposed_dt(p, 27, 32, 300, 1, p, 0, None) == -1
+    # BatchNorm statistics and apply: null pointers, no rows, no planes; an empty apply is D3D_OK
+    assert lib.d3d_bn_batch_invstd_dt(None, 10, 32, 1e-4, p, p, p, 1 << 20, 0, None) == -1
+    assert lib.d3d_bn_batch_invstd_dt(p, 10, 32, 1e-4, None, p, p, 1 << 20, 0, None) == -1
+    assert lib.d3d_bn_batch_invstd_dt(p, 10, 32, 1e-4, p, None, p, 1 << 20, 0, None) == -1
+    assert lib.d3d_bn_batch_invstd_dt(p, 0, 32, 1e-4, p, p, p, 1 << 20, 0, None) == -1
+    assert lib.d3d_bn_batch_invstd_dt(p, 10, 30, 1e-4, p, p, p, 1 << 20, 0, None) == -1      # planes % 4
+    assert lib.d3d_bn_batch_invstd_dt(p, 10, 32, 1e-4, p, p, None, 0, 0, None) == -1         # no scratch
+    assert lib.d3d_bn_apply_dt(None, None, 0, 32, None, None, None, None, 0.0, 0, None) == 0
+    assert lib.d3d_bn_apply_dt(None, p, 10, 32, p, p, None, None, 0.0, 0, None) == -1
+    assert lib.d3d_bn_apply_dt(p, None, 10, 32, p, p, None, None, 0.0, 0, None) == -1
+    assert lib.d3d_bn_apply_dt(p, p, 10, 32, None, p, None, None, 0.0, 0, None) == -1
+    assert lib.d3d_bn_apply_dt(p, p, 10, 32, p, None, None, None, 0.0, 0, None) == -1
+    assert lib.d3d_bn_apply_dt(p, p, 10, 0, p, p, None, None, 0.0, 0, None) == -1
+    assert lib.d3d_bn_apply_dt(p, p, -1, 32, p, p, None, None, 0.0, 0, None) == -1
+    # BatchNorm forward and backward: null statistics, no planes, negative rows, null features; no rows is D3D_OK
+    def fwd(i, o, rows, planes, save_mean):
+        return lib.d3d_bn_forward_dt(i, o, rows, planes, save_mean, p, p, p, None, None, 1e-4, 0.9, 1, 0.0, p, 1 << 20, 0, None)
+
+    assert fwd(p, p, 10, 32, None) == -1
+    assert fwd(p, p, 10, 0, p) == -1
+    assert fwd(p, p, -1, 32, p) == -1
+    assert fwd(None, None, 0, 32, p) == 0
+    assert fwd(None, p, 10, 32, p) == -1
+    assert fwd(p, None, 10, 32, p) == -1
+
+    def bwd(i, o, g, d, rows, planes, save_mean, scratch, nbytes):
+        return lib.d3d_bn_backward_dt(i, o, g, d, rows, planes, save_mean, p, None, None, None, 0.0, scratch, nbytes, 0, None)
+
+    assert bwd(p, p, p, p, 10, 0, p, p, 1 << 20) == -1
+    assert bwd(p, p, p, p, -1, 32, p, p, 1 << 20) == -1
+    assert bwd(p, p, p, p, 10, 32, None, p, 1 << 20) == -1
+    assert bwd(None, None, None, None, 0, 32, p, p, 1 << 20) == 0
+    assert bwd(None, p, p, p, 10, 32, p, p, 1 << 20) == -1
+    assert bwd(p, p, p, None, 10, 32, p, p, 1 << 20) == -1
+    assert bwd(p, p, p, p, 10, 48, p, p, 1 << 20) == -1                                     # 256 % planes
+    assert bwd(p, p, p, p, 10, 32, p, None, 0) == -1                                        # no scratch
+
+
 class _Recorder:
     def __init__(self):
         self.calls = []
+        self.args = []
 
     def __getattr__(self, name):
         def f(*args):
             self.calls.append(name)
+            self.args.append(args)
             return 0
         return f
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+def test_pack_paths_make_one_call_per_storage_type(monkeypatch, transposed):
+    """pack_weight / pack_weight_transposed: the size query, a buffer whose element type names the d3d_dtype, the _dt pack
+    call -- and for a contiguous fp32 parameter no copy of it, whatever the code"""
+    from detection_3d_amd.sparseconvnet import SCN
+
+    class Rec(_Recorder):
+        def d3d_packed_weight_bytes(self, fv, cin, cout, code):
+            self.calls.append("d3d_packed_weight_bytes")
+            self.args.append((fv, cin, cout, code))
+            return fv * cin * cout * (2 if code == SCN.BF16 else 4)
+
+    monkeypatch.setattr(SCN, "require_gpu", lambda *t: None)
+    monkeypatch.setattr(SCN, "stream_of", lambda: None)
+    w = torch.nn.Parameter(torch.zeros(27, 1, 32, 64))
+    entry = "d3d_pack_conv_weight_transposed_dt" if transposed else "d3d_pack_conv_weight_dt"
+    for code, elem in ((SCN.F32, torch.float32), (SCN.BF16, torch.bfloat16), (SCN.F32_X3, torch.int16)):
+        rec = Rec()
+        monkeypatch.setattr(SCN, "lib", lambda: rec)
+        dtype = torch.bfloat16 if code == SCN.BF16 else torch.float32
+        packed = SCN.pack_weight_transposed(w, True, dtype, code) if transposed else SCN.pack_weight(w, dtype, code)
+        assert rec.calls == ["d3d_packed_weight_bytes", entry]
+        assert rec.args[0] == ((27, 64, 32, code) if transposed else (27, 32, 64, code))
+        assert packed.dtype == elem and packed.numel() * packed.element_size() == 27 * 32 * 64 * (2 if code == SCN.BF16 else 4)
+        assert SCN._packed_code(packed) == code
+        call = rec.args[1]
+        assert call[0].value == w.data_ptr()                      # the parameter itself: no cast, no copy, no launch
+        assert call[1:4] == (27, 32, 64) and call[-2] == code
+        assert (call[5] if transposed else call[4]).value == packed.data_ptr()
 
 
 def test_backward_wrappers_guard_dtypes(monkeypatch):

@@ -260,7 +260,7 @@ def test_apply(dev, planes, typ):
             assert out.dtype == xt.dtype
             B.check_apply(tag, to_np(out), x, mean, invstd, w, b, leak, exact_data, typ == BF16)
             if typ == F32 and not B.apply_rows_kernel(planes):
-                # the same kernel through d3d_bn_forward in eval mode: running statistics, invstd = powf(var + eps, -1/2)
+                # the same kernel through d3d_bn_forward_dt in eval mode: running statistics, invstd = powf(var + eps, -1/2)
                 var = (invstd.astype(np.float64) ** -2).astype(np.float32)
                 sm, si = torch.empty(planes, device=dev), torch.empty(planes, device=dev)
                 out2 = xt.new_empty(0)

@@ -114,17 +114,17 @@ def test_conv_backward_dw_mode_per_call(monkeypatch, flag, on):
     SCN.Convolution_backward([8, 8, 8], [4, 4, 4], [2, 2, 2], [2, 2, 2], m, torch.zeros(5, 32), None, torch.zeros(3, 64), w,
                              torch.zeros_like(w), None, want_d_input=False)
     if on:
-        assert rec.calls == ["d3d_conv_dw_scratch_bytes", "d3d_conv_dw_thread_mode", "d3d_conv_backward",
+        assert rec.calls == ["d3d_conv_dw_scratch_bytes", "d3d_conv_dw_thread_mode", "d3d_conv_backward_dt",
                              "d3d_conv_dw_thread_mode"]
     else:
-        assert rec.calls == ["d3d_conv_backward"]
+        assert rec.calls == ["d3d_conv_backward_dt"]
     # an error inside the call still switches the mode off
     rec.calls.clear()
     monkeypatch.setattr(SCN, "check", lambda rc: (_ for _ in ()).throw(RuntimeError("boom")))
     with pytest.raises(RuntimeError, match="boom"):
         SCN.Convolution_backward([8, 8, 8], [4, 4, 4], [2, 2, 2], [2, 2, 2], m, torch.zeros(5, 32), None, torch.zeros(3, 64), w,
                                  torch.zeros_like(w), None, want_d_input=False)
-    assert rec.calls[-1] == ("d3d_conv_dw_thread_mode" if on else "d3d_conv_backward")
+    assert rec.calls[-1] == ("d3d_conv_dw_thread_mode" if on else "d3d_conv_backward_dt")
 
 
 def test_new_symbols_and_argument_checks(lib):

@@ -399,8 +399,8 @@ def test_empty_plan(dev):
             x32, g32 = torch.zeros((0, 64), device=dev), torch.zeros((0, 64), device=dev)
             dw_last_form()
             with dw_mode(mode):
-                rc = L.d3d_subm_conv_backward(t.metadata._h, ints(size), ints(filt), ptr(x32), 64, None, 64, ptr(g32), None,
-                                              ctypes.c_void_p(buf.data_ptr() + 4 * PAD), stream_of())
+                rc = L.d3d_subm_conv_backward_dt(t.metadata._h, ints(size), ints(filt), ptr(x32), 64, 64, None, 64, ptr(g32),
+                                                 None, ctypes.c_void_p(buf.data_ptr() + 4 * PAD), 0, stream_of())
                 rc16 = L.d3d_subm_conv_backward_dt(t.metadata._h, ints(size), ints(filt), ptr(x32.bfloat16()), 64, 64, None,
                                                    64, ptr(g32.bfloat16()), None,
                                                    ctypes.c_void_p(buf.data_ptr() + 4 * PAD), DT_BF16, stream_of())

@@ -344,7 +344,7 @@ def test_non_finite_row_stays_local(dev, fused):
 def test_conv_epilogue_column_sums_give_the_batchnorm_statistics(dev, n_points, cin, cout):
     """d3d_bn_prologue.out_stats: the per-row-block fp64 column sums a convolution leaves (unsplit launches: from k_conv's
     epilogue; offset-split few-row launches: from k_conv_reduce), finished by d3d_bn_stats_from_partials, are the
-    statistics d3d_bn_batch_invstd / d3d_bn_batch_stats compute from the stored tensor -- fp64 sums in another order, so
+    statistics d3d_bn_batch_invstd_dt / d3d_bn_batch_stats compute from the stored tensor -- fp64 sums in another order, so
     equal after the rounding to fp32 up to 1 ulp: tolerance 5e-7 relative.  Submanifold (+ residual), strided, deconvolution."""
     from detection_3d_amd import sparseconvnet as scn
     from detection_3d_amd.sparseconvnet import SCN, modules
