@@ -9,7 +9,6 @@
 #include "d3d_internal.h"
 
 #include <algorithm>
-#include <cstring>
 
 namespace d3d {
 
@@ -21,15 +20,6 @@ struct AugArgs {
   double m[9], nrm[9], color[3], u1[3], u2[3];
   int origin_offset, color_col, normal_col;
 };
-
-__device__ __forceinline__ unsigned long long encode_ordered(double x) {
-  unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double decode_ord(unsigned long long u) {
-  u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-  return __longlong_as_double((long long)u);
-}
 
 // ((x m0j + y m1j) + z m2j), the order of the oracle
 __device__ __forceinline__ double row_times(const double *m, int j, double x, double y, double z) {
@@ -76,9 +66,9 @@ __global__ __launch_bounds__(256) void k_aug_minmax(const float *__restrict__ pc
     double x = lds[0][d];
     for (int w = 1; w < 4; w++) x = d < 3 ? fmin(x, lds[w][d]) : fmax(x, lds[w][d]);
     if (d < 3)
-      atomicMin(&red[d], encode_ordered(x));
+      atomicMin(&red[d], f64_ordered(x));
     else
-      atomicMax(&red[d], encode_ordered(x));
+      atomicMax(&red[d], f64_ordered(x));
   }
 }
 
@@ -87,7 +77,7 @@ __global__ void k_aug_offset(const unsigned long long *red, AugArgs g, int fx, i
   const int d = threadIdx.x;
   if (d >= 3) return;
   const double full = (double)(d == 0 ? fx : d == 1 ? fy : fz);
-  const double lo = decode_ord(red[d]), hi = decode_ord(red[3 + d]);
+  const double lo = ordered_to_f64(red[d]), hi = ordered_to_f64(red[3 + d]);
   double o = -lo;
   if (g.origin_offset) {
     const double q = __dadd_rn(__dsub_rn(full, hi), lo);
@@ -134,17 +124,6 @@ __global__ void k_aug_write(const float *__restrict__ pcl, int n, int nfeat, con
     const double x = p[g.normal_col], y = p[g.normal_col + 1], z = p[g.normal_col + 2];
     for (int k = 0; k < 3; k++) f[g.normal_col + k] = (float)row_times(g.nrm, k, x, y, z);
   }
-}
-
-// the kept count and the offset -> the pinned words (system-scope stores, vector memory)
-__global__ void k_aug_publish(const int32_t *__restrict__ count, const double *__restrict__ off,
-                              const unsigned long long *__restrict__ red, unsigned long long *word) {
-  const int t = threadIdx.x;
-  if (t == 0 && count) __hip_atomic_store(word, (unsigned long long)(uint32_t)*count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (t < 3 && off)
-    __hip_atomic_store(word + 1 + t, (unsigned long long)__double_as_longlong(off[t]), __ATOMIC_RELEASE,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-  if (t < 6 && red) __hip_atomic_store(word + 1 + t, red[t], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // one pass of the 3-tap 1/3 box filter along `axis` of `nf` fields [nf][D0][D1][D2], zero padded: scipy.ndimage's
@@ -228,9 +207,9 @@ __global__ __launch_bounds__(256) void k_elastic_apply(double *pts, int n, const
     double x = lds[0][d];
     for (int w = 1; w < 4; w++) x = d < 3 ? fmin(x, lds[w][d]) : fmax(x, lds[w][d]);
     if (d < 3)
-      atomicMin(&red[d], encode_ordered(x));
+      atomicMin(&red[d], f64_ordered(x));
     else
-      atomicMax(&red[d], encode_ordered(x));
+      atomicMax(&red[d], f64_ordered(x));
   }
 }
 
@@ -253,23 +232,12 @@ AugArgs to_args(const d3d_augment_params *p) {
 
 unsigned reduce_blocks(int n) { return std::max(1u, std::min(1024u, (unsigned)((n + 255) / 256))); }
 
-// min / max words -> host doubles, through the pinned word of d3d_voxelize and its event
+// the six min / max words -> host doubles
 int read_minmax(const unsigned long long *red, double *minmax_host, hipStream_t s) {
-  VoxWord *w = vox_word();
-  if (!w) return D3D_ERR_HIP;
-  unsigned long long *word = (unsigned long long *)w->word;
-  hipLaunchKernelGGL(k_aug_publish, dim3(1), dim3(64), 0, s, (const int32_t *)nullptr, (const double *)nullptr, red,
-                     word);
-  D3D_LAUNCH_CHECK();
-  D3D_HIP_CHECK(hipEventRecord(w->ev, s));
-  D3D_HIP_CHECK(hipEventSynchronize(w->ev));
-  for (int d = 0; d < 6; d++) {
-    unsigned long long u = ((volatile unsigned long long *)word)[1 + d];
-    u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-    double x;
-    memcpy(&x, &u, 8);
-    minmax_host[d] = x;
-  }
+  unsigned long long u[6];
+  if (int rc = readback_publish(red, 12, s)) return rc;
+  if (int rc = readback_wait(u, 12)) return rc;
+  for (int d = 0; d < 6; d++) minmax_host[d] = ordered_to_f64(u[d]);
   return D3D_OK;
 }
 
@@ -362,22 +330,20 @@ int d3d_augment_voxelize(const float *pcl, int n, int nfeat, const double *point
   D3D_LAUNCH_CHECK();
   int rc = scan_exclusive_i32(flag, rank, n, total, A, s);
   if (rc) return rc;
-  // count and offset to the pinned word with an event behind the store; the write pass runs while the host waits
-  VoxWord *w = vox_word();
-  if (!w) return D3D_ERR_HIP;
-  unsigned long long *word = (unsigned long long *)w->word;
-  hipLaunchKernelGGL(k_aug_publish, dim3(1), dim3(64), 0, s, (const int32_t *)total, (const double *)off,
-                     (const unsigned long long *)nullptr, word);
-  D3D_HIP_CHECK(hipEventRecord(w->ev, s));
+  // offset and count (adjacent in `red`) are published with an event behind the store; the write pass runs while the
+  // host waits
+  rc = readback_publish(off, 7, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_aug_write, grid1d(n), dim3(256), 0, s, pcl, n, nfeat, points, g, scale, (const double *)off,
                      flag, rank, coords_out, feats_out);
   D3D_LAUNCH_CHECK();
-  D3D_HIP_CHECK(hipEventSynchronize(w->ev));
-  volatile unsigned long long *vw = word;
-  *n_kept_host = (int)(uint32_t)vw[0];
-  for (int d = 0; d < 3; d++) {
-    unsigned long long u = vw[1 + d];
-    memcpy(&offset_host[d], &u, 8);
-  }
+  struct {
+    double off[3];
+    int32_t kept;
+  } back;
+  rc = readback_wait(&back, 7);
+  if (rc) return rc;
+  *n_kept_host = back.kept;
+  for (int d = 0; d < 3; d++) offset_host[d] = back.off[d];
   return D3D_OK;
 }

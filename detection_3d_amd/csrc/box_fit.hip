@@ -255,18 +255,16 @@ int d3d_fit_boxes(const float *xyz, int n, int row_stride_floats, const double *
   D3D_ALLOC(zhi, uint32_t, A, k);
   uint32_t *acc_u = reinterpret_cast<uint32_t *>(acc);
   const dim3 cells = grid1d((long)k * kThreads), chunks = grid1d(n, kChunk);
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  if (phase_ms_host) {
-    for (int j = 0; j < 3; j++) D3D_HIP_CHECK(hipEventCreate(&ev[j]));
-    D3D_HIP_CHECK(hipEventRecord(ev[0], s));
-  }
+  Timer T;                            // coarse pass, fine pass
+  if (int rc = T.start(phase_ms_host != nullptr, 3)) return rc;
+  if (int rc = T.mark(0, s)) return rc;
   hipLaunchKernelGGL(k_fit_begin, cells, dim3(256), 0, s, k, acc, zlo, zhi);
   if (n > 0)
     hipLaunchKernelGGL(k_fit_sweep<1>, chunks, dim3(kThreads), 0, s, xyz, n, row_stride_floats, origin_dev, order,
                        sorted_id, offsets, k, coarse_dev, fine_dev, choice, acc_u, zlo, zhi);
   hipLaunchKernelGGL(k_fit_pick<1>, dim3(k), dim3(64), 0, s, k, acc, zlo, zhi, offsets, yaw_free, coarse_dev, fine_dev,
                      boxes, count, choice, extent);
-  if (phase_ms_host) D3D_HIP_CHECK(hipEventRecord(ev[1], s));
+  if (int rc = T.mark(1, s)) return rc;
   hipLaunchKernelGGL(k_fit_begin, cells, dim3(256), 0, s, k, acc, (uint32_t *)nullptr, (uint32_t *)nullptr);
   if (n > 0)
     hipLaunchKernelGGL(k_fit_sweep<2>, chunks, dim3(kThreads), 0, s, xyz, n, row_stride_floats, origin_dev, order,
@@ -274,12 +272,6 @@ int d3d_fit_boxes(const float *xyz, int n, int row_stride_floats, const double *
   hipLaunchKernelGGL(k_fit_pick<2>, dim3(k), dim3(64), 0, s, k, acc, zlo, zhi, offsets, yaw_free, coarse_dev, fine_dev,
                      boxes, count, choice, extent);
   D3D_LAUNCH_CHECK();
-  if (phase_ms_host) {
-    D3D_HIP_CHECK(hipEventRecord(ev[2], s));
-    D3D_HIP_CHECK(hipEventSynchronize(ev[2]));
-    D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms_host[0], ev[0], ev[1]));
-    D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms_host[1], ev[1], ev[2]));
-    for (int j = 0; j < 3; j++) D3D_HIP_CHECK(hipEventDestroy(ev[j]));
-  }
-  return D3D_OK;
+  if (int rc = T.mark(2, s)) return rc;
+  return T.finish(phase_ms_host);
 }

@@ -1,5 +1,5 @@
 // The one walk over a cloud's cell list (celllist.hip) with the query left open, the nearest-k cut that the queries
-// share and the host-side phase timer (consumers: normals.hip, clean.hip, planes.hip; register.hip takes the constants
+// share and the host-side helpers (consumers: normals.hip, clean.hip, planes.hip; register.hip takes the constants
 // and helpers for a walk of its own).  Included inside namespace d3d's anonymous namespace, after
 // `using namespace celllist`: every translation unit gets its own instantiations.
 
@@ -152,29 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_cln_walk(const float4 *__restrict_
 }
 
 // ---- host side ----
-constexpr int kPhases = 5;            // cells, sort, table, search, tail
-
-struct Timer {                        // events around the phases when the caller asked for their times
-  hipEvent_t ev[kPhases + 1] = {};
-  bool on = false;
-  int start(bool want) {
-    on = want;
-    if (on)
-      for (int k = 0; k <= kPhases; k++) D3D_HIP_CHECK(hipEventCreate(&ev[k]));
-    return D3D_OK;
-  }
-  int mark(int k, hipStream_t s) {
-    if (on) D3D_HIP_CHECK(hipEventRecord(ev[k], s));
-    return D3D_OK;
-  }
-  int finish(float *ms) {
-    if (!on) return D3D_OK;
-    D3D_HIP_CHECK(hipEventSynchronize(ev[kPhases]));
-    for (int k = 0; k < kPhases; k++) D3D_HIP_CHECK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-    for (int k = 0; k <= kPhases; k++) (void)hipEventDestroy(ev[k]);
-    return D3D_OK;
-  }
-};
+constexpr int kPhases = 5;            // cells, sort, table, search, tail: kPhases + 1 events of a Timer (d3d_internal.h)
 
 bool args_ok(int n, int stride, float radius) {
   return n >= 0 && n <= kMaxPoints && stride >= 3 && radius > 0.f && radius < INFINITY;

@@ -182,10 +182,10 @@ int d3d_radius_neighbors(const float *xyz, int n, int row_stride_floats, float r
   D3D_REQUIRE(scratch_bytes >= d3d_radius_neighbors_scratch_bytes(n), "d3d_radius_neighbors: scratch too small");
   hipStream_t s = (hipStream_t)stream;
   Timer T;
-  CLN_TRY(T.start(phase_ms_host != nullptr));
+  CLN_TRY(T.start(phase_ms_host != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   celllist::CellList L;
-  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.events()));
   CLN_TRY(launch_walk(L, n, CountQuery{r2_bits(radius), count}, s));
   CLN_TRY(T.mark(4, s));
   CLN_TRY(T.mark(5, s));
@@ -213,12 +213,12 @@ int d3d_knn_mean_distance(const float *xyz, int n, int row_stride_floats, float 
   D3D_REQUIRE(xyz && mean && found && scratch, "d3d_knn_mean_distance: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_knn_mean_distance_scratch_bytes(n), "d3d_knn_mean_distance: scratch too small");
   Timer T;
-  CLN_TRY(T.start(phase_ms_host != nullptr));
+  CLN_TRY(T.start(phase_ms_host != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   const int nb = stat_blocks(n);
   D3D_ALLOC(part, StatPartial, A, nb);
   celllist::CellList L;
-  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.events()));
   CLN_TRY(launch_walk(L, n, KnnQuery{r2_bits(radius), k, n, mean, found}, s));
   CLN_TRY(T.mark(4, s));
   hipLaunchKernelGGL(k_cln_stat_partial, dim3((unsigned)nb), dim3(kStatThreads), 0, s, (const double *)mean, n, part);
@@ -248,14 +248,14 @@ int d3d_connected_components(const float *xyz, int n, int row_stride_floats, flo
   D3D_REQUIRE(scratch_bytes >= d3d_connected_components_scratch_bytes(n), "d3d_connected_components: scratch too small");
   hipStream_t s = (hipStream_t)stream;
   Timer T;
-  CLN_TRY(T.start(phase_ms_host != nullptr));
+  CLN_TRY(T.start(phase_ms_host != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   D3D_ALLOC(par, int32_t, A, n);
   D3D_ALLOC(root, int32_t, A, n);
   D3D_ALLOC(min_index, int32_t, A, n);
   D3D_ALLOC(csize, int32_t, A, n);
   celllist::CellList L;
-  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.events()));
   hipLaunchKernelGGL(k_cln_iota, grid1d(n), dim3(256), 0, s, par, n);
   D3D_HIP_CHECK(hipMemsetAsync(min_index, 0x7F, (size_t)n * 4, s));      // above every index
   D3D_HIP_CHECK(hipMemsetAsync(csize, 0, (size_t)n * 4, s));

@@ -1,7 +1,7 @@
 // a6. Sparse convolution forward as ONE output-stationary launch per layer (the reference issues
 // one kernel + one blocking rule memcpy per filter offset, SCN/CUDA/RuleBookIterator.h:15-32).
 //
-// Work decomposition: a block of 32 output rows (rows sorted by neighbour mask, see grid.hip
+// Work decomposition: a block of 32 output rows (rows sorted by neighbour mask, see plan.hip
 // finalize_plan) is owned by COUT/32/NT waves, each holding NT 32x32 accumulator tiles.  For
 // every filter offset k present in the block's mask the waves gather the 32 input rows into an
 // LDS tile (full rows, 16 B per thread, coalesced; register-staged one step ahead so that the

@@ -25,13 +25,15 @@ void set_error(const char *fmt, ...);
     }                                                                                \
   } while (0)
 
-#define D3D_REQUIRE(cond, ...)        \
-  do {                                \
-    if (!(cond)) {                    \
-      d3d::set_error(__VA_ARGS__);    \
-      return D3D_ERR_ARG;             \
-    }                                 \
+#define D3D_REQUIRE_AS(code, cond, ...) \
+  do {                                  \
+    if (!(cond)) {                      \
+      d3d::set_error(__VA_ARGS__);      \
+      return code;                      \
+    }                                   \
   } while (0)
+#define D3D_REQUIRE(cond, ...) D3D_REQUIRE_AS(D3D_ERR_ARG, cond, __VA_ARGS__)          // a bad argument
+#define D3D_REQUIRE_STATE(cond, ...) D3D_REQUIRE_AS(D3D_ERR_STATE, cond, __VA_ARGS__)  // a call out of order
 
 #define D3D_LAUNCH_CHECK() D3D_HIP_CHECK(hipGetLastError())
 
@@ -70,13 +72,47 @@ inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block 
     return D3D_ERR_NOMEM;                                                              \
   }
 
-// per host thread and device: a 64-byte pinned word a kernel stores a count (or a few values) to and the event recorded
-// behind that store (d3d_voxelize, d3d_augment_*: the host waits for the event alone)
-struct VoxWord {
-  int32_t *word = nullptr;
-  hipEvent_t ev = nullptr;
+// Read-back of a few device words without a stream synchronise (voxelize.hip).  Every host thread has, per device, a
+// 64-byte pinned word and an event.  readback_publish enqueues on `s` one single-wave kernel that copies n_words
+// (1..16) consecutive 32-bit words from `src_dev` to the pinned word with system-scope release stores, and records the
+// event behind it; readback_wait waits for that event alone and copies the words to `dst_host`.  Two calls, so that a
+// caller can enqueue more work between them and have it run while the host waits (d3d_voxelize, d3d_augment_voxelize).
+int readback_publish(const void *src_dev, int n_words, hipStream_t s);
+int readback_wait(void *dst_host, int n_words);
+
+// Events around the phases of an op whose caller asked for their times; off (start(false, ..)), every call does nothing.
+struct Timer {
+  std::vector<hipEvent_t> ev;
+  bool on = false;
+  int start(bool want, size_t n_events) {
+    on = want;
+    if (on) ev.assign(n_events, nullptr);
+    for (hipEvent_t &e : ev) D3D_HIP_CHECK(hipEventCreate(&e));
+    return D3D_OK;
+  }
+  hipEvent_t *events() { return on ? ev.data() : nullptr; }
+  int mark(size_t k, hipStream_t s) {
+    if (on) D3D_HIP_CHECK(hipEventRecord(ev[k], s));
+    return D3D_OK;
+  }
+  // waits for the last event and adds the time between events k and k + 1 to ms[slot(k)], for every k
+  template <class Slot>
+  int finish(float *ms, Slot slot) {
+    if (!on) return D3D_OK;
+    D3D_HIP_CHECK(hipEventSynchronize(ev.back()));
+    for (size_t k = 0; k + 1 < ev.size(); k++) {
+      float t = 0.f;
+      D3D_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+      ms[slot(k)] += t;
+    }
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    return D3D_OK;
+  }
+  int finish(float *ms) {   // one phase per pair of consecutive events
+    for (size_t k = 0; on && k + 1 < ev.size(); k++) ms[k] = 0.f;
+    return finish(ms, [](size_t k) { return k; });
+  }
 };
-VoxWord *vox_word();
 
 static constexpr uint64_t kEmptyKey = ~uint64_t(0);
 
@@ -180,6 +216,14 @@ __device__ __forceinline__ uint32_t f32_ordered(float v) {
 __host__ __device__ __forceinline__ float ordered_to_f32(uint32_t u) {
   return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
+// the same pair for a double (host and device: the augmentation reports a cloud's extent with it)
+__device__ __forceinline__ unsigned long long f64_ordered(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__host__ __device__ __forceinline__ double ordered_to_f64(unsigned long long u) {
+  return __builtin_bit_cast(double, (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u);
+}
 // BoxCoder3D.decode of one row (box_coder_3d.py:38-65 / box_torch_ops.py:51-88, smooth_dim): e[7] encoding, a[7] anchor
 // (xa, ya, za, wa, la, ha, ra), w[7] the coder's weights, size deltas clamped to `clip`; yaw wrapped to [-pi/2, pi/2).
 __device__ __forceinline__ void box_decode_one(const float *e, const float *a, const float *w, float clip, float *o) {
@@ -253,19 +297,20 @@ struct d3d_meta {
   // the three maps above may be read by the caller's thread while the geometry thread (d3d_geometry_async_start) adds
   // to them: every lookup / insertion holds `mu` (map nodes do not move, so the pointers handed out stay valid)
   std::recursive_mutex mu;
-  void *geo_async = nullptr;       // grid.hip GeoAsync: the running / last geometry chain of this metadata
+  void *geo_async = nullptr;       // geometry_async.hip GeoAsync: the running / last geometry chain of this metadata
 };
 #define D3D_LOCK(m) std::lock_guard<std::recursive_mutex> d3d_lock_(m->mu)
 
 namespace d3d {
 
-// utilities implemented in grid.hip
+// scan_sort.hip
 int scan_exclusive_i32(const int32_t *in, int32_t *out, int n, int32_t *total_dev, Arena &scratch,
                        hipStream_t s);
 int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *vals_in,
                    int32_t *vals_out, int n, int bits, Arena &scratch, hipStream_t s, bool descending,
                    const int32_t *n_dev = nullptr);
 size_t sort_scratch_bytes(int n, int bits);   // what sort_pairs_u32 takes from its arena at most
+// plan.hip
 int finalize_plan(d3d_meta *m, const int32_t *nbr, int n_rows, int K, Plan &plan, hipStream_t s,
                   uint32_t *mask_in);
 int plan_rules(d3d_meta *m, Plan &p, hipStream_t s, long *out);
@@ -273,7 +318,8 @@ const Plan *find_plan(d3d_meta *m, int kind, const int *in_size, const int *filt
 int get_deconv_plan(d3d_meta *m, const int *fine_size, const int *filt, const int *stride,
                     hipStream_t s, const Plan **out);
 
-int grid_extent(d3d_meta *m, Grid &g, hipStream_t s);  // grid.hip: ensures g.extent (and, for small boxes, g.dense)
+int grid_extent(d3d_meta *m, Grid &g, hipStream_t s);  // grid_views.hip: ensures g.extent (and, for small boxes, g.dense)
+// grid.hip
 int check_build_stream(d3d_meta *m, hipStream_t s, const char *what);
 int ensure_point_lists(d3d_meta *m, hipStream_t s);
 Arena &lane_arena(d3d_meta *m, hipStream_t s);

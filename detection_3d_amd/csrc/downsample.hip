@@ -131,11 +131,6 @@ __global__ void k_ds_nch(const int32_t *__restrict__ segstart, const int32_t *__
   nch[s] = s < info[kInfoM] ? chunks_of(segstart[s + 1] - segstart[s]) : 0;
 }
 
-__global__ void k_ds_publish(const int32_t *__restrict__ info, int32_t *word) {
-  const int t = threadIdx.x;
-  if (t < 16) __hip_atomic_store(word + t, info[t], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // One wave per 512-row chunk of a long segment: lane l sums rows l, l + 64, ... of the chunk in that order, the lanes
 // are added by a fixed butterfly.  partial[t][c], t in chunk order over the segments.
 __global__ __launch_bounds__(256) void k_ds_partial(const float *__restrict__ pcl, int n, int C,
@@ -407,14 +402,11 @@ int d3d_voxel_downsample_cells(const float *pcl, int n, int ncols, double voxel,
   rc = scan_exclusive_i32(L.nch(), L.choff, n, L.info + kInfoChunks, A, s);
   if (rc) return rc;
   A.used = mark;
-  VoxWord *w = vox_word();
-  if (!w) return D3D_ERR_HIP;
-  hipLaunchKernelGGL(k_ds_publish, dim3(1), dim3(64), 0, s, (const int32_t *)L.info, w->word);
-  D3D_LAUNCH_CHECK();
-  D3D_HIP_CHECK(hipEventRecord(w->ev, s));
-  D3D_HIP_CHECK(hipEventSynchronize(w->ev));
   int32_t host[16];
-  for (int k = 0; k < 16; k++) host[k] = ((volatile int32_t *)w->word)[k];
+  rc = readback_publish(L.info, 16, s);
+  if (rc) return rc;
+  rc = readback_wait(host, 16);
+  if (rc) return rc;
   if (host[kInfoOverflow]) {
     double ext[3];
     for (int d = 0; d < 3; d++)

@@ -105,10 +105,10 @@ int estimate(const float *xyz, int n, int stride, float radius, int max_nn, cons
   D3D_REQUIRE(xyz && normals && scratch, "d3d_estimate_normals: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_estimate_normals_scratch_bytes(n, max_nn), "d3d_estimate_normals: scratch too small");
   Timer T;
-  CLN_TRY(T.start(phase_ms != nullptr));
+  CLN_TRY(T.start(phase_ms != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   CellList L;
-  CLN_TRY(celllist::build(xyz, n, stride, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(xyz, n, stride, radius, A, s, &L, T.events()));
   CLN_TRY(launch_walk(L, n, NormalQuery{r2_bits(radius), max_nn, n, vp != nullptr, vp ? vp[0] : 0.f, vp ? vp[1] : 0.f,
                                         vp ? vp[2] : 0.f, normals, counts}, s));
   CLN_TRY(T.mark(4, s));

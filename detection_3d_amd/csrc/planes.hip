@@ -256,7 +256,7 @@ int d3d_segment_planes(const float *xyz, int n, int row_stride_floats, const flo
   D3D_REQUIRE(scratch_bytes >= d3d_segment_planes_scratch_bytes(n), "d3d_segment_planes: scratch too small");
   hipStream_t s = (hipStream_t)stream;
   Timer T;
-  CLN_TRY(T.start(phase_ms_host != nullptr));
+  CLN_TRY(T.start(phase_ms_host != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   D3D_ALLOC(par, int32_t, A, n);
   D3D_ALLOC(root, int32_t, A, n);
@@ -264,7 +264,7 @@ int d3d_segment_planes(const float *xyz, int n, int row_stride_floats, const flo
   D3D_ALLOC(csize, int32_t, A, n);
   D3D_ALLOC(nrm, float4, A, n);
   celllist::CellList L;
-  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(xyz, n, row_stride_floats, radius, A, s, &L, T.events()));
   hipLaunchKernelGGL(k_pln_gather, grid1d(n), dim3(256), 0, s, L.pts, normals, n, nrm);
   hipLaunchKernelGGL(k_cln_iota, grid1d(n), dim3(256), 0, s, par, n);
   D3D_HIP_CHECK(hipMemsetAsync(min_index, 0x7F, (size_t)n * 4, s));      // above every index
@@ -300,24 +300,16 @@ int d3d_fit_planes(const float *xyz, int n, int row_stride_floats, const int32_t
   const int nchunks = fit_chunks(n, k);
   D3D_ALLOC(part, double, A, (size_t)nchunks * kMoments);
   D3D_ALLOC(cstart, int32_t, A, k + 1);
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  if (phase_ms_host) {
-    for (int j = 0; j < 3; j++) D3D_HIP_CHECK(hipEventCreate(&ev[j]));
-    D3D_HIP_CHECK(hipEventRecord(ev[0], s));
-  }
+  Timer T;                            // moments, solve
+  CLN_TRY(T.start(phase_ms_host != nullptr, 3));
+  CLN_TRY(T.mark(0, s));
   hipLaunchKernelGGL(k_pln_chunks, dim3(1), dim3(1024), 0, s, offsets, k, n, cstart);
   hipLaunchKernelGGL(k_pln_moments, dim3((unsigned)nchunks), dim3(kFitThreads), 0, s, xyz, n, row_stride_floats,
                      plane_of_point, order, offsets, k, (const int32_t *)cstart, part);
-  if (phase_ms_host) D3D_HIP_CHECK(hipEventRecord(ev[1], s));
+  CLN_TRY(T.mark(1, s));
   hipLaunchKernelGGL(k_pln_solve, grid1d(k, 64), dim3(64), 0, s, xyz, n, row_stride_floats, order, offsets, k,
                      (const int32_t *)cstart, nchunks, (const double *)part, normal, d, centroid, count, rms, eigenvalues);
   D3D_LAUNCH_CHECK();
-  if (phase_ms_host) {
-    D3D_HIP_CHECK(hipEventRecord(ev[2], s));
-    D3D_HIP_CHECK(hipEventSynchronize(ev[2]));
-    D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms_host[0], ev[0], ev[1]));
-    D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms_host[1], ev[1], ev[2]));
-    for (int j = 0; j < 3; j++) D3D_HIP_CHECK(hipEventDestroy(ev[j]));
-  }
-  return D3D_OK;
+  CLN_TRY(T.mark(2, s));
+  return T.finish(phase_ms_host);
 }

@@ -15,7 +15,6 @@
 #include "d3d_internal.h"
 
 #include <algorithm>
-#include <vector>
 
 namespace d3d {
 
@@ -354,10 +353,10 @@ int d3d_nearest(const float *cloud, int n, int row_stride_floats, const float *q
   D3D_REQUIRE(cloud && scratch, "d3d_nearest: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_nearest_scratch_bytes(n, m), "d3d_nearest: scratch too small");
   Timer T;
-  CLN_TRY(T.start(phase_ms_host != nullptr));
+  CLN_TRY(T.start(phase_ms_host != nullptr, kPhases + 1));
   Arena A = scratch_arena(scratch, scratch_bytes);
   celllist::CellList L;
-  CLN_TRY(celllist::build(cloud, n, row_stride_floats, radius, A, s, &L, T.on ? T.ev : nullptr));
+  CLN_TRY(celllist::build(cloud, n, row_stride_floats, radius, A, s, &L, T.events()));
   CLN_TRY(launch_nearest(L, n, query, m, query_stride_floats, radius, index, dist2, nullptr, s));
   CLN_TRY(T.mark(4, s));
   CLN_TRY(T.mark(5, s));
@@ -386,12 +385,8 @@ int d3d_icp(const float *source, int m, int source_stride_floats, const float *t
   D3D_REQUIRE(method != 0 || n == 0 || (target_normals && normal_stride_floats >= 3), "d3d_icp: point to plane needs the target's normals");
   D3D_REQUIRE(scratch_bytes >= d3d_icp_scratch_bytes(n, m), "d3d_icp: scratch too small");
   hipStream_t s = (hipStream_t)stream;
-  const bool timed = phase_ms_host != nullptr;
-  std::vector<hipEvent_t> ev;         // timed: 4 around the build, then one behind every kernel of every step
-  if (timed) {
-    ev.resize(4 + 4 * (size_t)iterations);
-    for (auto &e : ev) D3D_HIP_CHECK(hipEventCreate(&e));
-  }
+  Timer T;                            // timed: 4 events around the build, then one behind every kernel of every step
+  CLN_TRY(T.start(phase_ms_host != nullptr, 4 + 4 * (size_t)iterations));
   Arena A = scratch_arena(scratch, scratch_bytes);
   const int nb = acc_blocks(m);
   D3D_ALLOC(qbuf, float, A, (size_t)std::max(m, 1) * 3);
@@ -401,23 +396,22 @@ int d3d_icp(const float *source, int m, int source_stride_floats, const float *t
   D3D_HIP_CHECK(hipMemsetAsync(state_dev, 0, 2 * sizeof(int32_t), s));
   celllist::CellList L;
   if (n > 0) {
-    CLN_TRY(celllist::build(target, n, target_stride_floats, max_dist, A, s, &L, timed ? ev.data() : nullptr));
+    CLN_TRY(celllist::build(target, n, target_stride_floats, max_dist, A, s, &L, T.events()));
   } else {
-    if (timed)
-      for (int k = 0; k < 4; k++) D3D_HIP_CHECK(hipEventRecord(ev[k], s));
+    for (int k = 0; k < 4; k++) CLN_TRY(T.mark(k, s));
     if (m > 0) hipLaunchKernelGGL(k_reg_fill, grid1d(m), dim3(256), 0, s, m, index, (float *)nullptr);
     D3D_LAUNCH_CHECK();
   }
   for (int it = 0; it < iterations; it++) {
-    hipEvent_t *e = timed ? ev.data() + 4 + 4 * (size_t)it : nullptr;
+    const size_t e = 4 + 4 * (size_t)it;
     if (n > 0 && m > 0) {
       hipLaunchKernelGGL(k_reg_transform, grid1d(m), dim3(256), 0, s, source, m, source_stride_floats,
                          (const double *)pose_inout_dev, (const int32_t *)state_dev, qbuf);
       D3D_LAUNCH_CHECK();
     }
-    if (e) D3D_HIP_CHECK(hipEventRecord(e[0], s));
+    CLN_TRY(T.mark(e, s));
     if (n > 0 && m > 0) CLN_TRY(launch_nearest(L, n, qbuf, m, 3, max_dist, index, nullptr, state_dev, s));
-    if (e) D3D_HIP_CHECK(hipEventRecord(e[1], s));
+    CLN_TRY(T.mark(e + 1, s));
     if (method == 0)
       hipLaunchKernelGGL(k_reg_accumulate<0>, dim3((unsigned)nb), dim3(kAccThreads), 0, s, source, m, source_stride_floats,
                          target, n, target_stride_floats, target_normals, normal_stride_floats,
@@ -427,23 +421,13 @@ int d3d_icp(const float *source, int m, int source_stride_floats, const float *t
                          target, n, target_stride_floats, target_normals, normal_stride_floats,
                          (const double *)pose_inout_dev, (const int32_t *)index, (const int32_t *)state_dev, part);
     D3D_LAUNCH_CHECK();
-    if (e) D3D_HIP_CHECK(hipEventRecord(e[2], s));
+    CLN_TRY(T.mark(e + 2, s));
     hipLaunchKernelGGL(k_reg_solve, dim3(1), dim3(64), 0, s, (const double *)part, nb, tol, iterations, pose_inout_dev,
                        history_dev, state_dev, last_system);
     D3D_LAUNCH_CHECK();
-    if (e) D3D_HIP_CHECK(hipEventRecord(e[3], s));
+    CLN_TRY(T.mark(e + 3, s));
   }
-  if (timed) {
-    D3D_HIP_CHECK(hipEventSynchronize(ev.back()));
-    for (int k = 0; k < kIcpPhases; k++) phase_ms_host[k] = 0.f;
-    for (int k = 0; k < 3; k++) D3D_HIP_CHECK(hipEventElapsedTime(&phase_ms_host[k], ev[k], ev[k + 1]));
-    for (int it = 0; it < iterations; it++)
-      for (int k = 0; k < 4; k++) {
-        float ms = 0.f;
-        D3D_HIP_CHECK(hipEventElapsedTime(&ms, ev[3 + 4 * (size_t)it + k], ev[4 + 4 * (size_t)it + k]));
-        phase_ms_host[3 + k] += ms;
-      }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-  }
-  return D3D_OK;
+  for (int k = 0; T.on && k < kIcpPhases; k++) phase_ms_host[k] = 0.f;
+  // the build's three phases, then the four kernels of a step summed over the steps
+  return T.finish(phase_ms_host, [](size_t k) { return k < 3 ? k : 3 + (k - 3) % 4; });
 }

@@ -148,14 +148,6 @@ __global__ __launch_bounds__(kThreads) void k_rd_bin(Mesh M, Views C, int32_t *_
   }
 }
 
-__global__ void k_rd_publish(const unsigned long long *__restrict__ total, int32_t *word) {
-  if (threadIdx.x == 0) {
-    const unsigned long long t = total[0];
-    word[1] = (int32_t)(t >> 32);
-    __hip_atomic_store(word, (int32_t)(t & 0xffffffffull), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
 struct Output {
   void *depth;                               // fp32 or uint16 [F, H, W]
   int32_t *tri;                              // [F, H, W] or null
@@ -332,15 +324,9 @@ int d3d_render_bin(const float *vertices, int n_vertices, const int32_t *triangl
   D3D_LAUNCH_CHECK();
   rc = scan_exclusive_i32(L.counts, L.offsets, (int)n_tiles, nullptr, A, s);
   if (rc) return rc;
-  VoxWord *w = vox_word();
-  if (!w) return D3D_ERR_HIP;
-  hipLaunchKernelGGL(k_rd_publish, dim3(1), dim3(64), 0, s, (const unsigned long long *)L.total, w->word);
-  D3D_LAUNCH_CHECK();
-  D3D_HIP_CHECK(hipEventRecord(w->ev, s));
-  D3D_HIP_CHECK(hipEventSynchronize(w->ev));
-  const uint32_t lo = (uint32_t)((volatile int32_t *)w->word)[0], hi = (uint32_t)((volatile int32_t *)w->word)[1];
-  info_host[0] = (int64_t)(((uint64_t)hi << 32) | lo);
-  return D3D_OK;
+  rc = readback_publish(L.total, 2, s);
+  if (rc) return rc;
+  return readback_wait(info_host, 2);
 }
 
 int d3d_render_fill(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,

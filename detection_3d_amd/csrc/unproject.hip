@@ -73,10 +73,6 @@ __global__ __launch_bounds__(kThreads) void k_up_count(DepthView V, int32_t *__r
   if (tid == 0) counts[blockIdx.x] = (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
 }
 
-__global__ void k_up_publish(const int32_t *__restrict__ total, int32_t *word) {
-  if (threadIdx.x == 0) __hip_atomic_store(word, total[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 struct Camera {
   double fx, fy, cx, cy, R[3][3], t[3];
 };
@@ -268,14 +264,9 @@ int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int hei
   D3D_LAUNCH_CHECK();
   rc = scan_exclusive_i32(L.counts, L.bases, G, L.total, A, s);
   if (rc) return rc;
-  VoxWord *w = vox_word();
-  if (!w) return D3D_ERR_HIP;
-  hipLaunchKernelGGL(k_up_publish, dim3(1), dim3(64), 0, s, (const int32_t *)L.total, w->word);
-  D3D_LAUNCH_CHECK();
-  D3D_HIP_CHECK(hipEventRecord(w->ev, s));
-  D3D_HIP_CHECK(hipEventSynchronize(w->ev));
-  info_host[0] = ((volatile int32_t *)w->word)[0];
-  return D3D_OK;
+  rc = readback_publish(L.total, 1, s);
+  if (rc) return rc;
+  return readback_wait(info_host, 1);
 }
 
 int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,

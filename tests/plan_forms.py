@@ -1,5 +1,5 @@
-"""Model of the rulebook plan builder (detection_3d_amd/csrc/grid.hip: finalize_plan, d3d_subm_prepare, run_grid_chain,
-d3d_input_layer_build_prefetch) in numpy: which build form a plan takes, the row order that form defines, the
+"""Model of the rulebook plan builder (detection_3d_amd/csrc/plan.hip: finalize_plan, d3d_subm_prepare; grid_chain.hip:
+run_grid_chain; grid.hip: d3d_input_layer_build_prefetch) in numpy: which build form a plan takes, the row order that form defines, the
 properties every correct plan has, and the scenes the plan tests run on.  No GPU; the reference tables come from the
 CPU oracle alone (oracle.subm_nbr, oracle.conv_rules, the identity for a 1x1x1 filter).
 

@@ -58,7 +58,7 @@ ROI_BWD_CCH = 64               # kRoiBwdCch
 DET_CHUNK = 64                 # kRoiDetChunk
 DET_CPL = 4                    # kRoiDetCpl
 MAX_LEVELS = 4                 # kRoiMaxLevels
-DENSE_MAX_CELLS = 8 << 20      # kDenseMaxCells (grid.hip)
+DENSE_MAX_CELLS = 8 << 20      # kDenseMaxCells (grid_views.hip)
 LDS_BYTES = 64 * 1024
 
 U32 = 2.0 ** -24

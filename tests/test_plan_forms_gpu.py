@@ -1,4 +1,4 @@
-"""Every build form of the rulebook plans (detection_3d_amd/csrc/grid.hip) against exact tables.
+"""Every build form of the rulebook plans (detection_3d_amd/csrc/plan.hip, grid_chain.hip, grid.hip) against exact tables.
 
 Reference: the CPU oracle alone (oracle.subm_nbr, oracle.conv_rules scattered into nbr / nbr_dec, the identity table
 for a 1x1x1 filter), through tests/plan_forms.py.  All results are integers: every comparison is exact.  Every case

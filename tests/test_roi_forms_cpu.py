@@ -482,7 +482,7 @@ def test_position_bound_covers_the_model():
 
 def test_expect_roi_restates_the_constants():
     text = open(os.path.join(ROOT, "detection_3d_amd", "csrc", "roi_align.hip")).read()
-    grid = open(os.path.join(ROOT, "detection_3d_amd", "csrc", "grid.hip")).read()
+    grid = open(os.path.join(ROOT, "detection_3d_amd", "csrc", "grid_views.hip")).read()
 
     def const(name, src=text):
         return int(re.search(r"constexpr \w+ " + name + r" = (\d+)", src).group(1))
