@@ -123,6 +123,9 @@ _SIGS = {
     "d3d_fit_boxes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "d3d_fit_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp,
                                      vp, vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_manhattan_frame_scratch_bytes": (ctypes.c_size_t, []),
+    "d3d_manhattan_frame": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_double_p, c_float_p, vp, vp, vp, vp, vp, vp,
+                                           vp, ctypes.c_size_t, vp, c_float_p]),
     "d3d_voxel_downsample_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_voxel_downsample_cells": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, ctypes.c_size_t,
                                                   c_int_p, vp]),

@@ -48,11 +48,17 @@ class BuildingPipeline(object):
     the inputs that are unproject.DepthFrames: such an input becomes a cloud on its slot's geometry stream first, and
     the steps above follow as for a cloud ("raw cloud" then means the unprojected one).  With point_owner its result also
     carries "point_pixel" int32, the pixel (f H + v) W + u of every row of that cloud (unproject.pixel_labels paints
-    point_owner into the frames with it)."""
+    point_owner into the frames with it).
+    align: None, True / 'manhattan', or a dict of frame.manhattan_frame keywords (max_tilt, tol, up): every cloud is
+    levelled and squared to its walls by its normals (frame.align_cloud) on its slot's geometry stream, after the normals
+    and before it is voxelised, for scans that arrive in a camera's or a reference station's frame.  The detections live in
+    the aligned cloud's min-shifted frame; every result dict carries "frame_pose", fp64 [4, 4] on the device: that frame <-
+    the input cloud's frame (frame.detector_pose; frame.box_corners_in_scan_frame takes the boxes back).  point_owner
+    tests the points in the aligned frame.  Without align nothing changes and the key is absent."""
 
     def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None,
-                 unproject=None, clean=None):
-        self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals, clean=clean)
+                 unproject=None, clean=None, align=None):
+        self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals, clean=clean, align=align)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
         self.device = device if device is not None else next(model.parameters()).device
@@ -79,7 +85,7 @@ class BuildingPipeline(object):
         for st in self.hi:
             st.wait_event(ready)
         results, errors = [None] * n, []
-        kept = [None] * n           # with point_owner: what prepare.point_ownership needs, only until the tail has run
+        kept = [None] * n           # with point_owner or align: what the tail adds to the result, only until it has run
         slots = threading.Semaphore(self.in_flight)
         q_feat, q_tail = queue.Queue(), queue.Queue()
         stop = threading.Event()
@@ -139,10 +145,12 @@ class BuildingPipeline(object):
                 with torch.cuda.stream(slot(i)[0]):
                     results[i] = r = self.model.stage_tail(feats)
                     k, kept[i] = kept[i], None
-                    if k is not None:
+                    if k is not None and self.point_owner:
                         r["point_owner"], r["point_count"] = point_ownership(k, clouds[i], r["bbox3d"])
                         if k.pixels is not None:
                             r["point_pixel"] = k.pixels
+                    if k is not None and k.pose is not None:
+                        r["frame_pose"] = k.pose
                     del k
                 del feats, item
                 slots.release()

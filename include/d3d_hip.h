@@ -333,6 +333,39 @@ int d3d_fit_boxes(const float *xyz, int n, int row_stride_floats, const double *
                   const double *coarse_dev, const double *fine_dev, float *boxes, int32_t *count, int32_t *choice,
                   float *extent, void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* The Manhattan frame of a scan from its normals: the rotation from the scan's frame to a level, wall-aligned one, the
+ * best of 3 x 256 tilt and 2 x 256 heading candidates by a defined integer vote.  normals fp32, row i at normals +
+ * i * row_stride_floats (three floats; unit length, any sign).  Every fp32 operation below is a multiply, add, min or max
+ * of its own, in the order written, without contraction; no device sin / cos / sqrt / divide enters.
+ *   voting rows: m = (n0 n0 + n1 n1) + n2 n2; a row votes iff 0.5 <= m <= 2 (NaN, infinite and zero rows fail);
+ *   vote of a row for a unit direction u with tolerance s2: d = (n0 u0 + n1 u1) + n2 u2, a2 = d d, r = min(a2, max(m - a2,
+ *     0)), v = max(s2 - r, 0), the integer trunc(v 2^30): a truncated quadratic that peaks where the normal is along +-u
+ *     (floor, ceiling) or across it (walls).  Scores are 64-bit sums of these integers;
+ *   tilt, passes k = 1, 2, 3 (skipped when tilt_tables_dev is NULL: B_3 = B_0, choice 136, score 0): tilt_tables_dev fp64
+ *     [3, 256, 9], row-major rotations M_k[c] made on the host (entry 136 the identity); b0_host: 9 doubles on the host,
+ *     the row-major frame B_0 (NULL: the identity); candidate frame B_{k-1} M_k[c] in fp64, element (r, c) = (B[r,0] M[0,c]
+ *     + B[r,1] M[1,c]) + B[r,2] M[2,c]; the candidate direction is its third column rounded to fp32, the tolerance
+ *     s2_host[k - 1]; the winner a_k has the highest score, the lowest index among equals, 136 when that score is 0;
+ *     B_k = B_{k-1} M_k[a_k];
+ *   heading, two passes over the wall rows: the voting rows with a2 <= s2_host[3] for u = the fp32 third column of B_3;
+ *     p, q = the dot products (as d) of the normal with the fp32 first and second column of B_3; candidate (c, s):
+ *     d1 = c p + s q, d2 = c q - s p, r = min(d1 d1, d2 d2), v = max(s2_host[3] - r, 0), vote as above; coarse_dev, fine_dev
+ *     as d3d_fit_boxes takes them: coarse candidates float(C[a]), fine ones float(Ca Fc - Sa Fs), float(Sa Fc + Ca Fs);
+ *     winners as above, a score of 0 gives coarse 0 and fine 128;
+ *   result: t = 128 ia + ib - 128, (C, S) = (Ca Fc - Sa Fs, Sa Fc + Ca Fs) in fp64; t >= 16384: (C, S) <- (S, -C), the heading
+ *     within 45 degrees of the scan's own; pose fp64 [4, 4] = [(B_3 Rz(C, S))^T 0; 0 1], aligned <- scan, the product as
+ *     above with Rz = [C -S 0; S C 0; 0 0 1].
+ * Outputs (device): pose; choice int32 [5]; score int64 [5], the winner's score per pass; support int32 [2], the voting
+ * rows and the wall rows.  n == 0 gives B_0's pose, choice (136, 136, 136, 0, 128) and zeros.  Integer sums commute: the
+ * bits depend on the set of rows alone.  s2_host: four floats in (0, 0.125].  scratch: d3d_manhattan_frame_scratch_bytes()
+ * bytes.  Eleven launches on `stream`, asynchronous, no read-back.  phase_ms_host (NULL: none): five floats, the
+ * milliseconds of each pass (sweep and pick) between device events; the call then synchronises.                       */
+size_t d3d_manhattan_frame_scratch_bytes(void);
+int d3d_manhattan_frame(const float *normals, int n, int row_stride_floats, const double *tilt_tables_dev,
+                        const double *b0_host, const float *s2_host, const double *coarse_dev, const double *fine_dev,
+                        double *pose, int32_t *choice, int64_t *score, int32_t *support, void *scratch,
+                        size_t scratch_bytes, void *stream, float *phase_ms_host);
+
 /* Voxel down-sampling of a raw scan: one row per occupied voxel, every column the mean over the voxel's points
  * (data3d/suncg_utils/suncg_preprocess.py:748-767, open3d.voxel_down_sample(pcd, voxel_size=0.02)).  A restatement of
  * open3d's VoxelDownSample that is not pinned against open3d itself.  pcl fp32 [n, ncols], 3 <= ncols <= 16, contiguous,

@@ -12,7 +12,11 @@ config does not list are left out.
 
 --planes is for a scan nobody labelled: `pcl` float32 [N, 9] with normals in columns 6:9 and no `instance`.  The
 instances are then the planar patches of planes.label_planes (region growing over the normals on the GPU; defaults
-0.1 m, 10 degrees, 0.02 m, 100 points), classed floor, ceiling or wall by their fitted normal."""
+0.1 m, 10 degrees, 0.02 m, 100 points), classed floor, ceiling or wall by their fitted normal.
+
+--align[=MAX_TILT,TOL] (degrees, defaults 30 and 5) is for a scan that is not level or not square to its walls: the
+cloud (`pcl` [N, 9]) is first turned into its Manhattan frame by its normals (frame.align_cloud), so that --planes
+classes by the angle to the true vertical and the boxes are upright; the scene file holds the aligned cloud."""
 import argparse
 import os
 import sys
@@ -32,15 +36,19 @@ def main():
     ap.add_argument("--min-size", default="0,0,0", help="D3,D4,DZ in metres: smaller boxes are widened to these")
     ap.add_argument("--planes", nargs="?", const="", default=None, metavar="RADIUS,ANGLE,OFFSET,MIN_POINTS",
                     help="no `instance` in the input: label the planar patches of the cloud (planes.label_planes)")
+    ap.add_argument("--align", nargs="?", const="", default=None, metavar="MAX_TILT,TOL",
+                    help="level the cloud and square it to its walls by its normals first (frame.align_cloud)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     from detection_3d_amd.config import class_to_label, get_cfg
+    from detection_3d_amd.frame import align_cloud, parse_align
     from detection_3d_amd.planes import label_planes, parse_planes
     from detection_3d_amd.primitives import MIN_POINTS_ANY, targets_from_labels
     from detection_3d_amd.scene_io import save_scene, yx_zb_to_standard
     cfg = get_cfg(args.config)
     try:
         planes = parse_planes(args.planes)
+        align = parse_align(args.align)
     except ValueError as e:
         raise SystemExit(str(e))
     with np.load(args.labelled, allow_pickle=False) as d:
@@ -53,6 +61,12 @@ def main():
     l2c = {l: c for c, l in c2l.items()}
     dev = torch.device(args.device)
     cloud = torch.from_numpy(pcl).to(dev)
+    if align is not None:
+        if pcl.ndim != 2 or pcl.shape[1] != 9:
+            raise SystemExit(f"--align reads the normals from columns 6:9, pcl is {pcl.shape}")
+        cloud, frame = align_cloud(cloud, **align)
+        pcl = cloud.cpu().numpy()
+        print(f"aligned: {frame!r}")
     if planes is not None:
         if pcl.ndim != 2 or pcl.shape[1] < 9:
             raise SystemExit(f"--planes reads the normals from columns 6:9, pcl is {pcl.shape}")
