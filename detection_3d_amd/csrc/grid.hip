@@ -46,36 +46,46 @@ __global__ void k_iota(int32_t *p, int n) {
 
 // ------------------------------------------------------------------------------------------
 // a2. Input layer: hash insert + first-occurrence numbering (IOLayersRules.h:72-95).
-// ext (may be null): device int32[4] = 1 + the largest x, y, z and example index over all points (zero-initialised by the
-// caller): one atomicMax per dimension and 256-thread block.  The host reads it back with the site count and bounds the
-// site counts of the coarser grids with it (grid_chain.hip), so that no further count has to be read back.
+// ext (may be null): device int32[5], zero-initialised by the caller.  [0..3] = 1 + the largest x, y, z and example index
+// over all points: one atomicMax per dimension and 256-thread block.  The host reads them back with the site count and
+// bounds the site counts of the coarser grids with them (grid_chain.hip), so that no further count has to be read back.
+// [4] = 1 + the index of a point that cannot be a site of this grid (0: none): a coordinate outside [0, size), or an
+// example index outside [0, 32768).  Compared as int64, before pack_key keeps 16 bits of each.  The insertion itself
+// needs no valid coordinate (it hashes the packed key); what indexes memory BY a coordinate (the dense views, the grid
+// chain's cell bounds) runs only after the host has seen this word (d3d_input_layer_build_prefetch).
 __global__ __launch_bounds__(256) void k_insert_points(const int64_t *__restrict__ coords, int n, int ncols,
-                                                       HashEntry *tab, int cap, int32_t *pslot, int32_t *ext) {
+                                                       HashEntry *tab, int cap, int32_t *pslot, int32_t *ext, int sx,
+                                                       int sy, int sz) {
   D3D_SIDE_PRIO();
-  __shared__ int red[4][4];
+  __shared__ int red[4][5];
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int v[4] = {0, 0, 0, 0};
+  int v[5] = {0, 0, 0, 0, 0};
   if (i < n) {
     const int64_t *c = coords + (size_t)i * ncols;
-    int b = ncols == 4 ? (int)c[3] : 0;
+    const int64_t b64 = ncols == 4 ? c[3] : 0;
+    int b = (int)b64;
     int slot = hash_insert(tab, cap, pack_key(b, (int)c[0], (int)c[1], (int)c[2]));
     atomicMin(&tab[slot].first, (uint32_t)i);
     pslot[i] = slot;
-    v[0] = (int)c[0] + 1;
-    v[1] = (int)c[1] + 1;
-    v[2] = (int)c[2] + 1;
-    v[3] = b + 1;
+    if (c[0] < 0 || c[0] >= sx || c[1] < 0 || c[1] >= sy || c[2] < 0 || c[2] >= sz || b64 < 0 || b64 >= 32768) {
+      v[4] = i + 1;
+    } else {
+      v[0] = (int)c[0] + 1;
+      v[1] = (int)c[1] + 1;
+      v[2] = (int)c[2] + 1;
+      v[3] = b + 1;
+    }
   }
   if (!ext) return;
 #pragma unroll
-  for (int d = 0; d < 4; d++) {
+  for (int d = 0; d < 5; d++) {
     int m = v[d];
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][d] = m;
   }
   __syncthreads();
-  if (threadIdx.x < 4) {
+  if (threadIdx.x < 5) {
     const int d = threadIdx.x;
     const int m = max(max(red[0][d], red[1][d]), max(red[2][d], red[3][d]));
     if (m > 0) atomicMax(&ext[d], m);
@@ -347,8 +357,9 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
   m->in_idx = in_idx;
   int n_active = 0;
   if (n > 0) {
-    // [0] site count, [1..4] extents of the points (k_insert_points).  NOT part of the scratch released below: the
-    // prefetched neighbour probes read the count from it while other streams may already be allocating from this lane.
+    // [0] site count, [1..4] extents of the points, [5] 1 + a point outside the grid (k_insert_points).  NOT part of the
+    // scratch released below: the prefetched neighbour probes read the count from it while other streams may already be
+    // allocating from this lane.
     D3D_ALLOC(total, int32_t, A, 8);
     // (the arrays of the rulebook that is enqueued below before the count is back: sized by the point count)
     const int pre_K = prefetch_filter ? prefetch_filter[0] * prefetch_filter[1] * prefetch_filter[2] : 0;
@@ -405,13 +416,14 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
     }
     D3D_HIP_CHECK(fill_ones(tab, sizeof(HashEntry) * g.cap, s));
     D3D_HIP_CHECK(hipMemsetAsync(total, 0, 8 * sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_insert_points, grid1d(n), dim3(256), 0, s, coords, n, ncols, tab, g.cap, pslot, total + 1);
+    hipLaunchKernelGGL(k_insert_points, grid1d(n), dim3(256), 0, s, coords, n, ncols, tab, g.cap, pslot, total + 1,
+                       size[0], size[1], size[2]);
     hipLaunchKernelGGL(k_flag_first, grid1d(n), dim3(256), 0, s, pslot, tab, n, flag);
     int rc = scan_exclusive_i32(flag, rank, n, total, A, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_assign_input_sites, grid1d(n), dim3(256), 0, s, coords, n, ncols, pslot, flag, rank, tab, loc);
     D3D_LAUNCH_CHECK();
-    D3D_HIP_CHECK(hipMemcpyAsync(&m->host_words[0], total, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    D3D_HIP_CHECK(hipMemcpyAsync(&m->host_words[0], total, 6 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     bool prefetched = false;
     if (pre) {
       if (!m->count_ev) D3D_HIP_CHECK(hipEventCreateWithFlags(&m->count_ev, hipEventDisableTiming));
@@ -443,6 +455,18 @@ int d3d_input_layer_build_prefetch(d3d_meta *m, const int64_t *coords, int n, in
     if (prefetched) D3D_HIP_CHECK(hipEventSynchronize(m->count_ev));
     else D3D_HIP_CHECK(hipStreamSynchronize(s));
     n_active = (int)*(int32_t *)&m->host_words[0];
+    if (const int bad = ((const int32_t *)&m->host_words[0])[5]) {
+      // A point that is no cell of this grid.  Nothing enqueued above indexes memory by a coordinate: insert, flag, scan,
+      // assign, the probes, the point lists and the sorts go by hashes, ranks, site ids and point indices (all < n), so
+      // the work in flight is harmless.  The caller's stream is put behind the library's stream, the handle goes back to
+      // what d3d_meta_clear leaves (full arena, no prefetched plan, no input layer), and no grid is entered.
+      if (m->lists_on_aux) D3D_HIP_CHECK(hipStreamWaitEvent(s, m->lists_ev, 0));
+      d3d_meta_clear(m);
+      *n_active_host = 0;
+      set_error("input layer: point %d has a coordinate outside the spatial size [%d,%d,%d] or an example index outside "
+                "[0, 32768)", bad - 1, size[0], size[1], size[2]);
+      return D3D_ERR_ARG;
+    }
     for (int d = 0; d < 4; d++) m->in_ext[d] = ((const int32_t *)&m->host_words[0])[1 + d];
     A.used = mark;
   } else {
@@ -492,6 +516,10 @@ int d3d_input_layer_export(d3d_meta *m, int32_t *offsets, int32_t *idx, void *st
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(m && offsets && idx, "null argument");
   D3D_REQUIRE_STATE(m->in_off, "input layer export before build");
+  if (m->in_n == 0) {             // no points: no list was built, the one offset is 0
+    D3D_HIP_CHECK(hipMemsetAsync(offsets, 0, sizeof(int32_t), s));
+    return D3D_OK;
+  }
   if (int rc = ensure_point_lists(m, s)) return rc;
   hipLaunchKernelGGL(k_export_input, grid1d(m->in_active + 1), dim3(256), 0, s, m->in_off, offsets, m->in_active + 1);
   if (m->in_n) hipLaunchKernelGGL(k_export_input, grid1d(m->in_n), dim3(256), 0, s, m->in_idx, idx, m->in_n);

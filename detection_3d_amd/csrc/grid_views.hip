@@ -205,6 +205,10 @@ int d3d_sparse_to_dense_forward(d3d_meta *m, const int *size, const float *in, i
   D3D_REQUIRE(m && size && out && planes > 0 && batch > 0, "bad arguments");
   Grid *g = find_grid(m, size);
   D3D_REQUIRE_STATE(g, "sparse_to_dense: no grid of spatial size [%d,%d,%d]", size[0], size[1], size[2]);
+  // k_sparse_to_dense indexes the volume by every site's example index: the batch must cover them (hext[3] = 1 + the
+  // largest, 0 where it is not known; the coordinates themselves were checked against `size` when the grid was built)
+  D3D_REQUIRE(g->hext[3] <= batch, "sparse_to_dense: batch %d, but the grid holds examples up to index %d", batch,
+              g->hext[3] - 1);
   size_t vol = (size_t)size[0] * size[1] * size[2];
   D3D_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(float) * vol * planes * batch, s));
   if (g->n == 0) return D3D_OK;

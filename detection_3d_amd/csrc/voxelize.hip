@@ -4,6 +4,12 @@
 namespace d3d {
 
 // a1 -------------------------------------------------------------------------------------
+// d3d_voxelize: a = double(x) * scale, then a + (-min) as a second fp64 operation (never one fused multiply-add: the
+// truncation must be numpy's), keep 0 <= a < full, trunc.
+// Contract on non-finite coordinates: the minimum is an fmin reduction, which ignores a NaN, so a NaN coordinate drops
+// that point alone (its comparisons fail), and so does a +Inf one.  numpy's min propagates the NaN, makes the offset
+// NaN and drops the whole cloud: the deviation is deliberate.  A -Inf coordinate is the minimum, the shift is +Inf and
+// every point goes (Inf - Inf for the point itself), as in numpy.
 __global__ __launch_bounds__(256) void k_vox_min(const float *__restrict__ pcl, int n, int nfeat,
                                                  double scale,
                                                  unsigned long long *mins /*3, ordered-uint*/) {
@@ -116,7 +122,9 @@ size_t d3d_voxelize_scratch_bytes(int n) {
 int d3d_voxelize(const float *pcl, int n, int nfeat, double scale, const int *full, int64_t *coords,
                  float *feats, int *n_kept_host, void *scratch, size_t scratch_bytes, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(pcl && coords && feats && n_kept_host && full && nfeat >= 3 && n >= 0, "d3d_voxelize: bad arguments");
+  // (an empty cloud has no rows to point at: torch hands over null pointers for it)
+  D3D_REQUIRE(n_kept_host && full && nfeat >= 3 && n >= 0 && (n == 0 || (pcl && coords && feats)),
+              "d3d_voxelize: bad arguments");
   D3D_REQUIRE(scratch_bytes >= d3d_voxelize_scratch_bytes(n), "d3d_voxelize: scratch too small");
   *n_kept_host = 0;
   if (n == 0) return D3D_OK;

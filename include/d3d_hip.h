@@ -105,7 +105,12 @@ int d3d_sort_pairs(const uint32_t *keys, const int32_t *vals, int n, int bits, i
 /* a1. data3d/suncg_utils/suncg_dataset.py:97-177: a = xyz*scale in fp64, shift by per-axis min,
  * drop points outside [0, full_scale), trunc -> int64; feats[:,0:3] = a/scale.
  * pcl fp32 [n, nfeat] (xyz first).  coords_out int64 [n,3], feats_out fp32 [n,nfeat]
- * (compacted, input order preserved).  Synchronises; *n_kept_host = rows written.            */
+ * (compacted, input order preserved).  Synchronises; *n_kept_host = rows written.
+ * x*scale and the shift are two fp64 operations, never one fused multiply-add; columns 3.. are copied bit for bit.
+ * Non-finite coordinates: the per-axis minimum is an fmin, which IGNORES a NaN, so a NaN coordinate (like a +Inf one)
+ * drops that point only.  This departs from the numpy recipe, whose NaN-propagating min makes the offset NaN and drops
+ * the whole cloud (as it does for an Inf, which its product with the diagonal scale matrix turns into a NaN).  A -Inf
+ * coordinate is the minimum: the shift becomes +Inf and every point is dropped, as in numpy. */
 int d3d_voxelize(const float *pcl, int n, int nfeat, double scale, const int *full_scale_host,
                  int64_t *coords_out, float *feats_out, int *n_kept_host, void *scratch,
                  size_t scratch_bytes, void *stream);
@@ -493,7 +498,12 @@ int d3d_render_tiles(const float *vertices, int n_vertices, const int32_t *trian
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.
  * mode 3 = sum, 4 = mean.  Site ids follow first occurrence in input order (bit-exact with
- * the reference); duplicates are accumulated in input order.                                */
+ * the reference); duplicates are accumulated in input order.
+ * Every point must be a cell of the grid: 0 <= x, y, z < spatial_size (each at most 32768) and an example index in
+ * [0, 32768).  The build finds a point outside on the device, reads that back with the site count, and then returns
+ * D3D_ERR_ARG with a message that names the point: no grid is entered, and the handle is left as d3d_meta_clear leaves
+ * it, so the next build on it succeeds.  (Before that check the dense views and the site keys, which keep 16 bits of a
+ * coordinate, took such a point as it came.)  batch_size is not used.                        */
 int d3d_input_layer_build(d3d_meta *m, const int64_t *coords, int n, int ncols,
                           const int *spatial_size_host, int batch_size, int mode, void *stream,
                           int *n_active_host);
@@ -895,7 +905,9 @@ size_t d3d_bn_scratch_bytes(int planes);
 int d3d_add(const float *a, const float *b, float *out, size_t n, void *stream);
 
 /* a20. SparseToDense_updateOutput (SCN/sparseconvnet.h:214-217; SCN/CPU/SparseToDense.cpp:7-60):
- * zero-filled dense [batch, planes, X, Y, Z].                                                */
+ * zero-filled dense [batch, planes, X, Y, Z].  batch must cover the grid's examples (1 + the largest example
+ * index of the input points, where the library knows it): a smaller one is D3D_ERR_ARG before anything is
+ * enqueued; a larger one leaves the trailing volumes zero.                                    */
 int d3d_sparse_to_dense_forward(d3d_meta *m, const int *spatial_size_host, const float *in,
                                 int planes, int batch, float *out, void *stream);
 

@@ -35,6 +35,7 @@ def _input(dev, coords, feats, size):
     (40000, (5.0, 4.0, 0.6), (256, 256, 32)),
 ])
 def test_input_layer_exact(dev, n_points, extent, size):
+    # every build form, mode and size edge on designed cases, every site's point list: tests/test_front_forms_gpu.py
     _, coords, feats = small_scene(1, n_points, extent, size)
     t = _input(dev, coords, feats, size)
     sop, loc = oracle.input_sites(coords)
@@ -177,6 +178,7 @@ def test_batchnorm(dev):
 
 
 def test_sparse_to_dense(dev):
+    # non-cubic sizes, batches, corners, full grids, the backward, every cell compared: tests/test_front_forms_gpu.py
     from detection_3d_amd import sparseconvnet as scn
     size = (32, 32, 8)
     _, coords, feats = small_scene(6, 2000, (0.6, 0.6, 0.15), size)
