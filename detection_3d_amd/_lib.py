@@ -40,6 +40,12 @@ class AugmentParams(ctypes.Structure):
                 ("color_col", ctypes.c_int), ("normal_col", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
+class GlobalAlignDetails(ctypes.Structure):
+    """d3d_global_align_details (include/d3d_hip.h): device buffers for the tables of a call, each NULL or filled."""
+    _fields_ = [("hist", vp), ("cells", vp), ("cell_count", vp), ("target_bits", vp), ("corr", vp), ("peak_value", vp),
+                ("peak_shift", vp), ("scores", vp)]
+
+
 aug_p = ctypes.POINTER(AugmentParams)
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -126,6 +132,11 @@ _SIGS = {
     "d3d_manhattan_frame_scratch_bytes": (ctypes.c_size_t, []),
     "d3d_manhattan_frame": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_double_p, c_float_p, vp, vp, vp, vp, vp, vp,
                                            vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_global_align_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, c_int_p, ctypes.c_int]),
+    "d3d_global_align": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                        vp, ctypes.c_int, vp, ctypes.c_double, c_int_p, ctypes.c_float, ctypes.c_int,
+                                        ctypes.c_int, vp, vp, vp, vp, vp, ctypes.POINTER(GlobalAlignDetails), vp,
+                                        ctypes.c_size_t, vp, c_float_p]),
     "d3d_voxel_downsample_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "d3d_voxel_downsample_cells": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, ctypes.c_size_t,
                                                   c_int_p, vp]),

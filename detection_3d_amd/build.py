@@ -10,7 +10,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libd3d_hip.so")
 SOURCES = ["grid.hip", "grid_chain.hip", "plan.hip", "geometry_async.hip", "grid_views.hip", "scan_sort.hip", "voxelize.hip",
            "conv.hip", "conv_ws.hip", "conv_bf16.hip", "bn.hip", "boxes.hip", "roi_align.hip", "backward.hip", "rpn_head.hip", "topk.hip",
-           "augment.hip", "celllist.hip", "normals.hip", "points_in_boxes.hip", "box_fit.hip", "frame.hip", "downsample.hip", "unproject.hip", "render.hip", "clean.hip", "planes.hip", "register.hip"]
+           "augment.hip", "celllist.hip", "normals.hip", "points_in_boxes.hip", "box_fit.hip", "frame.hip", "downsample.hip", "unproject.hip", "render.hip", "clean.hip", "planes.hip", "register.hip", "global_align.hip"]
 # -ffp-contract=off: the box geometry shares an arithmetic contract with the CPU oracle
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17"]
 

@@ -8,7 +8,12 @@ Semantics (include/d3d_hip.h), restatements that are not pinned again
 row with the smallest (d2, row) among those with d2 = (dx dx + dy dy) + dz dz <= radius^2 in fp32, estimate_normals'
 test.  icp: Gauss-Newton steps on the point-to-plane (or point-to-point) residuals of the pairs nearest finds within
 max_dist, sums in fp64 in a fixed order, a 6 x 6 Cholesky solve on the device; pose = [R t; 0 1] with x' = R x + t
-mapping source into the target's frame.  The same input gives the same bits, whatever torch's deterministic mode says."""
+mapping source into the target's frame.  The same input gives the same bits, whatever torch's deterministic mode says.
+
+Scans that come without any pose (a tripod lidar moved from room to room, a second session, a BIM export) get their
+start from global_align (global_align.hip): each cloud levelled and squared by frame.manhattan_frame, then a
+quarter turn, a shift on a lattice and a z shift from integer histograms, their correlations' peaks and a verification
+against bird's-eye wall bitmaps; numpy reproduces every output bit for bit (tests/global_ref.py)."""
 import ctypes
 import math
 import warnings
@@ -213,18 +218,231 @@ def icp(source, target, target_normals=None, init=None, max_dist=0.1, iterations
                         dict(zip(ICP_PHASES, (float(v) for v in ms))) if phases else None)
 
 
-def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=None, seed=0, **icp_kw):
+GLOBAL_PHASES = ("rows", "cells", "correlate", "peaks", "verify", "pick")
+MAX_LATTICE = 4096
+MAX_PEAKS = 64
+MAX_SEP = 64
+MAX_TOL = 20.0
+MARGIN_MAX = 0.98     # merge_scans: a runner-up this close to the best is taken for an ambiguous building
+
+
+def _whole(value, lo, hi, what):
+    try:
+        ok = not isinstance(value, bool) and int(value) == value and lo <= int(value) <= hi
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} {value!r} must be an integer in [{lo}, {hi}]")
+    return int(value)
+
+
+def _check_global(bin, lattice, tol, peaks, sep, frame):
+    """-> (bin, (L, L, Lz), c2, peaks, sep, manhattan_frame's keywords)"""
+    from .frame import align_kwargs
+    try:
+        bin, tol = float(bin), float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"bin {bin!r} and tol {tol!r} must be numbers") from None
+    if not (bin > 0.0 and bin <= 1e6):
+        raise ValueError(f"bin {bin} must be positive and finite")
+    if not 0.0 < tol <= MAX_TOL:
+        raise ValueError(f"tol {tol} outside (0, {MAX_TOL:g}] degrees")
+    try:
+        lattice = tuple(lattice)
+    except TypeError:
+        raise ValueError(f"lattice {lattice!r} must be (Lx, Ly, Lz)") from None
+    if len(lattice) != 3:
+        raise ValueError(f"lattice {lattice!r} must be (Lx, Ly, Lz)")
+    lattice = (_whole(lattice[0], 32, MAX_LATTICE, "lattice: Lx"), _whole(lattice[1], 32, MAX_LATTICE, "lattice: Ly"),
+               _whole(lattice[2], 1, MAX_LATTICE, "lattice: Lz"))
+    if lattice[0] != lattice[1] or lattice[0] % 32:
+        raise ValueError(f"lattice {lattice}: Lx == Ly, a multiple of 32")
+    peaks = _whole(peaks, 1, MAX_PEAKS, "peaks")
+    sep = _whole(sep, 0, MAX_SEP, "sep")
+    frame_kw = align_kwargs(True if frame is None else frame)
+    if frame_kw is None:
+        raise ValueError(f"frame {frame!r}: a dict of manhattan_frame's keywords (max_tilt, tol, up)")
+    import numpy as np
+    c2 = float(np.float32(math.cos(math.radians(tol)) ** 2))
+    return bin, lattice, c2, peaks, sep, frame_kw
+
+
+class Alignment:
+    """What global_align returns.  pose fp64 [4, 4] (source frame -> target frame), lattice_pose (the same between the two
+    levelled frames), source_frame and target_frame (the Frames of align_cloud), choice int32 [4] = (q, sx, sy, sz), score
+    int64 [6] (the best score of each quarter turn, the best of all, the runner-up), support int32 [4] (rows used and
+    dropped, source then target) and state int32 [1] stay on the device; the properties read them back on first use.
+    details (return_details): the tables of the call as device tensors; phases: the dict of milliseconds, when asked for."""
+
+    def __init__(self, pose, lattice_pose, source_frame, target_frame, choice, score, support, state, details=None,
+                 phases=None):
+        self.pose, self.lattice_pose, self.source_frame, self.target_frame = pose, lattice_pose, source_frame, target_frame
+        self.choice, self.score, self.support, self.state = choice, score, support, state
+        self.details, self.phases = details, phases
+        self._host = None
+
+    def _read(self):
+        if self._host is None:
+            self._host = (int(self.state.cpu()[0]), [int(v) for v in self.score.cpu()], [int(v) for v in self.choice.cpu()])
+        return self._host
+
+    @property
+    def status(self):
+        """0: fine; 1: no wall of the source met a wall of the target, the pose is the origins' shift alone"""
+        return self._read()[0]
+
+    @property
+    def heading_scores(self):
+        """the best score of each quarter turn"""
+        return self._read()[1][:4]
+
+    @property
+    def best(self):
+        return self._read()[1][4]
+
+    @property
+    def margin(self):
+        """runner-up over best: near 1 the building looks the same under another turn or shift (inf for status 1)"""
+        sc = self._read()[1]
+        return max(sc[5], 0) / sc[4] if sc[4] > 0 else float("inf")
+
+    @property
+    def quarter_turns(self):
+        return self._read()[2][0]
+
+    def __repr__(self):
+        status, sc, ch = self._read()
+        return f"Alignment(status={status}, choice={ch}, best={sc[4]}, margin={self.margin:.3g})"
+
+
+def _with_normals(cloud, normals, normal_radius, max_nn, what):
+    """-> fp32 [N, 6]: position and normal of every row, the normals resolved as icp resolves its target's"""
+    xyz, n, _ = _xyz(cloud)
+    if normals is not None:
+        nrm, nn, _ = _xyz(normals)
+        if nn != n or nrm.device != xyz.device:
+            raise ValueError(f"global_align: {what}_normals [{nn}, ..] on {nrm.device} for {n} rows on {xyz.device}")
+    elif cloud.shape[1] == 9:
+        nrm = cloud.detach()[:, 6:9]
+    else:
+        from .normals import estimate_normals
+        nrm = estimate_normals(xyz, normal_radius, max_nn)
+    return torch.cat([xyz[:, :3], nrm[:, :3]], 1)
+
+
+def lattice_align(source, source_normals, source_origin, target, target_normals, target_origin, bin=0.05,
+                  lattice=(2048, 2048, 256), tol=5.0, peaks=64, sep=2, return_details=False, phases=False):
+    """d3d_global_align as it stands (include/d3d_hip.h): two clouds that are levelled and squared already, fp32 [rows, >= 3]
+    positions and normals on the GPU (column slices are read in place), and per cloud an origin, fp64 [3] on the device
+    (primitives.cloud_min) -> Alignment whose pose is the one between the two levelled frames.  Current stream, no
+    read-back."""
+    from ._lib import GlobalAlignDetails, ints
+    bin, lattice, c2, peaks, sep, _ = _check_global(bin, lattice, tol, peaks, sep, None)
+    src, m, sstride = _xyz(source)
+    snrm, sm, snstride = _xyz(source_normals)
+    tgt, n, tstride = _xyz(target)
+    tnrm, tn, tnstride = _xyz(target_normals)
+    dev = src.device
+    if sm != m or tn != n or any(t.device != dev for t in (snrm, tgt, tnrm)):
+        raise ValueError(f"lattice_align: {m} / {sm} source and {n} / {tn} target rows and normals, on one device")
+    origins = []
+    for o in (source_origin, target_origin):
+        if not isinstance(o, torch.Tensor) or o.shape != (3,) or o.dtype != torch.float64 or o.device != dev:
+            raise ValueError("lattice_align: an origin is a float64 tensor [3] on the clouds' device")
+        origins.append(o.detach().contiguous())
+    L, Lz, K = lattice[0], lattice[2], peaks
+    A = torch.empty((4, 4), dtype=torch.float64, device=dev)
+    choice = torch.empty((4,), dtype=torch.int32, device=dev)
+    score = torch.empty((6,), dtype=torch.int64, device=dev)
+    support = torch.empty((4,), dtype=torch.int32, device=dev)
+    state = torch.empty((1,), dtype=torch.int32, device=dev)
+    details, det = None, None
+    if return_details:
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        details = {"hist": torch.empty((2, 2 * L + Lz), **i32), "cells": torch.empty((2, max(1, min(m, L * L))), **i32),
+                   "cell_count": torch.empty((2,), **i32), "target_bits": torch.empty((2, L * L // 32), **i32),
+                   "corr": torch.empty((9, 2 * max(L, Lz) - 1), **i64), "peak_value": torch.empty((9, K), **i64),
+                   "peak_shift": torch.empty((9, K), **i32), "scores": torch.empty((4, K, K), **i32)}
+        det = GlobalAlignDetails(*(ptr(details[k]) for k, _ in GlobalAlignDetails._fields_))
+    lat = ints(lattice)
+    nbytes = lib().d3d_global_align_scratch_bytes(m, lat, K)
+    scratch = _scratch(nbytes, dev)
+    ms = (ctypes.c_float * len(GLOBAL_PHASES))() if phases else None
+    with torch.cuda.device(dev):
+        check(lib().d3d_global_align(ptr(src), m, sstride, ptr(snrm), snstride, ptr(origins[0]), ptr(tgt), n, tstride,
+                                     ptr(tnrm), tnstride, ptr(origins[1]), bin, lat, c2, K, sep, ptr(A), ptr(choice),
+                                     ptr(score), ptr(support), ptr(state), ctypes.byref(det) if det is not None else None,
+                                     ptr(scratch), nbytes, stream_of(dev), ms))
+    return Alignment(A, A, None, None, choice, score, support, state, details,
+                     dict(zip(GLOBAL_PHASES, (float(v) for v in ms))) if phases else None)
+
+
+def global_align(source, target, bin=0.05, lattice=(2048, 2048, 256), tol=5.0, peaks=64, sep=2, frame=None,
+                 normal_radius=0.1, max_nn=50, return_details=False, phases=False, source_normals=None,
+                 target_normals=None):
+    """source fp32 [M, >= 3], target fp32 [N, >= 3] on the GPU, each in a frame of its own with no pose between them ->
+    Alignment: the coarse pose that maps source onto target, for icp(init=...) to refine.  Both clouds are levelled and
+    squared (frame.align_cloud with the keywords in `frame`); what is left is one of four quarter turns, a shift on a
+    lattice of `bin` metres (`lattice` cells per axis from each cloud's minimum, Lx == Ly a multiple of 32, at most 4096)
+    and a z shift.  Walls (normals within `tol` degrees of x or y) and floors vote by integer histograms; the `peaks`
+    best shifts per axis and turn, more than `sep` bins apart, are verified against bird's-eye bitmaps of the walls.
+    Normals: *_normals fp32 [rows, >= 3], or columns 6:9 of a nine-column cloud, or estimate_normals(cloud,
+    normal_radius, max_nn).  Limits: overlap is maximised and free space costs nothing, so on a point-symmetric building
+    seen through a small overlap the half turn can win (Alignment.margin near 1 and heading_scores show it); z is the one
+    strongest floor / ceiling peak, a storey off in a multi-storey partial overlap; the accuracy is half a bin per axis
+    and the frames' heading error.  return_details: Alignment.details holds every table of the call (histograms, cell
+    lists, the target's bitmaps, correlations, peak tables, the [4, K, K] scores) as device tensors; phases:
+    Alignment.phases, the milliseconds of d3d_global_align's six phases (GLOBAL_PHASES), which synchronises.  Current
+    stream, no read-back; bad arguments raise ValueError before any GPU work."""
+    from .frame import align_cloud
+    from .normals import _check_args
+    from .primitives import cloud_min
+    bin, lattice, _, peaks, sep, frame_kw = _check_global(bin, lattice, tol, peaks, sep, frame)
+    _check_args(normal_radius, max_nn, None)
+    for c in (source, target):
+        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] < 3:
+            raise ValueError("xyz must be a tensor [N, >= 3]")
+    if source.device != target.device:
+        raise ValueError(f"global_align: source on {source.device}, target on {target.device}")
+    six_s = _with_normals(source, source_normals, normal_radius, max_nn, "source")
+    six_t = _with_normals(target, target_normals, normal_radius, max_nn, "target")
+    with torch.cuda.device(source.device):
+        src, fs = align_cloud(six_s, 3, **frame_kw)
+        tgt, ft = align_cloud(six_t, 3, **frame_kw)
+        found = lattice_align(src, src[:, 3:], cloud_min(src), tgt, tgt[:, 3:], cloud_min(tgt), bin, lattice, tol, peaks, sep,
+                              return_details, phases)
+        found.pose = inverse_pose(ft.pose) @ found.lattice_pose @ fs.pose
+    found.source_frame, found.target_frame = fs, ft
+    return found
+
+
+def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=None, seed=0, global_kw=None, **icp_kw):
     """clouds: fp32 [N_i, C] GPU tensors of one width, each in its own frame; init_poses: None or one 4 x 4 (or None) per
     cloud, its rough pose in the reference's frame -> (cloud, poses).  The scans are taken in order; each one is
     registered (icp, **icp_kw) to the voxel-down-sampled union of the reference and the scans placed so far, moved with
     apply_pose and added to the union.  cloud: the union through apply_downsample(voxel, max_points, seed), ready for
     prepare_cloud / BuildingPipeline.map; poses: fp64 [4, 4] device tensors, the identity for the reference.  One
     read-back per registration (its state); a registration that does not converge raises a warning and its pose is
-    used as it stands."""
+    used as it stands.  init_poses='global': the scans come without poses, and each one's start is global_align(scan,
+    union so far, **global_kw)'s; when that finds no walls (status 1) or its margin exceeds MARGIN_MAX (0.98: another
+    turn or shift fits as well) a warning is raised and the scan is registered from the identity."""
     from .downsample import apply_downsample, downsample_kwargs
     clouds = list(clouds)
     if not clouds:
         raise ValueError("merge_scans: no clouds")
+    use_global = isinstance(init_poses, str)
+    if use_global and init_poses != "global":
+        raise ValueError(f"merge_scans: init_poses {init_poses!r}: None, 'global' or one pose per cloud")
+    if global_kw is not None and not use_global:
+        raise ValueError("merge_scans: global_kw goes with init_poses='global'")
+    global_kw = dict(global_kw or {})
+    bad = sorted(set(global_kw) - {"bin", "lattice", "tol", "peaks", "sep", "frame", "normal_radius", "max_nn"})
+    if bad:
+        raise ValueError(f"merge_scans: unknown global_align keywords {bad}")
+    if use_global:
+        init_poses = None
+        _check_global(global_kw.get("bin", 0.05), global_kw.get("lattice", (2048, 2048, 256)), global_kw.get("tol", 5.0),
+                      global_kw.get("peaks", 64), global_kw.get("sep", 2), global_kw.get("frame"))
     try:
         ok = not isinstance(reference, bool) and int(reference) == reference and 0 <= int(reference) < len(clouds)
     except (TypeError, ValueError):
@@ -255,7 +473,16 @@ def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=Non
     for i, scan in enumerate(clouds):
         if i == reference:
             continue
-        reg = icp(scan, apply_downsample(union, model_kw), init=init_poses[i], **icp_kw)
+        model = apply_downsample(union, model_kw)
+        init = init_poses[i]
+        if use_global:
+            found = global_align(scan, model, **global_kw)
+            if found.status != 0 or found.margin > MARGIN_MAX:
+                warnings.warn(f"merge_scans: scan {i} has no clear global alignment ({found!r}); registering it from "
+                              "the identity")
+            else:
+                init = found.pose
+        reg = icp(scan, model, init=init, **icp_kw)
         if not reg.converged:
             warnings.warn(f"merge_scans: scan {i} did not converge ({STATUS.get(reg.status)} after {reg.steps} steps, "
                           f"{reg.inliers} pairs)")

@@ -371,6 +371,64 @@ int d3d_manhattan_frame(const float *normals, int n, int row_stride_floats, cons
                         double *pose, int32_t *choice, int64_t *score, int32_t *support, void *scratch,
                         size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* The coarse pose between two scans that come without one: a quarter turn, an integer shift on a lattice and a z shift,
+ * for two clouds that are each levelled and squared already (d3d_manhattan_frame).  d3d_icp refines it.  Every table is
+ * made of integers and every peak and pick is defined exactly, so the outputs depend on the sets of rows alone.
+ *   inputs: per cloud xyz fp32 (row i at xyz + i * stride) and normals fp32 (likewise), and an origin o (device, 3 doubles;
+ *     the cloud's per-axis minimum); bin > 0; lattice = (Lx, Ly, Lz), Lx == Ly = L a multiple of 32 in [32, 4096], Lz in
+ *     [1, 4096]; c2 = float(cos^2(tol)), tol in (0, 20] degrees; peaks = K in [1, 64]; sep in [0, 64] bins.
+ *   rows: m = (n0 n0 + n1 n1) + n2 n2 in fp32 without contraction; a row takes part iff 0.5 <= m <= 2 and its position is
+ *     finite.  Its cell is c_a = floor((double(p_a) - o_a) / bin) in fp64; a row with a cell outside [0, L_a) is dropped
+ *     and counted, the others are used.  The class of a used row is the axis a with n_a n_a >= c2 m (fp32; at most one
+ *     axis, possibly none: such a row is used and enters nothing).
+ *   per cloud: histograms H_a[c_a] over the rows of class a (int32), and for the wall classes x and y a bitmap of L x L
+ *     bits, bit (cx, cy) = bit (cy L + cx) mod 32 of word (cy L + cx) / 32.  The source's bitmaps hold its occupied cells;
+ *     the target's are dilated 3 x 3, clipped at the lattice edge.  The source's set bits are listed per class in
+ *     ascending order of cy L + cx as cy << 16 | cx.
+ *   quarter turns about the lattice centre, q = 0..3: (x, y) -> (x, y), (L-1-y, x), (L-1-x, L-1-y), (y, L-1-x); the source's
+ *     classes x and y swap for odd q.  The turned source histogram along x is Hs_x, rev(Hs_y), rev(Hs_x), Hs_y, along y
+ *     Hs_y, Hs_x, rev(Hs_y), rev(Hs_x).
+ *   correlations, int64: Ht~[c] = 2 Ht[c] + Ht[c-1] + Ht[c+1] (0 outside the lattice); C[s] = sum_c Hs'[c] Ht~[c + s] for
+ *     -L_a < s < L_a.  Correlation 2 q + 0 is along x and 2 q + 1 along y under turn q, correlation 8 is z.
+ *   peaks: s is a peak iff C[s] > 0, no s' in [s - sep, s) has C[s'] >= C[s] and no s' in (s, s + sep] has C[s'] > C[s]
+ *     (shifts outside the range do not count).  The K largest by (C descending, s ascending) are kept in that order;
+ *     an unused slot has the value -1 and the shift 0.  z takes the first slot of correlation 8, or 0 when it is unused.
+ *   verification of the candidates (q, i, j), 4 K K: with (sx, sy) = the shifts of slot i of correlation 2 q and slot j
+ *     of 2 q + 1, score = the number of listed source cells (both classes) whose turned cell plus (sx, sy) lies in the
+ *     lattice and is set in the target's dilated bitmap of the class the turn gives it.  A candidate with an unused
+ *     slot scores -1.  Every occupied cell counts once: point density does not weigh.
+ *   pick: the highest score, the lowest (q, i, j) among equals.  status 0; status 1 when that score is <= 0 (a cloud
+ *     without walls, or without rows): choice is then zero and the pose the translation o_t - o_s.
+ *   pose, fp64 row-major 4 x 4, x_t = R x_s + t: with h = L / 2, u = (o_s,x + bin h, o_s,y + bin h, o_s,z), v = (o_t,x + bin
+ *     double(sx + h), o_t,y + bin double(sy + h), o_t,z + bin double(sz)) and R = Rz(q), whose entries are exactly 0 and
+ *     +-1: t = v - R u, where R u is (ux, uy), (-uy, ux), (-ux, -uy), (uy, -ux) for q = 0..3 and uz.
+ * Outputs (device, no read-back): pose; choice int32 [4] = (q, sx, sy, sz); score int64 [6] = the best score of each
+ * heading, the best of all, and the runner-up (the highest score among all other candidates); support int32 [4] = rows
+ * used and dropped of the source, then of the target; status int32 [1].  details (NULL: none): device buffers, each NULL
+ * or filled with hist int32 [2, 2 L + Lz] (source, target; x, y, z), cells int32 [2, max(1, min(m, L L))] and cell_count
+ * int32 [2] (the source's lists), target_bits uint32 [2, L L / 32], corr int64 [9, 2 max(L, Lz) - 1] (entry s + L_a - 1,
+ * zeros behind), peak_value int64 [9, K], peak_shift int32 [9, K], scores int32 [4, K, K].
+ * Limits: the overlap is maximised and free space costs nothing, so a half turn of a point-symmetric building can win
+ * through a small overlap (score[5] / score[4] near 1 shows it); z is one peak, a storey off in a multi-storey partial
+ * overlap; the accuracy is half a bin per axis and the frames' heading error.  0 <= m, n <= 2^28; an empty cloud gives
+ * status 1.  Integer atomics only (add, or, max).  scratch: d3d_global_align_scratch_bytes(m, lattice, peaks) (0 for
+ * arguments out of range).  Asynchronous.  phase_ms_host (NULL: none): six floats, the milliseconds of rows, cells,
+ * correlate, peaks, verify, pick between device events; the call then synchronises.                                  */
+typedef struct d3d_global_align_details {
+  int32_t *hist, *cells, *cell_count;
+  uint32_t *target_bits;
+  int64_t *corr, *peak_value;
+  int32_t *peak_shift, *scores;
+} d3d_global_align_details;
+size_t d3d_global_align_scratch_bytes(int n_source, const int *lattice, int peaks);
+int d3d_global_align(const float *source, int m, int source_stride_floats, const float *source_normals,
+                     int source_normal_stride_floats, const double *source_origin_dev, const float *target, int n,
+                     int target_stride_floats, const float *target_normals, int target_normal_stride_floats,
+                     const double *target_origin_dev, double bin, const int *lattice, float c2, int peaks, int sep,
+                     double *pose, int32_t *choice, int64_t *score, int32_t *support, int32_t *status,
+                     const d3d_global_align_details *details, void *scratch, size_t scratch_bytes, void *stream,
+                     float *phase_ms_host);
+
 /* Voxel down-sampling of a raw scan: one row per occupied voxel, every column the mean over the voxel's points
  * (data3d/suncg_utils/suncg_preprocess.py:748-767, open3d.voxel_down_sample(pcd, voxel_size=0.02)).  A restatement of
  * open3d's VoxelDownSample that is not pinned against open3d itself.  pcl fp32 [n, ncols], 3 <= ncols <= 16, contiguous,
