@@ -72,6 +72,19 @@ _NMS_SCRATCH = {}
 _MATCH_MAX_SEGMENTS = 256
 
 
+def _nms_key(dev):      # one scratch per (device, stream): buildings in flight on different streams never share it
+    return (dev.index, _lib.raw_stream(dev))
+
+
+def _scratch(key, nbytes, dev):
+    """The scratch buffer kept under `key` (_nms_key, prefixed per op family), grown to nbytes (at least 1 MiB)."""
+    buf = _NMS_SCRATCH.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
+        _NMS_SCRATCH[key] = buf
+    return buf
+
+
 def match_segments(gt, gt_offsets, pred, pred_seg, aug_thickness=None, criterion=-1, yaw_threshold=4.0, high=0.5,
                    low=0.5, allow_low_quality=False, encode_weights=(1.0,) * 7, want_reg=True):
     """d3d_match_segments: label assignment of S segments in one launch set, no [M, N] IoU matrix, no host sync.
@@ -107,12 +120,7 @@ def match_segments(gt, gt_offsets, pred, pred_seg, aug_thickness=None, criterion
         aug_thickness = {'target_Y': 0.0, 'target_Z': 0.0, 'anchor_Y': 0.0, 'anchor_Z': 0.0}
     aug = floats([aug_thickness['target_Y'], aug_thickness['target_Z'], aug_thickness['anchor_Y'],
                   aug_thickness['anchor_Z']])
-    nbytes = int(lib().d3d_match_segments_scratch_bytes(M, N))
-    key = ("match",) + _nms_key(dev)
-    buf = _NMS_SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _NMS_SCRATCH[key] = buf
+    buf = _scratch(("match",) + _nms_key(dev), int(lib().d3d_match_segments_scratch_bytes(M, N)), dev)
     check(lib().d3d_match_segments(ptr(gt), _lib.ints(offs), S, ptr(pred), N, ptr(pred_seg), aug, int(criterion),
                                    float(yaw_threshold) if not yaw_threshold > 1.58 else 4.0, float(high), float(low), int(bool(allow_low_quality)),
                                    floats([float(w) for w in encode_weights]), ptr(matched), ptr(reg), ptr(buf),
@@ -120,19 +128,10 @@ def match_segments(gt, gt_offsets, pred, pred_seg, aug_thickness=None, criterion
     return matched, reg
 
 
-
-def _nms_key(dev):      # one scratch per (device, stream): buildings in flight on different streams never share it
-    return (dev.index, _lib.raw_stream(dev))
-
-
 def _nms_sorted(boxes_sorted, thresh, max_keep=0):
     n = boxes_sorted.shape[0]
     dev = boxes_sorted.device
-    nbytes = lib().d3d_nms_scratch_bytes(n)
-    buf = _NMS_SCRATCH.get(_nms_key(dev))
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _NMS_SCRATCH[_nms_key(dev)] = buf
+    buf = _scratch(_nms_key(dev), lib().d3d_nms_scratch_bytes(n), dev)
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     nk = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib().d3d_rotate_nms_3d_sorted(ptr(boxes_sorted), n, float(thresh), int(max_keep or 0), ptr(keep), ptr(nk),
@@ -156,11 +155,7 @@ def nms_3d_batched(boxes, order, counts, n_max, iou_threshold, aug_thickness=(0.
         B, stride = order.shape
     if counts is not None:
         assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] == B
-    nbytes = lib().d3d_nms_batched_scratch_bytes(B, n_max)
-    buf = _NMS_SCRATCH.get(_nms_key(dev))
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _NMS_SCRATCH[_nms_key(dev)] = buf
+    buf = _scratch(_nms_key(dev), lib().d3d_nms_batched_scratch_bytes(B, n_max), dev)
     keep = torch.empty((B, max(n_max, 1)), dtype=torch.int32, device=dev)
     nk = torch.empty(B, dtype=torch.int32, device=dev)      # every segment's count is written (zeros for n_max == 0)
     check(lib().d3d_rotate_nms_3d_batched(ptr(boxes), ptr(order), stride, ptr(counts), B, n_max, float(iou_threshold),
@@ -223,12 +218,7 @@ def topk_segments(vals, k, n=None, elem_stride=1, group_stride=0, n_groups=1, ex
     im = _lib.ints(tuple(int(v) for v in idx_map)) if idx_map is not None else None
     # key scratch: the selection evaluates every element once and re-reads the cached keys with wide loads
     nbytes = int(lib().d3d_topk_scratch_bytes(int(n), S)) if n >= 8192 else 0
-    buf = None
-    if nbytes:
-        buf = _NMS_SCRATCH.get(("topk",) + _nms_key(dev))
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-            _NMS_SCRATCH[("topk",) + _nms_key(dev)] = buf
+    buf = _scratch(("topk",) + _nms_key(dev), nbytes, dev) if nbytes else None
     check(lib().d3d_topk_segments(ptr(vals), int(n), int(elem_stride), int(group_stride), int(n_groups), ptr(example),
                                   int(n_examples), k, int(bool(sigmoid)), mv, im, ptr(reg),
                                   int(reg.shape[1]) if reg is not None else 0, ptr(anchors), float(clip), ptr(out["idx32"]),
@@ -250,11 +240,7 @@ def rotate_nms_3d(rbboxes, scores, pre_max_size=None, post_max_size=None, iou_th
     k = n if pre_max_size is None else min(n, int(pre_max_size))
     if k > topk_max():
         raise D3DError(f"rotate_nms_3d: more than {topk_max()} candidates; pass pre_max_size (reference uses 2000)")
-    nbytes = lib().d3d_rotate_nms_3d_scratch_bytes(k, n)
-    buf = _NMS_SCRATCH.get(_nms_key(dev))
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _NMS_SCRATCH[_nms_key(dev)] = buf
+    buf = _scratch(_nms_key(dev), lib().d3d_rotate_nms_3d_scratch_bytes(k, n), dev)
     keep = torch.empty(k, dtype=torch.int64, device=dev)
     nk = torch.empty(1, dtype=torch.int32, device=dev)
     import ctypes

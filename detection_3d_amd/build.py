@@ -9,9 +9,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libd3d_hip.so")
 SOURCES = ["grid.hip", "grid_chain.hip", "plan.hip", "geometry_async.hip", "grid_views.hip", "scan_sort.hip", "voxelize.hip",
-           "conv.hip", "conv_ws.hip", "conv_bf16.hip", "bn.hip", "boxes.hip", "roi_align.hip", "backward.hip", "rpn_head.hip", "topk.hip",
+           "conv.hip", "conv_ws.hip", "conv_bf16.hip", "bn.hip", "box_match.hip", "nms.hip", "box_tail.hip", "roi_align.hip", "backward.hip", "rpn_head.hip", "topk.hip",
            "augment.hip", "celllist.hip", "normals.hip", "points_in_boxes.hip", "box_fit.hip", "frame.hip", "downsample.hip", "unproject.hip", "render.hip", "clean.hip", "planes.hip", "register.hip", "global_align.hip"]
-# -ffp-contract=off: the box geometry shares an arithmetic contract with the CPU oracle
+# -ffp-contract=off: the box geometry (box_geometry.inc) shares an arithmetic contract with the CPU oracle
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17"]
 
 
@@ -27,7 +27,7 @@ def build_library(force=False, verbose=False):
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "d3d_internal.h"), os.path.join(CSRC, "grid_internal.h"), os.path.join(CSRC, "conv_block.inc"),
-               os.path.join(CSRC, "cell_walk.inc"), os.path.join(CSRC, "union_find.inc"), os.path.join(CSRC, "eigen3.inc"),
+               os.path.join(CSRC, "cell_walk.inc"), os.path.join(CSRC, "union_find.inc"), os.path.join(CSRC, "eigen3.inc"), os.path.join(CSRC, "box_geometry.inc"),
                os.path.join(HERE, "..", "include", "d3d_hip.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

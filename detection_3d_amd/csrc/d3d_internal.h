@@ -60,6 +60,9 @@ inline Arena scratch_arena(const void *scratch, size_t bytes) {
   A.cap = bytes;
   return A;
 }
+// an arena that only measures: no memory behind it and no limit.  After an op's carve, `used` is the size of the
+// scratch buffer that the same carve needs, so a *_scratch_bytes function and its entry cannot disagree.
+inline Arena sizing_arena() { return scratch_arena((const void *)uintptr_t(256), ~size_t(0) >> 1); }
 
 // one thread per item in blocks of `block`: the grid that covers n items (empty for n <= 0)
 inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
@@ -212,6 +215,8 @@ __device__ __forceinline__ uint32_t f32_ordered(float v) {
   const uint32_t b = __float_as_uint(v);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
+// the same image with a NaN of either sign as the top value, which ordered_to_f32 gives back as a NaN
+__device__ __forceinline__ uint32_t f32_ordered_nan_top(float v) { return v != v ? 0xffffffffu : f32_ordered(v); }
 // ... and back (host and device: d3d_voxel_downsample_cells reports a cloud's extent with it)
 __host__ __device__ __forceinline__ float ordered_to_f32(uint32_t u) {
   return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);

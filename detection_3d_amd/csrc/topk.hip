@@ -357,6 +357,26 @@ __global__ void k_keep_to_i64(const int32_t *__restrict__ keep, const int32_t *_
   if (i < cap && i < *n_keep) out[i] = keep[i];
 }
 
+namespace {
+
+// scratch of d3d_rotate_nms_3d: order [k] (candidates, descending score), keep32 [k] and cnt [1] (= k) in one block, the
+// batched NMS's own scratch, then the key scratch of the selection -- only if the caller provided that much, else null
+struct NmsLayout {
+  int32_t *order, *keep32, *cnt;
+  char *nms, *keys;
+  size_t nms_bytes, key_bytes;
+};
+
+int carve_nms(Arena &A, int k, int n, NmsLayout &L) {
+  const size_t nms_bytes = d3d_nms_batched_scratch_bytes(1, k), key_bytes = d3d_topk_scratch_bytes(n, 1);
+  D3D_ALLOC(order, int32_t, A, 2 * (size_t)k + 16);
+  D3D_ALLOC(nms, char, A, nms_bytes);
+  char *keys = key_bytes ? A.get<char>(key_bytes) : nullptr;
+  L = NmsLayout{order, order + k, order + 2 * k, nms, keys, nms_bytes, keys ? key_bytes : 0};
+  return D3D_OK;
+}
+
+}  // namespace
 }  // namespace d3d
 
 using namespace d3d;
@@ -406,8 +426,10 @@ int d3d_topk_segments(const float *vals, int n, int elem_stride, int group_strid
 
 // (n: the number of input boxes -- the selection keeps their keys in the scratch; 0: without, slower for large n)
 size_t d3d_rotate_nms_3d_scratch_bytes(int pre_max_size, int n) {
-  const int k = std::max(0, std::min(pre_max_size, kTopkMax));
-  return d3d_nms_batched_scratch_bytes(1, k) + (size_t)k * 8 + 1024 + 512 + d3d_topk_scratch_bytes(n, 1);
+  Arena A = sizing_arena();
+  NmsLayout L;
+  (void)carve_nms(A, std::max(0, std::min(pre_max_size, kTopkMax)), n, L);
+  return A.used;
 }
 
 // rotate_nms_3d as the reference defines it (box_torch_ops.py:489-514 behind boxlist_nms_3d's size clamp,
@@ -429,22 +451,17 @@ int d3d_rotate_nms_3d(const float *boxes, const float *scores, int n, int pre_ma
   }
   D3D_REQUIRE(boxes && scores && keep_out && scratch && scratch_bytes >= d3d_rotate_nms_3d_scratch_bytes(k, 0),
               "rotate_nms_3d: bad buffers");
-  char *base = (char *)scratch;
-  int32_t *order = (int32_t *)base;                       // [k] candidates, descending score
-  int32_t *keep32 = order + k;                            // [k]
-  int32_t *cnt = keep32 + k;                              // [1] candidates (= k)
-  const size_t off = (((size_t)k * 8 + 64) + 255) & ~size_t(255);
-  // (key scratch for the selection: what lies behind the NMS's own scratch, if the caller provided that much)
-  const size_t nms_bytes = d3d_nms_batched_scratch_bytes(1, k);
-  const size_t key_off = (off + nms_bytes + 255) & ~size_t(255);
-  void *key_scratch = scratch_bytes >= key_off + d3d_topk_scratch_bytes(n, 1) ? base + key_off : nullptr;
-  int rc = d3d_topk_segments(scores, n, 1, 0, 1, nullptr, 1, k, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, order, nullptr,
-                             nullptr, nullptr, cnt, key_scratch, key_scratch ? d3d_topk_scratch_bytes(n, 1) : 0, stream);
+  Arena A = scratch_arena(scratch, scratch_bytes);
+  NmsLayout L;
+  int rc = carve_nms(A, k, n, L);
   if (rc) return rc;
-  rc = d3d_rotate_nms_3d_batched(boxes, order, k, cnt, 1, k, thresh, aug_yx, aug_z, post_max_size > 0 ? post_max_size : 0,
-                                 keep32, n_keep_dev, base + off, scratch_bytes - off, stream);
+  rc = d3d_topk_segments(scores, n, 1, 0, 1, nullptr, 1, k, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.f, L.order, nullptr,
+                         nullptr, nullptr, L.cnt, L.keys, L.key_bytes, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_keep_to_i64, dim3((k + 255) / 256), dim3(256), 0, s, keep32, n_keep_dev, k, keep_out);
+  rc = d3d_rotate_nms_3d_batched(boxes, L.order, k, L.cnt, 1, k, thresh, aug_yx, aug_z, post_max_size > 0 ? post_max_size : 0,
+                                 L.keep32, n_keep_dev, L.nms, L.nms_bytes, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_keep_to_i64, dim3((k + 255) / 256), dim3(256), 0, s, L.keep32, n_keep_dev, k, keep_out);
   D3D_LAUNCH_CHECK();
   if (n_keep_host) {
     int32_t h = 0;

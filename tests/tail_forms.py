@@ -1,4 +1,4 @@
-"""References and designed cases of the detector tail (csrc/rpn_head.hip; csrc/boxes.hip from k_post_scores down;
+"""References and designed cases of the detector tail (csrc/rpn_head.hip; csrc/box_tail.hip from k_post_scores down;
 box_decode_one of d3d_internal.h).  Plain numpy, no GPU: tests/test_tail_forms_cpu.py keeps what is asserted about the
 cases here honest, tests/test_tail_forms_gpu.py runs them.
 

@@ -1,4 +1,4 @@
-"""Label assignment (csrc/boxes.hip: d3d_match_segments = k_match_pass1 / k_match_pass2) and the IoU matrix it shares its
+"""Label assignment (csrc/box_match.hip: d3d_match_segments = k_match_pass1 / k_match_pass2) and the IoU matrix it shares its
 device code with (k_iou_matrix: d3d_boxes_iou_3d, d3d_rotate_iou_eval) against results that involve neither the library
 nor, on lattice boxes, the oracle (tests/match_forms.py holds the boxes, the numpy Matcher and the scenes;
 tests/test_match_forms_cpu.py checks them without a GPU).
@@ -16,12 +16,12 @@ tests/test_match_forms_cpu.py checks them without a GPU).
   non-finite          one NaN (either sign), +Inf or -Inf field in a GT row or a prediction: the matrix has NaN where the
                       oracle has NaN and equal bits elsewhere, `matched` equals the numpy Matcher over the oracle's matrix
 
-What fails when a fix in csrc/boxes.hip is taken out again (each one alone, measured on an MI355X):
+What fails when a fix in csrc/box_match.hip or box_geometry.inc is taken out again (each one alone, measured on an MI355X):
   `v < bound ? bound : v` clamps in load_box   test_non_finite_matrix (gt[3]=nan, gt[5]=nan, pred[3]=nan, pred[5]=nan and their
                                                -nan forms), test_non_finite_matcher, the rotated family non_finite
   NaN z factor in iou_pair                     test_non_finite_matrix (gt[2]=nan, gt[5]=nan, pred[2]=nan, pred[5]=nan, -nan),
                                                test_non_finite_matcher, the rotated family non_finite
-  NaN of either sign on top in f2ord           test_non_finite_matcher[rpn] and [eq]: pred[2]=inf, pred[2]=-inf, pred[3]=-nan,
+  NaN of either sign on top in the ordered key test_non_finite_matcher[rpn] and [eq]: pred[2]=inf, pred[2]=-inf, pred[3]=-nan,
                                                pred[4]=-nan (the device gives these qualities as NaN with the sign bit set)
   no bounding-box early-out for a zero size    test_matrix_rotated_families_against_the_oracle, family tiny_sizes (800 of
                                                90,000 elements NaN where the oracle has a value, criterion -1)"""
@@ -160,7 +160,7 @@ def test_scratch_padding_and_no_reg(dev):
     N, M, S = sc["pred"].shape[0], sc["gt"].shape[0], len(sc["off"]) - 1
     need = int(lib().d3d_match_segments_scratch_bytes(M, N))
     nb, mb = (N * 4 + 255) & ~255, (M * 4 + 255) & ~255
-    assert need == 2 * nb + mb + 256 and N * 4 < nb and M * 4 < mb
+    assert need == 2 * nb + M * 4 and N * 4 < nb and M * 4 < mb
     guard = 4096
     gt, pred, seg = _t(dev, sc["gt"]), _t(dev, sc["pred"]), _t(dev, sc["seg"], np.int32)
     for with_reg in (True, False):
@@ -200,8 +200,8 @@ def test_non_finite_matrix(dev, clamps):
 @pytest.mark.parametrize("mode", sorted(F.MODES))
 def test_non_finite_matcher(dev, mode):
     """every variant is a segment of its own.  Besides the cases of test_non_finite_matrix, a quality that is a NaN with
-    the sign bit set (pred[k]=-nan, gt[k]=-nan) must make its GT row's `highest` NaN as q.max(1) does: f2ord has to put
-    a NaN of either sign on top"""
+    the sign bit set (pred[k]=-nan, gt[k]=-nan) must make its GT row's `highest` NaN as q.max(1) does:
+    f32_ordered_nan_top has to put a NaN of either sign on top"""
     sc, e = F.scene("non_finite"), F.expect("non_finite", mode)
     got, reg = run_match(dev, sc, F.MODES[mode])
     _, _, _, labels = F.non_finite_boxes()

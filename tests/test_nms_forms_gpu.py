@@ -1,4 +1,4 @@
-"""Every sweep form of the rotated NMS (csrc/boxes.hip: k_nms_prep -> k_nms_pairs -> k_nms_eval -> sweep) at its size
+"""Every sweep form of the rotated NMS (csrc/nms.hip: k_nms_prep -> k_nms_pairs -> k_nms_eval -> sweep) at its size
 edges, on scenes whose suppression graph is known in exact rational arithmetic, and the pair decision of k_nms_pairs /
 k_nms_eval on families of hard box pairs against the CPU oracle (tests/nms_forms.py holds the scenes, the references and
 the doubtful band; tests/test_nms_forms_cpu.py checks them without a GPU).

@@ -1,6 +1,6 @@
 """Every launch form of the detector tail against exact results: the RPN / box-head kernel (csrc/rpn_head.hip), the box
 decode (box_decode_one of d3d_internal.h behind k_box_decode and d3d_topk_segments) and the final selection and gathers
-(csrc/boxes.hip from k_post_scores down).  tests/tail_forms.py holds the references and the designed cases,
+(csrc/box_tail.hip from k_post_scores down).  tests/tail_forms.py holds the references and the designed cases,
 tests/test_tail_forms_cpu.py checks them without a GPU.
 
 The C entries are called through ctypes as they are, with operands packed by tail_forms (the Python packing is compared
