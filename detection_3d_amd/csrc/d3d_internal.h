@@ -385,7 +385,7 @@ inline size_t packed_weight_floats(int fv, int cin, int cout) {
   if (cp < 0 || fv <= 0 || cout <= 0) return 0;
   return (size_t)fv * cp * cout;
 }
-// the fp32 packings (conv.hip: k_pack_weight, backward.hip: k_pack_weight_t) of fv * cp * cout / fv * cp * cin elements,
+// the fp32 packings (conv.hip: k_pack_weight, conv_dw.hip: k_pack_weight_t) of fv * cp * cout / fv * cp * cin elements,
 // cp = padded_cin(cin) / padded_cin(cout); d3d_pack_conv_weight[_transposed]_dt checks the arguments
 void launch_pack_weight(const float *w, int fv, int cin, int cout, int cp, float *packed, hipStream_t s);
 void launch_pack_weight_t(const float *w, int fv, int cin, int cout, int cp, int flip, float *packed, hipStream_t s);

@@ -136,6 +136,18 @@ __global__ void k_input_forward(const float *__restrict__ in, int planes,
   for (int j = b; j < e; j++) acc += mult * in[(size_t)idx[j] * planes + c];
   out[t] = acc;
 }
+// Input layer backward (CPU/IOLayers.cpp:30-47): every point receives multiplier * d_out[site].
+__global__ void k_input_backward(const float *__restrict__ d_out, int planes, const int32_t *__restrict__ off,
+                                 const int32_t *__restrict__ idx, int n_active, int average,
+                                 float *__restrict__ d_in) {
+  long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)n_active * planes) return;
+  const int row = (int)(t / planes), c = (int)(t % planes);
+  const int b = off[row], e = off[row + 1];
+  const float mult = (average && e > b) ? (float)1 / (e - b) : (float)1;
+  const float g = mult * d_out[t];
+  for (int j = b; j < e; j++) d_in[(size_t)idx[j] * planes + c] = g;
+}
 __global__ void k_export_input(const int32_t *a, int32_t *b, int n) {
   D3D_SIDE_PRIO();
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -508,6 +520,23 @@ int d3d_input_layer_forward(d3d_meta *m, const float *feats, int planes, float *
   if (int rc = ensure_point_lists(m, s)) return rc;
   hipLaunchKernelGGL(k_input_forward, grid1d((long)m->in_active * planes), dim3(256), 0, s, feats,
                      planes, m->in_off, m->in_idx, m->in_active, m->in_mode == 4 ? 1 : 0, out);
+  D3D_LAUNCH_CHECK();
+  return D3D_OK;
+}
+
+int d3d_input_layer_backward(d3d_meta *m, const float *d_out, int planes, float *d_in, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  D3D_REQUIRE(m && planes > 0, "bad arguments");
+  if (!m->in_off) {
+    set_error("input layer backward before build");
+    return D3D_ERR_STATE;
+  }
+  if (m->in_active == 0) return D3D_OK;
+  D3D_REQUIRE(d_out && d_in, "null gradient pointer");
+  if (int rc = ensure_point_lists(m, s)) return rc;
+  long total = (long)m->in_active * planes;
+  hipLaunchKernelGGL(k_input_backward, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_out, planes,
+                     m->in_off, m->in_idx, m->in_active, m->in_mode == 4 ? 1 : 0, d_in);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

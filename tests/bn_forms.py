@@ -1,6 +1,6 @@
 """What the BatchNorm tests share and a machine without a GPU can check (test_bn_forms_cpu.py): the fp64 references of
 the statistics, the affine + activation pass and the backward pass, the generators of exact-arithmetic and of rounding
-data with their preconditions, the comparators with their bounds, and the dispatch arithmetic of bn.hip / backward.hip
+data with their preconditions, the comparators with their bounds, and the dispatch arithmetic of bn.hip / bn_backward.hip
 restated (run_stats, run_stats_partials, launch_bn_apply, d3d_bn_apply_dt, bn_backward_t) -- the record
 d3d_bn_last_form must give for (rows, planes, storage type, alignment).  expect_bn assumes D3D_BN_SLICES is unset."""
 import numpy as np

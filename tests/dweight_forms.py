@@ -1,6 +1,6 @@
 """What the dWeight tests share and a machine without a GPU can check (test_dweight_forms_cpu.py): the fp64 reference of
 dW over a rulebook, the precondition of the exact-arithmetic check, and the dispatcher's arithmetic restated
-(backward.hip launch_dw_with) -- the form d3d_conv_dw_last_form must report for a plan and a layer."""
+(conv_dw.hip launch_dw_with) -- the form d3d_conv_dw_last_form must report for a plan and a layer."""
 import numpy as np
 
 F32, BF16 = 1, 2                       # family

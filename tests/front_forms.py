@@ -1,5 +1,5 @@
 """The front of every pass restated in numpy, and the designed cases its tests run on: the voxelizer
-(detection_3d_amd/csrc/voxelize.hip), the input layer (grid.hip, k_input_backward in backward.hip; scan_exclusive_i32 of
+(detection_3d_amd/csrc/voxelize.hip), the input layer (grid.hip, k_input_backward with it; scan_exclusive_i32 of
 scan_sort.hip underneath both), the views of a finished grid (grid_views.hip: locations, sparse <-> dense, anchors) and the
 two row helpers at the end of bn.hip (d3d_add, d3d_rows_to_bf16).  numpy only: no GPU, no oracle library.  The references
 are plain fp64 / integer restatements; tests/test_front_forms_cpu.py holds them against the oracle and asserts that the

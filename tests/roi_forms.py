@@ -1,7 +1,7 @@
 """What the rotated-RoIAlign tests share and a machine without a GPU can check (test_roi_forms_cpu.py): the fp64 reference
 of the operation on a sparse map (forward, gradient of the feature rows, magnitude and slope terms, the tap list), the
 generators of exact-arithmetic and of rounding cases with their preconditions and discontinuity margins, the comparators
-with their bounds, and the dispatch arithmetic of roi_align.hip restated -- the record d3d_roi_last_form must give.
+with their bounds, and the dispatch arithmetic of the roi_*.hip files restated -- the record d3d_roi_last_form must give.
 
 The operation (ROIAlignRotated3D): a RoI row is (example, centre x, centre y, centre z, size x, size y, size z, yaw in
 degrees) in pixels of the full-resolution grid; y runs over the map's first spatial axis (H), x over the second (W).

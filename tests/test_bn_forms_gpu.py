@@ -2,7 +2,7 @@
 convolution's column sums), the affine + activation pass, the backward pass, for fp32 and bf16 rows, and k_add.
 
 Every case calls through the SCN wrappers, reads d3d_bn_last_form and asserts it equals tests.bn_forms.expect_bn (the
-dispatch arithmetic of bn.hip / backward.hip restated from the constants, itself checked in test_bn_forms_cpu.py), and
+dispatch arithmetic of bn.hip / bn_backward.hip restated from the constants, itself checked in test_bn_forms_cpu.py), and
 then compares what the kernels wrote with the fp64 reference of tests.bn_forms:
 
 * exact cases -- rows of non-zero integers in +-{1..4}, saved mean a small integer, invstd and gamma powers of two

@@ -30,7 +30,7 @@ k_conv<CT,1,COUT,1,BPW,true,LATE> CT 16 / 32 / 64 /    test_fp32_forms[cin-cout-
 split) / 64 / 128 / 256 (BPW 1); unsplit, and           16), test_row_structure, test_fp32_auto_threshold,
 offset-split + k_conv_reduce (+ column statistics)      test_stages, test_dinput_exact
 k_conv<..., VEC = false, LATE = false>                  test_fp32_unpadded_cin (Cin 9 / 20 / 48 / 100 / 200)
-dWeight, atomic and fixed-order (backward.hip)          test_dweight; every launch form of it in
+dWeight, atomic and fixed-order (conv_dw.hip)           test_dweight; every launch form of it in
                                                         test_dweight_forms_gpu.py (d3d_conv_dw_last_form)
 k_conv_ws<64,64,64,4>, k_conv_ws<128,128,32,4>          test_fp32_ws (d3d_conv_ws_mode 2, unsplit only: the
                                                         split form never takes it)

@@ -1,4 +1,4 @@
-"""Every launch form of the dWeight dispatcher (backward.hip launch_dw_with) against an fp64 result of the same sum.
+"""Every launch form of the dWeight dispatcher (conv_dw.hip launch_dw_with) against an fp64 result of the same sum.
 
 Reference: fp64 numpy on the rulebooks of the CPU oracle (tests.dweight_forms.dw64: dW[k] = x[in_k]^T gout[out_k] and
 a[k] = |x|^T |gout|; checked against oracle.rule_conv_backward in test_dweight_forms_cpu.py).  Two checks per case:

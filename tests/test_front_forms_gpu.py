@@ -1,5 +1,5 @@
 """The front of every pass on exact cases: the voxelizer (detection_3d_amd/csrc/voxelize.hip), the input layer (grid.hip,
-k_input_backward of backward.hip), the exclusive scan under both (scan_exclusive_i32, scan_sort.hip), the views of a finished
+k_input_backward with it), the exclusive scan under both (scan_exclusive_i32, scan_sort.hip), the views of a finished
 grid (grid_views.hip) and the row helpers at the end of bn.hip.
 
 References: tests/front_forms.py (numpy fp64 / integers; held against the CPU oracle in tests/test_front_forms_cpu.py,

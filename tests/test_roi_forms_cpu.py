@@ -1,7 +1,7 @@
 """What test_roi_forms_gpu.py relies on, checked without a GPU: the fp64 reference of tests.roi_forms against the oracle
 the suite already trusts, the comparators against an fp32 model of the kernels and against mutants of it, the coverage
 the case lists claim (read from the reference's tap lists), the exactness preconditions, the generators' termination
-and discontinuity margins, and expect_roi against the constants of roi_align.hip.
+and discontinuity margins, and expect_roi against the constants of the roi_*.hip files.
 
 `device_forward` / `device_backward` are a numpy float32 transcription of the kernels' arithmetic (roi_geom, sample_pos,
 tri_setup, the merge of a step's 64 taps by cell with the butterfly's pairing, the list sums in list order, the division;
@@ -481,11 +481,15 @@ def test_position_bound_covers_the_model():
 
 
 def test_expect_roi_restates_the_constants():
-    text = open(os.path.join(ROOT, "detection_3d_amd", "csrc", "roi_align.hip")).read()
-    grid = open(os.path.join(ROOT, "detection_3d_amd", "csrc", "grid_views.hip")).read()
+    csrc = os.path.join(ROOT, "detection_3d_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read()
+                   for f in ("roi_geometry.inc", "roi_forward.hip", "roi_backward.hip", "roi_backward_det.hip"))
+    grid = open(os.path.join(csrc, "grid_views.hip")).read()
 
     def const(name, src=text):
-        return int(re.search(r"constexpr \w+ " + name + r" = (\d+)", src).group(1))
+        found = re.findall(r"constexpr \w+ " + name + r" = (\d+)", src)
+        assert len(found) == 1, (name, found)                          # one definition across the files
+        return int(found[0])
     assert (const("kRoiG"), const("kRoiCch"), const("kRoiWaves"), const("kRoiBwdCch"), const("kRoiDetChunk"),
             const("kRoiDetCpl"), const("kRoiMaxLevels")) == (Rf.ROI_G, Rf.ROI_CCH, Rf.ROI_WAVES, Rf.ROI_BWD_CCH,
                                                              Rf.DET_CHUNK, Rf.DET_CPL, Rf.MAX_LEVELS)

@@ -3,7 +3,7 @@ dense-index lookup, host crop and device extent, one level and several, both lay
 fixed-order form, the bf16 gradient forms, and the dense kernels.
 
 Every case calls through the wrappers of detection_3d_amd/roi_align_rotated_3d.py, reads d3d_roi_last_form and asserts
-it equals tests.roi_forms.expect_roi (the dispatch arithmetic of roi_align.hip restated from its constants, itself
+it equals tests.roi_forms.expect_roi (the dispatch arithmetic of the roi_*.hip files restated from their constants, itself
 checked in test_roi_forms_cpu.py), and then compares what the kernels wrote, element by element, with the fp64
 reference of tests.roi_forms:
 

@@ -8,7 +8,7 @@ round-to-nearest-even.
 
 What is not observable here: the SHAPE of the tree that sums a cell's tap weights (levels 32, 16, 8, 4, 2, 1 of the xor
 butterfly).  On exact weights every tree gives the same number.  The shape is pinned by construction (roi_cells4_sum in
-csrc/roi_align.hip adds lane i to lane i ^ d at every level) and by the paired comparison of DESIGN.md section 5e: on
+csrc/roi_forward.hip adds lane i to lane i ^ d at every level) and by the paired comparison of DESIGN.md section 5e: on
 seeded cases of arbitrary yaw the pooled tensor is byte-identical to that of the serial butterfly it replaced.
 
 Cases (tests/roi_merge_ref.py; test_roi_merge_cpu.py asserts that they reach what they are named for):
