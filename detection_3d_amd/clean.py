@@ -14,50 +14,20 @@ neighbours within radius by (d2, index), their mean distance in fp64, the mean a
 over the points that have k neighbours; a point with fewer is dropped and enters neither.  connected_components labels
 the graph whose edges join points within radius.  The same input gives the same bits, whatever torch's deterministic
 mode says."""
-import ctypes
-import math
-
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
+from ._cloud import PhaseTimer, gpu_rows, number, options, run, scratch, whole
+from ._lib import ptr, stream_of
 
 PHASES = ("cells", "sort", "table", "search", "tail")
 
 
-def _check_radius(radius):
+def _check_statistical(statistical):
     try:
-        radius = float(radius)
+        k, std_ratio = statistical
     except (TypeError, ValueError):
-        raise ValueError(f"radius {radius!r} must be a number")
-    if not (radius > 0.0 and math.isfinite(radius)):
-        raise ValueError(f"radius {radius} must be positive and finite")
-    return radius
-
-
-def _as_int(value, what):
-    """an integer >= 1 given as an int (or a float with an integer value); anything else raises ValueError"""
-    try:
-        ok = not isinstance(value, bool) and int(value) == value and int(value) >= 1
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} {value!r} must be an integer >= 1")
-    return int(value)
-
-
-def _check_min_neighbors(min_neighbors):
-    return _as_int(min_neighbors, "min_neighbors")
-
-
-def _check_statistical(k, std_ratio):
-    k = _as_int(k, "statistical: k")
-    try:
-        std_ratio = float(std_ratio)
-    except (TypeError, ValueError):
-        raise ValueError(f"statistical: std_ratio {std_ratio!r} must be a number")
-    if not (std_ratio >= 0.0 and math.isfinite(std_ratio)):
-        raise ValueError(f"statistical: std_ratio {std_ratio} must be finite and not negative")
-    return k, std_ratio
+        raise ValueError(f"statistical must be None or (k, std_ratio), got {statistical!r}") from None
+    return whole(k, "statistical: k"), number(std_ratio, "statistical: std_ratio")
 
 
 def _check_min_component(min_component):
@@ -75,49 +45,26 @@ def _check_min_component(min_component):
     raise ValueError(f"min_component {min_component!r} must be an int >= 1 or a float in (0, 1)")
 
 
-def _xyz(xyz):
-    """-> (the tensor to read, n, row stride in floats), as estimate_normals takes it"""
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] < 3:
-        raise ValueError("xyz must be a tensor [N, >= 3]")
-    if not xyz.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % xyz.device)
-    if xyz.dtype != torch.float32:
-        raise ValueError(f"xyz must be float32, got {xyz.dtype}")
-    xyz = xyz.detach()
-    n = xyz.shape[0]
-    if n > 1 and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
-        xyz = xyz[:, :3].contiguous()        # a transposed or broadcast view: the three columns only
-    return xyz, n, (xyz.stride(0) if n > 1 else max(3, xyz.stride(0)))
-
-
-def _scratch(nbytes, dev):
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-
-def _phases(ms):
-    return dict(zip(PHASES, (float(v) for v in ms)))
-
-
 def radius_neighbors(xyz, radius=0.1, phases=False):
     """xyz fp32 [N, >= 3] on the GPU (a column slice of a wider cloud is read in place) -> count int32 [N], the points
     within `radius` of every point, itself included.  Current stream, no read-back.  phases: also a dict of milliseconds
     (PHASES), timed with events inside the library; synchronises."""
-    radius = _check_radius(radius)
-    xyz, n, stride = _xyz(xyz)
+    radius = number(radius, "radius", lo_open=True)
+    xyz, n, stride = gpu_rows(xyz)
     dev = xyz.device
     count = torch.empty((n,), dtype=torch.int32, device=dev)
-    ms = (ctypes.c_float * len(PHASES))() if phases else None
+    timer = PhaseTimer(PHASES, phases)
     if n > 0:
-        nbytes = lib().d3d_radius_neighbors_scratch_bytes(n)
-        scratch = _scratch(nbytes, dev)
-        check(lib().d3d_radius_neighbors(ptr(xyz), n, stride, radius, ptr(count), ptr(scratch), nbytes, stream_of(dev), ms))
-    return (count, _phases(ms)) if phases else count
+        buf, nbytes = scratch(dev, "d3d_radius_neighbors_scratch_bytes", n)
+        run(dev, "d3d_radius_neighbors", ptr(xyz), n, stride, radius, ptr(count), ptr(buf), nbytes, stream_of(dev),
+            timer.ms)
+    return (count, timer.read()) if phases else count
 
 
 def radius_outliers(xyz, radius=0.1, min_neighbors=8, return_counts=False):
     """-> keep bool [N]: the point has at least min_neighbors points within radius, itself counted; with return_counts
     also those counts, int32 [N]."""
-    min_neighbors = _check_min_neighbors(min_neighbors)
+    min_neighbors = whole(min_neighbors, "min_neighbors")
     count = radius_neighbors(xyz, radius)
     keep = count >= min_neighbors
     return (keep, count) if return_counts else keep
@@ -126,21 +73,20 @@ def radius_outliers(xyz, radius=0.1, min_neighbors=8, return_counts=False):
 def knn_mean_distance(xyz, k=20, std_ratio=2.0, radius=0.1, phases=False):
     """-> (mean fp64 [N], found int32 [N], stats fp64 [2] = (mu, sigma) on the device, keep bool [N]) of
     d3d_knn_mean_distance; phases: also the dict of milliseconds (synchronises)."""
-    radius = _check_radius(radius)
-    k, std_ratio = _check_statistical(k, std_ratio)
-    xyz, n, stride = _xyz(xyz)
+    radius = number(radius, "radius", lo_open=True)
+    k, std_ratio = _check_statistical((k, std_ratio))
+    xyz, n, stride = gpu_rows(xyz)
     dev = xyz.device
     mean = torch.empty((n,), dtype=torch.float64, device=dev)
     found = torch.empty((n,), dtype=torch.int32, device=dev)
     keep = torch.empty((n,), dtype=torch.bool, device=dev)
     stats = torch.empty((2,), dtype=torch.float64, device=dev)
-    ms = (ctypes.c_float * len(PHASES))() if phases else None
-    nbytes = lib().d3d_knn_mean_distance_scratch_bytes(n)
-    scratch = _scratch(nbytes, dev)
-    check(lib().d3d_knn_mean_distance(ptr(xyz), n, stride, radius, k, std_ratio, ptr(mean), ptr(found), ptr(stats),
-                                      ptr(keep), ptr(scratch), nbytes, stream_of(dev), ms))
+    timer = PhaseTimer(PHASES, phases)
+    buf, nbytes = scratch(dev, "d3d_knn_mean_distance_scratch_bytes", n)
+    run(dev, "d3d_knn_mean_distance", ptr(xyz), n, stride, radius, k, std_ratio, ptr(mean), ptr(found), ptr(stats),
+        ptr(keep), ptr(buf), nbytes, stream_of(dev), timer.ms)
     res = (mean, found, stats, keep)
-    return res + (_phases(ms),) if phases else res
+    return res + (timer.read(),) if phases else res
 
 
 def statistical_outliers(xyz, k=20, std_ratio=2.0, radius=0.1, return_stats=False):
@@ -158,18 +104,17 @@ def connected_components(xyz, radius=0.1, phases=False):
     """The components of the graph whose edges join points within `radius` of one another -> (label int32 [N], the
     smallest row index of the point's component; size int32 [N], that component's number of points).  Current stream,
     no read-back."""
-    radius = _check_radius(radius)
-    xyz, n, stride = _xyz(xyz)
+    radius = number(radius, "radius", lo_open=True)
+    xyz, n, stride = gpu_rows(xyz)
     dev = xyz.device
     label = torch.empty((n,), dtype=torch.int32, device=dev)
     size = torch.empty((n,), dtype=torch.int32, device=dev)
-    ms = (ctypes.c_float * len(PHASES))() if phases else None
+    timer = PhaseTimer(PHASES, phases)
     if n > 0:
-        nbytes = lib().d3d_connected_components_scratch_bytes(n)
-        scratch = _scratch(nbytes, dev)
-        check(lib().d3d_connected_components(ptr(xyz), n, stride, radius, ptr(label), ptr(size), ptr(scratch), nbytes,
-                                             stream_of(dev), ms))
-    return (label, size, _phases(ms)) if phases else (label, size)
+        buf, nbytes = scratch(dev, "d3d_connected_components_scratch_bytes", n)
+        run(dev, "d3d_connected_components", ptr(xyz), n, stride, radius, ptr(label), ptr(size), ptr(buf), nbytes,
+            stream_of(dev), timer.ms)
+    return (label, size, timer.read()) if phases else (label, size)
 
 
 def component_threshold(min_component, rows):
@@ -208,17 +153,9 @@ def clean_cloud(pcl, radius=0.1, min_neighbors=None, statistical=None, min_compo
     no kernel is issued.
     return_source: also source int32 [N], the row of the result every input row went to, -1 for a dropped row (None when
     every option is None)."""
-    radius = _check_radius(radius)
-    if min_neighbors is not None:
-        min_neighbors = _check_min_neighbors(min_neighbors)
-    if statistical is not None:
-        try:
-            k, std_ratio = statistical
-        except (TypeError, ValueError):
-            raise ValueError(f"statistical must be None or (k, std_ratio), got {statistical!r}")
-        statistical = _check_statistical(k, std_ratio)
-    if min_component is not None:
-        min_component = _check_min_component(min_component)
+    kw = clean_kwargs({"radius": radius, "min_neighbors": min_neighbors, "statistical": statistical,
+                       "min_component": min_component})
+    radius, min_neighbors, statistical, min_component = (kw.get(k) for k in _CLEAN_KEYS)
     if min_neighbors is None and statistical is None and min_component is None:
         return (pcl, None) if return_source else pcl
     if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2 or pcl.shape[1] < 3:
@@ -240,22 +177,14 @@ _CLEAN_KEYS = ("radius", "min_neighbors", "statistical", "min_component")
 def clean_kwargs(clean):
     """The `clean=` keyword of the loops: None -> None; a dict with keys among radius, min_neighbors, statistical,
     min_component (clean_cloud's keywords) -> a checked copy.  Unknown keys and bad values raise ValueError."""
+    clean = options(clean, "clean", _CLEAN_KEYS)
     if clean is None:
         return None
-    if not isinstance(clean, dict):
-        raise ValueError(f"clean must be None or a dict with keys among {', '.join(_CLEAN_KEYS)}, got {clean!r}")
-    bad = sorted(set(clean) - set(_CLEAN_KEYS))
-    if bad:
-        raise ValueError(f"clean: unknown keywords {bad} ({', '.join(_CLEAN_KEYS)})")
-    kw = {"radius": _check_radius(clean.get("radius", 0.1))}
+    kw = {"radius": number(clean.get("radius", 0.1), "radius", lo_open=True)}
     if clean.get("min_neighbors") is not None:
-        kw["min_neighbors"] = _check_min_neighbors(clean["min_neighbors"])
+        kw["min_neighbors"] = whole(clean["min_neighbors"], "min_neighbors")
     if clean.get("statistical") is not None:
-        try:
-            k, std_ratio = clean["statistical"]
-        except (TypeError, ValueError):
-            raise ValueError(f"clean: statistical must be (k, std_ratio), got {clean['statistical']!r}")
-        kw["statistical"] = _check_statistical(k, std_ratio)
+        kw["statistical"] = _check_statistical(clean["statistical"])
     if clean.get("min_component") is not None:
         kw["min_component"] = _check_min_component(clean["min_component"])
     return kw

@@ -10,45 +10,16 @@ division, one rounding to fp32), the normal columns scaled to unit length afterw
 their first point in the input.  The cap keeps the k rows with the smallest (key, row), the key an integer mix of
 (seed, row), in ascending row order.  The same input gives the same bits, whatever torch's deterministic mode says."""
 import ctypes
-import math
 
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
+from ._cloud import gpu_cloud, need_gpu, normal_column, number, options, run, scratch
+from ._lib import ptr, stream_of
 
 MAX_COLS = 16
 CELL_LIMIT = 1 << 21
 DEFAULT_VOXEL = 0.02
 DEFAULT_MAX_POINTS = 500_000
-
-
-def _check_voxel(voxel):
-    voxel = float(voxel)
-    if not (voxel > 0.0 and math.isfinite(voxel)):
-        raise ValueError(f"voxel {voxel} must be positive and finite")
-    return voxel
-
-
-def _normal_col(normal_col, ncols):
-    if isinstance(normal_col, str):
-        if normal_col != "auto":
-            raise ValueError(f"normal_col must be 'auto', None or a column index, got {normal_col!r}")
-        return 6 if ncols == 9 else -1
-    if normal_col is None:
-        return -1
-    nc = int(normal_col)
-    if nc < 0 or nc + 3 > ncols:
-        raise ValueError(f"normal_col {nc}: three columns inside the {ncols} of the cloud")
-    return nc
-
-
-def _check_cloud(pcl, what):
-    if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2:
-        raise ValueError(f"{what}: a tensor [N, C]")
-    if not pcl.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % pcl.device)
-    if pcl.dtype != torch.float32:
-        raise ValueError(f"{what}: float32, got {pcl.dtype}")
 
 
 def voxel_downsample(pcl, voxel=DEFAULT_VOXEL, normal_col="auto", return_inverse=False, return_counts=False):
@@ -59,27 +30,24 @@ def voxel_downsample(pcl, voxel=DEFAULT_VOXEL, normal_col="auto", return_inverse
     return_inverse: also voxel_of_point int32 [N], the output row of every input row, -1 for a row dropped because its
     position is not finite.  return_counts: also the points per voxel, int32 [M].
     Runs on the current stream with one host read-back (M); a cloud wider than 2^21 voxels on an axis raises D3DError."""
-    voxel = _check_voxel(voxel)
-    _check_cloud(pcl, "voxel_downsample")
+    voxel = number(voxel, "voxel", lo_open=True)
+    pcl = gpu_cloud(pcl, "pcl").contiguous()
     n, ncols = pcl.shape
-    if not 3 <= ncols <= MAX_COLS:
+    if ncols > MAX_COLS:
         raise ValueError(f"voxel_downsample: 3 to {MAX_COLS} columns, got {ncols}")
-    nc = _normal_col(normal_col, ncols)
-    pcl = pcl.detach().contiguous()
+    nc = normal_column(normal_col, ncols)
     dev = pcl.device
     info = (ctypes.c_int * 2)(0, 0)
-    scratch, nbytes = None, 0
     if n > 0:
-        nbytes = lib().d3d_voxel_downsample_scratch_bytes(n, ncols)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(lib().d3d_voxel_downsample_cells(ptr(pcl), n, ncols, voxel, ptr(scratch), nbytes, info, stream_of(dev)))
+        buf, nbytes = scratch(dev, "d3d_voxel_downsample_scratch_bytes", n, ncols)
+        run(dev, "d3d_voxel_downsample_cells", ptr(pcl), n, ncols, voxel, ptr(buf), nbytes, info, stream_of(dev))
     m = int(info[0])
     out = torch.empty((m, ncols), dtype=torch.float32, device=dev)
     inverse = torch.empty((n,), dtype=torch.int32, device=dev) if return_inverse else None
     counts = torch.empty((m,), dtype=torch.int32, device=dev) if return_counts else None
     if n > 0:
-        check(lib().d3d_voxel_downsample_rows(ptr(pcl), n, ncols, nc, info, ptr(scratch), nbytes, ptr(out), ptr(inverse),
-                                              ptr(counts), stream_of(dev)))
+        run(dev, "d3d_voxel_downsample_rows", ptr(pcl), n, ncols, nc, info, ptr(buf), nbytes, ptr(out), ptr(inverse),
+            ptr(counts), stream_of(dev))
     res = (out,) + ((inverse,) if return_inverse else ()) + ((counts,) if return_counts else ())
     return res[0] if len(res) == 1 else res
 
@@ -94,15 +62,12 @@ def sample_rows(n, k, seed, device):
     if n >= 1 << 31:
         raise ValueError(f"sample_rows: n {n} does not fit 31 bits")
     device = torch.device(device)
-    if device.type != "cuda":
-        raise D3DError("this op runs on the MI355X only: device is %s (no CPU fallback)" % device)
+    need_gpu(device, "the device")
     rows = torch.empty((min(k, n),), dtype=torch.int32, device=device)
     if rows.numel() == 0:
         return rows
-    nbytes = lib().d3d_sample_rows_scratch_bytes(n)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=device) if k < n else None
-    with torch.cuda.device(device):
-        check(lib().d3d_sample_rows(n, k, seed & 0xFFFFFFFFFFFFFFFF, ptr(rows), ptr(scratch), nbytes, stream_of(device)))
+    buf, nbytes = scratch(device, "d3d_sample_rows_scratch_bytes", n) if k < n else (None, 0)
+    run(device, "d3d_sample_rows", n, k, seed & 0xFFFFFFFFFFFFFFFF, ptr(rows), ptr(buf), nbytes, stream_of(device))
     return rows
 
 
@@ -125,20 +90,13 @@ def cap_points(pcl, max_points=DEFAULT_MAX_POINTS, seed=0, return_rows=False):
 def downsample_kwargs(downsample):
     """The `downsample=` keyword of the loops: None -> None; a voxel size -> {'voxel': v}; a dict with keys among voxel,
     max_points, seed -> a checked copy (voxel None or absent: no voxel step; max_points None or absent: no cap)."""
-    if downsample is None:
+    if isinstance(downsample, (int, float)) and not isinstance(downsample, bool):
+        downsample = {"voxel": downsample}
+    kw = options(downsample, "downsample", ("voxel", "max_points", "seed"), "None, a voxel size")
+    if kw is None:
         return None
-    if isinstance(downsample, dict):
-        bad = sorted(set(downsample) - {"voxel", "max_points", "seed"})
-        if bad:
-            raise ValueError(f"downsample: unknown keywords {bad} (voxel, max_points, seed)")
-        kw = dict(downsample)
-    elif isinstance(downsample, (int, float)) and not isinstance(downsample, bool):
-        kw = {"voxel": downsample}
-    else:
-        raise ValueError(f"downsample must be None, a voxel size or a dict with keys among voxel, max_points, seed, "
-                         f"got {downsample!r}")
     if kw.get("voxel") is not None:
-        kw["voxel"] = _check_voxel(kw["voxel"])
+        kw["voxel"] = number(kw["voxel"], "voxel", lo_open=True)
     if kw.get("max_points") is not None:
         kw["max_points"] = int(kw["max_points"])
         if kw["max_points"] < 1:

@@ -16,10 +16,10 @@ import math
 import numpy as np
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
-from .downsample import _normal_col
+from ._cloud import PhaseTimer, gpu_rows, normal_column, number, options, run, scratch
+from ._lib import ptr, stream_of
+from .pose import apply_pose
 from .primitives import FIT_Q, _fit_tables, cloud_min
-from .register import apply_pose
 
 FRAME_CHUNK = 1024             # frame.hip kChunk: the rows a workgroup of the sweep stages at a time
 MAX_TILT = 60.0
@@ -80,14 +80,7 @@ def _device_tables(dev, max_tilt):
 
 def _check_args(max_tilt, tol, up):
     """-> (max_tilt, tol, B_0 as a row-major fp64 numpy [9] or None)"""
-    try:
-        max_tilt, tol = float(max_tilt), float(tol)
-    except (TypeError, ValueError):
-        raise ValueError(f"max_tilt {max_tilt!r} and tol {tol!r} must be numbers of degrees") from None
-    if not 0.0 <= max_tilt <= MAX_TILT:
-        raise ValueError(f"max_tilt {max_tilt} outside [0, {MAX_TILT:g}] degrees")
-    if not 0.0 < tol <= MAX_TOL:
-        raise ValueError(f"tol {tol} outside (0, {MAX_TOL:g}] degrees")
+    max_tilt, tol = number(max_tilt, "max_tilt", 0.0, MAX_TILT), number(tol, "tol", 0.0, MAX_TOL, lo_open=True)
     if up is None:
         return max_tilt, tol, None
     try:
@@ -106,13 +99,8 @@ def align_kwargs(align):
         return None
     if align is True or align == "manhattan":
         return dict(DEFAULTS)
-    if not isinstance(align, dict):
-        raise ValueError(f"align must be None, True, 'manhattan' or a dict with keys among max_tilt, tol, up, got {align!r}")
-    bad = sorted(set(align) - set(DEFAULTS))
-    if bad:
-        raise ValueError(f"align: unknown keywords {bad} (max_tilt, tol, up)")
     kw = dict(DEFAULTS)
-    kw.update(align)
+    kw.update(options(align, "align", tuple(DEFAULTS), "None, True, 'manhattan'"))
     _check_args(kw["max_tilt"], kw["tol"], kw["up"])
     return kw
 
@@ -182,16 +170,8 @@ def manhattan_frame(normals, max_tilt=30.0, tol=5.0, up=None, phases=False):
     current stream without a read-back; bad arguments raise ValueError before any GPU work.  phases: Frame.phases is a
     dict of milliseconds per pass, timed with events inside the library; synchronises."""
     max_tilt, tol, b0 = _check_args(max_tilt, tol, up)
-    if not isinstance(normals, torch.Tensor) or normals.dim() != 2 or normals.shape[1] != 3:
-        raise ValueError("normals must be a tensor [N, 3]")
-    if normals.dtype != torch.float32:
-        raise ValueError(f"normals must be float32, got {normals.dtype}")
-    if not normals.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % normals.device)
-    nrm, n, dev = normals.detach(), normals.shape[0], normals.device
-    if n > 1 and (nrm.stride(1) != 1 or nrm.stride(0) < 3):
-        nrm = nrm.contiguous()                # a transposed or broadcast view
-    stride = nrm.stride(0) if n > 1 else max(3, nrm.stride(0))
+    nrm, n, stride = gpu_rows(normals, "normals", exact=True)
+    dev = nrm.device
     steps = tilt_steps(max_tilt)
     s2 = (ctypes.c_float * 4)(*([_s2(max(tol, st)) for st in steps] + [_s2(tol)]))
     b0_c = None if b0 is None else (ctypes.c_double * 9)(*b0.tolist())
@@ -201,13 +181,11 @@ def manhattan_frame(normals, max_tilt=30.0, tol=5.0, up=None, phases=False):
     choice = torch.empty((5,), dtype=torch.int32, device=dev)
     score = torch.empty((5,), dtype=torch.int64, device=dev)
     support = torch.empty((2,), dtype=torch.int32, device=dev)
-    nbytes = lib().d3d_manhattan_frame_scratch_bytes()
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    ms = (ctypes.c_float * len(PHASES))() if phases else None
-    with torch.cuda.device(dev):
-        check(lib().d3d_manhattan_frame(ptr(nrm), n, stride, ptr(tables), b0_c, s2, ptr(coarse), ptr(fine), ptr(pose),
-                                        ptr(choice), ptr(score), ptr(support), ptr(scratch), nbytes, stream_of(dev), ms))
-    return Frame(pose, choice, score, support, dict(zip(PHASES, (float(v) for v in ms))) if phases else None)
+    buf, nbytes = scratch(dev, "d3d_manhattan_frame_scratch_bytes")
+    timer = PhaseTimer(PHASES, phases)
+    run(dev, "d3d_manhattan_frame", ptr(nrm), n, stride, ptr(tables), b0_c, s2, ptr(coarse), ptr(fine), ptr(pose),
+        ptr(choice), ptr(score), ptr(support), ptr(buf), nbytes, stream_of(dev), timer.ms)
+    return Frame(pose, choice, score, support, timer.read())
 
 
 def align_cloud(pcl, normal_col="auto", **kw):
@@ -216,7 +194,7 @@ def align_cloud(pcl, normal_col="auto", **kw):
     and normals rotated, no read-back."""
     if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2 or pcl.shape[1] < 3:
         raise ValueError("align_cloud: a tensor [N, >= 3]")
-    nc = _normal_col(normal_col, pcl.shape[1])
+    nc = normal_column(normal_col, pcl.shape[1])
     if nc < 0:
         raise ValueError(f"align_cloud: a cloud of {pcl.shape[1]} columns carries no normals; estimate them first "
                          "(normals.with_normals, or normals='estimate' in Preparation / BuildingPipeline)")

@@ -9,21 +9,19 @@ distance, index); fewer than 3 neighbours, or coincident ones, give (0, 0, 1); o
 smallest eigenvalue of the neighbours' covariance.  open3d leaves the sign arbitrary: here the component of largest
 magnitude is made positive (ties: the lowest axis), or, with orient=(vx, vy, vz), the normal faces that viewpoint.  The
 same input gives the same bits, whatever torch's deterministic mode says."""
-import ctypes
-
 import torch
 
-from ._lib import D3DError, check, floats, lib, ptr, stream_of
+from ._cloud import PhaseTimer, gpu_rows, number, options, run, scratch, whole
+from ._lib import floats, ptr, stream_of
 
 ESTIMATE = "estimate"
+PHASES = ("cells", "sort", "table", "search")
+_KEYS = ("radius", "max_nn", "orient")
 
 
-def _check_args(radius, max_nn, orient):
-    radius, max_nn = float(radius), int(max_nn)
-    if not (radius > 0.0 and radius < float("inf")):
-        raise ValueError(f"radius {radius} must be positive and finite")
-    if max_nn < 3:
-        raise ValueError(f"max_nn {max_nn} < 3: a normal needs three neighbours")
+def check_args(radius=0.1, max_nn=50, orient=None):
+    """-> (radius, max_nn, the viewpoint as a list or None); a normal needs three neighbours, so max_nn >= 3"""
+    radius, max_nn = number(radius, "radius", lo_open=True), whole(max_nn, "max_nn", 3, 2 ** 31 - 1)
     vp = None
     if orient is not None:
         vp = [float(v) for v in orient]
@@ -37,43 +35,32 @@ def estimate_normals(xyz, radius=0.1, max_nn=50, orient=None, return_counts=Fals
     cloud (`pcl[:, :3]`), which is read in place through its row stride.  -> normals fp32 [N, 3], and with return_counts
     the number of neighbours kept per point, int32 [N] (below 3: the normal is (0, 0, 1)).  Runs on the current stream,
     without a host read-back."""
-    radius, max_nn, vp = _check_args(radius, max_nn, orient)
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] < 3:
-        raise ValueError("xyz must be a tensor [N, >= 3]")
-    if not xyz.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % xyz.device)
-    if xyz.dtype != torch.float32:
-        raise ValueError(f"xyz must be float32, got {xyz.dtype}")
-    xyz = xyz.detach()
-    n = xyz.shape[0]
-    if n > 1 and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
-        xyz = xyz[:, :3].contiguous()        # a transposed or broadcast view: the three columns only
-    stride = xyz.stride(0) if n > 1 else max(3, xyz.stride(0))
-    dev = xyz.device
-    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    counts = torch.empty((n,), dtype=torch.int32, device=dev) if return_counts else None
-    if n > 0:
-        nbytes = lib().d3d_estimate_normals_scratch_bytes(n, max_nn)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(lib().d3d_estimate_normals(ptr(xyz), n, stride, radius, max_nn, floats(vp) if vp else None, ptr(normals),
-                                         ptr(counts), ptr(scratch), nbytes, stream_of(dev)))
+    normals, counts, _ = _estimate(xyz, radius, max_nn, orient, return_counts, False)
     return (normals, counts) if return_counts else normals
 
 
-def estimate_normals_phases(xyz, radius=0.1, max_nn=50):
-    """estimate_normals on a contiguous fp32 [N, 3] GPU tensor, timed with events inside the library: -> (normals, dict of
-    milliseconds for the cells, sort, table and search phases).  Synchronises; for measurements."""
-    radius, max_nn, _ = _check_args(radius, max_nn, None)
-    if not xyz.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % xyz.device)
-    n, dev = xyz.shape[0], xyz.device
+def _estimate(xyz, radius, max_nn, orient, return_counts, phases):
+    """-> (normals, counts or None, the dict of milliseconds or None); the untimed entry point of the library enqueues
+    and returns, the timed one synchronises"""
+    radius, max_nn, vp = check_args(radius, max_nn, orient)
+    xyz, n, stride = gpu_rows(xyz)
+    dev = xyz.device
     normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    nbytes = lib().d3d_estimate_normals_scratch_bytes(n, max_nn)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ms = (ctypes.c_float * 4)()
-    check(lib().d3d_estimate_normals_phases(ptr(xyz), n, xyz.stride(0), radius, max_nn, None, ptr(normals), None,
-                                            ptr(scratch), nbytes, stream_of(dev), ms))
-    return normals, dict(zip(("cells", "sort", "table", "search"), (float(v) for v in ms)))
+    counts = torch.empty((n,), dtype=torch.int32, device=dev) if return_counts else None
+    timer = PhaseTimer(PHASES, phases)
+    if n > 0:
+        buf, nbytes = scratch(dev, "d3d_estimate_normals_scratch_bytes", n, max_nn)
+        run(dev, "d3d_estimate_normals_phases" if phases else "d3d_estimate_normals", ptr(xyz), n, stride, radius,
+            max_nn, floats(vp) if vp else None, ptr(normals), ptr(counts), ptr(buf), nbytes, stream_of(dev),
+            *((timer.ms,) if phases else ()))
+    return normals, counts, timer.read()
+
+
+def estimate_normals_phases(xyz, radius=0.1, max_nn=50):
+    """estimate_normals timed with events inside the library: -> (normals, dict of milliseconds for the cells, sort,
+    table and search phases).  Synchronises; for measurements."""
+    normals, _, ms = _estimate(xyz, radius, max_nn, None, False, True)
+    return normals, ms
 
 
 def with_normals(pcl, radius=0.1, max_nn=50, orient=None, estimator=estimate_normals):
@@ -95,20 +82,12 @@ def with_normals(pcl, radius=0.1, max_nn=50, orient=None, estimator=estimate_nor
 def normals_kwargs(normals):
     """The `normals=` keyword of the loops: None -> None, 'estimate' -> {}, a dict of estimate_normals keywords ->
     a checked copy."""
-    if normals is None:
-        return None
-    if isinstance(normals, str):
-        if normals != ESTIMATE:
-            raise ValueError(f"normals must be None, 'estimate' or a dict of estimate_normals keywords, got {normals!r}")
+    if isinstance(normals, str) and normals == ESTIMATE:
         return {}
-    if isinstance(normals, dict):
-        bad = sorted(set(normals) - {"radius", "max_nn", "orient"})
-        if bad:
-            raise ValueError(f"normals: unknown keywords {bad} (radius, max_nn, orient)")
-        kw = dict(normals)
-        _check_args(kw.get("radius", 0.1), kw.get("max_nn", 50), kw.get("orient"))
-        return kw
-    raise ValueError(f"normals must be None, 'estimate' or a dict of estimate_normals keywords, got {normals!r}")
+    kw = options(normals, "normals", _KEYS, "None, 'estimate'")
+    if kw is not None:
+        check_args(**kw)
+    return kw
 
 
 def parse_estimate_normals(spec):

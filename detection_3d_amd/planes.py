@@ -15,8 +15,9 @@ import math
 
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
-from .clean import PHASES, _check_radius, _phases, _scratch, _xyz
+from ._cloud import PhaseTimer, gpu_cloud, gpu_rows, number, run, same_device, scratch, whole
+from ._lib import ptr, stream_of
+from .clean import PHASES
 from .config import class_to_label
 
 MAX_PLANES = 4096              # planes.hip kMaxPlanes = box_fit.hip kMaxBoxes
@@ -25,35 +26,9 @@ FIT_PHASES = ("moments", "solve")
 Planes = collections.namedtuple("Planes", "plane_of_point normal d centroid count rms eigenvalues")
 
 
-def _number(value, what):
-    try:
-        return float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} {value!r} must be a number") from None
-
-
-def _check_angle(angle, what="angle"):
-    angle = _number(angle, what)
-    if not 0.0 <= angle <= 90.0:
-        raise ValueError(f"{what} {angle} must lie in [0, 90] degrees")
-    return angle
-
-
-def _check_offset(offset):
-    offset = _number(offset, "offset")
-    if not (offset >= 0.0 and math.isfinite(offset)):
-        raise ValueError(f"offset {offset} must be finite and not negative")
-    return offset
-
-
-def _check_min_points(min_points):
-    try:
-        ok = not isinstance(min_points, bool) and int(min_points) == min_points and int(min_points) >= 1
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"min_points {min_points!r} must be an integer >= 1")
-    return int(min_points)
+def _check_join(radius, angle, offset):
+    """segment_planes' three thresholds: metres, degrees in [0, 90], metres"""
+    return number(radius, "radius", lo_open=True), number(angle, "angle", 0.0, 90.0), number(offset, "offset")
 
 
 def cos_min(angle):
@@ -68,29 +43,20 @@ def segment_planes(xyz, normals, radius=0.1, angle=10.0, offset=0.02, phases=Fal
     max(|nP . d|, |nC . d|) <= offset (the exact arithmetic: include/d3d_hip.h, d3d_segment_planes).  A zero or non-finite
     normal and a NaN position leave the point a patch of its own.  Current stream, no read-back.  phases: also a dict of
     milliseconds (clean.PHASES); synchronises."""
-    radius = _check_radius(radius)
-    angle = _check_angle(angle)
-    offset = _check_offset(offset)
-    xyz, n, stride = _xyz(xyz)
-    if not isinstance(normals, torch.Tensor) or normals.dim() != 2 or normals.shape != (n, 3):
-        raise ValueError(f"normals must be a tensor [{n}, 3]")
-    if not normals.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % normals.device)
-    if normals.dtype != torch.float32:
-        raise ValueError(f"normals must be float32, got {normals.dtype}")
-    if normals.device != xyz.device:
-        raise ValueError(f"xyz is on {xyz.device}, normals on {normals.device}")
-    normals = normals.detach().contiguous()
-    dev = xyz.device
+    radius, angle, offset = _check_join(radius, angle, offset)
+    xyz, n, stride = gpu_rows(xyz)
+    normals = gpu_cloud(normals, "normals", exact=True).contiguous()       # d3d_segment_planes takes no stride for them
+    if normals.shape[0] != n:
+        raise ValueError(f"normals hold {normals.shape[0]} rows, xyz {n}")
+    dev = same_device(xyz=xyz, normals=normals)
     label = torch.empty((n,), dtype=torch.int32, device=dev)
     size = torch.empty((n,), dtype=torch.int32, device=dev)
-    ms = (ctypes.c_float * len(PHASES))() if phases else None
+    timer = PhaseTimer(PHASES, phases)
     if n > 0:
-        nbytes = lib().d3d_segment_planes_scratch_bytes(n)
-        scratch = _scratch(nbytes, dev)
-        check(lib().d3d_segment_planes(ptr(xyz), n, stride, ptr(normals), radius, cos_min(angle), offset, ptr(label),
-                                       ptr(size), ptr(scratch), nbytes, stream_of(dev), ms))
-    return (label, size, _phases(ms)) if phases else (label, size)
+        buf, nbytes = scratch(dev, "d3d_segment_planes_scratch_bytes", n)
+        run(dev, "d3d_segment_planes", ptr(xyz), n, stride, ptr(normals), radius, cos_min(angle), offset, ptr(label),
+            ptr(size), ptr(buf), nbytes, stream_of(dev), timer.ms)
+    return (label, size, timer.read()) if phases else (label, size)
 
 
 def _plane_lists(label, size, min_points):
@@ -124,14 +90,12 @@ def fit_planes(xyz, label, size, min_points=100, phases=False):
     d3d_fit_planes).  A patch of coincident points: normal, d and rms 0.  When more than 4096 patches reach min_points
     the 4096 largest stay (ties to the lower label).  One size read-back, for K.  phases: also a dict of milliseconds
     (FIT_PHASES); synchronises."""
-    min_points = _check_min_points(min_points)
-    xyz, n, stride = _xyz(xyz)
-    dev = xyz.device
+    min_points = whole(min_points, "min_points")
+    xyz, n, stride = gpu_rows(xyz)
     for t, what in ((label, "label"), (size, "size")):
         if not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != torch.int32:
             raise ValueError(f"{what} must be an int32 tensor [{n}]")
-        if t.device != dev:
-            raise ValueError(f"xyz is on {dev}, {what} on {t.device}")
+    dev = same_device(xyz=xyz, label=label, size=size)
     pop, order, offsets, k = _plane_lists(label, size, min_points)
     normal = torch.empty((k, 3), dtype=torch.float64, device=dev)
     d = torch.empty((k,), dtype=torch.float64, device=dev)
@@ -139,14 +103,13 @@ def fit_planes(xyz, label, size, min_points=100, phases=False):
     count = torch.empty((k,), dtype=torch.int32, device=dev)
     rms = torch.empty((k,), dtype=torch.float64, device=dev)
     eig = torch.empty((k, 3), dtype=torch.float64, device=dev)
-    ms = (ctypes.c_float * len(FIT_PHASES))() if phases else None
+    timer = PhaseTimer(FIT_PHASES, phases)
     if k > 0:
-        nbytes = lib().d3d_fit_planes_scratch_bytes(n, k)
-        scratch = _scratch(nbytes, dev)
-        check(lib().d3d_fit_planes(ptr(xyz), n, stride, ptr(pop), ptr(order), ptr(offsets), k, ptr(normal), ptr(d),
-                                   ptr(centroid), ptr(count), ptr(rms), ptr(eig), ptr(scratch), nbytes, stream_of(dev), ms))
+        buf, nbytes = scratch(dev, "d3d_fit_planes_scratch_bytes", n, k)
+        run(dev, "d3d_fit_planes", ptr(xyz), n, stride, ptr(pop), ptr(order), ptr(offsets), k, ptr(normal), ptr(d),
+            ptr(centroid), ptr(count), ptr(rms), ptr(eig), ptr(buf), nbytes, stream_of(dev), timer.ms)
     res = Planes(pop, normal, d, centroid, count, rms, eig)
-    return (res, dict(zip(FIT_PHASES, (float(v) for v in ms)))) if phases else res
+    return (res, timer.read()) if phases else res
 
 
 def label_planes(pcl, normals=None, radius=0.1, angle=10.0, offset=0.02, min_points=100, tilt=10.0, classes=None):
@@ -157,7 +120,7 @@ def label_planes(pcl, normals=None, radius=0.1, angle=10.0, offset=0.02, min_poi
     |n_z| >= cos(tilt) is horizontal, floor when the centroid's z lies below the middle of the cloud's z range and
     ceiling otherwise; |n_z| <= sin(tilt) is wall; anything else gets label 0, which targets_from_labels drops.
     classes: the config's class list (default: background, wall, ceiling, floor); a class it does not hold gets 0."""
-    tilt = _check_angle(tilt, "tilt")
+    tilt = number(tilt, "tilt", 0.0, 90.0)
     if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2 or pcl.shape[1] < 3:
         raise ValueError("pcl must be a tensor [N, >= 3]")
     if normals is None:
@@ -201,8 +164,6 @@ def parse_planes(spec):
             kw[name] = int(value) if name == "min_points" else float(value)
         except ValueError:
             raise ValueError(f"--planes: bad value {value!r} for {name}") from None
-    kw["radius"] = _check_radius(kw["radius"])
-    kw["angle"] = _check_angle(kw["angle"])
-    kw["offset"] = _check_offset(kw["offset"])
-    kw["min_points"] = _check_min_points(kw["min_points"])
+    kw["radius"], kw["angle"], kw["offset"] = _check_join(kw["radius"], kw["angle"], kw["offset"])
+    kw["min_points"] = whole(kw["min_points"], "min_points")
     return kw

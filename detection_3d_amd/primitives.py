@@ -18,7 +18,8 @@ import math
 import numpy as np
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
+from ._cloud import fp32_cloud, gpu_cloud, gpu_rows, need_gpu, options, run, same_device, scratch, whole
+from ._lib import ptr, stream_of
 from .config import class_to_label
 from .scene_io import _ZERO_YAW_CLASSES
 
@@ -32,14 +33,19 @@ FIT_CHUNK = 1024               # box_fit.hip kChunk: the sorted rows one workgro
 FIT_Q = math.pi / 65536        # fit_boxes' fine step of yaw
 
 
-def _grow(grow):
+def _sizes(values, what, names):
+    """-> a list of len(names) finite floats >= 0"""
     try:
-        g = [float(v) for v in grow]
+        v = [float(x) for x in values]
     except TypeError:
-        raise ValueError(f"grow must be (grow_yx, grow_z), got {grow!r}") from None
-    if len(g) != 2 or not all(0.0 <= v < float("inf") for v in g):
-        raise ValueError(f"grow must be two finite values >= 0 (grow_yx, grow_z), got {grow!r}")
-    return g
+        raise ValueError(f"{what} must be ({', '.join(names)}), got {values!r}") from None
+    if len(v) != len(names) or not all(0.0 <= x < float("inf") for x in v):
+        raise ValueError(f"{what} must be {len(names)} finite values >= 0 ({', '.join(names)}), got {values!r}")
+    return v
+
+
+def _grow(grow):
+    return _sizes(grow, "grow", ("grow_yx", "grow_z"))
 
 
 def cloud_min(xyz):
@@ -76,32 +82,24 @@ def points_in_boxes(xyz, boxes, grow=(0.0, 0.0), origin=None):
     Membership is closed on every face and a NaN point belongs to nothing.  Runs on the current stream without a host
     read-back; the same input gives the same bits."""
     g = _grow(grow)
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] < 3:
-        raise ValueError("xyz must be a tensor [N, >= 3]")
-    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 7:
-        raise ValueError("boxes must be a tensor [K, 7] (yx_zb)")
-    for t in (xyz, boxes):
-        if not t.is_cuda:
-            raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % t.device)
-    if xyz.dtype != torch.float32 or boxes.dtype != torch.float32:
-        raise ValueError(f"xyz and boxes must be float32, got {xyz.dtype} and {boxes.dtype}")
-    if boxes.device != xyz.device:
-        raise ValueError(f"xyz is on {xyz.device}, boxes on {boxes.device}")
-    n, k = xyz.shape[0], boxes.shape[0]
+    fp32_cloud(xyz)
+    if (not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 7 or
+            boxes.dtype != torch.float32):
+        raise ValueError("boxes must be a float32 tensor [K, 7] (yx_zb)")
+    k = boxes.shape[0]
     if k > MAX_BOXES:
         raise ValueError(f"{k} boxes: at most {MAX_BOXES} in one call")
-    xyz, boxes = xyz.detach(), boxes.detach().contiguous()
+    xyz, n, stride = gpu_rows(xyz)
+    need_gpu(boxes.device)
+    dev = same_device(xyz=xyz, boxes=boxes)
+    boxes = boxes.detach().contiguous()
     o = _origin(origin, xyz)
-    if n > 1 and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
-        xyz = xyz[:, :3].contiguous()        # a transposed or broadcast view: the three columns only
-    stride = xyz.stride(0) if n > 1 else max(3, xyz.stride(0))
-    dev = xyz.device
     owner = torch.empty((n,), dtype=torch.int32, device=dev)
     count = torch.empty((k,), dtype=torch.int32, device=dev)
     lo = torch.empty((k, 3), dtype=torch.float32, device=dev)
     hi = torch.empty((k, 3), dtype=torch.float32, device=dev)
-    check(lib().d3d_points_in_boxes(ptr(xyz), n, stride, ptr(o), ptr(boxes), k, g[0], g[1], ptr(owner), ptr(count),
-                                    ptr(lo), ptr(hi), stream_of(dev)))
+    run(dev, "d3d_points_in_boxes", ptr(xyz), n, stride, ptr(o), ptr(boxes), k, g[0], g[1], ptr(owner), ptr(count),
+        ptr(lo), ptr(hi), stream_of(dev))
     return owner, count, lo, hi
 
 
@@ -135,10 +133,8 @@ def _fit_lists(xyz, inst, k, o):
 def _fit_call(xyz, o, order, srt, offsets, k, yaw_free, phase_ms=None):
     """d3d_fit_boxes on the lists of _fit_lists -> boxes, count, choice, extent; phase_ms: a ctypes float [2] that takes
     the milliseconds of the two passes (the call then synchronises)"""
-    n, dev = xyz.shape[0], xyz.device
-    if n > 1 and (xyz.stride(1) != 1 or xyz.stride(0) < 3):
-        xyz = xyz[:, :3].contiguous()
-    stride = xyz.stride(0) if n > 1 else max(3, xyz.stride(0))
+    xyz, n, stride = gpu_rows(xyz)
+    dev = xyz.device
     free = None if yaw_free is None else yaw_free.to(dev).to(torch.uint8).contiguous()
     boxes = torch.empty((k, 7), dtype=torch.float32, device=dev)
     count = torch.empty((k,), dtype=torch.int32, device=dev)
@@ -146,11 +142,10 @@ def _fit_call(xyz, o, order, srt, offsets, k, yaw_free, phase_ms=None):
     extent = torch.empty((k, 6), dtype=torch.float32, device=dev)
     if k > 0:
         coarse, fine = _fit_tables(dev)
-        nbytes = lib().d3d_fit_boxes_scratch_bytes(k)
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        check(lib().d3d_fit_boxes(ptr(xyz), n, stride, ptr(o), ptr(order), ptr(srt), ptr(offsets), k, ptr(free),
-                                  ptr(coarse), ptr(fine), ptr(boxes), ptr(count), ptr(choice), ptr(extent), ptr(scratch),
-                                  nbytes, stream_of(dev), phase_ms))
+        buf, nbytes = scratch(dev, "d3d_fit_boxes_scratch_bytes", k)
+        run(dev, "d3d_fit_boxes", ptr(xyz), n, stride, ptr(o), ptr(order), ptr(srt), ptr(offsets), k, ptr(free),
+            ptr(coarse), ptr(fine), ptr(boxes), ptr(count), ptr(choice), ptr(extent), ptr(buf), nbytes, stream_of(dev),
+            phase_ms)
     return boxes, count, choice, extent
 
 
@@ -169,9 +164,7 @@ def fit_boxes(xyz, instance, k=None, yaw_free=None, origin=None, return_details=
     fp32 [k, 6] (umin, umax, vmin, vmax, zmin, zmax of the chosen direction).  An instance without points: a zero row,
     count 0, choice (-1, -1), extents +inf / -inf.  Only min, max and integer arithmetic: the bits depend on the set of
     points alone, not on the order of the rows.  Runs on the current stream."""
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] < 3:
-        raise ValueError("xyz must be a tensor [N, >= 3]")
-    n = xyz.shape[0]
+    n = fp32_cloud(xyz).shape[0]
     if (not isinstance(instance, torch.Tensor) or instance.dim() != 1 or instance.dtype.is_floating_point or
             instance.dtype.is_complex or instance.dtype == torch.bool):
         raise ValueError("instance must be an integer tensor [N]")
@@ -187,18 +180,13 @@ def fit_boxes(xyz, instance, k=None, yaw_free=None, origin=None, return_details=
         yaw_free = torch.as_tensor(yaw_free)
         if yaw_free.dtype != torch.bool or yaw_free.dim() != 1 or (k is not None and yaw_free.shape[0] != k):
             raise ValueError(f"yaw_free must be a bool tensor [k], got {yaw_free.dtype} {tuple(yaw_free.shape)}")
-    if xyz.dtype != torch.float32:
-        raise ValueError(f"xyz must be float32, got {xyz.dtype}")
     if isinstance(origin, str) and origin != "min":
         raise ValueError(f"origin must be None, a 3-vector or 'min', got {origin!r}")
     o = origin if origin is None or isinstance(origin, str) else _origin(origin, torch.empty(0))
-    for t in (xyz, instance):
-        if not t.is_cuda:
-            raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % t.device)
-    if instance.device != xyz.device:
-        raise ValueError(f"xyz is on {xyz.device}, instance on {instance.device}")
-    xyz, inst = xyz.detach(), instance.detach().to(torch.int64)
-    dev = xyz.device
+    xyz = gpu_cloud(xyz)                     # _fit_call reads it in place; the lists above it take the view as it is
+    need_gpu(instance.device)
+    dev = same_device(xyz=xyz, instance=instance)
+    inst = instance.detach().to(torch.int64)
     if k is None:
         k = max(int(inst.max()) + 1, 0) if n else 0
         if k > MAX_BOXES:
@@ -212,30 +200,15 @@ def fit_boxes(xyz, instance, k=None, yaw_free=None, origin=None, return_details=
 
 
 def _min_size(min_size):
-    try:
-        m = [float(v) for v in min_size]
-    except TypeError:
-        raise ValueError(f"min_size must be (d3, d4, dz) in metres, got {min_size!r}") from None
-    if len(m) != 3 or not all(0.0 <= v < float("inf") for v in m):
-        raise ValueError(f"min_size must be three finite values >= 0 (d3, d4, dz), got {min_size!r}")
-    return m
+    return _sizes(min_size, "min_size", ("d3", "d4", "dz"))
 
 
 def fit_kwargs(fit):
     """The `fit=` keyword of the loops: None -> targets_from_labels' defaults; a dict with keys among min_points,
     min_size -> a checked copy."""
     kw = {"min_points": MIN_POINTS_ANY, "min_size": (0.0, 0.0, 0.0)}
-    if fit is None:
-        return kw
-    if not isinstance(fit, dict):
-        raise ValueError(f"fit must be None or a dict with keys among min_points, min_size, got {fit!r}")
-    bad = sorted(set(fit) - set(kw))
-    if bad:
-        raise ValueError(f"fit: unknown keywords {bad} (min_points, min_size)")
-    kw.update(fit)
-    kw["min_points"] = int(kw["min_points"])
-    if kw["min_points"] < 0:
-        raise ValueError(f"fit: min_points {kw['min_points']} < 0")
+    kw.update(options(fit, "fit", tuple(kw)) or {})
+    kw["min_points"] = whole(kw["min_points"], "fit: min_points", 0)
     kw["min_size"] = tuple(_min_size(kw["min_size"]))
     return kw
 
@@ -256,9 +229,7 @@ def targets_from_labels(pcl, instance, instance_labels, min_points=MIN_POINTS_AN
     thickness of its own).
     -> {"bbox3d" fp32 [M, 7] yx_zb, "labels" int64 [M]} on the cloud's device and in the cloud's own frame."""
     ms = _min_size(min_size)
-    min_points = int(min_points)
-    if min_points < 0:
-        raise ValueError(f"min_points {min_points} < 0")
+    min_points = whole(min_points, "min_points", 0)
     labels = torch.as_tensor(instance_labels)
     if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
         raise ValueError("instance_labels must be an integer tensor [K]")
@@ -381,8 +352,7 @@ def crop_scene(pcl, targets, window, grow=(THICKNESS_AUG, THICKNESS_AUG)):
     x0, y0, x1, y1 = (float(v) for v in window)
     if not (x0 < x1 and y0 < y1):
         raise ValueError(f"window {window!r}: (xmin, ymin, xmax, ymax) with min < max")
-    if not pcl.is_cuda:
-        raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % pcl.device)
+    need_gpu(pcl.device)
     x, y = pcl[:, 0], pcl[:, 1]
     pcl = pcl[(x >= x0) & (x < x1) & (y >= y0) & (y < y1)]
     bx, lb = targets["bbox3d"], targets["labels"]

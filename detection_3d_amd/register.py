@@ -18,12 +18,17 @@ import ctypes
 import math
 import warnings
 
+import numpy as np
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
-from .clean import _as_int, _check_radius, _scratch, _xyz
+from ._cloud import PhaseTimer, fp32_cloud, gpu_rows, number, options, run, same_device, scratch, whole
+from ._lib import GlobalAlignDetails, ints, ptr, stream_of
 from .clean import PHASES as NEAREST_PHASES
-from .downsample import _normal_col
+from .downsample import apply_downsample, downsample_kwargs
+from .frame import align_cloud, align_kwargs
+from .normals import check_args as check_normals_args, estimate_normals
+from .pose import apply_pose, check_pose, inverse_pose          # noqa: F401  (apply_pose, inverse_pose: public here)
+from .primitives import cloud_min
 
 ICP_PHASES = ("cells", "sort", "table", "transform", "nearest", "accumulate", "solve")
 METHODS = {"plane": 0, "point": 1}
@@ -39,70 +44,19 @@ def nearest(query_xyz, cloud_xyz, radius=0.1, return_dist2=False, phases=False):
     -1 when there is none or the query is not finite; with return_dist2 also that squared distance, fp32 [M], +inf for
     none.  Current stream, no read-back.  phases: also a dict of milliseconds (cells, sort, table, search, tail), timed
     with events inside the library; synchronises."""
-    radius = _check_radius(radius)
-    query, m, qstride = _xyz(query_xyz)
-    cloud, n, cstride = _xyz(cloud_xyz)
-    if query.device != cloud.device:
-        raise ValueError(f"nearest: query on {query.device}, cloud on {cloud.device}")
-    dev = query.device
+    radius = number(radius, "radius", lo_open=True)
+    query, m, qstride = gpu_rows(query_xyz, "query_xyz")
+    cloud, n, cstride = gpu_rows(cloud_xyz, "cloud_xyz")
+    dev = same_device(query_xyz=query, cloud_xyz=cloud)
     index = torch.empty((m,), dtype=torch.int32, device=dev)
     dist2 = torch.empty((m,), dtype=torch.float32, device=dev) if return_dist2 else None
-    ms = (ctypes.c_float * len(NEAREST_PHASES))() if phases else None
+    timer = PhaseTimer(NEAREST_PHASES, phases)
     if m > 0:
-        nbytes = lib().d3d_nearest_scratch_bytes(n, m)
-        scratch = _scratch(nbytes, dev)
-        with torch.cuda.device(dev):
-            check(lib().d3d_nearest(ptr(cloud), n, cstride, ptr(query), m, qstride, radius, ptr(index), ptr(dist2),
-                                    ptr(scratch), nbytes, stream_of(dev), ms))
-    res = (index,) + ((dist2,) if return_dist2 else ())
-    if phases:
-        res += (dict(zip(NEAREST_PHASES, (float(v) for v in ms))),)
+        buf, nbytes = scratch(dev, "d3d_nearest_scratch_bytes", n, m)
+        run(dev, "d3d_nearest", ptr(cloud), n, cstride, ptr(query), m, qstride, radius, ptr(index), ptr(dist2), ptr(buf),
+            nbytes, stream_of(dev), timer.ms)
+    res = (index,) + ((dist2,) if return_dist2 else ()) + ((timer.read(),) if phases else ())
     return res[0] if len(res) == 1 else res
-
-
-def _check_pose(pose, what):
-    """-> fp64 [4, 4] on the CPU, finite, last row (0, 0, 0, 1)"""
-    try:
-        p = torch.as_tensor(pose).detach().to("cpu", torch.float64)
-    except (TypeError, ValueError, RuntimeError):
-        raise ValueError(f"{what}: a 4 x 4 matrix, got {pose!r}")
-    if p.shape != (4, 4):
-        raise ValueError(f"{what}: a 4 x 4 matrix, got shape {tuple(p.shape)}")
-    if not bool(torch.isfinite(p).all()):
-        raise ValueError(f"{what}: entries must be finite")
-    if p[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
-        raise ValueError(f"{what}: the last row must be (0, 0, 0, 1), got {p[3].tolist()}")
-    return p
-
-
-def apply_pose(pcl, pose, normal_col="auto"):
-    """pcl [N, C >= 3], columns 0:3 the position; pose 4 x 4, x' = R x + t -> a copy of the cloud with the position moved
-    and the normal columns rotated (normal_col as voxel_downsample takes it: 'auto' is 6 when C == 9, else none).  fp64
-    arithmetic, one rounding to the cloud's type.  Plain torch: it also runs on CPU tensors."""
-    if not isinstance(pcl, torch.Tensor) or pcl.dim() != 2 or pcl.shape[1] < 3:
-        raise ValueError("apply_pose: a tensor [N, >= 3]")
-    if not pcl.dtype.is_floating_point:
-        raise ValueError(f"apply_pose: a floating-point cloud, got {pcl.dtype}")
-    if isinstance(pose, torch.Tensor) and pose.is_cuda and pose.shape == (4, 4):
-        T = pose.detach().to(pcl.device, torch.float64)          # a registration's pose: no read-back
-    else:
-        T = _check_pose(pose, "apply_pose: pose").to(pcl.device)
-    nc = _normal_col(normal_col, pcl.shape[1])
-    R, t = T[:3, :3], T[:3, 3]
-    out = pcl.detach().clone()
-    out[:, :3] = (pcl[:, :3].to(torch.float64) @ R.T + t).to(pcl.dtype)
-    if nc >= 0:
-        out[:, nc:nc + 3] = (pcl[:, nc:nc + 3].to(torch.float64) @ R.T).to(pcl.dtype)
-    return out
-
-
-def inverse_pose(pose):
-    """the inverse of a rigid pose [R t; 0 1]: [R^T, -R^T t; 0 1], fp64, on the pose's device"""
-    T = pose.detach().to(torch.float64) if isinstance(pose, torch.Tensor) else _check_pose(pose, "inverse_pose")
-    out = torch.eye(4, dtype=torch.float64, device=T.device)
-    out[:3, :3] = T[:3, :3].T
-    out[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
-    return out
 
 
 class Registration:
@@ -155,19 +109,12 @@ class Registration:
 
 
 def _check_icp(max_dist, iterations, tol, method, init):
-    max_dist = _check_radius(max_dist)
-    iterations = _as_int(iterations, "iterations")
-    if iterations > MAX_ITERATIONS:
-        raise ValueError(f"iterations {iterations} > {MAX_ITERATIONS}")
-    try:
-        tol = float(tol)
-    except (TypeError, ValueError):
-        raise ValueError(f"tol {tol!r} must be a number")
-    if not (tol >= 0.0 and math.isfinite(tol)):
-        raise ValueError(f"tol {tol} must be finite and not negative")
+    max_dist = number(max_dist, "max_dist", lo_open=True)
+    iterations = whole(iterations, "iterations", 1, MAX_ITERATIONS)
+    tol = number(tol, "tol")
     if method not in METHODS:
         raise ValueError(f"method {method!r}: 'plane' or 'point'")
-    pose = torch.eye(4, dtype=torch.float64) if init is None else _check_pose(init, "init")
+    pose = torch.eye(4, dtype=torch.float64) if init is None else check_pose(init, "init")
     return max_dist, iterations, tol, method, pose
 
 
@@ -181,41 +128,32 @@ def icp(source, target, target_normals=None, init=None, max_dist=0.1, iterations
     the current stream at once and nothing is read back.  Bad arguments raise ValueError before any GPU work."""
     max_dist, iterations, tol, method, pose = _check_icp(max_dist, iterations, tol, method, init)
     if method == "plane" and target_normals is None:
-        from .normals import _check_args
-        _check_args(normal_radius, max_nn, None)
-    if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[1] < 3:
-        raise ValueError("xyz must be a tensor [N, >= 3]")
-    own_normals = method == "plane" and target_normals is None and target.shape[1] == 9
-    src, m, sstride = _xyz(source)
-    tgt, n, tstride = _xyz(target)
-    if src.device != tgt.device:
-        raise ValueError(f"icp: source on {src.device}, target on {tgt.device}")
-    dev = src.device
+        check_normals_args(normal_radius, max_nn)
+    fp32_cloud(target, "target")             # its faults come before the first word about the source's device
+    src, m, sstride = gpu_rows(source, "source")
+    tgt, n, tstride = gpu_rows(target, "target")
+    dev = same_device(source=src, target=tgt)
     nrm, nstride = None, 3
     if method == "plane":
         if target_normals is not None:
-            nrm, nn, nstride = _xyz(target_normals)
+            nrm, nn, nstride = gpu_rows(target_normals, "target_normals")
             if nn != n or nrm.device != dev:
                 raise ValueError(f"icp: target_normals [{nn}, ..] on {nrm.device} for a target of {n} rows on {dev}")
-        elif own_normals:
-            nrm, _, nstride = _xyz(target[:, 6:9])
+        elif target.shape[1] == 9:
+            nrm, _, nstride = gpu_rows(target[:, 6:9], "target")
         else:
-            from .normals import estimate_normals
             nrm = estimate_normals(tgt, normal_radius, max_nn)
     pose = pose.to(dev)
     state = torch.zeros((2,), dtype=torch.int32, device=dev)
     history = torch.full((iterations, HISTORY_COLS), float("nan"), dtype=torch.float64, device=dev)
     last_index = torch.full((m,), -1, dtype=torch.int32, device=dev) if return_details else None
     last_system = torch.zeros((SYSTEM_SIZE,), dtype=torch.float64, device=dev) if return_details else None
-    ms = (ctypes.c_float * len(ICP_PHASES))() if phases else None
-    nbytes = lib().d3d_icp_scratch_bytes(n, m)
-    scratch = _scratch(nbytes, dev)
-    with torch.cuda.device(dev):
-        check(lib().d3d_icp(ptr(src), m, sstride, ptr(tgt), n, tstride, ptr(nrm), nstride, max_dist, METHODS[method],
-                            iterations, tol, ptr(pose), ptr(history), ptr(state), ptr(last_index), ptr(last_system),
-                            ptr(scratch), nbytes, stream_of(dev), ms))
-    return Registration(pose, state, history, last_index, last_system,
-                        dict(zip(ICP_PHASES, (float(v) for v in ms))) if phases else None)
+    timer = PhaseTimer(ICP_PHASES, phases)
+    buf, nbytes = scratch(dev, "d3d_icp_scratch_bytes", n, m)
+    run(dev, "d3d_icp", ptr(src), m, sstride, ptr(tgt), n, tstride, ptr(nrm), nstride, max_dist, METHODS[method],
+        iterations, tol, ptr(pose), ptr(history), ptr(state), ptr(last_index), ptr(last_system), ptr(buf), nbytes,
+        stream_of(dev), timer.ms)
+    return Registration(pose, state, history, last_index, last_system, timer.read())
 
 
 GLOBAL_PHASES = ("rows", "cells", "correlate", "peaks", "verify", "pick")
@@ -226,43 +164,24 @@ MAX_TOL = 20.0
 MARGIN_MAX = 0.98     # merge_scans: a runner-up this close to the best is taken for an ambiguous building
 
 
-def _whole(value, lo, hi, what):
-    try:
-        ok = not isinstance(value, bool) and int(value) == value and lo <= int(value) <= hi
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} {value!r} must be an integer in [{lo}, {hi}]")
-    return int(value)
-
-
 def _check_global(bin, lattice, tol, peaks, sep, frame):
     """-> (bin, (L, L, Lz), c2, peaks, sep, manhattan_frame's keywords)"""
-    from .frame import align_kwargs
-    try:
-        bin, tol = float(bin), float(tol)
-    except (TypeError, ValueError):
-        raise ValueError(f"bin {bin!r} and tol {tol!r} must be numbers") from None
-    if not (bin > 0.0 and bin <= 1e6):
-        raise ValueError(f"bin {bin} must be positive and finite")
-    if not 0.0 < tol <= MAX_TOL:
-        raise ValueError(f"tol {tol} outside (0, {MAX_TOL:g}] degrees")
+    bin, tol = number(bin, "bin", 0.0, 1e6, lo_open=True), number(tol, "tol", 0.0, MAX_TOL, lo_open=True)
     try:
         lattice = tuple(lattice)
     except TypeError:
         raise ValueError(f"lattice {lattice!r} must be (Lx, Ly, Lz)") from None
     if len(lattice) != 3:
         raise ValueError(f"lattice {lattice!r} must be (Lx, Ly, Lz)")
-    lattice = (_whole(lattice[0], 32, MAX_LATTICE, "lattice: Lx"), _whole(lattice[1], 32, MAX_LATTICE, "lattice: Ly"),
-               _whole(lattice[2], 1, MAX_LATTICE, "lattice: Lz"))
+    lattice = (whole(lattice[0], "lattice: Lx", 32, MAX_LATTICE), whole(lattice[1], "lattice: Ly", 32, MAX_LATTICE),
+               whole(lattice[2], "lattice: Lz", 1, MAX_LATTICE))
     if lattice[0] != lattice[1] or lattice[0] % 32:
         raise ValueError(f"lattice {lattice}: Lx == Ly, a multiple of 32")
-    peaks = _whole(peaks, 1, MAX_PEAKS, "peaks")
-    sep = _whole(sep, 0, MAX_SEP, "sep")
+    peaks = whole(peaks, "peaks", 1, MAX_PEAKS)
+    sep = whole(sep, "sep", 0, MAX_SEP)
     frame_kw = align_kwargs(True if frame is None else frame)
     if frame_kw is None:
         raise ValueError(f"frame {frame!r}: a dict of manhattan_frame's keywords (max_tilt, tol, up)")
-    import numpy as np
     c2 = float(np.float32(math.cos(math.radians(tol)) ** 2))
     return bin, lattice, c2, peaks, sep, frame_kw
 
@@ -317,15 +236,14 @@ class Alignment:
 
 def _with_normals(cloud, normals, normal_radius, max_nn, what):
     """-> fp32 [N, 6]: position and normal of every row, the normals resolved as icp resolves its target's"""
-    xyz, n, _ = _xyz(cloud)
+    xyz, n, _ = gpu_rows(cloud, what)
     if normals is not None:
-        nrm, nn, _ = _xyz(normals)
+        nrm, nn, _ = gpu_rows(normals, f"{what}_normals")
         if nn != n or nrm.device != xyz.device:
             raise ValueError(f"global_align: {what}_normals [{nn}, ..] on {nrm.device} for {n} rows on {xyz.device}")
     elif cloud.shape[1] == 9:
         nrm = cloud.detach()[:, 6:9]
     else:
-        from .normals import estimate_normals
         nrm = estimate_normals(xyz, normal_radius, max_nn)
     return torch.cat([xyz[:, :3], nrm[:, :3]], 1)
 
@@ -336,12 +254,11 @@ def lattice_align(source, source_normals, source_origin, target, target_normals,
     positions and normals on the GPU (column slices are read in place), and per cloud an origin, fp64 [3] on the device
     (primitives.cloud_min) -> Alignment whose pose is the one between the two levelled frames.  Current stream, no
     read-back."""
-    from ._lib import GlobalAlignDetails, ints
     bin, lattice, c2, peaks, sep, _ = _check_global(bin, lattice, tol, peaks, sep, None)
-    src, m, sstride = _xyz(source)
-    snrm, sm, snstride = _xyz(source_normals)
-    tgt, n, tstride = _xyz(target)
-    tnrm, tn, tnstride = _xyz(target_normals)
+    src, m, sstride = gpu_rows(source, "source")
+    snrm, sm, snstride = gpu_rows(source_normals, "source_normals")
+    tgt, n, tstride = gpu_rows(target, "target")
+    tnrm, tn, tnstride = gpu_rows(target_normals, "target_normals")
     dev = src.device
     if sm != m or tn != n or any(t.device != dev for t in (snrm, tgt, tnrm)):
         raise ValueError(f"lattice_align: {m} / {sm} source and {n} / {tn} target rows and normals, on one device")
@@ -365,16 +282,12 @@ def lattice_align(source, source_normals, source_origin, target, target_normals,
                    "peak_shift": torch.empty((9, K), **i32), "scores": torch.empty((4, K, K), **i32)}
         det = GlobalAlignDetails(*(ptr(details[k]) for k, _ in GlobalAlignDetails._fields_))
     lat = ints(lattice)
-    nbytes = lib().d3d_global_align_scratch_bytes(m, lat, K)
-    scratch = _scratch(nbytes, dev)
-    ms = (ctypes.c_float * len(GLOBAL_PHASES))() if phases else None
-    with torch.cuda.device(dev):
-        check(lib().d3d_global_align(ptr(src), m, sstride, ptr(snrm), snstride, ptr(origins[0]), ptr(tgt), n, tstride,
-                                     ptr(tnrm), tnstride, ptr(origins[1]), bin, lat, c2, K, sep, ptr(A), ptr(choice),
-                                     ptr(score), ptr(support), ptr(state), ctypes.byref(det) if det is not None else None,
-                                     ptr(scratch), nbytes, stream_of(dev), ms))
-    return Alignment(A, A, None, None, choice, score, support, state, details,
-                     dict(zip(GLOBAL_PHASES, (float(v) for v in ms))) if phases else None)
+    buf, nbytes = scratch(dev, "d3d_global_align_scratch_bytes", m, lat, K)
+    timer = PhaseTimer(GLOBAL_PHASES, phases)
+    run(dev, "d3d_global_align", ptr(src), m, sstride, ptr(snrm), snstride, ptr(origins[0]), ptr(tgt), n, tstride,
+        ptr(tnrm), tnstride, ptr(origins[1]), bin, lat, c2, K, sep, ptr(A), ptr(choice), ptr(score), ptr(support),
+        ptr(state), ctypes.byref(det) if det is not None else None, ptr(buf), nbytes, stream_of(dev), timer.ms)
+    return Alignment(A, A, None, None, choice, score, support, state, details, timer.read())
 
 
 def global_align(source, target, bin=0.05, lattice=(2048, 2048, 256), tol=5.0, peaks=64, sep=2, frame=None,
@@ -394,16 +307,9 @@ def global_align(source, target, bin=0.05, lattice=(2048, 2048, 256), tol=5.0, p
     lists, the target's bitmaps, correlations, peak tables, the [4, K, K] scores) as device tensors; phases:
     Alignment.phases, the milliseconds of d3d_global_align's six phases (GLOBAL_PHASES), which synchronises.  Current
     stream, no read-back; bad arguments raise ValueError before any GPU work."""
-    from .frame import align_cloud
-    from .normals import _check_args
-    from .primitives import cloud_min
     bin, lattice, _, peaks, sep, frame_kw = _check_global(bin, lattice, tol, peaks, sep, frame)
-    _check_args(normal_radius, max_nn, None)
-    for c in (source, target):
-        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] < 3:
-            raise ValueError("xyz must be a tensor [N, >= 3]")
-    if source.device != target.device:
-        raise ValueError(f"global_align: source on {source.device}, target on {target.device}")
+    check_normals_args(normal_radius, max_nn)
+    same_device(source=fp32_cloud(source, "source"), target=fp32_cloud(target, "target"))
     six_s = _with_normals(source, source_normals, normal_radius, max_nn, "source")
     six_t = _with_normals(target, target_normals, normal_radius, max_nn, "target")
     with torch.cuda.device(source.device):
@@ -426,7 +332,6 @@ def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=Non
     used as it stands.  init_poses='global': the scans come without poses, and each one's start is global_align(scan,
     union so far, **global_kw)'s; when that finds no walls (status 1) or its margin exceeds MARGIN_MAX (0.98: another
     turn or shift fits as well) a warning is raised and the scan is registered from the identity."""
-    from .downsample import apply_downsample, downsample_kwargs
     clouds = list(clouds)
     if not clouds:
         raise ValueError("merge_scans: no clouds")
@@ -435,33 +340,24 @@ def merge_scans(clouds, init_poses=None, reference=0, voxel=0.02, max_points=Non
         raise ValueError(f"merge_scans: init_poses {init_poses!r}: None, 'global' or one pose per cloud")
     if global_kw is not None and not use_global:
         raise ValueError("merge_scans: global_kw goes with init_poses='global'")
-    global_kw = dict(global_kw or {})
-    bad = sorted(set(global_kw) - {"bin", "lattice", "tol", "peaks", "sep", "frame", "normal_radius", "max_nn"})
-    if bad:
-        raise ValueError(f"merge_scans: unknown global_align keywords {bad}")
+    global_kw = options(global_kw or {}, "merge_scans: global_kw",
+                        ("bin", "lattice", "tol", "peaks", "sep", "frame", "normal_radius", "max_nn"))
     if use_global:
         init_poses = None
         _check_global(global_kw.get("bin", 0.05), global_kw.get("lattice", (2048, 2048, 256)), global_kw.get("tol", 5.0),
                       global_kw.get("peaks", 64), global_kw.get("sep", 2), global_kw.get("frame"))
-    try:
-        ok = not isinstance(reference, bool) and int(reference) == reference and 0 <= int(reference) < len(clouds)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"merge_scans: reference {reference!r} is not one of the {len(clouds)} clouds")
-    reference = int(reference)
+    reference = whole(reference, "merge_scans: reference", 0, len(clouds) - 1)
     if init_poses is None:
         init_poses = [None] * len(clouds)
     init_poses = list(init_poses)
     if len(init_poses) != len(clouds):
         raise ValueError(f"merge_scans: {len(init_poses)} poses for {len(clouds)} clouds")
-    init_poses = [None if p is None else _check_pose(p, "merge_scans: init_poses") for p in init_poses]
+    init_poses = [None if p is None else check_pose(p, "merge_scans: init_poses") for p in init_poses]
     for c in clouds:
         if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != clouds[0].shape[1] or c.shape[1] < 3:
             raise ValueError("merge_scans: tensors [N, C >= 3] of one width")
-    bad = sorted(set(icp_kw) - {"max_dist", "iterations", "tol", "method", "normal_radius", "max_nn"})
-    if bad:                           # target_normals and init among them: the target and the start differ per scan
-        raise ValueError(f"merge_scans: unknown icp keywords {bad}")
+    # not target_normals and init: the target and the start differ per scan
+    options(icp_kw, "merge_scans: icp's", ("max_dist", "iterations", "tol", "method", "normal_radius", "max_nn"))
     _check_icp(icp_kw.get("max_dist", 0.1), icp_kw.get("iterations", 30), icp_kw.get("tol", 1e-6),
                icp_kw.get("method", "plane"), None)
     model_kw = downsample_kwargs({"voxel": voxel})

@@ -19,7 +19,8 @@ import math
 import numpy as np
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
+from ._cloud import need_gpu, number, run, scratch, whole
+from ._lib import lib, ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL
 from .unproject import PIXEL_LIMIT, DepthFrames, fuse_frames
 
@@ -47,8 +48,8 @@ class TriangleMesh(object):
             if vertex_color.dtype not in (torch.uint8, torch.float32):
                 raise ValueError(f"TriangleMesh: vertex_color is uint8 or float32, got {vertex_color.dtype}")
         for t in (vertices, triangles, vertex_color):
-            if t is not None and not t.is_cuda:
-                raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % t.device)
+            if t is not None:
+                need_gpu(t.device)
         for t in (triangles, vertex_color):
             if t is not None and t.device != vertices.device:
                 raise ValueError(f"TriangleMesh: vertices on {vertices.device}, another tensor on {t.device}")
@@ -75,20 +76,17 @@ def _cameras(who, intrinsics, extrinsics):
 
 
 def _check_args(who, mesh, height, width, min_depth, max_depth, depth_dtype, depth_scale, max_scratch_bytes):
-    if int(height) != height or int(width) != width or height < 1 or width < 1:
-        raise ValueError(f"{who}: images of {height!r} x {width!r} pixels")
-    min_depth, max_depth, depth_scale = float(min_depth), float(max_depth), float(depth_scale)
+    height, width = whole(height, f"{who}: height"), whole(width, f"{who}: width")
+    min_depth, max_depth = float(min_depth), float(max_depth)
     if math.isnan(min_depth) or math.isnan(max_depth):
         raise ValueError(f"{who}: min_depth / max_depth is NaN")
     if depth_dtype not in (torch.float32, torch.uint16):
         raise ValueError(f"{who}: depth_dtype is torch.float32 or torch.uint16, got {depth_dtype!r}")
-    if not (depth_scale > 0.0 and math.isfinite(depth_scale)):
-        raise ValueError(f"{who}: depth_scale {depth_scale} must be positive and finite")
-    if int(max_scratch_bytes) != max_scratch_bytes or max_scratch_bytes < 1:
-        raise ValueError(f"{who}: max_scratch_bytes {max_scratch_bytes!r} is a whole number >= 1")
+    depth_scale = number(depth_scale, f"{who}: depth_scale", lo_open=True)
+    max_scratch_bytes = whole(max_scratch_bytes, f"{who}: max_scratch_bytes")
     if not isinstance(mesh, TriangleMesh):
         raise ValueError(f"{who}: mesh is a TriangleMesh, got {type(mesh).__name__}")
-    return int(height), int(width), min_depth, max_depth, depth_scale, int(max_scratch_bytes)
+    return height, width, min_depth, max_depth, depth_scale, max_scratch_bytes
 
 
 class _Call(object):
@@ -109,11 +107,10 @@ class _Call(object):
 
     def bin(self, f0, f1):
         """-> (scratch, all list entries of the frames)"""
-        nbytes = lib().d3d_render_scratch_bytes(f1 - f0, self.h, self.w)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        check(lib().d3d_render_bin(*self.head(), *self.views(f0, f1), ptr(scratch), nbytes, self.info,
-                                   stream_of(self.dev)))
-        return scratch, int(self.info[0])
+        buf, nbytes = scratch(self.dev, "d3d_render_scratch_bytes", f1 - f0, self.h, self.w)
+        run(self.dev, "d3d_render_bin", *self.head(), *self.views(f0, f1), ptr(buf), nbytes, self.info,
+            stream_of(self.dev))
+        return buf, int(self.info[0])
 
 
 def frame_scratch_bytes(mesh, intrinsics, extrinsics, height, width):
@@ -174,8 +171,8 @@ def render_depth(mesh, intrinsics, extrinsics, height, width, min_depth=0.0, max
         f0 = 0
         while f0 < f:
             f1 = min(f, f0 + step)
-            scratch, entries = call.bin(f0, f1)
-            need = scratch.numel() + 4 * entries
+            buf, entries = call.bin(f0, f1)
+            need = buf.numel() + 4 * entries
             if need > budget or entries >= (1 << 31):
                 if f1 - f0 == 1:
                     raise ValueError(f"render_depth: frame {f0} needs {need} bytes of scratch ({entries} list entries of 4 "
@@ -184,13 +181,11 @@ def render_depth(mesh, intrinsics, extrinsics, height, width, min_depth=0.0, max
                 continue
             lists = torch.empty(max(entries, 1), dtype=torch.int32, device=dev)
             s = stream_of(dev)
-            check(lib().d3d_render_fill(*call.head(), *call.views(f0, f1), call.info, ptr(scratch), scratch.numel(),
-                                        ptr(lists), s))
-            check(lib().d3d_render_tiles(*call.head(), ptr(vc), int(vc is not None and vc.dtype == torch.uint8),
-                                         *call.views(f0, f1), min_depth, max_depth, int(depth_dtype == torch.uint16),
-                                         depth_scale, call.info, ptr(scratch), scratch.numel(), ptr(lists),
-                                         ptr(depth[f0:f1]), ptr(None if tri is None else tri[f0:f1]),
-                                         ptr(None if color is None else color[f0:f1]), s))
+            run(dev, "d3d_render_fill", *call.head(), *call.views(f0, f1), call.info, ptr(buf), buf.numel(), ptr(lists), s)
+            run(dev, "d3d_render_tiles", *call.head(), ptr(vc), int(vc is not None and vc.dtype == torch.uint8),
+                *call.views(f0, f1), min_depth, max_depth, int(depth_dtype == torch.uint16), depth_scale, call.info,
+                ptr(buf), buf.numel(), ptr(lists), ptr(depth[f0:f1]), ptr(None if tri is None else tri[f0:f1]),
+                ptr(None if color is None else color[f0:f1]), s)
             _LAST_CHUNKS.append((f0, f1))
             f0 = f1
     frames = DepthFrames(depth, intrinsics, extrinsics, color=color, depth_scale=depth_scale)

@@ -18,7 +18,8 @@ import math
 import numpy as np
 import torch
 
-from ._lib import D3DError, check, lib, ptr, stream_of
+from ._cloud import need_gpu, number, options, run, scratch, whole
+from ._lib import ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL, apply_downsample, downsample_kwargs
 
 PIXEL_LIMIT = 1 << 31
@@ -64,8 +65,8 @@ class DepthFrames(object):
         if f * h * w >= PIXEL_LIMIT:
             raise ValueError(f"DepthFrames: {f} x {h} x {w} pixels do not fit 31 bits; pass fewer frames per call")
         for t in (depth, color):
-            if t is not None and not t.is_cuda:
-                raise D3DError("this op runs on the MI355X only: tensor is on %s (no CPU fallback)" % t.device)
+            if t is not None:
+                need_gpu(t.device)
         if color is not None and color.device != depth.device:
             raise ValueError(f"DepthFrames: depth on {depth.device}, color on {color.device}")
         self.depth = _contiguous(depth.detach())
@@ -94,30 +95,22 @@ def _contiguous(t):
 def unproject_kwargs(unproject):
     """The `unproject=` keyword of BuildingPipeline: None -> {}, or a dict of unproject keywords (columns, step,
     min_depth, max_depth, edge, color_div) -> a checked copy."""
-    if unproject is None:
-        return {}
-    if not isinstance(unproject, dict):
-        raise ValueError(f"unproject must be None or a dict with keys among {', '.join(UNPROJECT_KEYS)}, got {unproject!r}")
-    bad = sorted(set(unproject) - set(UNPROJECT_KEYS))
-    if bad:
-        raise ValueError(f"unproject: unknown keywords {bad} ({', '.join(UNPROJECT_KEYS)})")
-    _check_args(**unproject)
-    return dict(unproject)
+    kw = options(unproject, "unproject", UNPROJECT_KEYS) or {}
+    _check_args(**kw)
+    return kw
 
 
 def _check_args(columns=9, step=1, min_depth=0.0, max_depth=math.inf, edge=0.05, color_div=256.0):
     if columns not in COLUMNS:
         raise ValueError(f"unproject: columns is 3 (position), 6 (+ colour) or 9 (+ normal), got {columns!r}")
-    if int(step) != step or step < 1:
-        raise ValueError(f"unproject: step {step!r} is a whole number >= 1")
-    min_depth, max_depth, edge, color_div = float(min_depth), float(max_depth), float(edge), float(color_div)
+    step = whole(step, "unproject: step")
+    min_depth, max_depth, edge = float(min_depth), float(max_depth), float(edge)
     if math.isnan(min_depth) or math.isnan(max_depth):
         raise ValueError("unproject: min_depth / max_depth is NaN")
-    if not edge >= 0.0:
+    if not edge >= 0.0:                        # inf is allowed, so this is not _cloud.number's check
         raise ValueError(f"unproject: edge {edge} must not be negative")
-    if not (color_div > 0.0 and math.isfinite(color_div)):
-        raise ValueError(f"unproject: color_div {color_div} must be positive and finite")
-    return int(columns), int(step), min_depth, max_depth, edge, color_div
+    color_div = number(color_div, "unproject: color_div", lo_open=True)
+    return int(columns), step, min_depth, max_depth, edge, color_div
 
 
 def unproject(frames, columns=9, step=1, min_depth=0.0, max_depth=math.inf, edge=0.05, color_div=256.0,
@@ -139,21 +132,18 @@ def unproject(frames, columns=9, step=1, min_depth=0.0, max_depth=math.inf, edge
     depth, color = frames.depth, frames.color
     is_u16 = int(depth.dtype == torch.uint16)
     info = (ctypes.c_int * 1)(0)
-    scratch, nbytes = None, 0
     if f * h * w > 0:
-        nbytes = lib().d3d_unproject_scratch_bytes(f, h, w, step)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(lib().d3d_unproject_count(ptr(depth), is_u16, f, h, w, step, frames.depth_scale, min_depth, max_depth,
-                                        ptr(scratch), nbytes, info, stream_of(dev)))
+        buf, nbytes = scratch(dev, "d3d_unproject_scratch_bytes", f, h, w, step)
+        run(dev, "d3d_unproject_count", ptr(depth), is_u16, f, h, w, step, frames.depth_scale, min_depth, max_depth,
+            ptr(buf), nbytes, info, stream_of(dev))
     n = int(info[0])
     out = torch.empty((n, columns), dtype=torch.float32, device=dev)
     pixels = torch.empty((n,), dtype=torch.int32, device=dev) if return_pixels else None
     if n > 0:
-        check(lib().d3d_unproject_rows(ptr(depth), is_u16, ptr(color),
-                                       int(color is not None and color.dtype == torch.uint8), color_div,
-                                       ptr(frames.intrinsics), ptr(frames.extrinsics), f, h, w, step, frames.depth_scale,
-                                       min_depth, max_depth, edge, columns, info, ptr(scratch), nbytes, ptr(out),
-                                       ptr(pixels), stream_of(dev)))
+        run(dev, "d3d_unproject_rows", ptr(depth), is_u16, ptr(color),
+            int(color is not None and color.dtype == torch.uint8), color_div, ptr(frames.intrinsics),
+            ptr(frames.extrinsics), f, h, w, step, frames.depth_scale, min_depth, max_depth, edge, columns, info, ptr(buf),
+            nbytes, ptr(out), ptr(pixels), stream_of(dev))
     return (out, pixels) if return_pixels else out
 
 
