@@ -134,10 +134,13 @@ def elastic_displace(points, minmax, gran, mag, generator, scratch):
     """One pass of elastic() (suncg_dataset.py:220-233) on fp64 points [n, 3] on the GPU, in place: the grid
     bb = |a|.max(0) // gran + 3 from the per-axis `minmax` [6] of the points (host), three N(0, 1) fields drawn with the
     device `generator`, the 6-pass box blur (d3d_elastic_blur) and the trilinear displacement (d3d_elastic_apply).
-    -> minmax of the displaced points."""
+    -> minmax of the displaced points.  `minmax` is taken over the finite coordinates only (d3d_augment_transform,
+    d3d_elastic_apply): a NaN or +-Inf row is outside every grid, keeps its value and is dropped by the voxelizer's
+    contract; an axis without a finite value (min > max) counts as extent 0."""
     require_gpu(points)
     n = points.shape[0]
-    absmax = np.maximum(np.abs(minmax[:3]), np.abs(minmax[3:]))
+    minmax = np.asarray(minmax, np.float64)
+    absmax = np.where(minmax[:3] <= minmax[3:], np.maximum(np.abs(minmax[:3]), np.abs(minmax[3:])), 0.0)
     bb = tuple(int(v) for v in (absmax.astype(np.int32) // int(gran) + 3))
     fields = torch.randn((3,) + bb, dtype=torch.float32, device=points.device, generator=generator)
     tmp = torch.empty_like(fields)
@@ -185,7 +188,11 @@ class Augment(object):
     __call__(pcl_dev, targets, cfg) -> (coords int64 [M, 3], feats fp32 [M, F], targets): pcl_dev fp32 [N, F] on the GPU
     with the columns of cfg.INPUT.ELEMENTS; targets {"bbox3d": yx_zb [K, 7], "labels": [K]} in the scene's own frame
     (scene_targets(..., shift=False), ScenePrefetcher(shift_targets=False)); the returned boxes are in the frame of the
-    returned coordinates.  The boxes do not follow the elastic distortion (as in the reference)."""
+    returned coordinates.  The boxes do not follow the elastic distortion (as in the reference).
+
+    Non-finite coordinates follow voxelize's contract, elastic on or off: a point whose transformed coordinate is NaN or
+    +Inf is dropped alone (the result is that of the cloud without it), a -Inf one drops the whole cloud; none of them
+    sizes an elastic noise grid."""
 
     def __init__(self, rotate="none", flip_x=False, scale_jitter=0.0, origin_offset=False, elastic=False,
                  color_noise=0.0, seed=0):

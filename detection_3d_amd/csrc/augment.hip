@@ -39,9 +39,11 @@ __device__ __forceinline__ void point_at(const float *__restrict__ pcl, int nfea
 
 // per-axis min and max of the transformed points (red[0..2] min, red[3..5] max, order-preserving uint64): grid-stride,
 // wave shuffle, LDS, one atomic per block and value -- order-independent.  pts_out: the fp64 points are written too.
+// finite_only: +-Inf is skipped like a NaN (the extent that sizes the elastic noise grid); the voxelizer's minimum keeps
+// a -Inf, by d3d_voxelize's contract.
 __global__ __launch_bounds__(256) void k_aug_minmax(const float *__restrict__ pcl, int n, int nfeat,
                                                     const double *__restrict__ pts, AugArgs g, double *pts_out,
-                                                    unsigned long long *red) {
+                                                    int finite_only, unsigned long long *red) {
   __shared__ double lds[4][6];
   double v[6] = {1e300, 1e300, 1e300, -1e300, -1e300, -1e300};
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(256) void k_aug_minmax(const float *__restrict__ pc
     if (pts_out)
       for (int d = 0; d < 3; d++) pts_out[(size_t)i * 3 + d] = a[d];
     for (int d = 0; d < 3; d++) {
+      if (finite_only && !isfinite(a[d])) continue;
       v[d] = fmin(v[d], a[d]);
       v[3 + d] = fmax(v[3 + d], a[d]);
     }
@@ -151,6 +154,7 @@ __global__ void k_elastic_blur(const float *__restrict__ in, float *__restrict__
 
 // RegularGridInterpolator(linear, bounds_error=False, fill_value=0) of the 3 fields on the axes
 // linspace(-(b-1) gran, (b-1) gran, b) (spacing 2 gran), then a += disp * mag; red: min / max of the displaced points
+// that are finite (the extent sizes the next pass's grid)
 __global__ __launch_bounds__(256) void k_elastic_apply(double *pts, int n, const float *__restrict__ fields, int D0,
                                                        int D1, int D2, double gran, double mag,
                                                        unsigned long long *red) {
@@ -191,6 +195,7 @@ __global__ __launch_bounds__(256) void k_elastic_apply(double *pts, int n, const
     for (int d = 0; d < 3; d++) {
       const double b = __dadd_rn(a[d], __dmul_rn(disp[d], mag));
       pts[(size_t)i * 3 + d] = b;
+      if (!isfinite(b)) continue;             // a NaN or +-Inf row keeps its bits and sizes no grid
       v[d] = fmin(v[d], b);
       v[3 + d] = fmax(v[3 + d], b);
     }
@@ -258,7 +263,7 @@ int d3d_augment_transform(const float *pcl, int n, int nfeat, const d3d_augment_
   D3D_HIP_CHECK(hipMemsetAsync(red, 0xFF, 3 * 8, s));
   D3D_HIP_CHECK(hipMemsetAsync(red + 3, 0, 3 * 8, s));
   hipLaunchKernelGGL(k_aug_minmax, dim3(reduce_blocks(n)), dim3(256), 0, s, pcl, n, nfeat, (const double *)nullptr,
-                     to_args(prm_host), points_out, red);
+                     to_args(prm_host), points_out, 1, red);
   D3D_LAUNCH_CHECK();
   return read_minmax(red, minmax_host, s);
 }
@@ -323,7 +328,7 @@ int d3d_augment_voxelize(const float *pcl, int n, int nfeat, const double *point
   D3D_HIP_CHECK(hipMemsetAsync(red, 0xFF, 3 * 8, s));
   D3D_HIP_CHECK(hipMemsetAsync(red + 3, 0, 3 * 8, s));
   hipLaunchKernelGGL(k_aug_minmax, dim3(reduce_blocks(n)), dim3(256), 0, s, pcl, n, nfeat, points, g, (double *)nullptr,
-                     red);
+                     0, red);
   hipLaunchKernelGGL(k_aug_offset, dim3(1), dim3(64), 0, s, (const unsigned long long *)red, g, fx, fy, fz, off);
   hipLaunchKernelGGL(k_aug_flag, grid1d(n), dim3(256), 0, s, pcl, n, nfeat, points, g, (const double *)off, fx, fy, fz,
                      flag);

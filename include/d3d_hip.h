@@ -142,7 +142,8 @@ int d3d_augment_voxelize(const float *pcl, int n, int nfeat, const double *point
                          int *n_kept_host, double *offset_host, void *scratch, size_t scratch_bytes, void *stream);
 size_t d3d_augment_scratch_bytes(int n);
 /* a = xyz . M into points_out (fp64 [n,3]) for the elastic passes; minmax_host[6] = per-axis min, then max (the grid of
- * elastic(), :221, needs max |a|).  Synchronises once.  scratch: >= 64 bytes.                                         */
+ * elastic(), :221, needs max |a|) over the finite values only: a NaN or +-Inf coordinate sizes no grid (1e300 / -1e300
+ * for an axis without a finite value).  Synchronises once.  scratch: >= 64 bytes.                                      */
 int d3d_augment_transform(const float *pcl, int n, int nfeat, const d3d_augment_params *prm_host, double *points_out,
                           double *minmax_host, void *scratch, size_t scratch_bytes, void *stream);
 /* elastic(), :223-228: the 3-tap 1/3 box filter along axes 0, 1, 2, 0, 1, 2 of nfields fp32 fields [nfields][d0][d1][d2]
@@ -151,7 +152,8 @@ int d3d_augment_transform(const float *pcl, int n, int nfeat, const d3d_augment_
 int d3d_elastic_blur(float *fields, int nfields, const int *dims_host, float *tmp, void *stream);
 /* elastic(), :229-233: points += mag * (3 blurred fields [3][d0][d1][d2] sampled trilinearly in fp64 on the axes
  * linspace(-(d-1) gran, (d-1) gran, d), 0 outside -- RegularGridInterpolator(bounds_error=0, fill_value=0)).
- * minmax_host: null (asynchronous) or [6], per-axis min and max of the displaced points (synchronises once).
+ * A point outside the axes, NaN and +-Inf included, keeps its bits.
+ * minmax_host: null (asynchronous) or [6], per-axis min and max of the finite displaced points (synchronises once).
  * scratch: >= 64 bytes.                                                                                              */
 int d3d_elastic_apply(double *points, int n, const float *fields, const int *dims_host, double gran, double mag,
                       double *minmax_host, void *scratch, size_t scratch_bytes, void *stream);
