@@ -129,6 +129,15 @@ _SIGS = {
     "d3d_fit_boxes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "d3d_fit_boxes": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp,
                                      vp, vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_floorplan_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "d3d_floorplan_raster": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_int, ctypes.c_int, vp, vp]),
+    "d3d_floorplan_rooms": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
+                                           vp, ctypes.c_size_t, vp, c_float_p]),
+    "d3d_floorplan_sides": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "d3d_floorplan_points": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, vp]),
     "d3d_manhattan_frame_scratch_bytes": (ctypes.c_size_t, []),
     "d3d_manhattan_frame": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_double_p, c_float_p, vp, vp, vp, vp, vp, vp,
                                            vp, ctypes.c_size_t, vp, c_float_p]),

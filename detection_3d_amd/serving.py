@@ -54,13 +54,26 @@ class BuildingPipeline(object):
     and before it is voxelised, for scans that arrive in a camera's or a reference station's frame.  The detections live in
     the aligned cloud's min-shifted frame; every result dict carries "frame_pose", fp64 [4, 4] on the device: that frame <-
     the input cloud's frame (frame.detector_pose; frame.box_corners_in_scan_frame takes the boxes back).  point_owner
-    tests the points in the aligned frame.  Without align nothing changes and the key is absent."""
+    tests the points in the aligned frame.  Without align nothing changes and the key is absent.
+    rooms: None, True, or a dict with keys among cell, grow, min_area, reach, max_rooms (floorplan.rooms_kwargs): every
+    result dict gets the floor plan of its detections (floorplan.floorplan_of with the config's classes), computed on its
+    slot's tail stream after the detections and before point_owner: "rooms" {"bbox3d" fp32 [max_rooms, 7], "area" fp64
+    [max_rooms], "count" int32 [1]} and "box_rooms" int32 [detections, 2], what lies on either side of every detection.
+    The lattice is explicit (floorplan.detector_lattice: the detections' min-shifted frame at `cell`), so nothing is read
+    back.  With point_owner also "point_room" int32, one entry per row of the RAW cloud: floorplan.room_of_points of the
+    point the row went into, floorplan.NONE for a row that went nowhere.  With rooms=None nothing is imported, launched
+    or added."""
 
     def __init__(self, model, cfg, in_flight=2, device=None, normals=None, point_owner=False, downsample=None,
-                 unproject=None, clean=None, align=None):
+                 unproject=None, clean=None, align=None, rooms=None):
         self.prepare = Preparation(unproject=unproject, downsample=downsample, normals=normals, clean=clean, align=align)
         self.model, self.cfg = model, cfg
         self.point_owner = bool(point_owner)
+        self.rooms = self.rooms_lattice = None
+        if rooms is not None and rooms is not False:
+            from .floorplan import detector_lattice, rooms_kwargs
+            self.rooms = rooms_kwargs(rooms)
+            self.rooms_lattice = detector_lattice(cfg, self.rooms["cell"])
         self.device = device if device is not None else next(model.parameters()).device
         self.in_flight = max(1, int(in_flight))
         # streams live as long as the pipeline: metadata arenas and scratch buffers are recycled per stream
@@ -145,6 +158,13 @@ class BuildingPipeline(object):
                 with torch.cuda.stream(slot(i)[0]):
                     results[i] = r = self.model.stage_tail(feats)
                     k, kept[i] = kept[i], None
+                    if self.rooms is not None:
+                        from .floorplan import floorplan_of, point_rooms
+                        plan = floorplan_of(r, self.cfg.INPUT.CLASSES, lattice=self.rooms_lattice, **self.rooms)
+                        r["rooms"], r["box_rooms"] = plan["rooms"], plan["box_rooms"]
+                        if k is not None and self.point_owner:
+                            r["point_room"] = point_rooms(k, clouds[i], plan["plan"])
+                        del plan
                     if k is not None and self.point_owner:
                         r["point_owner"], r["point_count"] = point_ownership(k, clouds[i], r["bbox3d"])
                         if k.pixels is not None:
@@ -167,7 +187,7 @@ class BuildingPipeline(object):
         for st in self.hi:
             caller.wait_stream(st)
         for r in results:
-            for v in r.values():
+            for v in list(r.values()) + list(r["rooms"].values() if self.rooms is not None else ()):
                 if torch.is_tensor(v) and v.is_cuda:
                     v.record_stream(caller)
         return results

@@ -340,6 +340,43 @@ int d3d_fit_boxes(const float *xyz, int n, int row_stride_floats, const double *
                   const double *coarse_dev, const double *fine_dev, float *boxes, int32_t *count, int32_t *choice,
                   float *extent, void *scratch, size_t scratch_bytes, void *stream, float *phase_ms_host);
 
+/* Rooms from boxes: a floor plan of square cells.  Lattice: cell (iy, ix), 0 <= iy < h, 0 <= ix < w, h, w <= 4096, id
+ * iy w + ix, centre X = ox + (ix + 0.5) cell, Y = oy + (iy + 0.5) cell; a coordinate x lies in ix = floor((x - ox) /
+ * cell), a non-finite or out-of-range index is off the lattice.  Everything is fp64, every product, sum and quotient
+ * rounded on its own.  table fp64 [k, 6] on the device: (xc, yc, c, s, hx, hy) of every box, c, s = cos, sin of its yaw,
+ * hx, hy its half sizes along lx = c (X - xc) - s (Y - yc) and ly = s (X - xc) + c (Y - yc); the caller makes it.
+ * 0 <= k <= 4096.  All calls are asynchronous on `stream` and read nothing back; the same input gives the same bits.
+ *
+ * d3d_floorplan_raster: bitmap uint32 [h, ceil(w / 32)], bit ix & 31 of word ix >> 5 of row iy set iff for at least one
+ * row j of the table with select[j] != 0 (select NULL: every row) |lx| <= hx and |ly| <= hy at the cell's centre; faces
+ * are closed; a row with a non-finite entry blocks nothing.  The call clears the bitmap first; bits from w on stay 0.
+ *
+ * d3d_floorplan_rooms: the free cells (bit clear) joined over 4-connectivity.  label int32 [h, w]: -2 for a blocked
+ * cell, -1 for a component that holds a cell of the lattice's border, -3 for one of fewer than min_cells (>= 1) cells,
+ * else the room's number: rooms are numbered 0 .. R - 1 by ascending smallest cell id.  count int32 [1] = R.  Per room
+ * below max_rooms: cells int32 (its cell count), bounds int32 [max_rooms, 4] (ix_min, iy_min, ix_max, iy_max), seed int32
+ * (its smallest cell id); rows from R on hold 0, (w, h, -1, -1) and -1.  Rooms from max_rooms on keep their number in
+ * label.  scratch: d3d_floorplan_scratch_bytes(h, w, k) bytes (k does not matter today).  phase_ms_host: NULL, or [5] =
+ * milliseconds of the runs, the links, the roots, the ranking and the final write; the call then synchronises.
+ *
+ * d3d_floorplan_sides: sides int32 [k, 2], column 0 the -lx side.  Probe p = 0 .. n_probe - 1 of a side sits at
+ * t = -+(hx + (p + 0.5) cell) along lx, the world point (xc + c t, yc - s t); the first probe whose cell is not blocked
+ * gives the value (its label); a probe off the lattice gives -1 and ends the walk; no value: -4.
+ *
+ * d3d_floorplan_points: point i as in d3d_points_in_boxes (row stride; origin_dev subtracted in fp64, the difference is
+ * not rounded to fp32).  room int32 [n]: the label of the point's cell, -1 off the lattice, -4 for a position with a
+ * non-finite x, y or z.                                                                                              */
+size_t d3d_floorplan_scratch_bytes(int h, int w, int k);
+int d3d_floorplan_raster(const double *table, const uint8_t *select, int k, double cell, double ox, double oy, int h,
+                         int w, uint32_t *bitmap, void *stream);
+int d3d_floorplan_rooms(const uint32_t *bitmap, int h, int w, int min_cells, int max_rooms, int32_t *label,
+                        int32_t *count, int32_t *cells, int32_t *bounds, int32_t *seed, void *scratch,
+                        size_t scratch_bytes, void *stream, float *phase_ms_host);
+int d3d_floorplan_sides(const double *table, int k, const int32_t *label, double cell, double ox, double oy, int h,
+                        int w, int n_probe, int32_t *sides, void *stream);
+int d3d_floorplan_points(const float *xyz, int n, int row_stride_floats, const double *origin_dev, const int32_t *label,
+                         double cell, double ox, double oy, int h, int w, int32_t *room, void *stream);
+
 /* The Manhattan frame of a scan from its normals: the rotation from the scan's frame to a level, wall-aligned one, the
  * best of 3 x 256 tilt and 2 x 256 heading candidates by a defined integer vote.  normals fp32, row i at normals +
  * i * row_stride_floats (three floats; unit length, any sign).  Every fp32 operation below is a multiply, add, min or max

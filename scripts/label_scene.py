@@ -16,7 +16,11 @@ instances are then the planar patches of planes.label_planes (region growing ove
 
 --align[=MAX_TILT,TOL] (degrees, defaults 30 and 5) is for a scan that is not level or not square to its walls: the
 cloud (`pcl` [N, 9]) is first turned into its Manhattan frame by its normals (frame.align_cloud), so that --planes
-classes by the angle to the true vertical and the boxes are upright; the scene file holds the aligned cloud."""
+classes by the angle to the true vertical and the boxes are upright; the scene file holds the aligned cloud.
+
+--rooms[=CELL,MIN_AREA] (metres and square metres, defaults 0.05 and 1.0) is for a config that lists the class `room`:
+a labelled scan has no room nodes, so one room box per room of the floor plan between the fitted walls, windows and
+doors is appended (floorplan.room_targets; z from the walls).  Nothing is added when the scan labels rooms itself."""
 import argparse
 import os
 import sys
@@ -38,9 +42,12 @@ def main():
                     help="no `instance` in the input: label the planar patches of the cloud (planes.label_planes)")
     ap.add_argument("--align", nargs="?", const="", default=None, metavar="MAX_TILT,TOL",
                     help="level the cloud and square it to its walls by its normals first (frame.align_cloud)")
+    ap.add_argument("--rooms", nargs="?", const="", default=None, metavar="CELL,MIN_AREA",
+                    help="append one `room` box per room of the floor plan between the fitted walls (floorplan.room_targets)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     from detection_3d_amd.config import class_to_label, get_cfg
+    from detection_3d_amd.floorplan import parse_rooms, room_targets
     from detection_3d_amd.frame import align_cloud, parse_align
     from detection_3d_amd.planes import label_planes, parse_planes
     from detection_3d_amd.primitives import MIN_POINTS_ANY, targets_from_labels
@@ -49,6 +56,7 @@ def main():
     try:
         planes = parse_planes(args.planes)
         align = parse_align(args.align)
+        rooms = parse_rooms(args.rooms)
     except ValueError as e:
         raise SystemExit(str(e))
     with np.load(args.labelled, allow_pickle=False) as d:
@@ -80,6 +88,10 @@ def main():
     tg = targets_from_labels(cloud, inst, labels,
                              min_points=MIN_POINTS_ANY if args.min_points is None else args.min_points,
                              min_size=[float(v) for v in args.min_size.split(",")], classes=cfg.INPUT.CLASSES)
+    if rooms is not None:
+        if "room" not in c2l:
+            raise SystemExit(f"--rooms: the config {args.config} does not list the class `room`")
+        tg = room_targets(tg, cfg.INPUT.CLASSES, **rooms)
     boxes, kept = tg["bbox3d"].cpu().numpy(), tg["labels"].cpu().numpy()
     per_class = {l2c[int(l)]: yx_zb_to_standard(boxes[kept == l]) for l in np.unique(kept)}
     save_scene(args.scene, pcl, per_class)
