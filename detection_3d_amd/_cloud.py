@@ -1,4 +1,4 @@
-"""What every raw-scan wrapper (clean, planes, normals, downsample, register, frame, primitives, unproject, render) does
+"""What every raw-scan wrapper (clean, planes, normals, downsample, register, frame, primitives, unproject, tsdf, render) does
 before and around its library call, in one place.  Three rules live here and nowhere else:
 
 rows in place: a cloud is fp32 [N, >= 3] rows read through their row stride (`row_stride_floats` of the C entry points),

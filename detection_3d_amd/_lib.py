@@ -161,6 +161,22 @@ _SIGS = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t,
                                           vp, vp, vp]),
+    "d3d_tsdf_table_slots": (ctypes.c_int, [ctypes.c_int]),
+    "d3d_tsdf_touch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p,
+                                      ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, c_int_p, vp]),
+    "d3d_tsdf_integrate": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, c_double_p, vp, ctypes.c_int, ctypes.c_int,
+                                          vp, vp, vp, vp, vp, vp]),
+    "d3d_tsdf_order_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_tsdf_order": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
+    "d3d_tsdf_surface_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_tsdf_surface_count": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_double, vp,
+                                              ctypes.c_size_t, c_int_p, vp]),
+    "d3d_tsdf_surface_rows": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double,
+                                             c_double_p, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp,
+                                             vp, vp]),
     "d3d_render_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "d3d_render_bin": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, vp, ctypes.c_size_t, c_int64_p, vp]),

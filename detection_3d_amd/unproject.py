@@ -9,9 +9,9 @@ reference (its module imports open3d).  Two deliberate differences: the kept pix
 where the reference flattens every image column by column, and a pixel needs min_depth <= z <= max_depth and a finite z
 besides the reference's z > 0.  The same input gives the same bits.
 
-Out of scope: reading PNG, JPG or .sens files (bring tensors); lens distortion (undistort first); TSDF or any other
-surface fusion (frames are merged by the voxel mean alone); chunking scans whose F H W rows do not fit in memory
-(`step` is the knob: it keeps one pixel in step x step)."""
+Out of scope: reading PNG, JPG or .sens files (bring tensors); lens distortion (undistort first); chunking scans whose
+F H W rows do not fit in memory (`step` is the knob: it keeps one pixel in step x step).  fuse_frames merges frames by
+the voxel mean alone; tsdf.fuse_frames_tsdf fuses the same frames into a signed-distance volume and returns its surface."""
 import ctypes
 import math
 

@@ -552,6 +552,70 @@ int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, i
                        const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
                        int32_t *pixel_of_point, void *stream);
 
+/* Posed depth frames -> a truncated signed-distance volume (TSDF) -> its surface cloud: KinectFusion-style projective
+ * fusion; the reference has nothing like it.  Frames (depth, color, intrinsics, extrinsics, depth_scale,
+ * min_depth, max_depth, step, color_div) as for d3d_unproject_*.  Every operation below is fp64 in exactly this order,
+ * without contraction; each stored or returned value is rounded once to fp32.
+ *   volume: voxel > 0, trunc > 0, origin fp64 [3] (host).  Block b in [0, 65536)^3, voxel g = 8 b + l, l in [0, 8)^3,
+ *     voxel position X_i = origin_i + double(g_i) * voxel.  The caller owns: table (d3d_tsdf_table_slots(max_blocks) hash
+ *     slots of 16 bytes, all ones when empty), block_coords int32 [max_blocks, 3], state int32 [3] (blocks handed out,
+ *     clipped, full; zero when empty), and per voxel, block id major and (lx 8 + ly) 8 + lz inside the block: tsdf D,
+ *     weight W, color_state C [.., 3], color_weight CW, all fp32.  Block ids depend on scheduling; d3d_tsdf_order gives
+ *     the ids in ascending (x, y, z) of their coordinates and every output follows it.
+ *   _touch (allocation), for every kept pixel (valid, u % step == 0 and v % step == 0) of depth z and k = -reach ..
+ *     reach (the host's ceil(trunc / voxel)): z_k = z + double(k) * voxel, skipped when z_k <= 0; C = ((double(u) - cx)
+ *     * (z_k / fx), (double(v) - cy) * (z_k / fy), z_k); X as in d3d_unproject_rows; q_i = floor((X_i - origin_i) /
+ *     (8.0 * voxel)); a sample with a q_i outside [0, 65536) is dropped and sets `clipped`; otherwise block q is
+ *     allocated if absent.  A block that no sample of a ray hits is not allocated.  One read-back: info_host[0] = blocks
+ *     allocated so far, [1] = clipped, [2] = full.  Full: a block was wanted past max_blocks; it got no storage, nothing
+ *     was written out of bounds, the table is then unspecified and wants clearing (all ones; state zero).
+ *   _integrate: first sets the state of blocks [first_new, n_blocks) to zero, then every voxel of blocks [0, n_blocks)
+ *     walks the frames f = 0 .. frames - 1 in ascending order with S = n = CS = cn = 0: d = X - t; c_j = (R[0][j] * d.x
+ *     + R[1][j] * d.y) + R[2][j] * d.z; skip unless c.z > 0; pu = floor((c.x * fx / c.z + cx) + 0.5), pv likewise with
+ *     fy, cy; skip unless 0 <= pu < width and 0 <= pv < height (compared in fp64; a NaN skips); zp = depth of pixel (f,
+ *     pv, pu), skip unless valid (step plays no part); sdf = zp - c.z, skip when sdf < -trunc; S += min(1.0, sdf /
+ *     trunc), n += 1; when sdf <= trunc and there is a colour image: CS_k += colour_k (uint8: double(c) / color_div;
+ *     fp32: double(c)), cn += 1.  After the last frame, where n > 0: D = float((double(W) * double(D) + S) / (double(W)
+ *     + double(n))), W = float(double(W) + double(n)); the same for C_k and CW with CS_k and cn where cn > 0; where n ==
+ *     0 the stored bits do not change.  A (block, frame) pair is skipped as a whole only when no voxel of the block can
+ *     pass the tests; culled_pairs (device, or NULL) is incremented by the number of such pairs.  One call of F frames
+ *     and F calls of one frame may differ in the last bit.  Asynchronous.
+ *   _order: order int32 [n_blocks], the block ids in ascending (x, y, z).  Asynchronous.
+ *   _surface_*: a voxel is seen when double(W) >= min_weight.  Seen voxels in the order (block as in `order`, l with z
+ *     fastest), and for each axis a = x, y, z: h = g + e_a (in a neighbouring block where l_a = 7) must be allocated and
+ *     seen; the edge crosses when (D_g < 0) != (D_h < 0) and then gives one row: s = double(D_g) / (double(D_g) -
+ *     double(D_h)); position X_g with s * voxel added on axis a; colour (ncols >= 6): C_g + s * (C_h - C_g) per channel
+ *     when both CW > 0, the one that has colour when only one does, else 0 (and 0 without colour state); normal (ncols
+ *     == 9), shared by the voxel's rows: when |D_g| < 1 and all three g + e_k are allocated, seen and have |D| < 1: m_k
+ *     = double(D_{g + e_k}) - double(D_g), l2 = (m.x m.x + m.y m.y) + m.z m.z, m / sqrt(l2) per component when l2 > 0;
+ *     otherwise (0, 0, 0).  The gradient points into free space, towards the cameras.
+ *     _count: one read-back, info_host[0] = N.  _rows: out fp32 [N, ncols], voxels int32 [N, 3] (g) or NULL; same
+ *     arguments, `scratch` and info_host as _count left them; asynchronous; never writes past N rows.
+ * The same calls give the same bits whatever the block ids were.  No float atomics.                                   */
+int d3d_tsdf_table_slots(int max_blocks);
+int d3d_tsdf_touch(const void *depth, int depth_is_u16, const double *intrinsics, const double *extrinsics, int frames,
+                   int height, int width, int step, double depth_scale, double min_depth, double max_depth, double voxel,
+                   const double *origin, int reach, void *table, int table_slots, int32_t *block_coords, int max_blocks,
+                   int32_t *state, int *info_host /* [3] */, void *stream);
+int d3d_tsdf_integrate(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
+                       const double *intrinsics, const double *extrinsics, int frames, int height, int width,
+                       double depth_scale, double min_depth, double max_depth, double voxel, double trunc,
+                       const double *origin, const int32_t *block_coords, int n_blocks, int first_new, float *tsdf,
+                       float *weight, float *color_state, float *color_weight, unsigned long long *culled_pairs,
+                       void *stream);
+size_t d3d_tsdf_order_scratch_bytes(int n_blocks);
+int d3d_tsdf_order(const int32_t *block_coords, int n_blocks, int32_t *order, void *scratch, size_t scratch_bytes,
+                   void *stream);
+size_t d3d_tsdf_surface_scratch_bytes(int n_blocks);
+int d3d_tsdf_surface_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
+                           int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
+                           size_t scratch_bytes, int *info_host /* [0] = N */, void *stream);
+int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
+                          int table_slots, const float *tsdf, const float *weight, const float *color_state,
+                          const float *color_weight, double voxel, const double *origin, double min_weight, int ncols,
+                          const int *info_host, const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels,
+                          void *stream);
+
 /* Posed depth frames from a triangle mesh: the step between gen_house_obj and gen_pcl of
  * data3d/suncg_utils/suncg_preprocess.py, which the reference leaves to an external OpenGL tool (scn2img).  vertices fp32
  * [n_vertices, 3] in world coordinates, triangles int32 [n_triangles, 3], vertex_color fp32 or uint8 [n_vertices, 3] or

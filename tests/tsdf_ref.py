@@ -1,0 +1,247 @@
+"""numpy fp64 restatement of the semantics of d3d_tsdf_* (include/d3d_hip.h), and the scenes the tests of
+detection_3d_amd.tsdf share.  TsdfRef uses element-wise operations in the stated order only: no `@`, matmul or dot,
+which a BLAS or a fused loop may reorder (the scene builders below are free to)."""
+import numpy as np
+
+from detection_3d_amd.unproject import suncg_cameras
+from tests.unproject_ref import ROOM, holes_scene, rigid, room_scene  # noqa: F401  (the tests take the scenes from here)
+
+
+def _depth_metres(depth, depth_scale):
+    depth = np.asarray(depth)
+    if depth.dtype == np.uint16:
+        return depth.astype(np.float64) * np.float64(depth_scale)
+    return depth.astype(np.float64)
+
+
+class TsdfRef(object):
+    """The volume of detection_3d_amd.tsdf.TsdfVolume on the CPU.  Blocks are kept in the order they were allocated
+    (any order serves: every output is sorted by block coordinate)."""
+
+    def __init__(self, voxel, trunc=None, origin=(0.0, 0.0, 0.0), color=True):
+        self.voxel = np.float64(voxel)
+        self.trunc = np.float64(4.0 * voxel if trunc is None else trunc)
+        self.origin = np.asarray(origin, np.float64)
+        self.color = color
+        self.index = {}                                   # block coordinate -> row of the arrays below
+        self.coords = np.zeros((0, 3), np.int64)
+        self.D = np.zeros((0, 512), np.float32)
+        self.W = np.zeros((0, 512), np.float32)
+        self.C = np.zeros((0, 512, 3), np.float32)
+        self.CW = np.zeros((0, 512), np.float32)
+        self.clipped = False
+
+    # ---- allocation ----
+    def _touch(self, z, valid, K, E, step):
+        F, H, W = z.shape
+        u = np.arange(W, dtype=np.int64)[None, None, :]
+        v = np.arange(H, dtype=np.int64)[None, :, None]
+        kept = valid & (u % step == 0) & (v % step == 0)
+        fx, fy, cx, cy = (K[:, j][:, None, None] for j in range(4))
+        reach = int(np.ceil(self.trunc / self.voxel))
+        block = np.float64(8.0) * self.voxel
+        found = set()
+        for k in range(-reach, reach + 1):
+            zk = z + np.float64(k) * self.voxel
+            use = kept & (zk > 0)
+            C = [(u.astype(np.float64) - cx) * (zk / fx), (v.astype(np.float64) - cy) * (zk / fy), zk]
+            q = []
+            for i in range(3):
+                X = ((E[:, i, 0][:, None, None] * C[0] + E[:, i, 1][:, None, None] * C[1])
+                     + E[:, i, 2][:, None, None] * C[2]) + E[:, i, 3][:, None, None]
+                q.append(np.floor((X - self.origin[i]) / block))
+            inside = (q[0] >= 0) & (q[0] < 65536) & (q[1] >= 0) & (q[1] < 65536) & (q[2] >= 0) & (q[2] < 65536)
+            if (use & ~inside).any():
+                self.clipped = True
+            sel = use & inside
+            if sel.any():
+                found.update(map(tuple, np.unique(np.stack([c[sel] for c in q], 1).astype(np.int64), axis=0)))
+        new = sorted(b for b in found if b not in self.index)
+        for b in new:
+            self.index[b] = len(self.index)
+        if new:
+            n = len(new)
+            self.coords = np.concatenate([self.coords, np.array(new, np.int64).reshape(n, 3)])
+            self.D = np.concatenate([self.D, np.zeros((n, 512), np.float32)])
+            self.W = np.concatenate([self.W, np.zeros((n, 512), np.float32)])
+            self.C = np.concatenate([self.C, np.zeros((n, 512, 3), np.float32)])
+            self.CW = np.concatenate([self.CW, np.zeros((n, 512), np.float32)])
+
+    def _voxels(self, coords):
+        """g int64 [B, 512, 3] of blocks [B, 3], the voxel inside the block as (lx 8 + ly) 8 + lz"""
+        l = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(512, 3)
+        return 8 * coords[:, None, :] + l[None, :, :]
+
+    # ---- integration ----
+    def integrate(self, depth, intrinsics, extrinsics, color=None, depth_scale=0.001, step=1, min_depth=0.0,
+                  max_depth=np.inf, color_div=256.0):
+        depth = np.asarray(depth)
+        F, H, W = depth.shape
+        K = np.broadcast_to(np.asarray(intrinsics, np.float64).reshape(-1, 4), (F, 4))
+        E = np.asarray(extrinsics, np.float64).reshape(F, -1, 4)[:, :3, :]
+        if not self.color:
+            color = None
+        with np.errstate(all="ignore"):
+            z = _depth_metres(depth, depth_scale)
+            valid = np.isfinite(z) & (z > 0) & (z >= min_depth) & (z <= max_depth)
+            self._touch(z, valid, K, E, step)
+            g = self._voxels(self.coords)
+            X = [self.origin[i] + g[..., i].astype(np.float64) * self.voxel for i in range(3)]
+            S, n = np.zeros(g.shape[:2]), np.zeros(g.shape[:2], np.int64)
+            CS, cn = [np.zeros(g.shape[:2]) for _ in range(3)], np.zeros(g.shape[:2], np.int64)
+            for f in range(F):
+                fx, fy, cx, cy = K[f]
+                d = [X[i] - E[f, i, 3] for i in range(3)]
+                c = [(E[f, 0, j] * d[0] + E[f, 1, j] * d[1]) + E[f, 2, j] * d[2] for j in range(3)]
+                ok = c[2] > 0
+                pu = np.floor((c[0] * fx / c[2] + cx) + 0.5)
+                pv = np.floor((c[1] * fy / c[2] + cy) + 0.5)
+                ok &= (pu >= 0) & (pu < W) & (pv >= 0) & (pv < H)
+                iu, iv = np.where(ok, pu, 0).astype(np.int64), np.where(ok, pv, 0).astype(np.int64)
+                zp = z[f][iv, iu]
+                ok &= valid[f][iv, iu]
+                sdf = zp - c[2]
+                ok &= ~(sdf < -self.trunc)
+                q = sdf / self.trunc
+                S = np.where(ok, S + np.where(q > 1.0, 1.0, q), S)
+                n += ok
+                if color is not None:
+                    okc = ok & (sdf <= self.trunc)
+                    px = color[f][iv, iu]
+                    for k in range(3):
+                        ck = px[..., k].astype(np.float64)
+                        if color.dtype == np.uint8:
+                            ck = ck / np.float64(color_div)
+                        CS[k] = np.where(okc, CS[k] + ck, CS[k])
+                    cn += okc
+            w = self.W.astype(np.float64)
+            wn = w + n.astype(np.float64)
+            self.D = np.where(n > 0, ((w * self.D.astype(np.float64) + S) / wn).astype(np.float32), self.D)
+            self.W = np.where(n > 0, wn.astype(np.float32), self.W)
+            if color is not None:
+                w = self.CW.astype(np.float64)
+                wn = w + cn.astype(np.float64)
+                for k in range(3):
+                    self.C[..., k] = np.where(cn > 0, ((w * self.C[..., k].astype(np.float64) + CS[k]) / wn)
+                                              .astype(np.float32), self.C[..., k])
+                self.CW = np.where(cn > 0, wn.astype(np.float32), self.CW)
+        return self
+
+    # ---- outputs ----
+    def _order(self):
+        c = self.coords
+        return np.lexsort((c[:, 2], c[:, 1], c[:, 0])) if len(c) else np.zeros(0, np.int64)
+
+    def blocks(self):
+        """-> coords int32 [B, 3] ascending in (x, y, z), tsdf, weight [B, 8, 8, 8], color [B, 8, 8, 8, 3], color_weight"""
+        o = self._order()
+        return (self.coords[o].astype(np.int32), self.D[o].reshape(-1, 8, 8, 8), self.W[o].reshape(-1, 8, 8, 8),
+                self.C[o].reshape(-1, 8, 8, 8, 3), self.CW[o].reshape(-1, 8, 8, 8))
+
+    def surface_points(self, columns=9, min_weight=1):
+        """-> (rows fp32 [N, columns], voxels int32 [N, 3], has_normal bool [N])"""
+        coords, D, W, C, CW = self.blocks()
+        B = len(coords)
+        if B == 0:
+            return np.zeros((0, columns), np.float32), np.zeros((0, 3), np.int32), np.zeros(0, bool)
+        where = {tuple(c): j for j, c in enumerate(coords.tolist())}
+        seen = W.astype(np.float64) >= min_weight
+
+        def forward(a, arrays, fills):
+            """the arrays shifted by one voxel along +axis a, across block borders; `fills` where no block is"""
+            nb = np.array([where.get(tuple(c + np.eye(3, dtype=np.int64)[a]), -1) for c in coords.astype(np.int64)])
+            out = []
+            for t, fill in zip(arrays, fills):
+                first = [slice(None)] * 4
+                first[1 + a] = slice(0, 1)
+                rest = [slice(None)] * 4
+                rest[1 + a] = slice(1, 8)
+                border = np.where((nb >= 0).reshape((B, 1, 1, 1) + (1,) * (t.ndim - 4)), t[np.maximum(nb, 0)][tuple(first)],
+                                  np.asarray(fill, t.dtype))
+                out.append(np.concatenate([t[tuple(rest)], border], 1 + a))
+            return out
+
+        g = self._voxels(coords.astype(np.int64)).reshape(B, 8, 8, 8, 3)
+        Dg = D.astype(np.float64)
+        Dh, seen_h, Ch, CWh = [], [], [], []
+        for a in range(3):
+            d, s, c, cw = forward(a, (D, seen, C, CW), (0.0, False, 0.0, 0.0))
+            Dh.append(d), seen_h.append(s), Ch.append(c), CWh.append(cw)
+        cross = np.stack([seen & seen_h[a] & ((D < 0) != (Dh[a] < 0)) for a in range(3)], -1)      # [B, 8, 8, 8, 3]
+        with np.errstate(all="ignore"):
+            ok = np.abs(D) < 1
+            for k in range(3):
+                ok &= seen_h[k] & (np.abs(Dh[k]) < 1)
+            m = [Dh[k].astype(np.float64) - Dg for k in range(3)]
+            l2 = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]
+            has = ok & (l2 > 0)
+            length = np.sqrt(l2)
+            normal = [np.where(has, m[k] / length, 0.0).astype(np.float32) for k in range(3)]
+            rows_b, rows_x, rows_y, rows_z, rows_a = np.nonzero(cross.reshape(B, 8, 8, 8, 3))
+            at = (rows_b, rows_x, rows_y, rows_z)
+            N = len(rows_b)
+            out = np.zeros((N, columns), np.float32)
+            dg = Dg[at]
+            dh = np.choose(rows_a, [Dh[a][at].astype(np.float64) for a in range(3)]) if N else np.zeros(0)
+            s = dg / (dg - dh)
+            for i in range(3):
+                Xi = self.origin[i] + g[at + (i,)].astype(np.float64) * self.voxel
+                out[:, i] = np.where(rows_a == i, Xi + s * self.voxel, Xi).astype(np.float32)
+            if columns >= 6 and self.color:
+                cwg = CW[at]
+                cwh = np.choose(rows_a, [CWh[a][at] for a in range(3)]) if N else np.zeros(0, np.float32)
+                for k in range(3):
+                    cg = C[at + (k,)]
+                    ch = np.choose(rows_a, [Ch[a][at + (k,)] for a in range(3)]) if N else np.zeros(0, np.float32)
+                    both = (cg.astype(np.float64) + s * (ch.astype(np.float64) - cg.astype(np.float64))).astype(np.float32)
+                    out[:, 3 + k] = np.where((cwg > 0) & (cwh > 0), both,
+                                             np.where(cwg > 0, cg, np.where(cwh > 0, ch, np.float32(0))))
+            if columns >= 9:
+                for k in range(3):
+                    out[:, 6 + k] = normal[k][at]
+        return out, g[at].astype(np.int32), has[at]
+
+
+# ---- scenes ----
+def room_depth(cam, H, W):
+    """The analytic depth image of unproject_ref.room_scene for one camera row (centre, forward, up, xf, yf, score)"""
+    half_fov = cam[9]
+    f = 0.5 * W / np.tan(half_fov)
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    r = np.stack([(u - 0.5 * (W - 1)) / f, (v - 0.5 * (H - 1)) / f, np.ones_like(u)], -1)
+    o, t, up = cam[0:3], cam[3:6], cam[6:9]
+    R = np.stack([np.cross(t, up), -up, t], 1)
+    d = r @ R.T
+    with np.errstate(divide="ignore"):
+        far = np.where(d > 0, (ROOM - o) / d, np.where(d < 0, (0.0 - o) / d, np.inf))
+    return far.min(-1).astype(np.float32)
+
+
+def room_camera(centre, yaw, pitch, H, W, half_fov=0.62):
+    t = np.array([np.cos(yaw) * np.cos(pitch), np.sin(yaw) * np.cos(pitch), np.sin(pitch)])
+    right = np.cross(t, [0.0, 0.0, 1.0])
+    right /= np.linalg.norm(right)
+    up = np.cross(right, t)
+    return np.concatenate([centre, t, up, [half_fov, np.arctan(np.tan(half_fov) * H / W), 1.0]])
+
+
+def room_frames(H, W, near_wall=False):
+    """room_scene's four frames -> (depth fp32 [F, H, W], intrinsics [F, 4], extrinsics [F, 3, 4]); near_wall: a fifth
+    camera 0.3 m from the wall x = 0 and looking at it obliquely, which puts it inside the culling sphere of the blocks
+    around it"""
+    depth, cams = room_scene(H, W)
+    if near_wall:
+        cam = room_camera((0.3, 1.5, 1.2), 2.6, 0.05, H, W)
+        depth = np.concatenate([depth, room_depth(cam, H, W)[None]])
+        cams = np.concatenate([cams, cam[None]])
+    intr, extr = suncg_cameras(cams, H, W)
+    return depth, intr, extr
+
+
+def room_colors(depth, seed=0):
+    """uint8 colours [F, H, W, 3] for the room's frames: a smooth pattern plus seeded noise"""
+    rs = np.random.RandomState(seed)
+    F, H, W = depth.shape
+    v, u = np.mgrid[0:H, 0:W]
+    base = np.stack([(u * 3 + f * 40) % 256 for f in range(F)])[..., None] + np.array([0, 85, 170])
+    return ((base + rs.randint(0, 32, (F, H, W, 3))) % 256).astype(np.uint8)
