@@ -177,6 +177,15 @@ _SIGS = {
     "d3d_tsdf_surface_rows": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double,
                                              c_double_p, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp,
                                              vp, vp]),
+    "d3d_tsdf_mesh_table": (ctypes.c_int, [vp]),
+    "d3d_tsdf_mesh_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "d3d_tsdf_mesh_count": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_double, vp,
+                                           ctypes.c_size_t, c_int_p, vp]),
+    "d3d_tsdf_mesh_vertices": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, ctypes.c_double,
+                                              c_double_p, c_int_p, vp, ctypes.c_size_t, vp, vp, vp, vp]),
+    "d3d_tsdf_mesh_triangles": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp,
+                                               vp]),
+    "d3d_tsdf_insert_blocks": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp]),
     "d3d_render_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "d3d_render_bin": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, vp, ctypes.c_size_t, c_int64_p, vp]),

@@ -22,6 +22,8 @@
 //              (voxel, axis) with mbcnt over the wave's ballots, packs rows in LDS and stores whole lines, and never
 //              writes past the rows it was given.
 // No float atomics: the only atomics are the swap on a table key and integer counters.
+// The volume as a kernel sees it (sizes, state words, VolumeView, block_find, Apron) is tsdf_volume.inc, shared with
+// tsdf_mesh.hip, which turns the same volume into a triangle mesh.
 #include "d3d_internal.h"
 
 #include <algorithm>
@@ -32,23 +34,14 @@ namespace d3d {
 namespace {
 
 #include "depth_frames.inc"
+#include "tsdf_volume.inc"
 
 constexpr int kTouchThreads = 256;
 constexpr int kTouchSteps = 8;
 constexpr int kTouchRun = kTouchThreads * kTouchSteps;   // pixels of one workgroup
-constexpr int kVox = 512;                                // voxels of a block = threads of its workgroup
-constexpr int kApron = 9 * 9 * 9;
 constexpr int kStageRows = 512;                          // rows packed in LDS per round of k_tsdf_rows
 constexpr int kMaxReach = 256;
-constexpr int kMaxBlocks = 1 << 22;
 constexpr double kBlockCoords = 65536.0;
-
-enum { kStBlocks = 0, kStClipped = 1, kStFull = 2, kStWords = 3 };   // state (device int32[>= 3])
-
-struct VolumeView {
-  double voxel, trunc, block;                // block = 8 voxel
-  double origin[3];
-};
 
 // ---- touch ----
 
@@ -269,27 +262,7 @@ int carve_order(Arena &A, int n, OrderLayout &L) {
 
 // ---- surface ----
 
-// the id of block (x, y, z), or -1: absent, without storage, or outside the coordinate range.  At most `cap` probes.
-__device__ __forceinline__ int block_find(const HashEntry *__restrict__ tab, int cap, int x, int y, int z, int n_blocks) {
-  if (((x | y | z) & ~0xffff) != 0) return -1;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  const uint64_t key = pack_key(0, x, y, z);
-  uint32_t slot = hash_key(key) & (uint32_t)(cap - 1), round = 0;
-  for (int probes = 0; probes < cap; probes++) {
-    const u32x4 e = *(const u32x4 *)&tab[slot];
-    const uint64_t k = ((uint64_t)e[1] << 32) | e[0];
-    if (k == key) return (unsigned)e[2] < (unsigned)n_blocks ? (int)e[2] : -1;
-    if (k == kEmptyKey) return -1;
-    slot = probe_next(slot, round, cap);
-  }
-  return -1;
-}
-
-struct Apron {
-  float D[kApron], W[kApron];                // W = NaN: no such voxel (its block is not allocated)
-  int nb[3];                                 // the +x, +y, +z neighbour blocks, or -1
-};
-
+// block_find, Apron: tsdf_volume.inc
 __device__ __forceinline__ void load_apron(Apron &S, int b, const int32_t *__restrict__ coords,
                                            const HashEntry *__restrict__ tab, int cap, int n_blocks,
                                            const float *__restrict__ tsdf, const float *__restrict__ weight) {
@@ -368,10 +341,6 @@ __global__ __launch_bounds__(kVox) void k_tsdf_count(const int32_t *__restrict__
     for (int w = 0; w < kVox / 64; w++) total += wave_cnt[w];
     counts[blockIdx.x] = total;
   }
-}
-
-__device__ __forceinline__ int lanes_below(unsigned long long ballot) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
 template <int NC>
@@ -506,20 +475,6 @@ size_t surface_bytes(int n) {
   SurfaceLayout L;
   (void)carve_surface(A, n, L);
   return A.used + ((size_t)n / 2048 + 1) * 4 + 4096;
-}
-
-int make_volume(const char *who, double voxel, double trunc, const double *origin, VolumeView &G) {
-  D3D_REQUIRE(voxel > 0.0 && voxel < (double)INFINITY, "%s: voxel %g must be positive and finite", who, voxel);
-  D3D_REQUIRE(trunc > 0.0 && trunc < (double)INFINITY, "%s: trunc %g must be positive and finite", who, trunc);
-  D3D_REQUIRE(origin, "%s: null pointer", who);
-  for (int i = 0; i < 3; i++)
-    D3D_REQUIRE(fabs(origin[i]) < (double)INFINITY, "%s: origin[%d] = %g must be finite", who, i, origin[i]);
-  G = VolumeView{voxel, trunc, 8.0 * voxel, {origin[0], origin[1], origin[2]}};
-  return D3D_OK;
-}
-
-bool table_ok(const void *table, int slots, int max_blocks) {
-  return table && slots >= 1024 && (slots & (slots - 1)) == 0 && (long)slots >= 2l * max_blocks;
 }
 
 }  // namespace

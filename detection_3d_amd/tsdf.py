@@ -12,17 +12,23 @@ ids depend on scheduling, every output is ordered by block coordinate and so doe
 of one frame may differ in the last bit (the mean is folded into fp32 once per call).  Weights count observations, exact
 up to 2^24 per voxel.
 
-Out of scope: triangle extraction (marching cubes); weights other than 1 per observation; a weight cap for moving
-scenes; ray-exact block allocation (a block that the voxel-spaced samples of every ray miss is not allocated); growing
-max_blocks (a volume that runs full raises and wants reset())."""
+Out of scope: weights other than 1 per observation; a weight cap for moving scenes; ray-exact block allocation (a block
+that the voxel-spaced samples of every ray miss is not allocated); growing max_blocks (a volume that runs full raises
+and wants reset()).
+
+TsdfVolume.mesh() gives the zero crossing as a render.TriangleMesh (marching tetrahedra; the restatement is
+tests/tsdf_mesh_ref.py), TsdfVolume.from_blocks() is the inverse of blocks(), fuse_frames_mesh() is around, integrate,
+mesh.  Out of scope there: writing .ply or .obj files, mesh simplification, vertex normals, dropping the vertices that
+no triangle refers to."""
 import ctypes
 import math
 
 import torch
 
-from ._cloud import need_gpu, number, run, scratch, whole
+from ._cloud import need_gpu, number, run, same_device, scratch, whole
 from ._lib import D3DError, lib, ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL, cap_points
+from .render import TriangleMesh
 from .unproject import COLUMNS, DepthFrames
 
 MAX_BLOCKS = 1 << 22
@@ -228,6 +234,96 @@ class TsdfVolume(object):
                 min_weight, int(columns), info, ptr(buf), nbytes, ptr(out), ptr(voxels), stream_of(dev))
         return (out, voxels) if return_voxels else out
 
+    def mesh(self, min_weight=1, color=True, return_edges=False):
+        """The zero crossing as a render.TriangleMesh: marching tetrahedra on the Kuhn split of every cell whose eight
+        voxels are allocated and seen by at least min_weight observations.  One vertex per crossed edge from a voxel g to
+        g + e, e one of x, y, z, xy, xz, yz, xyz (kinds 0..6; kinds 0..2 are surface_points' rows), in (block coordinate,
+        voxel, kind) order; a vertex none of whose cells is emitted stays in the list, unreferenced.  Triangles int32 [T,
+        3] in (block coordinate, voxel, tetrahedron) order, counter-clockwise seen from free space.  vertex_color fp32
+        [V, 3], or None for a volume without colour or with color=False.  return_edges: also int32 [V, 4], the voxel g and
+        the kind of every vertex.  One host read-back (V and T); D3DError when either is past 2^31 - 1."""
+        min_weight = number(min_weight, "tsdf: min_weight")
+        self._alive("tsdf.mesh")
+        dev, n = self.device, self.n_blocks
+        if dev is None:
+            raise D3DError("tsdf.mesh: the volume has seen no frame and has no device yet")
+        info = (ctypes.c_int * 2)(0, 0)
+        if n > 0:
+            order = self._sorted()
+            buf, nbytes = scratch(dev, "d3d_tsdf_mesh_scratch_bytes", n)
+            run(dev, "d3d_tsdf_mesh_count", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
+                ptr(self._tsdf), ptr(self._weight), min_weight, ptr(buf), nbytes, info, stream_of(dev))
+        nv, nt = int(info[0]), int(info[1])
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((nv, 3), dtype=torch.float32, device=dev) if color and self.color else None
+        edges = torch.empty((nv, 4), dtype=torch.int32, device=dev) if return_edges else None
+        if nv > 0:
+            run(dev, "d3d_tsdf_mesh_vertices", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
+                ptr(self._tsdf), ptr(self._color), ptr(self._cweight), self.voxel, self._origin, info, ptr(buf), nbytes,
+                ptr(vertices), ptr(colors), ptr(edges), stream_of(dev))
+        if nt > 0:
+            run(dev, "d3d_tsdf_mesh_triangles", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots, info,
+                ptr(buf), nbytes, ptr(triangles), stream_of(dev))
+        mesh = TriangleMesh(vertices, triangles, colors)
+        return (mesh, edges) if return_edges else mesh
+
+    @classmethod
+    def from_blocks(cls, coords, tsdf, weight, color=None, color_weight=None, voxel=DEFAULT_VOXEL, trunc=None,
+                    origin=(0.0, 0.0, 0.0), max_blocks=None):
+        """The inverse of blocks(): a volume that holds the given blocks, in any order.  coords int32 [B, 3] in [0,
+        65536), no coordinate twice; tsdf, weight fp32 [B, 8, 8, 8]; color fp32 [B, 8, 8, 8, 3] and color_weight fp32 [B,
+        8, 8, 8], both or neither (neither: a volume without colour); all on one GPU.  max_blocks: None for max(B, 2^18).
+        integrate() afterwards finds the blocks and carries on.  The host waits for the checks of the coordinates (two
+        torch expressions) and for the insertion's read-back."""
+        voxel, trunc = _check_volume(voxel, trunc)
+
+        def need(t, what, shape, dtype):
+            if not isinstance(t, torch.Tensor) or t.dim() != len(shape) or \
+                    any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
+                raise ValueError(f"tsdf.from_blocks: {what} is a tensor [{', '.join('B' if s is None else str(s) for s in shape)}]")
+            if t.dtype != dtype:
+                raise ValueError(f"tsdf.from_blocks: {what} is {dtype}, got {t.dtype}")
+            return t.detach()
+
+        coords = need(coords, "coords", (None, 3), torch.int32)
+        n = coords.shape[0]
+        tsdf = need(tsdf, "tsdf", (n, 8, 8, 8), torch.float32)
+        weight = need(weight, "weight", (n, 8, 8, 8), torch.float32)
+        if (color is None) != (color_weight is None):
+            raise ValueError("tsdf.from_blocks: color and color_weight go together")
+        if color is not None:
+            color = need(color, "color", (n, 8, 8, 8, 3), torch.float32)
+            color_weight = need(color_weight, "color_weight", (n, 8, 8, 8), torch.float32)
+        same_device(coords=coords, tsdf=tsdf, weight=weight, color=color, color_weight=color_weight)
+        max_blocks = max(n, 1 << 18) if max_blocks is None else whole(max_blocks, "tsdf: max_blocks", 1, MAX_BLOCKS)
+        if n > max_blocks:
+            raise ValueError(f"tsdf.from_blocks: {n} blocks and max_blocks {max_blocks}")
+        vol = cls(voxel=voxel, trunc=trunc, origin=origin, max_blocks=max_blocks, color=color is not None)
+        if n > 0:
+            c = coords.long()
+            if bool(((c < 0) | (c > 0xFFFF)).any()):
+                raise ValueError("tsdf.from_blocks: a block coordinate outside [0, 65536)")
+            if torch.unique((c[:, 0] << 32) | (c[:, 1] << 16) | c[:, 2]).numel() != n:
+                raise ValueError("tsdf.from_blocks: a block coordinate is given twice")
+        need_gpu(coords.device, "the blocks")
+        dev = vol._on(coords.device)
+        if n > 0:
+            try:
+                run(dev, "d3d_tsdf_insert_blocks", ptr(coords.contiguous()), n, ptr(vol._table), vol._slots,
+                    ptr(vol._coords), vol.max_blocks, ptr(vol._state), stream_of(dev))
+            except D3DError:
+                vol.reset()
+                raise
+            vol._reserve(n)
+            vol._tsdf[:n] = tsdf.reshape(n, BLOCK_VOXELS)
+            vol._weight[:n] = weight.reshape(n, BLOCK_VOXELS)
+            if color is not None:
+                vol._color[:n] = color.reshape(n, BLOCK_VOXELS, 3)
+                vol._cweight[:n] = color_weight.reshape(n, BLOCK_VOXELS)
+            vol.n_blocks = n
+        return vol
+
     @property
     def state_bytes(self):
         """bytes of voxel state, table and coordinates held on the device"""
@@ -287,3 +383,19 @@ def fuse_frames_tsdf(frames, voxel=DEFAULT_VOXEL, trunc=None, max_points=DEFAULT
         volume.integrate(frames_slice(frames, a, min(a + batch, f)), **integrate_kw)
     cloud = volume.surface_points(9, min_weight)
     return cloud if max_points is None else cap_points(cloud, max_points, seed)
+
+
+def fuse_frames_mesh(frames, voxel=DEFAULT_VOXEL, trunc=None, batch=None, min_weight=1, max_blocks=1 << 18, **integrate_kw):
+    """Posed depth frames to a surface mesh: TsdfVolume.around(frames, voxel, trunc), integrate in batches of `batch`
+    frames (None: all at once), mesh(min_weight) -> a render.TriangleMesh, coloured when the frames are.  integrate_kw:
+    step, min_depth, max_depth, color_div."""
+    integrate_kw = dict(zip(("step", "min_depth", "max_depth", "color_div"), _check_integrate(**integrate_kw)))
+    min_weight = number(min_weight, "tsdf: min_weight")
+    _need_frames(frames, "fuse_frames_mesh")
+    f = frames.shape[0]
+    batch = f if batch is None else whole(batch, "fuse_frames_mesh: batch")
+    volume = TsdfVolume.around(frames, voxel, trunc, integrate_kw["min_depth"], integrate_kw["max_depth"],
+                               max_blocks=max_blocks, color=frames.color is not None)
+    for a in range(0, f, max(batch, 1)):
+        volume.integrate(frames_slice(frames, a, min(a + batch, f)), **integrate_kw)
+    return volume.mesh(min_weight)

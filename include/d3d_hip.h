@@ -616,6 +616,52 @@ int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int
                           const int *info_host, const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels,
                           void *stream);
 
+/* The TSDF volume above -> a triangle mesh of its zero crossing: marching tetrahedra on the Kuhn split of
+ * every voxel cell; the reference has nothing like it.  Volume arguments as for d3d_tsdf_surface_*; `seen`, `inside`
+ * (D < 0), X_i, s and the colour rule are those of d3d_tsdf_surface_rows.
+ *   cells: the cell of voxel g has the corners g + c, c in {0, 1}^3, in up to eight blocks (a block coordinate outside
+ *     [0, 65536) is absent); it is emitted when all eight are allocated and seen.
+ *   tetrahedra: t = 0..5 for the permutations p of the axes (x = 0, y = 1, z = 2) in lexicographic order xyz, xzy, yxz,
+ *     yzx, zxy, zyx with signs + - - + + -; corners c_0 = 0, c_1 = e_p1, c_2 = c_1 + e_p2, c_3 = (1, 1, 1); mask = sum of
+ *     inside(c_j) 2^j.
+ *   vertices: one per (g, k), k = 0..6 for e = x, y, z, xy, xz, yz, xyz, when g and g + e are allocated and seen and
+ *     inside(g) != inside(g + e): s = double(D_g) / (double(D_g) - double(D_{g+e})); coordinate i is float(X_i + s *
+ *     voxel) where e_i = 1 and float(X_i) elsewhere; the colour as for a surface row over g and g + e.  Ordered by
+ *     (block as in `order`, l with z fastest, k); kinds 0..2 are exactly the rows of d3d_tsdf_surface_rows.  A vertex
+ *     none of whose cells is emitted stays in the list, unreferenced.
+ *   triangles of a tetrahedron, v(i, o) the vertex on the edge between inside corner i and outside corner o (owned by
+ *     the corner with the smaller index): one inside corner a, outside b < c < d: (v(a,b), v(a,c), v(a,d)); one outside
+ *     corner a, inside b < c < d: (v(b,a), v(c,a), v(d,a)); inside a < b, outside c < d: q = v(a,c), v(a,d), v(b,d),
+ *     v(b,c) gives (q0, q1, q2) and (q0, q2, q3).  The last two indices of each triangle are then swapped for sign + and
+ *     mask in {2, 5, 8, 10, 11, 14}, and for sign - and every other non-empty mask, so that (v1 - v0) x (v2 - v0) points
+ *     from inside to outside: into free space, the normals' convention.  Ordered by (block, l, t, triangle); int32
+ *     indices into the vertex list.
+ *   _mesh_table: out int8 [6][16][13], per (t, mask) the triangle count, then for two triangles x three vertices, after
+ *     the swap, the pair (inside corner, outside corner) as tetrahedron corners j = 0..3, -1 where unused.  Host only.
+ *   _mesh_count: one read-back, info_host[0] = V, [1] = T; fails (and sets both to 0) when either is past 2^31 - 1.
+ *     scratch: d3d_tsdf_mesh_scratch_bytes(n_blocks), about 4 bytes per voxel of the allocated blocks.
+ *   _mesh_vertices: vertices fp32 [V, 3]; vertex_color fp32 [V, 3] or NULL (zeros without colour state); edges int32
+ *     [V, 4] (g, k) or NULL.  _mesh_triangles: triangles int32 [T, 3].  Both take `scratch` and info_host as _mesh_count
+ *     left them, are asynchronous and never write past V rows or T rows.
+ *   _insert_blocks: puts coords int32 [n, 3] (device) into an empty table (all ones, state zero) with ids 0..n-1, the
+ *     touch pass's probe sequence and bounds, and copies them to block_coords; one read-back; fails when a coordinate is
+ *     outside [0, 65536) or given twice (the table then wants clearing).  The caller fills the voxel state.
+ * The same calls give the same bits whatever the block ids were.  Integer counters only, no float atomics.            */
+int d3d_tsdf_mesh_table(int8_t *out /* [6][16][13] */);
+size_t d3d_tsdf_mesh_scratch_bytes(int n_blocks);
+int d3d_tsdf_mesh_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
+                        int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
+                        size_t scratch_bytes, int *info_host /* [0] = V, [1] = T */, void *stream);
+int d3d_tsdf_mesh_vertices(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
+                           int table_slots, const float *tsdf, const float *color_state, const float *color_weight,
+                           double voxel, const double *origin, const int *info_host, const void *scratch,
+                           size_t scratch_bytes, float *vertices, float *vertex_color, int32_t *edges, void *stream);
+int d3d_tsdf_mesh_triangles(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
+                            int table_slots, const int *info_host, const void *scratch, size_t scratch_bytes,
+                            int32_t *triangles, void *stream);
+int d3d_tsdf_insert_blocks(const int32_t *coords, int n, void *table, int table_slots, int32_t *block_coords,
+                           int max_blocks, int32_t *state, void *stream);
+
 /* Posed depth frames from a triangle mesh: the step between gen_house_obj and gen_pcl of
  * data3d/suncg_utils/suncg_preprocess.py, which the reference leaves to an external OpenGL tool (scn2img).  vertices fp32
  * [n_vertices, 3] in world coordinates, triangles int32 [n_triangles, 3], vertex_color fp32 or uint8 [n_vertices, 3] or

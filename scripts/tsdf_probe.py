@@ -8,6 +8,8 @@ building of scripts/render_probe.py, cameras scattered through it.
 Timed, each on its own: the allocation pass on an empty volume ("touch_insert": every block is inserted) and on a volume
 that holds the blocks already ("touch_found": plain loads only; both include the call's read-back), the integration pass
 over all blocks, and the extraction (block sort, count, scan, read-back, rows; nine columns).  Warm calls first, then
+Beside the extraction, on the same volume, the mesh ("mesh": block sort, count, two scans, read-back, vertices with
+colours, triangles; TsdfVolume.mesh), with its vertex and triangle counts and scratch bytes.
 `rounds` rounds over the cases, interleaved.  "cold": a 1 GiB buffer is rewritten before the call, so that inputs and
 voxel state come from HBM; "warm": calls back to back.  Medians with quartiles.  Beside them fuse_frames and
 fuse_frames_tsdf as a user calls them.
@@ -162,6 +164,7 @@ def main():
     cases = {"touch_insert": touch_insert, "touch_found": lambda: vol._touch(fr, 1, *kw),
              "integrate": lambda: vol._update(fr, n, 0, *kw, 256.0),       # from zero state: the ids above are new ones
              "extract9": lambda: (setattr(vol, "_order", None), vol.surface_points(9))[1],
+             "mesh": lambda: (setattr(vol, "_order", None), vol.mesh())[1],
              "fuse_frames": lambda: fuse_frames(fr, voxel=args.voxel),
              "fuse_frames_tsdf": lambda: fuse_frames_tsdf(fr, voxel=args.voxel, max_blocks=args.max_blocks)}
     for fn in cases.values():
@@ -175,6 +178,11 @@ def main():
     for k in cases:
         row[k] = dict(_stats(cold[k]), warm=_stats(warm[k]))
     row["surface_rows"] = int(vol.surface_points(3).shape[0])
+    fused = vol.mesh()
+    row.update(mesh_vertices=int(fused.vertices.shape[0]), mesh_triangles=int(fused.triangles.shape[0]),
+               mesh_scratch_MB=round(_lib.lib().d3d_tsdf_mesh_scratch_bytes(n) / 1e6, 1),
+               mesh_referenced_vertices=int(torch.unique(fused.triangles).numel()))
+    del fused
     row["torch_over_kernel_integrate"] = round(row["torch_fp64_integrate_ms"] / row["integrate"]["median_ms"], 1)
     del evict, vol
     torch.cuda.empty_cache()
