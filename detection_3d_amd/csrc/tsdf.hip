@@ -290,6 +290,7 @@ __device__ __forceinline__ void load_apron(Apron &S, int b, const int32_t *__res
       const size_t at = (size_t)src * kVox + (a[0] * 8 + a[1]) * 8 + a[2];
       D = tsdf[at];
       W = weight[at];
+      if (!(fabsf(D) < INFINITY)) W = __builtin_nanf("");   // a tsdf that is not finite: not seen
     }
     S.D[i] = D;
     S.W[i] = W;

@@ -177,6 +177,7 @@ __global__ __launch_bounds__(kVox) void k_mesh_count(const int32_t *__restrict__
     if (src >= 0) {
       d = tsdf[(size_t)src * kVox + voxel];
       w = weight[(size_t)src * kVox + voxel];
+      if (!(fabsf(d) < INFINITY)) w = __builtin_nanf("");   // a tsdf that is not finite: not seen
     }
     D[i] = d;
     W[i] = w;

@@ -30,7 +30,7 @@ __device__ __forceinline__ int block_find(const HashEntry *__restrict__ tab, int
 }
 
 struct Apron {
-  float D[kApron], W[kApron];                // W = NaN: no such voxel (its block is not allocated)
+  float D[kApron], W[kApron];                // W = NaN: no such voxel (its block is not allocated, or its D is not finite)
   int nb[3];                                 // the +x, +y, +z neighbour blocks, or -1
 };
 

@@ -132,7 +132,8 @@ class TsdfVolume(object):
         """Fuses a batch of frames (DepthFrames) and returns the volume.  Allocates the blocks within trunc of every kept
         pixel's measurement along its ray (a pixel is kept as in unproject: valid depth, u and v multiples of `step`), then
         updates every voxel of every block, old and new, from every valid pixel of the frames in order (step plays no
-        part there).  One host read-back (the block count).  Raises D3DError when the blocks run out; the volume then
+        part there).  A voxel that from_blocks() gave a tsdf of NaN or +-inf keeps it: (w NaN + S) / (w + n).  One host
+        read-back (the block count).  Raises D3DError when the blocks run out; the volume then
         raises on every call until reset()."""
         step, min_depth, max_depth, color_div = _check_integrate(step, min_depth, max_depth, color_div)
         _need_frames(frames, "tsdf.integrate")
@@ -274,7 +275,9 @@ class TsdfVolume(object):
         """The inverse of blocks(): a volume that holds the given blocks, in any order.  coords int32 [B, 3] in [0,
         65536), no coordinate twice; tsdf, weight fp32 [B, 8, 8, 8]; color fp32 [B, 8, 8, 8, 3] and color_weight fp32 [B,
         8, 8, 8], both or neither (neither: a volume without colour); all on one GPU.  max_blocks: None for max(B, 2^18).
-        integrate() afterwards finds the blocks and carries on.  The host waits for the checks of the coordinates (two
+        integrate() afterwards finds the blocks and carries on.  Any fp32 state is taken as it is; a voxel whose tsdf is
+        NaN or +-inf is not seen by surface_points() and mesh() at any min_weight, whatever its weight, and integrate()
+        keeps it (the mean of a NaN stays NaN).  The host waits for the checks of the coordinates (two
         torch expressions) and for the insertion's read-back."""
         voxel, trunc = _check_volume(voxel, trunc)
 

@@ -581,7 +581,9 @@ int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, i
  *     pass the tests; culled_pairs (device, or NULL) is incremented by the number of such pairs.  One call of F frames
  *     and F calls of one frame may differ in the last bit.  Asynchronous.
  *   _order: order int32 [n_blocks], the block ids in ascending (x, y, z).  Asynchronous.
- *   _surface_*: a voxel is seen when double(W) >= min_weight.  Seen voxels in the order (block as in `order`, l with z
+ *   _surface_*: a voxel is seen when double(W) >= min_weight (false for a NaN) and its D is finite.  A D of NaN or +-inf is
+ *     not seen at any min_weight, so every row is finite; _integrate never produces one from finite state, and where a
+ *     caller stored one it stays ((W NaN + S) / (W + n) is NaN).  Seen voxels in the order (block as in `order`, l with z
  *     fastest), and for each axis a = x, y, z: h = g + e_a (in a neighbouring block where l_a = 7) must be allocated and
  *     seen; the edge crosses when (D_g < 0) != (D_h < 0) and then gives one row: s = double(D_g) / (double(D_g) -
  *     double(D_h)); position X_g with s * voxel added on axis a; colour (ncols >= 6): C_g + s * (C_h - C_g) per channel
@@ -618,7 +620,8 @@ int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int
 
 /* The TSDF volume above -> a triangle mesh of its zero crossing: marching tetrahedra on the Kuhn split of
  * every voxel cell; the reference has nothing like it.  Volume arguments as for d3d_tsdf_surface_*; `seen`, `inside`
- * (D < 0), X_i, s and the colour rule are those of d3d_tsdf_surface_rows.
+ * (D < 0), X_i, s and the colour rule are those of d3d_tsdf_surface_rows; so a voxel whose D is NaN or +-inf is not seen,
+ * gives no vertex, and no cell it is a corner of is emitted: every vertex is finite.
  *   cells: the cell of voxel g has the corners g + c, c in {0, 1}^3, in up to eight blocks (a block coordinate outside
  *     [0, 65536) is absent); it is emitted when all eight are allocated and seen.
  *   tetrahedra: t = 0..5 for the permutations p of the axes (x = 0, y = 1, z = 2) in lexicographic order xyz, xzy, yxz,

@@ -103,7 +103,9 @@ def mesh_ref(blocks, voxel, origin, min_weight=1, color=True):
     for j, c in enumerate(coords - lo):
         s = tuple(slice(8 * c[i], 8 * c[i] + 8) for i in range(3))
         Dd[s] = D[j]
-        seen[s] = W[j].astype(np.float64) >= min_weight              # a block coordinate past 65535 is never present
+        with np.errstate(invalid="ignore"):
+            seen[s] = W[j].astype(np.float64) >= min_weight          # a block coordinate past 65535 is never present
+        seen[s] &= np.isfinite(D[j])                                 # a tsdf that is not finite: not seen
         block_rank[s] = j
         if has_color:
             Cd[s], CWd[s] = C[j], CW[j]

@@ -145,7 +145,9 @@ class TsdfRef(object):
         if B == 0:
             return np.zeros((0, columns), np.float32), np.zeros((0, 3), np.int32), np.zeros(0, bool)
         where = {tuple(c): j for j, c in enumerate(coords.tolist())}
-        seen = W.astype(np.float64) >= min_weight
+        with np.errstate(invalid="ignore"):
+            seen = W.astype(np.float64) >= min_weight
+        seen &= np.isfinite(D)                            # a tsdf that is not finite: not seen
 
         def forward(a, arrays, fills):
             """the arrays shifted by one voxel along +axis a, across block borders; `fills` where no block is"""
