@@ -33,6 +33,27 @@ class ConvDesc(ctypes.Structure):
                 ("form", c_int_p)]
 
 
+class DepthFramesDesc(ctypes.Structure):
+    """d3d_depth_frames (include/d3d_hip.h): a batch of posed depth frames, device pointers."""
+    _fields_ = [("depth", vp), ("depth_is_u16", ctypes.c_int), ("color", vp), ("color_is_u8", ctypes.c_int),
+                ("intrinsics", vp), ("extrinsics", vp), ("frames", ctypes.c_int), ("height", ctypes.c_int),
+                ("width", ctypes.c_int), ("depth_scale", ctypes.c_double)]
+
+
+class TsdfVolumeDesc(ctypes.Structure):
+    """d3d_tsdf_volume (include/d3d_hip.h): a TSDF block volume, device pointers (origin: host values)."""
+    _fields_ = [("voxel", ctypes.c_double), ("trunc", ctypes.c_double), ("origin", ctypes.c_double * 3), ("table", vp),
+                ("table_slots", ctypes.c_int), ("block_coords", vp), ("max_blocks", ctypes.c_int),
+                ("n_blocks", ctypes.c_int), ("state", vp), ("order", vp), ("tsdf", vp), ("weight", vp),
+                ("color_state", vp), ("color_weight", vp)]
+
+
+class TriangleMeshDesc(ctypes.Structure):
+    """d3d_triangle_mesh (include/d3d_hip.h): a triangle mesh, device pointers."""
+    _fields_ = [("vertices", vp), ("n_vertices", ctypes.c_int), ("triangles", vp), ("n_triangles", ctypes.c_int),
+                ("vertex_color", vp), ("color_is_u8", ctypes.c_int)]
+
+
 class AugmentParams(ctypes.Structure):
     """d3d_augment_params (include/d3d_hip.h): one scene's augmentation, host memory."""
     _fields_ = [("m", ctypes.c_double * 9), ("nrm", ctypes.c_double * 9), ("color", ctypes.c_double * 3),
@@ -47,6 +68,9 @@ class GlobalAlignDetails(ctypes.Structure):
 
 
 aug_p = ctypes.POINTER(AugmentParams)
+frames_p = ctypes.POINTER(DepthFramesDesc)
+volume_p = ctypes.POINTER(TsdfVolumeDesc)
+mesh_p = ctypes.POINTER(TriangleMeshDesc)
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
@@ -154,46 +178,32 @@ _SIGS = {
     "d3d_sample_rows_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "d3d_sample_rows": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, vp, ctypes.c_size_t, vp]),
     "d3d_unproject_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "d3d_unproject_count": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_size_t,
+    "d3d_unproject_count": (ctypes.c_int, [frames_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_size_t,
                                            c_int_p, vp]),
-    "d3d_unproject_rows": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t,
-                                          vp, vp, vp]),
+    "d3d_unproject_rows": (ctypes.c_int, [frames_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp, vp, vp]),
     "d3d_tsdf_table_slots": (ctypes.c_int, [ctypes.c_int]),
-    "d3d_tsdf_touch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p,
-                                      ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, c_int_p, vp]),
-    "d3d_tsdf_integrate": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_double, c_double_p, vp, ctypes.c_int, ctypes.c_int,
-                                          vp, vp, vp, vp, vp, vp]),
+    "d3d_tsdf_touch": (ctypes.c_int, [frames_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, volume_p, ctypes.c_int,
+                                      c_int_p, vp]),
+    "d3d_tsdf_integrate": (ctypes.c_int, [frames_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, volume_p,
+                                          ctypes.c_int, vp, vp]),
     "d3d_tsdf_order_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "d3d_tsdf_order": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
     "d3d_tsdf_surface_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "d3d_tsdf_surface_count": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_double, vp,
-                                              ctypes.c_size_t, c_int_p, vp]),
-    "d3d_tsdf_surface_rows": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double,
-                                             c_double_p, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp,
-                                             vp, vp]),
+    "d3d_tsdf_surface_count": (ctypes.c_int, [volume_p, ctypes.c_double, vp, ctypes.c_size_t, c_int_p, vp]),
+    "d3d_tsdf_surface_rows": (ctypes.c_int, [volume_p, ctypes.c_double, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp, vp,
+                                             vp]),
     "d3d_tsdf_mesh_table": (ctypes.c_int, [vp]),
     "d3d_tsdf_mesh_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "d3d_tsdf_mesh_count": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_double, vp,
-                                           ctypes.c_size_t, c_int_p, vp]),
-    "d3d_tsdf_mesh_vertices": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, ctypes.c_double,
-                                              c_double_p, c_int_p, vp, ctypes.c_size_t, vp, vp, vp, vp]),
-    "d3d_tsdf_mesh_triangles": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, vp,
-                                               vp]),
-    "d3d_tsdf_insert_blocks": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp]),
+    "d3d_tsdf_mesh_count": (ctypes.c_int, [volume_p, ctypes.c_double, vp, ctypes.c_size_t, c_int_p, vp]),
+    "d3d_tsdf_mesh_vertices": (ctypes.c_int, [volume_p, c_int_p, vp, ctypes.c_size_t, vp, vp, vp, vp]),
+    "d3d_tsdf_mesh_triangles": (ctypes.c_int, [volume_p, c_int_p, vp, ctypes.c_size_t, vp, vp]),
+    "d3d_tsdf_insert_blocks": (ctypes.c_int, [vp, ctypes.c_int, volume_p, vp]),
     "d3d_render_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "d3d_render_bin": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, vp, ctypes.c_size_t, c_int64_p, vp]),
-    "d3d_render_fill": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_int, c_int64_p, vp, ctypes.c_size_t, vp, vp]),
-    "d3d_render_tiles": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                        ctypes.c_double, c_int64_p, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]),
+    "d3d_render_bin": (ctypes.c_int, [mesh_p, frames_p, vp, ctypes.c_size_t, c_int64_p, vp]),
+    "d3d_render_fill": (ctypes.c_int, [mesh_p, frames_p, c_int64_p, vp, ctypes.c_size_t, vp, vp]),
+    "d3d_render_tiles": (ctypes.c_int, [mesh_p, frames_p, ctypes.c_double, ctypes.c_double, c_int64_p, vp, ctypes.c_size_t,
+                                        vp, vp, vp]),
     "d3d_input_layer_build": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                              ctypes.c_int, vp, c_int_p]),
     "d3d_input_layer_build_prefetch": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,

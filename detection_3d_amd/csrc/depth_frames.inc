@@ -1,6 +1,7 @@
 // A batch of posed depth frames as the kernels of unproject.hip and tsdf.hip read it: the depth of a pixel, which
 // depths count as a measurement, which pixels a call keeps, and the camera of a frame.  The arithmetic is the contract
-// of include/d3d_hip.h (d3d_unproject_*); both files include this one so that there is one definition of it.
+// of include/d3d_hip.h (d3d_unproject_*); both files, and render.hip for the camera and the frames it fills, include this
+// one so that there is one definition of it, and one host-side check of a d3d_depth_frames.
 // Included inside namespace d3d's anonymous namespace.
 
 struct DepthView {
@@ -55,17 +56,34 @@ __device__ __forceinline__ void cam_point(const Camera &K, int u, int v, double 
   C[2] = z;
 }
 
-// the checked shape -> the view (depth pointer aside); D3D_OK with P == 0 for an empty batch
-inline int make_view(const char *who, int frames, int height, int width, int step, int depth_is_u16, double depth_scale,
-                     double min_depth, double max_depth, DepthView &V) {
-  D3D_REQUIRE(frames >= 0 && height >= 1 && width >= 1, "%s: %d frames of %d x %d pixels", who, frames, height, width);
+// ---- the host's check of a d3d_depth_frames ----
+
+enum { kFramesDepth = 1, kFramesCameras = 2 };   // what a call reads of a batch that has pixels
+
+// the descriptor's shape -> its pixels; D3D_OK with P == 0 for an empty batch
+inline int frames_shape(const char *who, const d3d_depth_frames *F, long &P) {
+  D3D_REQUIRE(F, "%s: null pointer", who);
+  D3D_REQUIRE(F->frames >= 0 && F->height >= 1 && F->width >= 1, "%s: %d frames of %d x %d pixels", who, F->frames,
+              F->height, F->width);
+  const double pixels = (double)F->frames * (double)F->height * (double)F->width;
+  D3D_REQUIRE(pixels < 2147483648.0, "%s: %d x %d x %d = %.0f pixels do not fit 31 bits (use fewer frames per call)", who,
+              F->frames, F->height, F->width, pixels);
+  P = (long)pixels;
+  return D3D_OK;
+}
+
+// the checked descriptor and the call's own choices -> the view; `needs`: the pointers that must not be null when P > 0
+inline int frames_view(const char *who, const d3d_depth_frames *F, int step, double min_depth, double max_depth, int needs,
+                       DepthView &V) {
+  long P = 0;
+  const int rc = frames_shape(who, F, P);
+  if (rc) return rc;
   D3D_REQUIRE(step >= 1, "%s: step %d < 1", who, step);
-  const double P = (double)frames * (double)height * (double)width;
-  D3D_REQUIRE(P < 2147483648.0, "%s: %d x %d x %d = %.0f pixels do not fit 31 bits (use fewer frames per call)", who,
-              frames, height, width, P);
-  D3D_REQUIRE(!depth_is_u16 || (depth_scale > 0.0 && depth_scale < (double)INFINITY),
-              "%s: depth_scale %g must be positive and finite", who, depth_scale);
+  D3D_REQUIRE(!F->depth_is_u16 || (F->depth_scale > 0.0 && F->depth_scale < (double)INFINITY),
+              "%s: depth_scale %g must be positive and finite", who, F->depth_scale);
   D3D_REQUIRE(min_depth == min_depth && max_depth == max_depth, "%s: min_depth / max_depth is NaN", who);
-  V = DepthView{nullptr, depth_is_u16 ? 1 : 0, height, width, step, (long)P, depth_scale, min_depth, max_depth};
+  D3D_REQUIRE(P == 0 || ((!(needs & kFramesDepth) || F->depth) && (!(needs & kFramesCameras) || (F->intrinsics && F->extrinsics))),
+              "%s: null pointer", who);
+  V = DepthView{F->depth, F->depth_is_u16 ? 1 : 0, F->height, F->width, step, P, F->depth_scale, min_depth, max_depth};
   return D3D_OK;
 }

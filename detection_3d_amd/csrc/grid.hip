@@ -216,7 +216,7 @@ using namespace d3d;
 extern "C" {
 
 const char *d3d_last_error(void) { return d3d::g_err; }
-int d3d_abi_version(void) { return 2; }
+int d3d_abi_version(void) { return 3; }
 
 int d3d_meta_create(d3d_meta **out, size_t arena_bytes) {
   D3D_REQUIRE(out && arena_bytes >= (1u << 20), "d3d_meta_create: bad arguments");

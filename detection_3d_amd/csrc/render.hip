@@ -26,6 +26,8 @@ namespace d3d {
 
 namespace {
 
+#include "depth_frames.inc"   // Camera, load_camera; DepthView and frames_shape, frames_view for the frames a call fills
+
 constexpr int kTile = 16;
 constexpr int kThreads = kTile * kTile;
 constexpr int kBatch = 256;                  // triangles staged at a time: 10 doubles + an index each, 21 KiB of LDS
@@ -41,21 +43,6 @@ struct Views {
   const double *intr, *extr;                 // [F, 4], [F, 3, 4]
   int F, H, W, tx, ty;                       // tiles per row and per column of one frame
 };
-
-struct Camera {
-  double fx, fy, cx, cy, E[12];
-};
-
-__device__ __forceinline__ Camera load_camera(const Views &C, int f) {
-  Camera K;
-  K.fx = C.intr[4 * f + 0];
-  K.fy = C.intr[4 * f + 1];
-  K.cx = C.intr[4 * f + 2];
-  K.cy = C.intr[4 * f + 3];
-#pragma unroll
-  for (int k = 0; k < 12; k++) K.E[k] = C.extr[12 * f + k];
-  return K;
-}
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }      // false for NaN
 __device__ __forceinline__ bool finite_d(double v) { return fabs(v) < (double)INFINITY; }
@@ -75,9 +62,9 @@ __device__ __forceinline__ bool camera_vertices(const Mesh &M, const Camera &K, 
     const float *x = M.vertices + 3 * (long)idx[j];
     const float x0 = x[0], x1 = x[1], x2 = x[2];
     ok = ok && finite_f(x0) && finite_f(x1) && finite_f(x2);
-    const double d0 = (double)x0 - K.E[3], d1 = (double)x1 - K.E[7], d2 = (double)x2 - K.E[11];
+    const double d0 = (double)x0 - K.t[0], d1 = (double)x1 - K.t[1], d2 = (double)x2 - K.t[2];
 #pragma unroll
-    for (int k = 0; k < 3; k++) P[j][k] = (K.E[k] * d0 + K.E[4 + k] * d1) + K.E[8 + k] * d2;
+    for (int k = 0; k < 3; k++) P[j][k] = (K.R[0][k] * d0 + K.R[1][k] * d1) + K.R[2][k] * d2;
   }
   return ok;
 }
@@ -130,7 +117,8 @@ __global__ __launch_bounds__(kThreads) void k_rd_bin(Mesh M, Views C, int32_t *_
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i < (long)C.F * M.T) {
     const int f = (int)(i / M.T), tri = (int)(i - (long)f * M.T);
-    const Camera K = load_camera(C, f);
+    Camera K;
+    load_camera(C.intr, C.extr, f, K);
     int x0, x1, y0, y1;
     if (tile_rect(M, C, K, tri, x0, x1, y0, y1)) {
       int32_t *tiles = counts_or_cursor + (long)f * C.tx * C.ty;
@@ -166,7 +154,8 @@ __global__ __launch_bounds__(kThreads) void k_rd_tiles(Mesh M, Views C, const in
   const int per_frame = C.tx * C.ty;
   const int f = blockIdx.x / per_frame, t = blockIdx.x - f * per_frame;
   const int u = (t % C.tx) * kTile + (tid & (kTile - 1)), v = (t / C.tx) * kTile + tid / kTile;
-  const Camera K = load_camera(C, f);
+  Camera K;
+  load_camera(C.intr, C.extr, f, K);
   const double dx = ((double)u - K.cx) / K.fx, dy = ((double)v - K.cy) / K.fy;
   double bz = INFINITY, be0 = 0.0, be1 = 0.0, be2 = 0.0;
   int bid = -1;
@@ -263,27 +252,28 @@ int carve(Arena &A, long n_tiles, Layout &L) {
   return D3D_OK;
 }
 
-// the checked shapes -> mesh and views (pointers aside); n_tiles == 0 or T == 0 or V == 0: nothing to do
-int make_views(const char *who, int n_vertices, int n_triangles, int frames, int height, int width, Mesh &M, Views &C,
+// the checked descriptors -> mesh and views; n_tiles == 0 or T == 0 or V == 0: nothing to do, and no pointer is wanted
+int make_views(const char *who, const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, Mesh &M, Views &C,
                long &n_tiles) {
-  D3D_REQUIRE(n_vertices >= 0 && n_triangles >= 0, "%s: %d vertices, %d triangles", who, n_vertices, n_triangles);
-  D3D_REQUIRE(frames >= 0 && height >= 1 && width >= 1, "%s: %d frames of %d x %d pixels", who, frames, height, width);
-  const double P = (double)frames * (double)height * (double)width;
-  D3D_REQUIRE(P < 2147483648.0, "%s: %d x %d x %d = %.0f pixels do not fit 31 bits (use fewer frames per call)", who,
-              frames, height, width, P);
-  D3D_REQUIRE((double)frames * (double)n_triangles < 2147483648.0 * (double)kThreads,
-              "%s: %d frames x %d triangles are too many for one call (use fewer frames per call)", who, frames,
-              n_triangles);
-  M = Mesh{nullptr, nullptr, n_vertices, n_triangles};
-  C = Views{nullptr, nullptr, frames, height, width, (int)tiles_of(width), (int)tiles_of(height)};
-  n_tiles = (long)frames * C.tx * C.ty;
+  D3D_REQUIRE(mesh, "%s: null pointer", who);
+  D3D_REQUIRE(mesh->n_vertices >= 0 && mesh->n_triangles >= 0, "%s: %d vertices, %d triangles", who, mesh->n_vertices,
+              mesh->n_triangles);
+  long P = 0;
+  const int rc = frames_shape(who, frames, P);
+  if (rc) return rc;
+  D3D_REQUIRE((double)frames->frames * (double)mesh->n_triangles < 2147483648.0 * (double)kThreads,
+              "%s: %d frames x %d triangles are too many for one call (use fewer frames per call)", who, frames->frames,
+              mesh->n_triangles);
+  M = Mesh{mesh->vertices, mesh->triangles, mesh->n_vertices, mesh->n_triangles};
+  C = Views{frames->intrinsics, frames->extrinsics, frames->frames, frames->height, frames->width,
+            (int)tiles_of(frames->width), (int)tiles_of(frames->height)};
+  n_tiles = (long)C.F * C.tx * C.ty;
   return D3D_OK;
 }
 
-int open_scratch(const char *who, void *scratch, size_t scratch_bytes, int frames, int height, int width, long n_tiles,
-                 Arena &A, Layout &L) {
+int open_scratch(const char *who, void *scratch, size_t scratch_bytes, const Views &C, long n_tiles, Arena &A, Layout &L) {
   D3D_REQUIRE(scratch, "%s: null pointer", who);
-  D3D_REQUIRE(scratch_bytes >= d3d_render_scratch_bytes(frames, height, width), "%s: scratch too small", who);
+  D3D_REQUIRE(scratch_bytes >= d3d_render_scratch_bytes(C.F, C.H, C.W), "%s: scratch too small", who);
   A = scratch_arena(scratch, scratch_bytes);
   return carve(A, n_tiles, L);
 }
@@ -298,27 +288,25 @@ size_t d3d_render_scratch_bytes(int frames, int height, int width) {
   return 512 + 2 * ((n + 2) * 4 + 256) + (n / 2048 + 1) * 4 + 4096;
 }
 
-int d3d_render_bin(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                   const double *intrinsics, const double *extrinsics, int frames, int height, int width, void *scratch,
-                   size_t scratch_bytes, int64_t *info_host, void *stream) {
+int d3d_render_bin(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, void *scratch, size_t scratch_bytes,
+                   int64_t *info_host, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_render_bin: null pointer");
   info_host[0] = 0;
   Mesh M;
   Views C;
   long n_tiles;
-  int rc = make_views("d3d_render_bin", n_vertices, n_triangles, frames, height, width, M, C, n_tiles);
+  int rc = make_views("d3d_render_bin", mesh, frames, M, C, n_tiles);
   if (rc) return rc;
   if (n_tiles == 0 || M.T == 0 || M.V == 0) return D3D_OK;
-  D3D_REQUIRE(vertices && triangles && intrinsics && extrinsics, "d3d_render_bin: null pointer");
+  D3D_REQUIRE(M.vertices && M.triangles && C.intr && C.extr, "d3d_render_bin: null pointer");
   Arena A;
   Layout L;
-  rc = open_scratch("d3d_render_bin", scratch, scratch_bytes, frames, height, width, n_tiles, A, L);
+  rc = open_scratch("d3d_render_bin", scratch, scratch_bytes, C, n_tiles, A, L);
   if (rc) return rc;
-  M.vertices = vertices, M.triangles = triangles, C.intr = intrinsics, C.extr = extrinsics;
   D3D_HIP_CHECK(hipMemsetAsync(L.total, 0, 32 * sizeof(unsigned long long), s));
   D3D_HIP_CHECK(hipMemsetAsync(L.counts, 0, ((size_t)n_tiles + 2) * sizeof(int32_t), s));
-  const long work = (long)frames * M.T;
+  const long work = (long)C.F * M.T;
   hipLaunchKernelGGL(k_rd_bin<false>, dim3((unsigned)((work + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, M, C,
                      L.counts, L.total, (int32_t *)nullptr, 0L);
   D3D_LAUNCH_CHECK();
@@ -329,61 +317,55 @@ int d3d_render_bin(const float *vertices, int n_vertices, const int32_t *triangl
   return readback_wait(info_host, 2);
 }
 
-int d3d_render_fill(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                    const double *intrinsics, const double *extrinsics, int frames, int height, int width,
-                    const int64_t *info_host, void *scratch, size_t scratch_bytes, int32_t *lists, void *stream) {
+int d3d_render_fill(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, const int64_t *info_host,
+                    void *scratch, size_t scratch_bytes, int32_t *lists, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_render_fill: null pointer");
   Mesh M;
   Views C;
   long n_tiles;
-  int rc = make_views("d3d_render_fill", n_vertices, n_triangles, frames, height, width, M, C, n_tiles);
+  int rc = make_views("d3d_render_fill", mesh, frames, M, C, n_tiles);
   if (rc) return rc;
   const int64_t E = info_host[0];
   D3D_REQUIRE(E >= 0 && E < 2147483648LL, "d3d_render_fill: %lld list entries do not fit 31 bits (use fewer frames per call)",
               (long long)E);
   if (n_tiles == 0 || M.T == 0 || M.V == 0 || E == 0) return D3D_OK;
-  D3D_REQUIRE(vertices && triangles && intrinsics && extrinsics && lists, "d3d_render_fill: null pointer");
+  D3D_REQUIRE(M.vertices && M.triangles && C.intr && C.extr && lists, "d3d_render_fill: null pointer");
   Arena A;
   Layout L;
-  rc = open_scratch("d3d_render_fill", scratch, scratch_bytes, frames, height, width, n_tiles, A, L);
+  rc = open_scratch("d3d_render_fill", scratch, scratch_bytes, C, n_tiles, A, L);
   if (rc) return rc;
-  M.vertices = vertices, M.triangles = triangles, C.intr = intrinsics, C.extr = extrinsics;
-  const long work = (long)frames * M.T;
+  const long work = (long)C.F * M.T;
   hipLaunchKernelGGL(k_rd_bin<true>, dim3((unsigned)((work + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, M, C,
                      L.offsets, (unsigned long long *)nullptr, lists, (long)E);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
 
-int d3d_render_tiles(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                     const void *vertex_color, int color_is_u8, const double *intrinsics, const double *extrinsics,
-                     int frames, int height, int width, double min_depth, double max_depth, int depth_is_u16,
-                     double depth_scale, const int64_t *info_host, const void *scratch, size_t scratch_bytes,
-                     const int32_t *lists, void *depth, int32_t *tri, void *color, void *stream) {
+int d3d_render_tiles(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, double min_depth, double max_depth,
+                     const int64_t *info_host, const void *scratch, size_t scratch_bytes, const int32_t *lists,
+                     int32_t *tri, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_render_tiles: null pointer");
-  D3D_REQUIRE(min_depth == min_depth && max_depth == max_depth, "d3d_render_tiles: min_depth / max_depth is NaN");
-  D3D_REQUIRE(!depth_is_u16 || (depth_scale > 0.0 && depth_scale < (double)INFINITY),
-              "d3d_render_tiles: depth_scale %g must be positive and finite", depth_scale);
-  D3D_REQUIRE(!color == !vertex_color, "d3d_render_tiles: a colour image needs vertex colours and the reverse");
   Mesh M;
   Views C;
   long n_tiles;
-  int rc = make_views("d3d_render_tiles", n_vertices, n_triangles, frames, height, width, M, C, n_tiles);
+  int rc = make_views("d3d_render_tiles", mesh, frames, M, C, n_tiles);
   if (rc) return rc;
+  DepthView V;                               // the images to fill: the depth format, and the pointers wanted when P > 0
+  rc = frames_view("d3d_render_tiles", frames, 1, min_depth, max_depth, kFramesDepth | kFramesCameras, V);
+  if (rc) return rc;
+  D3D_REQUIRE(!frames->color == !mesh->vertex_color, "d3d_render_tiles: a colour image needs vertex colours and the reverse");
   const int64_t E = info_host[0];
   D3D_REQUIRE(E >= 0 && E < 2147483648LL, "d3d_render_tiles: %lld list entries do not fit 31 bits", (long long)E);
   if (n_tiles == 0) return D3D_OK;
   D3D_REQUIRE(M.T > 0 && M.V > 0, "d3d_render_tiles: an empty mesh has no lists (the images are zeros)");
-  D3D_REQUIRE(vertices && triangles && intrinsics && extrinsics && depth && (lists || E == 0),
-              "d3d_render_tiles: null pointer");
+  D3D_REQUIRE(M.vertices && M.triangles && (lists || E == 0), "d3d_render_tiles: null pointer");
   Arena A;
   Layout L;
-  rc = open_scratch("d3d_render_tiles", const_cast<void *>(scratch), scratch_bytes, frames, height, width, n_tiles, A, L);
+  rc = open_scratch("d3d_render_tiles", const_cast<void *>(scratch), scratch_bytes, C, n_tiles, A, L);
   if (rc) return rc;
-  M.vertices = vertices, M.triangles = triangles, C.intr = intrinsics, C.extr = extrinsics;
-  const Output O{depth, tri, color, vertex_color, depth_is_u16 ? 1 : 0, color_is_u8 ? 1 : 0, depth_scale, min_depth, max_depth};
+  const Output O{frames->depth, tri, frames->color, mesh->vertex_color, V.is_u16, mesh->color_is_u8 ? 1 : 0, V.scale, V.zmin, V.zmax};
   hipLaunchKernelGGL(k_rd_tiles, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, M, C, (const int32_t *)L.counts,
                      (const int32_t *)L.offsets, lists, (long)E, O);
   D3D_LAUNCH_CHECK();

@@ -22,8 +22,8 @@
 //              (voxel, axis) with mbcnt over the wave's ballots, packs rows in LDS and stores whole lines, and never
 //              writes past the rows it was given.
 // No float atomics: the only atomics are the swap on a table key and integer counters.
-// The volume as a kernel sees it (sizes, state words, VolumeView, block_find, Apron) is tsdf_volume.inc, shared with
-// tsdf_mesh.hip, which turns the same volume into a triangle mesh.
+// The volume as a kernel sees it (sizes, state words, VolumeView, block_find, Apron and its staging) and the host's check
+// of a d3d_tsdf_volume are tsdf_volume.inc, shared with tsdf_mesh.hip, which turns the same volume into a triangle mesh.
 #include "d3d_internal.h"
 
 #include <algorithm>
@@ -262,42 +262,7 @@ int carve_order(Arena &A, int n, OrderLayout &L) {
 
 // ---- surface ----
 
-// block_find, Apron: tsdf_volume.inc
-__device__ __forceinline__ void load_apron(Apron &S, int b, const int32_t *__restrict__ coords,
-                                           const HashEntry *__restrict__ tab, int cap, int n_blocks,
-                                           const float *__restrict__ tsdf, const float *__restrict__ weight) {
-  const int tid = threadIdx.x;
-  if (tid < 3) {
-    int q[3] = {coords[3 * (size_t)b + 0], coords[3 * (size_t)b + 1], coords[3 * (size_t)b + 2]};
-    q[tid] += 1;
-    S.nb[tid] = block_find(tab, cap, q[0], q[1], q[2], n_blocks);
-  }
-  __syncthreads();
-  for (int i = tid; i < kApron; i += kVox) {
-    int a[3] = {i / 81, (i / 9) % 9, i % 9};
-    int src = b, over = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      if (a[k] == 8) {
-        over++;
-        src = S.nb[k];
-        a[k] = 0;
-      }
-    }
-    if (over > 1) src = -1;                  // an edge or corner of the apron: no forward neighbour lies there
-    float D = 0.f, W = __builtin_nanf("");
-    if (src >= 0) {
-      const size_t at = (size_t)src * kVox + (a[0] * 8 + a[1]) * 8 + a[2];
-      D = tsdf[at];
-      W = weight[at];
-      if (!(fabsf(D) < INFINITY)) W = __builtin_nanf("");   // a tsdf that is not finite: not seen
-    }
-    S.D[i] = D;
-    S.W[i] = W;
-  }
-  __syncthreads();
-}
-
+// block_find, Apron, load_apron: tsdf_volume.inc.  The edges of a voxel run along the axes, so the face neighbours do.
 struct Edges {
   float Dg, Dh[3];
   bool seen_h[3], cross[3];
@@ -330,7 +295,7 @@ __global__ __launch_bounds__(kVox) void k_tsdf_count(const int32_t *__restrict__
     if (tid == 0) counts[blockIdx.x] = 0;
     return;
   }
-  load_apron(S, b, coords, tab, cap, n_blocks, tsdf, weight);
+  load_apron<false>(S, b, coords, tab, cap, n_blocks, tsdf, weight);
   Edges E;
   voxel_edges(S, tid, min_weight, E);
   const int cnt = (__popcll(__ballot(E.cross[0])) + __popcll(__ballot(E.cross[1]))) + __popcll(__ballot(E.cross[2]));
@@ -357,7 +322,7 @@ __global__ __launch_bounds__(kVox) void k_tsdf_rows(const int32_t *__restrict__ 
   const int tid = threadIdx.x, wave = tid >> 6;
   const int b = order[blockIdx.x];
   if ((unsigned)b >= (unsigned)n_blocks) return;   // the same in every thread
-  load_apron(S, b, coords, tab, cap, n_blocks, tsdf, weight);
+  load_apron<false>(S, b, coords, tab, cap, n_blocks, tsdf, weight);
   Edges E;
   voxel_edges(S, tid, min_weight, E);
   const unsigned long long b0 = __ballot(E.cross[0]), b1 = __ballot(E.cross[1]), b2 = __ballot(E.cross[2]);
@@ -412,7 +377,7 @@ __global__ __launch_bounds__(kVox) void k_tsdf_rows(const int32_t *__restrict__ 
         float col[3] = {0.f, 0.f, 0.f};
         if (cstate) {
           int lh[3] = {l[0], l[1], l[2]};
-          const int hb = lh[a] == 7 ? S.nb[a] : b;   // >= 0: the edge crosses, so the neighbour is allocated
+          const int hb = lh[a] == 7 ? S.nb[1 << a] : b;   // >= 0: the edge crosses, so the neighbour is allocated
           lh[a] = (lh[a] + 1) & 7;
           const size_t ig = (size_t)b * kVox + tid, ih = (size_t)hb * kVox + (lh[0] * 8 + lh[1]) * 8 + lh[2];
           const bool has_g = cweight[ig] > 0.f, has_h = hb >= 0 && cweight[ih] > 0.f;
@@ -489,61 +454,54 @@ int d3d_tsdf_table_slots(int max_blocks) {
   return (int)c;
 }
 
-int d3d_tsdf_touch(const void *depth, int depth_is_u16, const double *intrinsics, const double *extrinsics, int frames,
-                   int height, int width, int step, double depth_scale, double min_depth, double max_depth, double voxel,
-                   const double *origin, int reach, void *table, int table_slots, int32_t *block_coords, int max_blocks,
-                   int32_t *state, int *info_host, void *stream) {
+int d3d_tsdf_touch(const d3d_depth_frames *frames, int step, double min_depth, double max_depth,
+                   const d3d_tsdf_volume *volume, int reach, int *info_host, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_tsdf_touch: null pointer");
   info_host[0] = info_host[1] = info_host[2] = 0;
   DepthView V;
-  int rc = make_view("d3d_tsdf_touch", frames, height, width, step, depth_is_u16, depth_scale, min_depth, max_depth, V);
+  int rc = frames_view("d3d_tsdf_touch", frames, step, min_depth, max_depth, kFramesDepth | kFramesCameras, V);
   if (rc) return rc;
   VolumeView G;
-  rc = make_volume("d3d_tsdf_touch", voxel, voxel, origin, G);
+  rc = volume_view("d3d_tsdf_touch", volume, kVolGeometry | kVolGrow, G);
   if (rc) return rc;
   D3D_REQUIRE(reach >= 0 && reach <= kMaxReach, "d3d_tsdf_touch: reach %d outside [0, %d] voxels", reach, kMaxReach);
-  D3D_REQUIRE(max_blocks >= 1 && max_blocks <= kMaxBlocks, "d3d_tsdf_touch: max_blocks %d outside [1, 2^22]", max_blocks);
-  D3D_REQUIRE(table_ok(table, table_slots, max_blocks) && block_coords && state,
-              "d3d_tsdf_touch: the table has d3d_tsdf_table_slots(max_blocks) slots; null pointer");
   if (V.P > 0) {
-    D3D_REQUIRE(depth && intrinsics && extrinsics, "d3d_tsdf_touch: null pointer");
-    V.depth = depth;
     hipLaunchKernelGGL(k_tsdf_touch, dim3((unsigned)((V.P + kTouchRun - 1) / kTouchRun)), dim3(kTouchThreads), 0, s, V,
-                       intrinsics, extrinsics, G, reach, (HashEntry *)table, table_slots, block_coords, max_blocks, state);
+                       frames->intrinsics, frames->extrinsics, G, reach, (HashEntry *)volume->table, volume->table_slots,
+                       volume->block_coords, volume->max_blocks, volume->state);
     D3D_LAUNCH_CHECK();
   }
-  rc = readback_publish(state, kStWords, s);
+  rc = readback_publish(volume->state, kStWords, s);
   if (rc) return rc;
   int32_t host[kStWords];
   rc = readback_wait(host, kStWords);
   if (rc) return rc;
   info_host[0] = host[kStBlocks];
   info_host[1] = host[kStClipped];
-  info_host[2] = (host[kStFull] || host[kStBlocks] > max_blocks || host[kStBlocks] < 0) ? 1 : 0;
+  info_host[2] = (host[kStFull] || host[kStBlocks] > volume->max_blocks || host[kStBlocks] < 0) ? 1 : 0;
   return D3D_OK;
 }
 
-int d3d_tsdf_integrate(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
-                       const double *intrinsics, const double *extrinsics, int frames, int height, int width,
-                       double depth_scale, double min_depth, double max_depth, double voxel, double trunc,
-                       const double *origin, const int32_t *block_coords, int n_blocks, int first_new, float *tsdf,
-                       float *weight, float *color_state, float *color_weight, unsigned long long *culled_pairs,
-                       void *stream) {
+int d3d_tsdf_integrate(const d3d_depth_frames *frames, double min_depth, double max_depth, double color_div,
+                       const d3d_tsdf_volume *volume, int first_new, unsigned long long *culled_pairs, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   DepthView V;
-  int rc = make_view("d3d_tsdf_integrate", frames, height, width, 1, depth_is_u16, depth_scale, min_depth, max_depth, V);
+  int rc = frames_view("d3d_tsdf_integrate", frames, 1, min_depth, max_depth, kFramesDepth | kFramesCameras, V);
   if (rc) return rc;
   VolumeView G;
-  rc = make_volume("d3d_tsdf_integrate", voxel, trunc, origin, G);
+  rc = volume_view("d3d_tsdf_integrate", volume, kVolGeometry | kVolTrunc | kVolBlocks | kVolTsdf | kVolWeight, G);
   if (rc) return rc;
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks && first_new >= 0 && first_new <= n_blocks,
-              "d3d_tsdf_integrate: %d blocks, the new ones from %d", n_blocks, first_new);
-  D3D_REQUIRE(!(color && color_is_u8) || (color_div > 0.0 && color_div < (double)INFINITY),
+  const int n_blocks = volume->n_blocks;
+  float *tsdf = volume->tsdf, *weight = volume->weight, *color_state = volume->color_state,
+        *color_weight = volume->color_weight;
+  const void *color = frames->color;
+  D3D_REQUIRE(first_new >= 0 && first_new <= n_blocks, "d3d_tsdf_integrate: %d blocks, the new ones from %d", n_blocks,
+              first_new);
+  D3D_REQUIRE(!(color && frames->color_is_u8) || (color_div > 0.0 && color_div < (double)INFINITY),
               "d3d_tsdf_integrate: color_div %g must be positive and finite", color_div);
   D3D_REQUIRE(!color || (color_state && color_weight), "d3d_tsdf_integrate: a colour image and a volume without colour");
   if (n_blocks == 0) return D3D_OK;
-  D3D_REQUIRE(block_coords && tsdf && weight, "d3d_tsdf_integrate: null pointer");
   const size_t at = (size_t)first_new * kVox, fresh = (size_t)(n_blocks - first_new) * kVox;
   if (fresh > 0) {                           // blocks the touch pass added: all state zero
     D3D_HIP_CHECK(hipMemsetAsync(tsdf + at, 0, fresh * sizeof(float), s));
@@ -552,18 +510,15 @@ int d3d_tsdf_integrate(const void *depth, int depth_is_u16, const void *color, i
     if (color_weight) D3D_HIP_CHECK(hipMemsetAsync(color_weight + at, 0, fresh * sizeof(float), s));
   }
   if (V.P == 0) return D3D_OK;
-  D3D_REQUIRE(depth && intrinsics && extrinsics, "d3d_tsdf_integrate: null pointer");
-  V.depth = depth;
   const dim3 grid((unsigned)n_blocks), block(kVox);
-  if (!color)
-    hipLaunchKernelGGL(k_tsdf_integrate<0>, grid, block, 0, s, V, color, color_div, intrinsics, extrinsics, frames, G,
-                       block_coords, tsdf, weight, color_state, color_weight, culled_pairs);
-  else if (color_is_u8)
-    hipLaunchKernelGGL(k_tsdf_integrate<1>, grid, block, 0, s, V, color, color_div, intrinsics, extrinsics, frames, G,
-                       block_coords, tsdf, weight, color_state, color_weight, culled_pairs);
-  else
-    hipLaunchKernelGGL(k_tsdf_integrate<2>, grid, block, 0, s, V, color, color_div, intrinsics, extrinsics, frames, G,
-                       block_coords, tsdf, weight, color_state, color_weight, culled_pairs);
+#define D3D_TSDF_INTEGRATE(COLOR)                                                                                         \
+  hipLaunchKernelGGL(k_tsdf_integrate<COLOR>, grid, block, 0, s, V, color, color_div, frames->intrinsics,                \
+                     frames->extrinsics, frames->frames, G, (const int32_t *)volume->block_coords, tsdf, weight, color_state, \
+                     color_weight, culled_pairs)
+  if (!color) D3D_TSDF_INTEGRATE(0);
+  else if (frames->color_is_u8) D3D_TSDF_INTEGRATE(1);
+  else D3D_TSDF_INTEGRATE(2);
+#undef D3D_TSDF_INTEGRATE
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
@@ -588,24 +543,26 @@ int d3d_tsdf_order(const int32_t *block_coords, int n_blocks, int32_t *order, vo
 
 size_t d3d_tsdf_surface_scratch_bytes(int n_blocks) { return surface_bytes(std::max(0, std::min(n_blocks, kMaxBlocks))); }
 
-int d3d_tsdf_surface_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                           int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
-                           size_t scratch_bytes, int *info_host, void *stream) {
+int d3d_tsdf_surface_count(const d3d_tsdf_volume *volume, double min_weight, void *scratch, size_t scratch_bytes,
+                           int *info_host, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_tsdf_surface_count: null pointer");
   info_host[0] = 0;
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks, "d3d_tsdf_surface_count: %d blocks", n_blocks);
+  VolumeView G;
+  int rc = volume_view("d3d_tsdf_surface_count", volume, kVolBlocks | kVolLookup | kVolTsdf | kVolWeight, G);
+  if (rc) return rc;
+  const int n_blocks = volume->n_blocks;
   D3D_REQUIRE(min_weight >= 0.0, "d3d_tsdf_surface_count: min_weight %g must not be negative", min_weight);
   if (n_blocks == 0) return D3D_OK;
-  D3D_REQUIRE(table_ok(table, table_slots, n_blocks) && block_coords && order && tsdf && weight && scratch,
-              "d3d_tsdf_surface_count: null pointer, or a table of fewer than two slots per block");
+  D3D_REQUIRE(scratch, "d3d_tsdf_surface_count: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_tsdf_surface_scratch_bytes(n_blocks), "d3d_tsdf_surface_count: scratch too small");
   Arena A = scratch_arena(scratch, scratch_bytes);
   SurfaceLayout L;
-  int rc = carve_surface(A, n_blocks, L);
+  rc = carve_surface(A, n_blocks, L);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tsdf_count, dim3((unsigned)n_blocks), dim3(kVox), 0, s, block_coords, order, n_blocks,
-                     (const HashEntry *)table, table_slots, tsdf, weight, min_weight, L.counts);
+  hipLaunchKernelGGL(k_tsdf_count, dim3((unsigned)n_blocks), dim3(kVox), 0, s, (const int32_t *)volume->block_coords,
+                     volume->order, n_blocks, (const HashEntry *)volume->table, volume->table_slots,
+                     (const float *)volume->tsdf, (const float *)volume->weight, min_weight, L.counts);
   D3D_LAUNCH_CHECK();
   rc = scan_exclusive_i32(L.counts, L.bases, n_blocks, L.total, A, s);
   if (rc) return rc;
@@ -614,25 +571,21 @@ int d3d_tsdf_surface_count(const int32_t *block_coords, const int32_t *order, in
   return readback_wait(info_host, 1);
 }
 
-int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                          int table_slots, const float *tsdf, const float *weight, const float *color_state,
-                          const float *color_weight, double voxel, const double *origin, double min_weight, int ncols,
-                          const int *info_host, const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels,
-                          void *stream) {
+int d3d_tsdf_surface_rows(const d3d_tsdf_volume *volume, double min_weight, int ncols, const int *info_host,
+                          const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_tsdf_surface_rows: null pointer");
   D3D_REQUIRE(ncols == 3 || ncols == 6 || ncols == 9, "d3d_tsdf_surface_rows: %d columns (3, 6 or 9)", ncols);
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks, "d3d_tsdf_surface_rows: %d blocks", n_blocks);
-  D3D_REQUIRE(min_weight >= 0.0, "d3d_tsdf_surface_rows: min_weight %g must not be negative", min_weight);
   VolumeView G;
-  int rc = make_volume("d3d_tsdf_surface_rows", voxel, voxel, origin, G);
+  int rc = volume_view("d3d_tsdf_surface_rows", volume,
+                       kVolGeometry | kVolBlocks | kVolLookup | kVolTsdf | kVolWeight | kVolColor, G);
   if (rc) return rc;
+  const int n_blocks = volume->n_blocks;
+  D3D_REQUIRE(min_weight >= 0.0, "d3d_tsdf_surface_rows: min_weight %g must not be negative", min_weight);
   const int N = info_host[0];
   D3D_REQUIRE(N >= 0 && (long)N <= 3l * kVox * n_blocks, "d3d_tsdf_surface_rows: %d rows of %d blocks", N, n_blocks);
   if (n_blocks == 0 || N == 0) return D3D_OK;
-  D3D_REQUIRE(table_ok(table, table_slots, n_blocks) && block_coords && order && tsdf && weight && scratch && out,
-              "d3d_tsdf_surface_rows: null pointer, or a table of fewer than two slots per block");
-  D3D_REQUIRE(!color_state == !color_weight, "d3d_tsdf_surface_rows: colour and colour weight go together");
+  D3D_REQUIRE(scratch && out, "d3d_tsdf_surface_rows: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_tsdf_surface_scratch_bytes(n_blocks), "d3d_tsdf_surface_rows: scratch too small");
   Arena A = scratch_arena(scratch, scratch_bytes);
   SurfaceLayout L;
@@ -640,9 +593,10 @@ int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int
   if (rc) return rc;
   const dim3 grid((unsigned)n_blocks), block(kVox);
 #define D3D_TSDF_ROWS(NC)                                                                                              \
-  hipLaunchKernelGGL(k_tsdf_rows<NC>, grid, block, 0, s, block_coords, order, n_blocks, (const HashEntry *)table,      \
-                     table_slots, tsdf, weight, color_state, color_weight, G, min_weight, (const int32_t *)L.bases, N, \
-                     out, voxels)
+  hipLaunchKernelGGL(k_tsdf_rows<NC>, grid, block, 0, s, (const int32_t *)volume->block_coords, volume->order, n_blocks, \
+                     (const HashEntry *)volume->table, volume->table_slots, (const float *)volume->tsdf,               \
+                     (const float *)volume->weight, (const float *)volume->color_state,                                \
+                     (const float *)volume->color_weight, G, min_weight, (const int32_t *)L.bases, N, out, voxels)
   if (ncols == 3) D3D_TSDF_ROWS(3);
   else if (ncols == 6) D3D_TSDF_ROWS(6);
   else D3D_TSDF_ROWS(9);

@@ -5,7 +5,7 @@
 // xy, xz, yz, xyz), and is owned by g: kinds 0..2 are the rows of d3d_tsdf_surface_rows.
 //
 // One workgroup of 512 lanes per block in coordinate order, one lane per voxel (and per cell), as in tsdf.hip.
-//   count      stages the full 9^3 apron of tsdf and weight (the seven forward neighbour blocks through block_find),
+//   count      stages the full 9^3 apron of tsdf and weight (load_apron with the seven forward neighbour blocks),
 //              finds the voxel's 7-bit vertex mask and its cell's triangle count, ranks the vertices inside the block
 //              and leaves one word per voxel: rank (12 bits, <= 3584), mask (7), inside (1), seen (1).  Per-block
 //              totals, two 64-bit integer sums for the limits, two scans, one read-back.
@@ -110,34 +110,6 @@ __constant__ const uint32_t kTetWords[2][16] = {D3D_TET_ROW(true), D3D_TET_ROW(f
 // the word of a voxel that the count pass leaves
 constexpr int kWordMaskShift = 12, kWordInside = 1 << 19, kWordSeen = 1 << 20;
 
-// ---- staging ----
-
-// nb[o], o = ox | oy << 1 | oz << 2: the block at +o of block b, or -1; nb[0] = b
-__device__ __forceinline__ void find_neighbours(int *nb, int b, const int32_t *__restrict__ coords,
-                                                const HashEntry *__restrict__ tab, int cap, int n_blocks) {
-  const int o = threadIdx.x;
-  if (o < 8) {
-    const int x = coords[3 * (size_t)b + 0] + (o & 1), y = coords[3 * (size_t)b + 1] + ((o >> 1) & 1),
-              z = coords[3 * (size_t)b + 2] + ((o >> 2) & 1);
-    nb[o] = o == 0 ? b : block_find(tab, cap, x, y, z, n_blocks);
-  }
-  __syncthreads();
-}
-
-// apron cell i -> the neighbour o it lies in and its voxel there
-__device__ __forceinline__ void apron_source(int i, int &o, int &voxel) {
-  int a[3] = {i / 81, (i / 9) % 9, i % 9};
-  o = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    if (a[k] == 8) {
-      o |= 1 << k;
-      a[k] = 0;
-    }
-  }
-  voxel = (a[0] * 8 + a[1]) * 8 + a[2];
-}
-
 // ---- count ----
 
 // the triangles of the cell whose corners' inside bits are in8
@@ -159,8 +131,7 @@ __global__ __launch_bounds__(kVox) void k_mesh_count(const int32_t *__restrict__
                                                      double min_weight, uint32_t *__restrict__ words,
                                                      int32_t *__restrict__ vcounts, int32_t *__restrict__ tcounts,
                                                      unsigned long long *__restrict__ totals) {
-  __shared__ float D[kApron], W[kApron];
-  __shared__ int nb[8];
+  __shared__ Apron S;
   __shared__ int wave_v[kVox / 64], wave_t[kVox / 64];
   const int tid = threadIdx.x, wave = tid >> 6;
   const int b = order[blockIdx.x];
@@ -168,29 +139,15 @@ __global__ __launch_bounds__(kVox) void k_mesh_count(const int32_t *__restrict__
     if (tid == 0) vcounts[blockIdx.x] = tcounts[blockIdx.x] = 0;
     return;
   }
-  find_neighbours(nb, b, coords, tab, cap, n_blocks);
-  for (int i = tid; i < kApron; i += kVox) {
-    int o, voxel;
-    apron_source(i, o, voxel);
-    const int src = nb[o];
-    float d = 0.f, w = __builtin_nanf("");   // W = NaN: no such voxel
-    if (src >= 0) {
-      d = tsdf[(size_t)src * kVox + voxel];
-      w = weight[(size_t)src * kVox + voxel];
-      if (!(fabsf(d) < INFINITY)) w = __builtin_nanf("");   // a tsdf that is not finite: not seen
-    }
-    D[i] = d;
-    W[i] = w;
-  }
-  __syncthreads();
+  load_apron<true>(S, b, coords, tab, cap, n_blocks, tsdf, weight);
   const int at = ((tid >> 6) * 9 + ((tid >> 3) & 7)) * 9 + (tid & 7);
-  const bool seen_g = (double)W[at] >= min_weight, in_g = D[at] < 0.f;   // false for NaN
+  const bool seen_g = (double)S.W[at] >= min_weight, in_g = S.D[at] < 0.f;   // false for NaN
   int mask = 0, in8 = in_g ? 1 : 0;
   bool all_seen = seen_g;
 #pragma unroll
   for (int k = 0; k < 7; k++) {
     const int c = kind_dir(k), h = at + apron_offset(c);
-    const bool seen_h = (double)W[h] >= min_weight, in_h = D[h] < 0.f;
+    const bool seen_h = (double)S.W[h] >= min_weight, in_h = S.D[h] < 0.f;
     all_seen = all_seen && seen_h;
     in8 |= (in_h ? 1 : 0) << c;
     mask |= (seen_g && seen_h && in_g != in_h ? 1 : 0) << k;
@@ -249,7 +206,7 @@ __global__ __launch_bounds__(kVox) void k_mesh_vertices(const int32_t *__restric
   if ((unsigned)b >= (unsigned)n_blocks) return;   // the same in every thread
   const int total = min(max(vcounts[blockIdx.x], 0), kMaxBlockVerts);
   if (total == 0) return;                    // the same in every thread
-  find_neighbours(nb, b, coords, tab, cap, n_blocks);
+  find_neighbours<true>(nb, b, coords, tab, cap, n_blocks);
   for (int i = tid; i < kApron; i += kVox) {
     int o, voxel;
     apron_source(i, o, voxel);
@@ -347,7 +304,7 @@ __global__ __launch_bounds__(kVox) void k_mesh_triangles(const int32_t *__restri
   const int b = order[blockIdx.x];
   if ((unsigned)b >= (unsigned)n_blocks) return;   // the same in every thread
   if (tcounts[blockIdx.x] <= 0) return;      // the same in every thread
-  find_neighbours(nb, b, coords, tab, cap, n_blocks);
+  find_neighbours<true>(nb, b, coords, tab, cap, n_blocks);
   for (int i = tid; i < kApron; i += kVox) {
     int o, voxel;
     apron_source(i, o, voxel);
@@ -497,25 +454,27 @@ int d3d_tsdf_mesh_table(int8_t *out) {
 
 size_t d3d_tsdf_mesh_scratch_bytes(int n_blocks) { return mesh_bytes(std::max(0, std::min(n_blocks, kMaxBlocks))); }
 
-int d3d_tsdf_mesh_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                        int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
-                        size_t scratch_bytes, int *info_host, void *stream) {
+int d3d_tsdf_mesh_count(const d3d_tsdf_volume *volume, double min_weight, void *scratch, size_t scratch_bytes,
+                        int *info_host, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_tsdf_mesh_count: null pointer");
   info_host[0] = info_host[1] = 0;
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks, "d3d_tsdf_mesh_count: %d blocks", n_blocks);
+  VolumeView G;
+  int rc = volume_view("d3d_tsdf_mesh_count", volume, kVolBlocks | kVolLookup | kVolTsdf | kVolWeight, G);
+  if (rc) return rc;
+  const int n_blocks = volume->n_blocks;
   D3D_REQUIRE(min_weight >= 0.0, "d3d_tsdf_mesh_count: min_weight %g must not be negative", min_weight);
   if (n_blocks == 0) return D3D_OK;
-  D3D_REQUIRE(table_ok(table, table_slots, n_blocks) && block_coords && order && tsdf && weight && scratch,
-              "d3d_tsdf_mesh_count: null pointer, or a table of fewer than two slots per block");
+  D3D_REQUIRE(scratch, "d3d_tsdf_mesh_count: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_tsdf_mesh_scratch_bytes(n_blocks), "d3d_tsdf_mesh_count: scratch too small");
   Arena A = scratch_arena(scratch, scratch_bytes);
   MeshLayout L;
-  int rc = carve_mesh(A, n_blocks, L);
+  rc = carve_mesh(A, n_blocks, L);
   if (rc) return rc;
   D3D_HIP_CHECK(hipMemsetAsync(L.totals, 0, 2 * sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(k_mesh_count, dim3((unsigned)n_blocks), dim3(kVox), 0, s, block_coords, order, n_blocks,
-                     (const HashEntry *)table, table_slots, tsdf, weight, min_weight, L.words, L.vcounts, L.tcounts,
+  hipLaunchKernelGGL(k_mesh_count, dim3((unsigned)n_blocks), dim3(kVox), 0, s, (const int32_t *)volume->block_coords,
+                     volume->order, n_blocks, (const HashEntry *)volume->table, volume->table_slots,
+                     (const float *)volume->tsdf, (const float *)volume->weight, min_weight, L.words, L.vcounts, L.tcounts,
                      L.totals);
   D3D_LAUNCH_CHECK();
   rc = readback_publish(L.totals, 4, s);
@@ -526,8 +485,8 @@ int d3d_tsdf_mesh_count(const int32_t *block_coords, const int32_t *order, int n
   if (rc) return rc;
   rc = scan_exclusive_i32(L.tcounts, L.tbases, n_blocks, nullptr, A, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_mesh_block_bases, grid1d(n_blocks), dim3(256), 0, s, order, (const int32_t *)L.vbases, n_blocks,
-                     L.base_of_block);
+  hipLaunchKernelGGL(k_mesh_block_bases, grid1d(n_blocks), dim3(256), 0, s, volume->order, (const int32_t *)L.vbases,
+                     n_blocks, L.base_of_block);
   D3D_LAUNCH_CHECK();
   unsigned long long totals[2] = {0, 0};
   rc = readback_wait(totals, 4);
@@ -540,73 +499,70 @@ int d3d_tsdf_mesh_count(const int32_t *block_coords, const int32_t *order, int n
   return D3D_OK;
 }
 
-int d3d_tsdf_mesh_vertices(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                           int table_slots, const float *tsdf, const float *color_state, const float *color_weight,
-                           double voxel, const double *origin, const int *info_host, const void *scratch,
+int d3d_tsdf_mesh_vertices(const d3d_tsdf_volume *volume, const int *info_host, const void *scratch,
                            size_t scratch_bytes, float *vertices, float *vertex_color, int32_t *edges, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks, "d3d_tsdf_mesh_vertices: %d blocks", n_blocks);
   VolumeView G;
-  int rc = make_volume("d3d_tsdf_mesh_vertices", voxel, voxel, origin, G);
+  int rc = volume_view("d3d_tsdf_mesh_vertices", volume, kVolGeometry | kVolBlocks | kVolLookup | kVolTsdf | kVolColor, G);
   if (rc) return rc;
+  const int n_blocks = volume->n_blocks;
   int V = 0, T = 0;
   rc = mesh_counts("d3d_tsdf_mesh_vertices", info_host, n_blocks, V, T);
   if (rc) return rc;
   if (n_blocks == 0 || V == 0) return D3D_OK;
-  D3D_REQUIRE(table_ok(table, table_slots, n_blocks) && block_coords && order && tsdf && scratch && vertices,
-              "d3d_tsdf_mesh_vertices: null pointer, or a table of fewer than two slots per block");
-  D3D_REQUIRE(!color_state == !color_weight, "d3d_tsdf_mesh_vertices: colour and colour weight go together");
+  D3D_REQUIRE(scratch && vertices, "d3d_tsdf_mesh_vertices: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_tsdf_mesh_scratch_bytes(n_blocks), "d3d_tsdf_mesh_vertices: scratch too small");
   Arena A = scratch_arena(scratch, scratch_bytes);
   MeshLayout L;
   rc = carve_mesh(A, n_blocks, L);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_mesh_vertices, dim3((unsigned)n_blocks), dim3(kVox), 0, s, block_coords, order, n_blocks,
-                     (const HashEntry *)table, table_slots, tsdf, color_state, color_weight, G,
-                     (const uint32_t *)L.words, (const int32_t *)L.vcounts, (const int32_t *)L.vbases, V, vertices,
+  hipLaunchKernelGGL(k_mesh_vertices, dim3((unsigned)n_blocks), dim3(kVox), 0, s, (const int32_t *)volume->block_coords,
+                     volume->order, n_blocks, (const HashEntry *)volume->table, volume->table_slots,
+                     (const float *)volume->tsdf, (const float *)volume->color_state, (const float *)volume->color_weight,
+                     G, (const uint32_t *)L.words, (const int32_t *)L.vcounts, (const int32_t *)L.vbases, V, vertices,
                      vertex_color, edges);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
 
-int d3d_tsdf_mesh_triangles(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                            int table_slots, const int *info_host, const void *scratch, size_t scratch_bytes,
-                            int32_t *triangles, void *stream) {
+int d3d_tsdf_mesh_triangles(const d3d_tsdf_volume *volume, const int *info_host, const void *scratch,
+                            size_t scratch_bytes, int32_t *triangles, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(n_blocks >= 0 && n_blocks <= kMaxBlocks, "d3d_tsdf_mesh_triangles: %d blocks", n_blocks);
+  VolumeView G;
+  int rc = volume_view("d3d_tsdf_mesh_triangles", volume, kVolBlocks | kVolLookup, G);
+  if (rc) return rc;
+  const int n_blocks = volume->n_blocks;
   int V = 0, T = 0;
-  int rc = mesh_counts("d3d_tsdf_mesh_triangles", info_host, n_blocks, V, T);
+  rc = mesh_counts("d3d_tsdf_mesh_triangles", info_host, n_blocks, V, T);
   if (rc) return rc;
   if (n_blocks == 0 || T == 0) return D3D_OK;
-  D3D_REQUIRE(table_ok(table, table_slots, n_blocks) && block_coords && order && scratch && triangles,
-              "d3d_tsdf_mesh_triangles: null pointer, or a table of fewer than two slots per block");
+  D3D_REQUIRE(scratch && triangles, "d3d_tsdf_mesh_triangles: null pointer");
   D3D_REQUIRE(scratch_bytes >= d3d_tsdf_mesh_scratch_bytes(n_blocks), "d3d_tsdf_mesh_triangles: scratch too small");
   Arena A = scratch_arena(scratch, scratch_bytes);
   MeshLayout L;
   rc = carve_mesh(A, n_blocks, L);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_mesh_triangles, dim3((unsigned)n_blocks), dim3(kVox), 0, s, block_coords, order, n_blocks,
-                     (const HashEntry *)table, table_slots, (const uint32_t *)L.words,
-                     (const int32_t *)L.base_of_block, (const int32_t *)L.tcounts, (const int32_t *)L.tbases, T,
-                     triangles);
+  hipLaunchKernelGGL(k_mesh_triangles, dim3((unsigned)n_blocks), dim3(kVox), 0, s, (const int32_t *)volume->block_coords,
+                     volume->order, n_blocks, (const HashEntry *)volume->table, volume->table_slots,
+                     (const uint32_t *)L.words, (const int32_t *)L.base_of_block, (const int32_t *)L.tcounts,
+                     (const int32_t *)L.tbases, T, triangles);
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }
 
-int d3d_tsdf_insert_blocks(const int32_t *coords, int n, void *table, int table_slots, int32_t *block_coords,
-                           int max_blocks, int32_t *state, void *stream) {
+int d3d_tsdf_insert_blocks(const int32_t *coords, int n, const d3d_tsdf_volume *volume, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(max_blocks >= 1 && max_blocks <= kMaxBlocks, "d3d_tsdf_insert_blocks: max_blocks %d outside [1, 2^22]",
-              max_blocks);
-  D3D_REQUIRE(n >= 0 && n <= max_blocks, "d3d_tsdf_insert_blocks: %d blocks into a volume of %d", n, max_blocks);
-  D3D_REQUIRE(table_ok(table, table_slots, max_blocks) && block_coords && state,
-              "d3d_tsdf_insert_blocks: the table has d3d_tsdf_table_slots(max_blocks) slots; null pointer");
+  VolumeView G;
+  int rc = volume_view("d3d_tsdf_insert_blocks", volume, kVolGrow, G);
+  if (rc) return rc;
+  D3D_REQUIRE(n >= 0 && n <= volume->max_blocks, "d3d_tsdf_insert_blocks: %d blocks into a volume of %d", n,
+              volume->max_blocks);
   if (n == 0) return D3D_OK;
   D3D_REQUIRE(coords, "d3d_tsdf_insert_blocks: null pointer");
-  hipLaunchKernelGGL(k_tsdf_insert, grid1d(n), dim3(256), 0, s, coords, n, (HashEntry *)table, table_slots,
-                     block_coords, state);
+  hipLaunchKernelGGL(k_tsdf_insert, grid1d(n), dim3(256), 0, s, coords, n, (HashEntry *)volume->table, volume->table_slots,
+                     volume->block_coords, volume->state);
   D3D_LAUNCH_CHECK();
-  int rc = readback_publish(state, kStWords, s);
+  rc = readback_publish(volume->state, kStWords, s);
   if (rc) return rc;
   int32_t host[kStWords];
   rc = readback_wait(host, kStWords);

@@ -32,7 +32,7 @@ constexpr int kThreads = 256;
 constexpr int kSteps = 8;
 constexpr int kRun = kThreads * kSteps;      // pixels of one workgroup
 
-#include "depth_frames.inc"   // DepthView, depth_at, valid_z, kept_at, Camera, cam_point, make_view
+#include "depth_frames.inc"   // DepthView, depth_at, valid_z, kept_at, Camera, cam_point, frames_view
 
 __global__ __launch_bounds__(kThreads) void k_up_count(DepthView V, int32_t *__restrict__ counts) {
   __shared__ int wave_cnt[kThreads / 64];
@@ -182,20 +182,18 @@ size_t d3d_unproject_scratch_bytes(int frames, int height, int width, int step) 
   return 512 + 2 * (G * 4 + 256) + (G / 2048 + 1) * 4 + 4096;
 }
 
-int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int height, int width, int step,
-                        double depth_scale, double min_depth, double max_depth, void *scratch, size_t scratch_bytes,
-                        int *info_host, void *stream) {
+int d3d_unproject_count(const d3d_depth_frames *frames, int step, double min_depth, double max_depth, void *scratch,
+                        size_t scratch_bytes, int *info_host, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   D3D_REQUIRE(info_host, "d3d_unproject_count: null pointer");
   info_host[0] = 0;
   DepthView V;
-  int rc = make_view("d3d_unproject_count", frames, height, width, step, depth_is_u16, depth_scale, min_depth, max_depth, V);
+  int rc = frames_view("d3d_unproject_count", frames, step, min_depth, max_depth, kFramesDepth, V);
   if (rc) return rc;
   if (V.P == 0) return D3D_OK;
-  D3D_REQUIRE(depth && scratch, "d3d_unproject_count: null pointer");
-  D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames, height, width, step),
+  D3D_REQUIRE(scratch, "d3d_unproject_count: null pointer");
+  D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames->frames, V.H, V.W, step),
               "d3d_unproject_count: scratch too small");
-  V.depth = depth;
   Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   rc = carve(A, V.P, L);
@@ -210,42 +208,38 @@ int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int hei
   return readback_wait(info_host, 1);
 }
 
-int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
-                       const double *intrinsics, const double *extrinsics, int frames, int height, int width, int step,
-                       double depth_scale, double min_depth, double max_depth, double edge, int ncols,
-                       const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
+int d3d_unproject_rows(const d3d_depth_frames *frames, int step, double min_depth, double max_depth, double color_div,
+                       double edge, int ncols, const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
                        int32_t *pixel_of_point, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  D3D_REQUIRE(info_host, "d3d_unproject_rows: null pointer");
+  D3D_REQUIRE(info_host && frames, "d3d_unproject_rows: null pointer");
   D3D_REQUIRE(ncols == 3 || ncols == 6 || ncols == 9, "d3d_unproject_rows: %d columns (3, 6 or 9)", ncols);
   D3D_REQUIRE(edge >= 0.0, "d3d_unproject_rows: edge %g must not be negative", edge);
-  D3D_REQUIRE(!(color && color_is_u8) || (color_div > 0.0 && color_div < (double)INFINITY),
+  const void *color = frames->color;
+  const int u8 = frames->color_is_u8 ? 1 : 0;
+  D3D_REQUIRE(!(color && u8) || (color_div > 0.0 && color_div < (double)INFINITY),
               "d3d_unproject_rows: color_div %g must be positive and finite", color_div);
   DepthView V;
-  int rc = make_view("d3d_unproject_rows", frames, height, width, step, depth_is_u16, depth_scale, min_depth, max_depth, V);
+  int rc = frames_view("d3d_unproject_rows", frames, step, min_depth, max_depth, kFramesDepth | kFramesCameras, V);
   if (rc) return rc;
   const int N = info_host[0];
   D3D_REQUIRE(N >= 0 && (long)N <= V.P, "d3d_unproject_rows: %d rows of %ld pixels", N, V.P);
   if (V.P == 0 || N == 0) return D3D_OK;
-  D3D_REQUIRE(depth && intrinsics && extrinsics && scratch && out, "d3d_unproject_rows: null pointer");
-  D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames, height, width, step),
+  D3D_REQUIRE(scratch && out, "d3d_unproject_rows: null pointer");
+  D3D_REQUIRE(scratch_bytes >= d3d_unproject_scratch_bytes(frames->frames, V.H, V.W, step),
               "d3d_unproject_rows: scratch too small");
-  V.depth = depth;
   Arena A = scratch_arena(scratch, scratch_bytes);
   Layout L;
   rc = carve(A, V.P, L);
   if (rc) return rc;
   const dim3 grid((unsigned)n_groups(V.P)), block(kThreads);
-  const int u8 = color_is_u8 ? 1 : 0;
-  if (ncols == 3)
-    hipLaunchKernelGGL(k_up_rows<3>, grid, block, 0, s, V, color, u8, color_div, intrinsics, extrinsics, edge,
-                       (const int32_t *)L.bases, N, out, pixel_of_point);
-  else if (ncols == 6)
-    hipLaunchKernelGGL(k_up_rows<6>, grid, block, 0, s, V, color, u8, color_div, intrinsics, extrinsics, edge,
-                       (const int32_t *)L.bases, N, out, pixel_of_point);
-  else
-    hipLaunchKernelGGL(k_up_rows<9>, grid, block, 0, s, V, color, u8, color_div, intrinsics, extrinsics, edge,
-                       (const int32_t *)L.bases, N, out, pixel_of_point);
+#define D3D_UP_ROWS(NC)                                                                                                \
+  hipLaunchKernelGGL(k_up_rows<NC>, grid, block, 0, s, V, color, u8, color_div, frames->intrinsics, frames->extrinsics, \
+                     edge, (const int32_t *)L.bases, N, out, pixel_of_point)
+  if (ncols == 3) D3D_UP_ROWS(3);
+  else if (ncols == 6) D3D_UP_ROWS(6);
+  else D3D_UP_ROWS(9);
+#undef D3D_UP_ROWS
   D3D_LAUNCH_CHECK();
   return D3D_OK;
 }

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._cloud import need_gpu, number, run, scratch, whole
-from ._lib import lib, ptr, stream_of
+from ._lib import DepthFramesDesc, TriangleMeshDesc, lib, ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL
 from .unproject import PIXEL_LIMIT, DepthFrames, fuse_frames
 
@@ -56,6 +56,9 @@ class TriangleMesh(object):
         self.vertices = vertices.detach().contiguous()
         self.triangles = triangles.detach().contiguous()
         self.vertex_color = None if vertex_color is None else vertex_color.detach().contiguous()
+        vc = self.vertex_color
+        self.desc = TriangleMeshDesc(ptr(self.vertices), self.vertices.shape[0], ptr(self.triangles), self.triangles.shape[0],
+                                     ptr(vc), int(vc is not None and vc.dtype == torch.uint8))
 
     @property
     def device(self):
@@ -92,23 +95,24 @@ def _check_args(who, mesh, height, width, min_depth, max_depth, depth_dtype, dep
 class _Call(object):
     """the arguments the three library calls share, for frames [f0, f1)"""
 
-    def __init__(self, mesh, intrinsics, extrinsics, height, width):
+    def __init__(self, mesh, intrinsics, extrinsics, height, width, depth=None, color=None, depth_scale=0.0):
         self.mesh, self.h, self.w, self.dev = mesh, height, width, mesh.device
         self.intr = intrinsics.to(self.dev).contiguous()
         self.extr = extrinsics.to(self.dev).contiguous()
+        self.depth, self.color, self.depth_scale = depth, color, depth_scale
         self.info = (ctypes.c_int64 * 1)(0)
 
-    def head(self):
-        m = self.mesh
-        return (ptr(m.vertices), m.vertices.shape[0], ptr(m.triangles), m.triangles.shape[0])
-
-    def views(self, f0, f1):
-        return (ptr(self.intr[f0:f1]), ptr(self.extr[f0:f1]), f1 - f0, self.h, self.w)
+    def frames(self, f0, f1):
+        """the d3d_depth_frames the calls fill: the cameras and the shape, and for d3d_render_tiles the images"""
+        depth, color = (None if t is None else t[f0:f1] for t in (self.depth, self.color))
+        return DepthFramesDesc(ptr(depth), int(depth is not None and depth.dtype == torch.uint16), ptr(color),
+                               int(color is not None and color.dtype == torch.uint8), ptr(self.intr[f0:f1]),
+                               ptr(self.extr[f0:f1]), f1 - f0, self.h, self.w, self.depth_scale)
 
     def bin(self, f0, f1):
         """-> (scratch, all list entries of the frames)"""
         buf, nbytes = scratch(self.dev, "d3d_render_scratch_bytes", f1 - f0, self.h, self.w)
-        run(self.dev, "d3d_render_bin", *self.head(), *self.views(f0, f1), ptr(buf), nbytes, self.info,
+        run(self.dev, "d3d_render_bin", self.mesh.desc, self.frames(f0, f1), ptr(buf), nbytes, self.info,
             stream_of(self.dev))
         return buf, int(self.info[0])
 
@@ -160,7 +164,7 @@ def render_depth(mesh, intrinsics, extrinsics, height, width, min_depth=0.0, max
         depth = _empty((f, height, width), depth_dtype, dev)
         color = None if vc is None else torch.empty((f, height, width, 3), dtype=vc.dtype, device=dev)
         tri = torch.empty((f, height, width), dtype=torch.int32, device=dev) if return_triangles else None
-        call = _Call(mesh, intrinsics, extrinsics, height, width)
+        call = _Call(mesh, intrinsics, extrinsics, height, width, depth, color, depth_scale)
         scratch_of = lib().d3d_render_scratch_bytes
         if scratch_of(1, height, width) > budget:
             raise ValueError(f"render_depth: one frame of {height} x {width} pixels needs {scratch_of(1, height, width)} "
@@ -180,12 +184,10 @@ def render_depth(mesh, intrinsics, extrinsics, height, width, min_depth=0.0, max
                 step = (f1 - f0) // 2              # ... and the lists decide the rest: halve and bin again
                 continue
             lists = torch.empty(max(entries, 1), dtype=torch.int32, device=dev)
-            s = stream_of(dev)
-            run(dev, "d3d_render_fill", *call.head(), *call.views(f0, f1), call.info, ptr(buf), buf.numel(), ptr(lists), s)
-            run(dev, "d3d_render_tiles", *call.head(), ptr(vc), int(vc is not None and vc.dtype == torch.uint8),
-                *call.views(f0, f1), min_depth, max_depth, int(depth_dtype == torch.uint16), depth_scale, call.info,
-                ptr(buf), buf.numel(), ptr(lists), ptr(depth[f0:f1]), ptr(None if tri is None else tri[f0:f1]),
-                ptr(None if color is None else color[f0:f1]), s)
+            s, views = stream_of(dev), call.frames(f0, f1)
+            run(dev, "d3d_render_fill", mesh.desc, views, call.info, ptr(buf), buf.numel(), ptr(lists), s)
+            run(dev, "d3d_render_tiles", mesh.desc, views, min_depth, max_depth, call.info, ptr(buf), buf.numel(), ptr(lists),
+                ptr(None if tri is None else tri[f0:f1]), s)
             _LAST_CHUNKS.append((f0, f1))
             f0 = f1
     frames = DepthFrames(depth, intrinsics, extrinsics, color=color, depth_scale=depth_scale)

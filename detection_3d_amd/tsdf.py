@@ -26,7 +26,7 @@ import math
 import torch
 
 from ._cloud import need_gpu, number, run, same_device, scratch, whole
-from ._lib import D3DError, lib, ptr, stream_of
+from ._lib import D3DError, DepthFramesDesc, TsdfVolumeDesc, lib, ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL, cap_points
 from .render import TriangleMesh
 from .unproject import COLUMNS, DepthFrames
@@ -77,7 +77,6 @@ class TsdfVolume(object):
         self.device = None if device is None else torch.device(device)
         if self.device is not None:
             need_gpu(self.device, "the volume")
-        self._origin = (ctypes.c_double * 3)(*self.origin)
         self.count_cull = False                  # scripts/tsdf_probe.py: count the (block, frame) pairs the cull removes
         self._table = None
         self.reset()
@@ -122,6 +121,12 @@ class TsdfVolume(object):
             self._color, self._cweight = grown(self._color, 3), grown(self._cweight)
         self._cap = cap
 
+    def _desc(self, n_blocks=None, order=None):
+        """the library's d3d_tsdf_volume of the state as it is now; n_blocks: the count a pass is about to commit"""
+        return TsdfVolumeDesc(self.voxel, self.trunc, self.origin, ptr(self._table), self._slots, ptr(self._coords),
+                              self.max_blocks, self.n_blocks if n_blocks is None else n_blocks, ptr(self._state),
+                              ptr(order), ptr(self._tsdf), ptr(self._weight), ptr(self._color), ptr(self._cweight))
+
     def _alive(self, who):
         if self._full:
             raise D3DError(f"{who}: the volume ran out of its {self.max_blocks} blocks; its contents are unspecified "
@@ -148,13 +153,9 @@ class TsdfVolume(object):
     def _touch(self, frames, step, min_depth, max_depth):
         """the allocation pass and the call's read-back -> the number of blocks now allocated"""
         dev = self._on(frames.device)
-        f, h, w = frames.shape
         info = (ctypes.c_int * 3)(0, 0, 0)
         reach = int(math.ceil(self.trunc / self.voxel))
-        run(dev, "d3d_tsdf_touch", ptr(frames.depth), int(frames.depth.dtype == torch.uint16), ptr(frames.intrinsics),
-            ptr(frames.extrinsics), f, h, w, step, frames.depth_scale, min_depth, max_depth, self.voxel, self._origin,
-            reach, ptr(self._table), self._slots, ptr(self._coords), self.max_blocks, ptr(self._state), info,
-            stream_of(dev))
+        run(dev, "d3d_tsdf_touch", frames.desc, step, min_depth, max_depth, self._desc(), reach, info, stream_of(dev))
         n, clipped, full = int(info[0]), bool(info[1]), bool(info[2])
         self.clipped = self.clipped or clipped
         if full:
@@ -170,11 +171,12 @@ class TsdfVolume(object):
         color = frames.color if self.color else None
         culled = torch.zeros(1, dtype=torch.int64, device=dev) if self.count_cull else None
         if n > 0:
-            run(dev, "d3d_tsdf_integrate", ptr(frames.depth), int(frames.depth.dtype == torch.uint16), ptr(color),
-                int(color is not None and color.dtype == torch.uint8), color_div, ptr(frames.intrinsics),
-                ptr(frames.extrinsics), f, h, w, frames.depth_scale, min_depth, max_depth, self.voxel, self.trunc,
-                self._origin, ptr(self._coords), n, first_new, ptr(self._tsdf), ptr(self._weight), ptr(self._color),
-                ptr(self._cweight), ptr(culled), stream_of(dev))
+            desc = frames.desc
+            if color is not frames.color:        # a volume without colour does not read the images
+                desc = DepthFramesDesc.from_buffer_copy(desc)
+                desc.color = None
+            run(dev, "d3d_tsdf_integrate", desc, min_depth, max_depth, color_div, self._desc(n), first_new,
+                ptr(culled), stream_of(dev))
         self.n_blocks, self._order = n, None
         if culled is not None:
             self.culled_pairs += int(culled.item())
@@ -224,15 +226,14 @@ class TsdfVolume(object):
         if n > 0:
             order = self._sorted()
             buf, nbytes = scratch(dev, "d3d_tsdf_surface_scratch_bytes", n)
-            run(dev, "d3d_tsdf_surface_count", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
-                ptr(self._tsdf), ptr(self._weight), min_weight, ptr(buf), nbytes, info, stream_of(dev))
+            vol = self._desc(order=order)
+            run(dev, "d3d_tsdf_surface_count", vol, min_weight, ptr(buf), nbytes, info, stream_of(dev))
         rows = int(info[0])
         out = torch.empty((rows, int(columns)), dtype=torch.float32, device=dev)
         voxels = torch.empty((rows, 3), dtype=torch.int32, device=dev) if return_voxels else None
         if rows > 0:
-            run(dev, "d3d_tsdf_surface_rows", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
-                ptr(self._tsdf), ptr(self._weight), ptr(self._color), ptr(self._cweight), self.voxel, self._origin,
-                min_weight, int(columns), info, ptr(buf), nbytes, ptr(out), ptr(voxels), stream_of(dev))
+            run(dev, "d3d_tsdf_surface_rows", vol, min_weight, int(columns), info, ptr(buf), nbytes, ptr(out), ptr(voxels),
+                stream_of(dev))
         return (out, voxels) if return_voxels else out
 
     def mesh(self, min_weight=1, color=True, return_edges=False):
@@ -252,20 +253,18 @@ class TsdfVolume(object):
         if n > 0:
             order = self._sorted()
             buf, nbytes = scratch(dev, "d3d_tsdf_mesh_scratch_bytes", n)
-            run(dev, "d3d_tsdf_mesh_count", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
-                ptr(self._tsdf), ptr(self._weight), min_weight, ptr(buf), nbytes, info, stream_of(dev))
+            vol = self._desc(order=order)
+            run(dev, "d3d_tsdf_mesh_count", vol, min_weight, ptr(buf), nbytes, info, stream_of(dev))
         nv, nt = int(info[0]), int(info[1])
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
         colors = torch.empty((nv, 3), dtype=torch.float32, device=dev) if color and self.color else None
         edges = torch.empty((nv, 4), dtype=torch.int32, device=dev) if return_edges else None
         if nv > 0:
-            run(dev, "d3d_tsdf_mesh_vertices", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots,
-                ptr(self._tsdf), ptr(self._color), ptr(self._cweight), self.voxel, self._origin, info, ptr(buf), nbytes,
-                ptr(vertices), ptr(colors), ptr(edges), stream_of(dev))
+            run(dev, "d3d_tsdf_mesh_vertices", vol, info, ptr(buf), nbytes, ptr(vertices), ptr(colors), ptr(edges),
+                stream_of(dev))
         if nt > 0:
-            run(dev, "d3d_tsdf_mesh_triangles", ptr(self._coords), ptr(order), n, ptr(self._table), self._slots, info,
-                ptr(buf), nbytes, ptr(triangles), stream_of(dev))
+            run(dev, "d3d_tsdf_mesh_triangles", vol, info, ptr(buf), nbytes, ptr(triangles), stream_of(dev))
         mesh = TriangleMesh(vertices, triangles, colors)
         return (mesh, edges) if return_edges else mesh
 
@@ -313,8 +312,7 @@ class TsdfVolume(object):
         dev = vol._on(coords.device)
         if n > 0:
             try:
-                run(dev, "d3d_tsdf_insert_blocks", ptr(coords.contiguous()), n, ptr(vol._table), vol._slots,
-                    ptr(vol._coords), vol.max_blocks, ptr(vol._state), stream_of(dev))
+                run(dev, "d3d_tsdf_insert_blocks", ptr(coords.contiguous()), n, vol._desc(), stream_of(dev))
             except D3DError:
                 vol.reset()
                 raise

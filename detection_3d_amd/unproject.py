@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ._cloud import need_gpu, number, options, run, scratch, whole
-from ._lib import ptr, stream_of
+from ._lib import DepthFramesDesc, ptr, stream_of
 from .downsample import DEFAULT_MAX_POINTS, DEFAULT_VOXEL, apply_downsample, downsample_kwargs
 
 PIXEL_LIMIT = 1 << 31
@@ -74,6 +74,9 @@ class DepthFrames(object):
         self.intrinsics = intrinsics.to(depth.device).contiguous()
         self.extrinsics = extrinsics[:, :3, :].to(depth.device).contiguous()
         self.depth_scale = depth_scale
+        self.desc = DepthFramesDesc(ptr(self.depth), int(depth.dtype == torch.uint16), ptr(self.color),      # the tensors stay
+                                    int(color is not None and color.dtype == torch.uint8), ptr(self.intrinsics),
+                                    ptr(self.extrinsics), f, h, w, depth_scale)
 
     @property
     def shape(self):
@@ -129,20 +132,15 @@ def unproject(frames, columns=9, step=1, min_depth=0.0, max_depth=math.inf, edge
         raise ValueError(f"unproject: frames is a DepthFrames, got {type(frames).__name__}")
     f, h, w = frames.shape
     dev = frames.device
-    depth, color = frames.depth, frames.color
-    is_u16 = int(depth.dtype == torch.uint16)
     info = (ctypes.c_int * 1)(0)
     if f * h * w > 0:
         buf, nbytes = scratch(dev, "d3d_unproject_scratch_bytes", f, h, w, step)
-        run(dev, "d3d_unproject_count", ptr(depth), is_u16, f, h, w, step, frames.depth_scale, min_depth, max_depth,
-            ptr(buf), nbytes, info, stream_of(dev))
+        run(dev, "d3d_unproject_count", frames.desc, step, min_depth, max_depth, ptr(buf), nbytes, info, stream_of(dev))
     n = int(info[0])
     out = torch.empty((n, columns), dtype=torch.float32, device=dev)
     pixels = torch.empty((n,), dtype=torch.int32, device=dev) if return_pixels else None
     if n > 0:
-        run(dev, "d3d_unproject_rows", ptr(depth), is_u16, ptr(color),
-            int(color is not None and color.dtype == torch.uint8), color_div, ptr(frames.intrinsics),
-            ptr(frames.extrinsics), f, h, w, step, frames.depth_scale, min_depth, max_depth, edge, columns, info, ptr(buf),
+        run(dev, "d3d_unproject_rows", frames.desc, step, min_depth, max_depth, color_div, edge, columns, info, ptr(buf),
             nbytes, ptr(out), ptr(pixels), stream_of(dev))
     return (out, pixels) if return_pixels else out
 

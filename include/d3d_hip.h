@@ -512,12 +512,66 @@ int d3d_voxel_downsample_rows(const float *pcl, int n, int ncols, int normal_col
 size_t d3d_sample_rows_scratch_bytes(int n);
 int d3d_sample_rows(int n, int k, uint64_t seed, int32_t *rows, void *scratch, size_t scratch_bytes, void *stream);
 
+/* The descriptors of the raw-scan chain below (d3d_unproject_*, d3d_tsdf_*, d3d_render_*): a batch of posed depth frames,
+ * a TSDF block volume and a triangle mesh, each spelled out once.  Host structs of device pointers (origin: host values),
+ * read during the call only; a NULL descriptor is an error.  What a call chooses for itself (step, the depth range,
+ * color_div, min_weight, scratch, outputs, the stream) stays an argument.  The fields mean what the API group that
+ * follows says; a call reads every field of its descriptors except those it ignores:
+ *   call                      ignores of d3d_depth_frames             ignores of d3d_tsdf_volume
+ *   d3d_unproject_count       color, color_is_u8, in-, extrinsics
+ *   d3d_unproject_rows        -
+ *   d3d_tsdf_touch            color, color_is_u8                      trunc, n_blocks, order, tsdf .. color_weight
+ *   d3d_tsdf_integrate        -                                       table, table_slots, max_blocks, state, order
+ *   d3d_tsdf_insert_blocks                                            voxel, trunc, origin, and as _touch
+ *   d3d_tsdf_surface_count                                            voxel, trunc, origin, max_blocks, state, color_*
+ *   d3d_tsdf_surface_rows                                             trunc, max_blocks, state
+ *   d3d_tsdf_mesh_count                                               as _surface_count
+ *   d3d_tsdf_mesh_vertices                                            trunc, max_blocks, state, weight
+ *   d3d_tsdf_mesh_triangles                                           as _surface_count, and tsdf, weight
+ *   d3d_render_bin, _fill     depth .. color_is_u8, depth_scale       (of d3d_triangle_mesh: vertex_color, color_is_u8)
+ *   d3d_render_tiles          color_is_u8 (the mesh's holds)
+ * _touch and _insert_blocks write table, block_coords and state; _integrate writes tsdf .. color_weight; _render_tiles
+ * writes depth and color.  The calls that read n_blocks want a table of two slots per block at least, _touch and
+ * _insert_blocks one of d3d_tsdf_table_slots(max_blocks) slots; color_state and color_weight go together.              */
+typedef struct d3d_depth_frames {
+  void *depth;                /* uint16 or fp32 [frames, height, width] */
+  int depth_is_u16;
+  void *color;                /* uint8 or fp32 [frames, height, width, 3], or NULL */
+  int color_is_u8;
+  const double *intrinsics;   /* fp64 [frames, 4] (fx, fy, cx, cy) */
+  const double *extrinsics;   /* fp64 [frames, 3, 4] (camera to world, R | t) */
+  int frames, height, width;
+  double depth_scale;         /* z = double(d) * depth_scale for uint16; ignored for fp32 */
+} d3d_depth_frames;
+
+typedef struct d3d_tsdf_volume {
+  double voxel, trunc, origin[3];
+  void *table;                /* table_slots hash slots of 16 bytes, all ones when empty */
+  int table_slots;
+  int32_t *block_coords;      /* [max_blocks, 3] */
+  int max_blocks, n_blocks;   /* the storage; the blocks allocated so far */
+  int32_t *state;             /* [3]: blocks handed out, clipped, full; zero when empty */
+  const int32_t *order;       /* [n_blocks], as d3d_tsdf_order leaves it */
+  float *tsdf, *weight;       /* [n_blocks, 512] */
+  float *color_state;         /* [n_blocks, 512, 3], or NULL */
+  float *color_weight;        /* [n_blocks, 512], or NULL */
+} d3d_tsdf_volume;
+
+typedef struct d3d_triangle_mesh {
+  const float *vertices;      /* fp32 [n_vertices, 3], world coordinates */
+  int n_vertices;
+  const int32_t *triangles;   /* int32 [n_triangles, 3] */
+  int n_triangles;
+  const void *vertex_color;   /* uint8 or fp32 [n_vertices, 3], or NULL */
+  int color_is_u8;
+} d3d_triangle_mesh;
+
 /* Posed depth frames -> one cloud with colours and image-space normals: depth_2_pcl of
  * data3d/suncg_utils/suncg_preprocess.py:790-832 for a batch of frames, and what gen_pcl (:718-764) concatenates.  A
- * restatement that is not pinned against a run of the reference.  depth [frames, height, width], uint16 or fp32;
- * color [frames, height, width, 3], uint8 or fp32, or NULL; intrinsics fp64 [frames, 4] (fx, fy, cx, cy) and extrinsics
- * fp64 [frames, 3, 4] (camera to world, R | t), both on the device.  Every operation below is fp64 in exactly this
- * order, without contraction; each output value is rounded once to fp32.
+ * restatement that is not pinned against a run of the reference.  frames, a d3d_depth_frames: depth [frames, height,
+ * width], uint16 or fp32; color [frames, height, width, 3], uint8 or fp32, or NULL; intrinsics fp64 [frames, 4] (fx, fy,
+ * cx, cy) and extrinsics fp64 [frames, 3, 4] (camera to world, R | t), both on the device.  Every operation below is fp64
+ * in exactly this order, without contraction; each output value is rounded once to fp32.
  *   pixel (f, v, u), u the column in 0 .. width - 1, v the row in 0 .. height - 1;
  *   depth: z = double(d) * depth_scale for uint16, z = double(d) for fp32 (depth_scale is ignored);
  *   valid: z is finite, z > 0 and min_depth <= z <= max_depth; kept: valid, u % step == 0 and v % step == 0;
@@ -539,29 +593,26 @@ int d3d_sample_rows(int n, int k, uint64_t seed, int32_t *rows, void *scratch, s
  * Two calls, because the caller allocates the rows from their number:
  *   _count: one count of kept pixels per run of 2048 pixels, their scan, and the one host read-back: info_host[0] = N
  *     (0 for an empty batch); synchronises once.
- *   _rows:  out fp32 [N, ncols], ncols 3, 6 or 9; pixel_of_point int32 [N] or NULL.  Same depth, shape, step, depth
+ *   _rows:  out fp32 [N, ncols], ncols 3, 6 or 9; pixel_of_point int32 [N] or NULL.  Same frames, step, depth
  *     range, stream, and `scratch` and info_host as _count left them.  Asynchronous.  Never writes past N rows.
  * scratch: d3d_unproject_scratch_bytes bytes: 8 per run of 2048 pixels plus a few KiB, whatever step is.              */
 size_t d3d_unproject_scratch_bytes(int frames, int height, int width, int step);
-int d3d_unproject_count(const void *depth, int depth_is_u16, int frames, int height, int width, int step,
-                        double depth_scale, double min_depth, double max_depth, void *scratch, size_t scratch_bytes,
-                        int *info_host /* [0] = N */, void *stream);
-int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
-                       const double *intrinsics, const double *extrinsics, int frames, int height, int width, int step,
-                       double depth_scale, double min_depth, double max_depth, double edge, int ncols /* 3, 6 or 9 */,
-                       const int *info_host, const void *scratch, size_t scratch_bytes, float *out,
-                       int32_t *pixel_of_point, void *stream);
+int d3d_unproject_count(const d3d_depth_frames *frames, int step, double min_depth, double max_depth, void *scratch,
+                        size_t scratch_bytes, int *info_host /* [0] = N */, void *stream);
+int d3d_unproject_rows(const d3d_depth_frames *frames, int step, double min_depth, double max_depth, double color_div,
+                       double edge, int ncols /* 3, 6 or 9 */, const int *info_host, const void *scratch,
+                       size_t scratch_bytes, float *out, int32_t *pixel_of_point, void *stream);
 
 /* Posed depth frames -> a truncated signed-distance volume (TSDF) -> its surface cloud: KinectFusion-style projective
- * fusion; the reference has nothing like it.  Frames (depth, color, intrinsics, extrinsics, depth_scale,
- * min_depth, max_depth, step, color_div) as for d3d_unproject_*.  Every operation below is fp64 in exactly this order,
+ * fusion; the reference has nothing like it.  Frames (a d3d_depth_frames; min_depth,
+ * max_depth, step, color_div) as for d3d_unproject_*.  Every operation below is fp64 in exactly this order,
  * without contraction; each stored or returned value is rounded once to fp32.
- *   volume: voxel > 0, trunc > 0, origin fp64 [3] (host).  Block b in [0, 65536)^3, voxel g = 8 b + l, l in [0, 8)^3,
- *     voxel position X_i = origin_i + double(g_i) * voxel.  The caller owns: table (d3d_tsdf_table_slots(max_blocks) hash
- *     slots of 16 bytes, all ones when empty), block_coords int32 [max_blocks, 3], state int32 [3] (blocks handed out,
- *     clipped, full; zero when empty), and per voxel, block id major and (lx 8 + ly) 8 + lz inside the block: tsdf D,
- *     weight W, color_state C [.., 3], color_weight CW, all fp32.  Block ids depend on scheduling; d3d_tsdf_order gives
- *     the ids in ascending (x, y, z) of their coordinates and every output follows it.
+ *   volume, a d3d_tsdf_volume: voxel > 0, trunc > 0, origin fp64 [3] (host).  Block b in [0, 65536)^3, voxel g = 8 b +
+ *     l, l in [0, 8)^3, voxel position X_i = origin_i + double(g_i) * voxel.  The caller owns: table
+ *     (d3d_tsdf_table_slots(max_blocks) hash slots of 16 bytes, all ones when empty), block_coords int32 [max_blocks, 3],
+ *     state int32 [3] (blocks handed out, clipped, full; zero when empty), and per voxel, block id major and (lx 8 + ly)
+ *     8 + lz inside the block: tsdf D, weight W, color_state C [.., 3], color_weight CW, all fp32.  Block ids depend on
+ *     scheduling; d3d_tsdf_order gives the ids in ascending (x, y, z) of their coordinates and every output follows it.
  *   _touch (allocation), for every kept pixel (valid, u % step == 0 and v % step == 0) of depth z and k = -reach ..
  *     reach (the host's ceil(trunc / voxel)): z_k = z + double(k) * voxel, skipped when z_k <= 0; C = ((double(u) - cx)
  *     * (z_k / fx), (double(v) - cy) * (z_k / fy), z_k); X as in d3d_unproject_rows; q_i = floor((X_i - origin_i) /
@@ -595,31 +646,21 @@ int d3d_unproject_rows(const void *depth, int depth_is_u16, const void *color, i
  *     arguments, `scratch` and info_host as _count left them; asynchronous; never writes past N rows.
  * The same calls give the same bits whatever the block ids were.  No float atomics.                                   */
 int d3d_tsdf_table_slots(int max_blocks);
-int d3d_tsdf_touch(const void *depth, int depth_is_u16, const double *intrinsics, const double *extrinsics, int frames,
-                   int height, int width, int step, double depth_scale, double min_depth, double max_depth, double voxel,
-                   const double *origin, int reach, void *table, int table_slots, int32_t *block_coords, int max_blocks,
-                   int32_t *state, int *info_host /* [3] */, void *stream);
-int d3d_tsdf_integrate(const void *depth, int depth_is_u16, const void *color, int color_is_u8, double color_div,
-                       const double *intrinsics, const double *extrinsics, int frames, int height, int width,
-                       double depth_scale, double min_depth, double max_depth, double voxel, double trunc,
-                       const double *origin, const int32_t *block_coords, int n_blocks, int first_new, float *tsdf,
-                       float *weight, float *color_state, float *color_weight, unsigned long long *culled_pairs,
-                       void *stream);
+int d3d_tsdf_touch(const d3d_depth_frames *frames, int step, double min_depth, double max_depth,
+                   const d3d_tsdf_volume *volume, int reach, int *info_host /* [3] */, void *stream);
+int d3d_tsdf_integrate(const d3d_depth_frames *frames, double min_depth, double max_depth, double color_div,
+                       const d3d_tsdf_volume *volume, int first_new, unsigned long long *culled_pairs, void *stream);
 size_t d3d_tsdf_order_scratch_bytes(int n_blocks);
 int d3d_tsdf_order(const int32_t *block_coords, int n_blocks, int32_t *order, void *scratch, size_t scratch_bytes,
                    void *stream);
 size_t d3d_tsdf_surface_scratch_bytes(int n_blocks);
-int d3d_tsdf_surface_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                           int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
-                           size_t scratch_bytes, int *info_host /* [0] = N */, void *stream);
-int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                          int table_slots, const float *tsdf, const float *weight, const float *color_state,
-                          const float *color_weight, double voxel, const double *origin, double min_weight, int ncols,
-                          const int *info_host, const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels,
-                          void *stream);
+int d3d_tsdf_surface_count(const d3d_tsdf_volume *volume, double min_weight, void *scratch, size_t scratch_bytes,
+                           int *info_host /* [0] = N */, void *stream);
+int d3d_tsdf_surface_rows(const d3d_tsdf_volume *volume, double min_weight, int ncols, const int *info_host,
+                          const void *scratch, size_t scratch_bytes, float *out, int32_t *voxels, void *stream);
 
 /* The TSDF volume above -> a triangle mesh of its zero crossing: marching tetrahedra on the Kuhn split of
- * every voxel cell; the reference has nothing like it.  Volume arguments as for d3d_tsdf_surface_*; `seen`, `inside`
+ * every voxel cell; the reference has nothing like it.  The volume as for d3d_tsdf_surface_*; `seen`, `inside`
  * (D < 0), X_i, s and the colour rule are those of d3d_tsdf_surface_rows; so a voxel whose D is NaN or +-inf is not seen,
  * gives no vertex, and no cell it is a corner of is emitted: every vertex is finite.
  *   cells: the cell of voxel g has the corners g + c, c in {0, 1}^3, in up to eight blocks (a block coordinate outside
@@ -652,25 +693,21 @@ int d3d_tsdf_surface_rows(const int32_t *block_coords, const int32_t *order, int
  * The same calls give the same bits whatever the block ids were.  Integer counters only, no float atomics.            */
 int d3d_tsdf_mesh_table(int8_t *out /* [6][16][13] */);
 size_t d3d_tsdf_mesh_scratch_bytes(int n_blocks);
-int d3d_tsdf_mesh_count(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                        int table_slots, const float *tsdf, const float *weight, double min_weight, void *scratch,
-                        size_t scratch_bytes, int *info_host /* [0] = V, [1] = T */, void *stream);
-int d3d_tsdf_mesh_vertices(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                           int table_slots, const float *tsdf, const float *color_state, const float *color_weight,
-                           double voxel, const double *origin, const int *info_host, const void *scratch,
+int d3d_tsdf_mesh_count(const d3d_tsdf_volume *volume, double min_weight, void *scratch, size_t scratch_bytes,
+                        int *info_host /* [0] = V, [1] = T */, void *stream);
+int d3d_tsdf_mesh_vertices(const d3d_tsdf_volume *volume, const int *info_host, const void *scratch,
                            size_t scratch_bytes, float *vertices, float *vertex_color, int32_t *edges, void *stream);
-int d3d_tsdf_mesh_triangles(const int32_t *block_coords, const int32_t *order, int n_blocks, const void *table,
-                            int table_slots, const int *info_host, const void *scratch, size_t scratch_bytes,
-                            int32_t *triangles, void *stream);
-int d3d_tsdf_insert_blocks(const int32_t *coords, int n, void *table, int table_slots, int32_t *block_coords,
-                           int max_blocks, int32_t *state, void *stream);
+int d3d_tsdf_mesh_triangles(const d3d_tsdf_volume *volume, const int *info_host, const void *scratch,
+                            size_t scratch_bytes, int32_t *triangles, void *stream);
+int d3d_tsdf_insert_blocks(const int32_t *coords, int n, const d3d_tsdf_volume *volume, void *stream);
 
 /* Posed depth frames from a triangle mesh: the step between gen_house_obj and gen_pcl of
- * data3d/suncg_utils/suncg_preprocess.py, which the reference leaves to an external OpenGL tool (scn2img).  vertices fp32
- * [n_vertices, 3] in world coordinates, triangles int32 [n_triangles, 3], vertex_color fp32 or uint8 [n_vertices, 3] or
- * NULL; intrinsics fp64 [frames, 4] (fx, fy, cx, cy) and extrinsics fp64 [frames, 3, 4] (camera to world, R | t, the
- * camera looking along +z with x right and y down) as for d3d_unproject_*, all on the device.  Every operation below is
- * fp64 in exactly this order, without contraction:
+ * data3d/suncg_utils/suncg_preprocess.py, which the reference leaves to an external OpenGL tool (scn2img).  mesh, a
+ * d3d_triangle_mesh: vertices fp32 [n_vertices, 3] in world coordinates, triangles int32 [n_triangles, 3], vertex_color
+ * fp32 or uint8 [n_vertices, 3] or NULL; frames, the d3d_depth_frames the calls fill: intrinsics fp64 [frames, 4] (fx,
+ * fy, cx, cy) and extrinsics fp64 [frames, 3, 4] (camera to world, R | t, the camera looking along +z with x right and y
+ * down) as for d3d_unproject_*, all on the device.  Every operation below is fp64 in exactly this order, without
+ * contraction:
  *   camera-space vertex p = R^T (x - t): d = double(x) - t, p_k = (R[0][k] * d.x + R[1][k] * d.y) + R[2][k] * d.z, a
  *     function of (frame, vertex) alone;
  *   triangle with camera-space vertices a, b, c: n_bc = b x c with (p x q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z,
@@ -681,10 +718,10 @@ int d3d_tsdf_insert_blocks(const int32_t *coords, int n, void *table, int table_
  *     d3d_unproject_*; it counts when z is finite, z > 0 and min_depth <= z <= max_depth.  A triangle with a vertex
  *     index outside [0, n_vertices) or a non-finite vertex never hits (and nothing is read out of bounds);
  *   winner of a pixel: the smallest z, then the lowest triangle index: independent of any processing order;
- *   depth [frames, height, width]: fp32: float(z), 0 without a hit; uint16: rint(z / depth_scale), and 0 where that is 0
- *     or above 65535; tri int32 [frames, height, width] or NULL: the winner, -1 for none; color [frames, height, width, 3]
- *     (with vertex_color, of its type): (w0 * c_a + w1 * c_b) + w2 * c_c with w_i = e_i / S, fp32: rounded once, uint8:
- *     rint clamped to [0, 255]; 0 without a hit.
+ *   the images of `frames`: depth [frames, height, width]: fp32: float(z), 0 without a hit; uint16: rint(z /
+ *     depth_scale), and 0 where that is 0 or above 65535; tri int32 [frames, height, width] or NULL: the winner, -1 for
+ *     none; color [frames, height, width, 3] (with vertex_color, of its type): (w0 * c_a + w1 * c_b) + w2 * c_c with w_i
+ *     = e_i / S, fp32: rounded once, uint8: rint clamped to [0, 255]; 0 without a hit.
  * Tiles of 16 x 16 pixels, three calls on one stream with the same mesh, cameras and shape:
  *   _bin:   a conservative rectangle of tiles per (frame, triangle), the list length of every tile and their scan; the
  *           one host read-back: info_host[0] = E, all list entries (0 for an empty mesh or no frame); synchronises once.
@@ -693,17 +730,13 @@ int d3d_tsdf_insert_blocks(const int32_t *coords, int n, void *table, int table_
  *           (use fewer frames per call), as is frames * height * width >= 2^31 everywhere.
  * scratch: d3d_render_scratch_bytes bytes, 8 per tile plus a few KiB; the lists take 4 E bytes more.                     */
 size_t d3d_render_scratch_bytes(int frames, int height, int width);
-int d3d_render_bin(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                   const double *intrinsics, const double *extrinsics, int frames, int height, int width, void *scratch,
-                   size_t scratch_bytes, int64_t *info_host /* [0] = E */, void *stream);
-int d3d_render_fill(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                    const double *intrinsics, const double *extrinsics, int frames, int height, int width,
-                    const int64_t *info_host, void *scratch, size_t scratch_bytes, int32_t *lists, void *stream);
-int d3d_render_tiles(const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                     const void *vertex_color, int color_is_u8, const double *intrinsics, const double *extrinsics,
-                     int frames, int height, int width, double min_depth, double max_depth, int depth_is_u16,
-                     double depth_scale, const int64_t *info_host, const void *scratch, size_t scratch_bytes,
-                     const int32_t *lists, void *depth, int32_t *tri, void *color, void *stream);
+int d3d_render_bin(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, void *scratch, size_t scratch_bytes,
+                   int64_t *info_host /* [0] = E */, void *stream);
+int d3d_render_fill(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, const int64_t *info_host,
+                    void *scratch, size_t scratch_bytes, int32_t *lists, void *stream);
+int d3d_render_tiles(const d3d_triangle_mesh *mesh, const d3d_depth_frames *frames, double min_depth, double max_depth,
+                     const int64_t *info_host, const void *scratch, size_t scratch_bytes, const int32_t *lists,
+                     int32_t *tri, void *stream);
 
 /* a2/a3. InputLayer_updateOutput (SCN/sparseconvnet.h:159-163; SCN/Metadata/IOLayersRules.h:19-125;
  * SCN/CPU/IOLayers.cpp:11-47), split into the hash build (sizes) and the feature pass.

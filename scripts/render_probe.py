@@ -116,20 +116,19 @@ def phases(mesh, intr, extr, size, rounds):
     from detection_3d_amd._lib import check, lib, ptr, stream_of
     from detection_3d_amd.render import _Call, _cameras
     K, E = _cameras("probe", intr, extr)
-    call = _Call(mesh, K, E, size, size)
     F, dev = E.shape[0], mesh.device
     depth = torch.empty((F, size, size), dtype=torch.float32, device=dev)
     color = torch.empty((F, size, size, 3), dtype=torch.uint8, device=dev)
+    call = _Call(mesh, K, E, size, size, depth, color, 0.001)
     ms = {"bin": [], "fill": [], "tiles": []}
     for r in range(rounds + 2):
         t_bin, (scratch, entries) = _timed(lambda: call.bin(0, F))
         lists = torch.empty(max(entries, 1), dtype=torch.int32, device=dev)
-        s = stream_of(dev)
-        t_fill, _ = _timed(lambda: check(lib().d3d_render_fill(*call.head(), *call.views(0, F), call.info, ptr(scratch),
-                                                                scratch.numel(), ptr(lists), s)))
-        t_tiles, _ = _timed(lambda: check(lib().d3d_render_tiles(
-            *call.head(), ptr(mesh.vertex_color), 1, *call.views(0, F), 0.0, math.inf, 0, 0.001, call.info, ptr(scratch),
-            scratch.numel(), ptr(lists), ptr(depth), None, ptr(color), s)))
+        s, views = stream_of(dev), call.frames(0, F)
+        t_fill, _ = _timed(lambda: check(lib().d3d_render_fill(mesh.desc, views, call.info, ptr(scratch), scratch.numel(),
+                                                                ptr(lists), s)))
+        t_tiles, _ = _timed(lambda: check(lib().d3d_render_tiles(mesh.desc, views, 0.0, math.inf, call.info, ptr(scratch),
+                                                                  scratch.numel(), ptr(lists), None, s)))
         if r >= 2:
             ms["bin"].append(t_bin), ms["fill"].append(t_fill), ms["tiles"].append(t_tiles)
     n_tiles = F * ((size + 15) // 16) ** 2

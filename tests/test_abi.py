@@ -25,7 +25,7 @@ def test_header_symbols_exported_and_bound():
         assert hasattr(handle, n), f"{n} declared in d3d_hip.h but not exported"
     assert set(names) == set(_lib.EXPORTED_SYMBOLS), set(names) ^ set(_lib.EXPORTED_SYMBOLS)
     lib = _lib.lib()
-    assert lib.d3d_abi_version() == 2
+    assert lib.d3d_abi_version() == 3
     # pure host-side helpers are callable without a GPU
     assert lib.d3d_packed_weight_bytes(27, 9, 32, 0) == 27 * 16 * 32 * 4
     assert lib.d3d_packed_weight_bytes(8, 128, 128, 0) == 8 * 128 * 128 * 4

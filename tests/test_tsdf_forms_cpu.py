@@ -83,6 +83,33 @@ def test_random1_has_no_neighbour():
     assert len(triangles) > 0
 
 
+def _cells(name):
+    """the cells that gave a triangle: the lowest corner over the ends of the edges of its three vertices"""
+    _, triangles, _, edges = F.case_mesh(name)
+    g, h = F.vertex_ends(edges)
+    return {tuple(c) for c in np.concatenate([g[triangles], h[triangles]], 1).min(1).tolist()}
+
+
+def test_corner_voxel_crosses_into_every_forward_neighbour():
+    """voxel CORNER_VOXEL of block BASE owns a vertex of every kind, each on an edge that ends in another block; the twin
+    without neighbour o loses the vertex that ends there and keeps the other six, and a cell that needs o is not emitted"""
+    from tests.tsdf_mesh_ref import KIND_DIR
+    g = 8 * np.array(F.BASE, np.int64) + np.array(F.CORNER_VOXEL, np.int64)
+    kinds_of = lambda edges: sorted(edges[(edges[:, :3] == g).all(1)][:, 3].tolist())
+    full_edges = F.case_mesh("corner")[3]
+    assert kinds_of(full_edges) == list(range(7))
+    assert all(((g + KIND_DIR[k]) // 8 != g // 8).any() for k in range(7))
+    rows_at = lambda name: int((F.case_surface(name, 9)[1] == g).all(1).sum())
+    assert rows_at("corner") == 3
+    for o in range(1, 8):
+        name = f"corner_without_{o}"
+        assert len(F.case(name)["blocks"][0]) == 7
+        lost = [k for k in range(7) if (KIND_DIR[k] * (1, 2, 4)).sum() == o]
+        assert len(lost) == 1 and kinds_of(F.case_mesh(name)[3]) == [k for k in range(7) if k != lost[0]]
+        assert rows_at(name) == (2 if lost[0] < 3 else 3)
+        assert tuple(g) in _cells("corner") and tuple(g) not in _cells(name)
+
+
 def test_checker_ends_on_round_boundaries():
     rows, verts, _ = _counts("checker")
     assert rows[0] == 3 * STAGE and verts[0] == 4 * STAGE  # block (0, 0, 0) of the eight has all seven forward neighbours

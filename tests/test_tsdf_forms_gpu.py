@@ -32,6 +32,8 @@ volumes only and is asserted on signs and parity; tests/test_tsdf_forms_cpu.py h
                                             2, NaN, +inf, -1} at min_weight 0, 0.5, 1, 2
   kTouchRun edges of k_tsdf_touch           test_pixels[2048, 2049, 2049 step 2]: the last pixel alone needs its blocks
   a tsdf that is not finite                 [nonfinite], test_nonfinite_equals_unseen, test_integrate_keeps_nonfinite
+  load_apron<true> / <false>, each of the   test_forward_neighbours[corner, corner_without_1 .. 7]: one voxel whose seven
+  seven forward neighbours absent in turn   forward edges each end in another block; the twins leave one block out
 
 Not reached: more than 212 blocks or 513 frames of 48 pixels (the old modules have the larger scenes); fp32 colour images
 and uint16 depth in the second round of frames (test_tsdf_gpu.py has both in the first; the round changes nothing about
@@ -42,7 +44,7 @@ pass torch's current stream only, and every launch of both files takes the one s
 
 Fixes these tests asked for: one.  A voxel whose stored tsdf is NaN or +-inf (reachable through TsdfVolume.from_blocks
 only) counted as seen and outside, and every crossing edge at it gave a NaN position.  Such a voxel is now not seen
-(load_apron in tsdf.hip, the staging loop of k_mesh_count in tsdf_mesh.hip; both restatements say the same).
+(load_apron in tsdf_volume.inc, which both files use; both restatements say the same).
 
 Mutants (each built apart, this module run once against it on an MI355X, not kept; all arithmetic or loop-bound
 changes that cannot leave a buffer or lengthen a walk).  Every one of the nine fails at least one test:
@@ -68,7 +70,8 @@ changes that cannot leave a buffer or lengthen a walk).  Every one of the nine f
                                             test_integrate_keeps_nonfinite fail
 
 Cost: the module's 18 tests take 4.8 s on an MI355X, restatements included; the slowest is
-test_mesh_and_surface[random8] at 0.8 s, which also builds the restatements the later tests share."""
+test_mesh_and_surface[random8] at 0.8 s, which also builds the restatements the later tests share.  The eight cases of
+test_forward_neighbours came later and are of random8's size, one pass each."""
 import ctypes
 
 import numpy as np
@@ -207,6 +210,13 @@ def test_mesh_and_surface(dev, name):
         assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
+@pytest.mark.parametrize("name", F.CORNER_CASES)
+def test_forward_neighbours(dev, name):
+    """eight blocks with a sign change exactly across a block face, a block edge and the shared corner, and the seven
+    twins with one forward neighbour of the first block left out: the one apron routine with and without diagonals"""
+    _check_case(dev, name, 17)
+
+
 def test_parity(dev):
     """a table whose keys all share one position inside a group: insertion, look-up and the touch pass take the turn"""
     c = F.case("parity")
@@ -269,12 +279,12 @@ def test_guards(dev):
     nan_rows = lambda t, a: bool(torch.isnan(t[a:]).all())
     with torch.cuda.device(dev):
         s = stream_of(dev)
-        common = (ptr(vol._coords), ptr(order), n, ptr(vol._table), vol._slots)
+        desc = vol._desc(order=order)
         # the surface rows
         nbytes = L.d3d_tsdf_surface_scratch_bytes(n)
         buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         info = (ctypes.c_int * 1)(0)
-        check(L.d3d_tsdf_surface_count(*common, ptr(vol._tsdf), ptr(vol._weight), 1.0, ptr(buf), nbytes, info, s))
+        check(L.d3d_tsdf_surface_count(desc, 1.0, ptr(buf), nbytes, info, s))
         for columns in (3, 6, 9):
             r_rows, r_voxels, _ = F.case_surface("random8", columns)
             N = len(r_rows)
@@ -282,9 +292,7 @@ def test_guards(dev):
             for cut in (0, 5):
                 out, voxels = full(N, columns, NAN, torch.float32), full(N, 3, SENT_I, torch.int32)
                 given = (ctypes.c_int * 1)(N - cut)
-                check(L.d3d_tsdf_surface_rows(*common, ptr(vol._tsdf), ptr(vol._weight), ptr(vol._color), ptr(vol._cweight),
-                                              vol.voxel, vol._origin, 1.0, columns, given, ptr(buf), nbytes, ptr(out),
-                                              ptr(voxels), s))
+                check(L.d3d_tsdf_surface_rows(desc, 1.0, columns, given, ptr(buf), nbytes, ptr(out), ptr(voxels), s))
                 torch.cuda.synchronize()
                 k, m = min(columns, 6), N - cut
                 assert np.array_equal(_bits(out[:m, :k].cpu().numpy()), _bits(r_rows[:m, :k])), (columns, cut)
@@ -294,15 +302,14 @@ def test_guards(dev):
         nbytes = L.d3d_tsdf_mesh_scratch_bytes(n)
         buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         info = (ctypes.c_int * 2)(0, 0)
-        check(L.d3d_tsdf_mesh_count(*common, ptr(vol._tsdf), ptr(vol._weight), 1.0, ptr(buf), nbytes, info, s))
+        check(L.d3d_tsdf_mesh_count(desc, 1.0, ptr(buf), nbytes, info, s))
         assert (info[0], info[1]) == (V, T)
         for cut_v, cut_t in ((0, 0), (5, 7)):
             vertices, colors = full(V, 3, NAN, torch.float32), full(V, 3, NAN, torch.float32)
             edges, triangles = full(V, 4, SENT_I, torch.int32), full(T, 3, SENT_I, torch.int32)
             given = (ctypes.c_int * 2)(V - cut_v, T - cut_t)
-            check(L.d3d_tsdf_mesh_vertices(*common, ptr(vol._tsdf), ptr(vol._color), ptr(vol._cweight), vol.voxel,
-                                           vol._origin, given, ptr(buf), nbytes, ptr(vertices), ptr(colors), ptr(edges), s))
-            check(L.d3d_tsdf_mesh_triangles(*common, given, ptr(buf), nbytes, ptr(triangles), s))
+            check(L.d3d_tsdf_mesh_vertices(desc, given, ptr(buf), nbytes, ptr(vertices), ptr(colors), ptr(edges), s))
+            check(L.d3d_tsdf_mesh_triangles(desc, given, ptr(buf), nbytes, ptr(triangles), s))
             torch.cuda.synchronize()
             v, t = V - cut_v, T - cut_t
             assert np.array_equal(_bits(vertices[:v].cpu().numpy()), _bits(r_vertices[:v])), cut_v

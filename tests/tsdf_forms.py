@@ -137,6 +137,23 @@ def nonfinite(twin=False):
     return _case(coords, *dense_to_blocks(coords, D, W, C, CW), bad=np.stack(at, 1) + 8 * np.array(BASE, np.int64))
 
 
+CORNER_VOXEL = (7, 7, 7)                                  # of block BASE: its seven forward edges each end in another block
+
+
+def corner(without=0):
+    """random8 with voxel CORNER_VOXEL of block BASE inside and its seven forward neighbours outside: a sign changes
+    exactly across a block face (+x, +y, +z), a block edge (+xy, +xz, +yz) and the corner the eight blocks share (+xyz).
+    without: the forward neighbour o = ox | oy << 1 | oz << 2 of block BASE that is left out, 0 for none"""
+    D, W, C, CW = _random8_dense()
+    D = D.copy()
+    D[7:9, 7:9, 7:9] = 0.5
+    D[CORNER_VOXEL] = -0.25
+    coords = cube_coords()
+    if without:
+        coords = np.delete(coords, 4 * (without & 1) + 2 * ((without >> 1) & 1) + ((without >> 2) & 1), 0)
+    return _case(coords, *dense_to_blocks(coords, D, W, C, CW))        # block BASE stays, so the dense box starts there
+
+
 PARITY_BASE = (4, 6, 8)
 PARITY_MAX_BLOCKS = 512
 
@@ -178,8 +195,10 @@ def nonfinite_frame():
     return look_frame(np.array(ORIGIN) + 8.0 * VOXEL * np.array(BASE) + np.array([-2.5, 2.0, 2.0]))
 
 
+CORNER_CASES = ("corner",) + tuple(f"corner_without_{o}" for o in range(1, 8))
 CASES = dict(random8=random8, random1=random1, checker=checker, closed=closed, weights=weights, signs=signs,
-             nonfinite=nonfinite, nonfinite_twin=lambda: nonfinite(twin=True), parity=parity)
+             nonfinite=nonfinite, nonfinite_twin=lambda: nonfinite(twin=True), parity=parity, corner=corner,
+             **{f"corner_without_{o}": (lambda o=o: corner(o)) for o in range(1, 8)})
 MESH_CASES = ("random8", "random1", "checker", "closed", "weights", "signs", "nonfinite", "parity")
 _CACHE = {}
 
